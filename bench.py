@@ -15,10 +15,14 @@ Every wait of the N > 1 path is bounded (communicator id hand-over, ncclCommInit
 Watchdog); on any failure rank 0 prints ONE JSON line with "error" and the process exits non-zero instead of hanging.
 
 Prints ONE JSON line on rank 0 (see the contract in the task description).
+A plain run sets up, warms up, times --steps steps and prints the headline (metric, value, ms_per_step, config); `--full`
+adds the per-pass device times with the roofline figures and the side rows (other circuits, keys, schedules and batch
+sizes, OT, host API, streaming, config 3, CPU baseline).  `--dump-outputs DIR` writes what the last timed step computed.
 """
 import argparse
 import json
 import os
+import signal
 import sys
 import time
 
@@ -259,6 +263,147 @@ def reference_bench_rows(batch, circ, ctx):
     return {"key16": k16, "and_chain_10000": chain}
 
 
+def pass_figures(args, info, batch, world, value, launches, g_ms, e_ms):
+    """--full: the garble and eval passes by HIP events (g_ms / e_ms, from extra steps after the timed ones) and what they
+    make of the headline — per-pass rates, the roofline fractions and the AES-core figures"""
+    import numpy as np
+    n_and = info.n_and
+    algb = alg_bytes_per_instance(info)
+    g_avg = float(np.mean(g_ms))
+    e_avg = float(np.mean(e_ms))
+    # dominant kernel: the garble pass (schedule 1: ONE k_garble_flat launch; schedule 0: one
+    # k_garble_level launch per level).  Algorithmic bytes per launch = garble bytes per instance x batch
+    # / launches; launch duration from HIP events recorded on the engine's stream (gc_batch_last_ms).
+    achieved = algb * batch / (g_avg * 1e-3) / 1e9
+    kernel_name = {0: "k_garble_level", 1: "k_garble_flat", 2: "k_garble_lds"}[args.schedule]
+    blocks_g = sum(getattr(info, "n_" + k) * v[0] for k, v in AES_BLOCKS.items())
+    blocks_e = sum(getattr(info, "n_" + k) * v[1] for k, v in AES_BLOCKS.items())
+    # HBM traffic of the garble launch: PMC counters cannot be read from inside the run; the figure is the one
+    # scripts/profile.sh measured with rocprofv3 --pmc for this batch / schedule / key size AND this build of the
+    # kernels (profiles/latest_pmc.json carries the hash of the kernel sources) — null otherwise.
+    traffic, traffic_src = None, None
+    build_hash = kernel_build_hash(args.circuit)
+    pmc = os.path.join(ROOT, "profiles", "latest_pmc.json")
+    if os.path.exists(pmc):
+        try:
+            with open(pmc) as f:
+                pj = json.load(f)
+            if (pj.get("batch") == batch and pj.get("schedule") == args.schedule and pj.get("key_bytes") == args.key_bytes
+                    and pj.get("kernel_build_hash") == build_hash):
+                traffic = pj.get("garble_hbm_bytes_per_launch")
+                traffic_src = "profiles/latest_pmc.json (rocprofv3 --pmc, %s)" % pj.get("source", "scripts/profile.sh")
+            elif pj.get("kernel_build_hash") != build_hash:
+                traffic_src = "null: profiles/latest_pmc.json was measured on kernel build %s, this is %s" % (
+                    pj.get("kernel_build_hash"), build_hash)
+        except Exception:
+            traffic = None
+    read_b = sum(getattr(info, "n_" + k) * (v[0] + v[1]) for k, v in READ_BYTES.items())  # per instance, both passes
+    rounds = {16: 10, 24: 12, 32: 14}[args.key_bytes]
+    lookups_per_block = 16 * rounds
+    lds_g = blocks_g * batch * lookups_per_block / (g_avg * 1e-3) / LDS_B32_PEAK_LOOKUPS
+    lds_e = blocks_e * batch * lookups_per_block / (e_avg * 1e-3) / LDS_B32_PEAK_LOOKUPS
+    frac_read = value / world * (read_b / max(n_and, 1)) / 1e9 / HBM_PEAK_GBS
+    return {
+        "garble_ms": g_avg,
+        "eval_ms": e_avg,
+        "and_gates_per_s_garble_only": n_and * batch / (g_avg * 1e-3),
+        "and_gates_per_s_eval_only": n_and * batch / (e_avg * 1e-3),
+        "hbm_alg_GBs_garble_plus_eval": 2 * algb * batch / ((g_avg + e_avg) * 1e-3) / 1e9,
+        "roofline": {
+            # what binds the dominant kernel: the T-table AES out of LDS (LDS array + VALU issue), not HBM — the wires
+            # never leave the CU.  achieved / peak / frac keep the contract's definition (SURVEY §8d algorithmic bytes of
+            # the garble launch over its HIP-event duration against the 8 TB/s HBM peak): a NOMINAL figure, restated as
+            # frac_nominal_model; frac_read is the north star's "HBM-read roofline" of the whole step; frac_bound prices
+            # the kernel against the resource that binds it.
+            "bound": "lds/valu-issue" if args.schedule != 0 else "hbm",
+            "kernel": kernel_name,
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS,
+            "frac_nominal_model": achieved / HBM_PEAK_GBS,
+            "frac_read": frac_read,
+            "frac_bound": lds_g,
+            "frac_bound_definition": "T-table look-ups/s of the garble launch over the LDS array's ds_read_b32 rate "
+                                     "(75 TB/s / 4 B: 128 B per clock per CU on every CU)",
+            "traffic": traffic,
+            "traffic_source": traffic_src,
+            "kernel_build_hash": build_hash,
+            "alg_bytes_per_launch": algb * batch / max(launches, 1),
+            "avg_launch_us": g_avg * 1e3 / max(launches, 1),
+            "hbm_counter_GBs": (traffic / (g_avg * 1e-3) / 1e9) if traffic else None,  # what HBM really carried
+            "hbm_counter_frac": (traffic / (g_avg * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
+            "limiter": "LDS array + VALU issue of the T-table AES core (see aes_core); HBM is at hbm_counter_frac",
+        },
+        # what actually limits the kernels: AES blocks through the LDS T-table core (VALU issue + LDS address path)
+        "aes_core": {
+            "garble_blocks_per_s": blocks_g * batch / (g_avg * 1e-3),
+            "eval_blocks_per_s": blocks_e * batch / (e_avg * 1e-3),
+            "peak_blocks_per_s": AES_CORE_PEAK_BLOCKS,
+            "frac_garble": blocks_g * batch / (g_avg * 1e-3) / AES_CORE_PEAK_BLOCKS,
+            "frac_eval": blocks_e * batch / (e_avg * 1e-3) / AES_CORE_PEAK_BLOCKS,
+            "peak_source": "tools/aes_ubench: the production AES core alone, 16 waves/CU (own micro-benchmark)",
+            # against the hardware figure instead: table look-ups/s over the LDS array's ds_read_b32 rate
+            "lds_array_frac_garble": lds_g,
+            "lds_array_frac_eval": lds_e,
+            "lds_array_peak_lookups_per_s": LDS_B32_PEAK_LOOKUPS,
+        },
+    }
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_TABLE_BYTES = 16 << 20  # of which the sample of garbled tables
+DUMP_SEED = 20240611  # which instances / table rows a sample holds
+
+
+def _label_words(labels):
+    """LABEL records [..] -> their four little-endian u32 words [.., 4] as float64 (exact)"""
+    import numpy as np
+    a = np.ascontiguousarray(labels)
+    return a.view(np.uint32).reshape(a.shape + (4,)).astype(np.float64)
+
+
+def _sample(n, cap, rng):
+    """all of range(n) when it fits under cap, else a sorted sample of cap of them"""
+    import numpy as np
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(rng.choice(n, size=max(1, cap), replace=False))
+
+
+def dump_outputs(path, gb, ev, decoded, mismatches):
+    """--dump-outputs: what the timed path handed its caller in its last step, as <name>.npy (float32 / float64).
+    decoded_outputs [batch, outputs] (the output bits, BitFromLabel), output_labels [batch, outputs, 4] (the evaluator's
+    output wire labels as u32 words), garbler_R [batch, 4], mismatches_all_steps [1] (the decode's counter, which every
+    step of the run adds to), and garbled_tables [n, rows, 4] for a seeded sample of instances (garbled_tables_instances)
+    and, if one instance's tables alone exceed their share, of rows (garbled_tables_rows).  If the per-instance arrays
+    exceed their share, they too hold a seeded sample of instances, named by `instances`.  Same arguments -> same inputs
+    -> same files."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    batch = decoded.shape[0]
+    per = {"decoded_outputs": decoded.astype(np.float32), "output_labels": _label_words(ev.read_outputs()),
+           "garbler_R": _label_words(gb.read_r())}
+    row_bytes = sum(a[:1].nbytes for a in per.values()) + 8  # (+ its entry in `instances`)
+    inst = _sample(batch, (DUMP_BYTES - DUMP_TABLE_BYTES - (64 << 10)) // row_bytes, rng)  # (64 KiB: headers, small arrays)
+    out = {k: a[inst] for k, a in per.items()}
+    out["instances"] = inst.astype(np.float64)
+    out["mismatches_all_steps"] = np.array([mismatches], np.float64)
+    slab = gb.read_slab()
+    rows = np.arange(slab.shape[1])
+    if slab.shape[1] * 32 > DUMP_TABLE_BYTES:
+        rows = _sample(slab.shape[1], DUMP_TABLE_BYTES // 40, rng)  # (32 B of words + 8 B of index per row)
+        out["garbled_tables_rows"] = rows.astype(np.float64)
+    tinst = _sample(batch, min(16, DUMP_TABLE_BYTES // max(len(rows) * 32, 1)), rng)
+    out["garbled_tables"] = _label_words(slab[tinst][:, rows])
+    out["garbled_tables_instances"] = tinst.astype(np.float64)
+    del slab
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(out)
+
+
 METRIC = "AND-gates/sec (garble+eval), AES-128 circuit batch"
 
 
@@ -272,6 +417,10 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     stage = ["start"]
+    if world > 1 and hasattr(signal, "pthread_sigmask") and hasattr(signal, "sigtimedwait"):
+        # the launcher's SIGTERM (another rank failed) may come while this rank is still importing or parsing, before run()
+        # starts its Watchdog: blocked from the start, it stays pending until the Watchdog's thread takes it and says why
+        signal.pthread_sigmask(signal.SIG_BLOCK, {signal.SIGTERM})
     try:
         run(stage)
     except SystemExit:
@@ -295,6 +444,13 @@ def run(stage):
     ap.add_argument("--run-timeout", type=float, default=1500.0, help="N > 1: seconds the whole run may take")
     ap.add_argument("--circuit", default=os.path.join(ROOT, "tests", "golden", "aes_128.gcf"))
     ap.add_argument("--key-bytes", type=int, default=32, choices=[16, 24, 32])
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure everything else the line can carry: "
+                    "per-pass device times with the roofline and AES-core figures, the gather alone (N > 1), and the side rows "
+                    "(synthetic circuits, key16 / AND chain / level-launch / 8 192-instance rows, IKNP and OT, host API, stream, "
+                    "config 3, CPU baseline) unless a --no-* option below drops one; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step "
+                    "computed (decoded output bits, the evaluator's output labels, every instance's R, a seeded sample of the "
+                    "garbled tables) as DIR/<name>.npy in float32 / float64, at most 64 MB in all (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-iknp", action="store_true", help="skip the IKNP OT-extension side measurement")
     ap.add_argument("--no-host-api", action="store_true", help="skip the PCIe-inclusive gc_garble / gc_eval side measurement")
@@ -311,6 +467,8 @@ def run(stage):
     ap.add_argument("--sweep", action="store_true", help="synthetic levelised circuits (SURVEY §8d): W x AND-fraction grid + "
                     "AND chain, AND/s and roofline fractions per circuit, one JSON line")
     args = ap.parse_args()
+    if args.sweep and args.dump_outputs:
+        ap.error("--dump-outputs dumps the headline's step; --sweep does not run it")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -406,8 +564,10 @@ def run(stage):
         gb.decode(ev, d_acc + j * slot_bytes, d_mis)
 
     graphs = None  # the step's kernels recorded once per output slot in a hipGraph (gc_ctx_capture_*): one launch per step
+    last_slot = [0]  # output slot of the latest step (--dump-outputs)
 
     def launch(j):
+        last_slot[0] = j
         if graphs is not None:
             graphs[j].launch()
         else:
@@ -443,8 +603,13 @@ def run(stage):
                               allreduce_max=comm.allreduce_max if comm is not None else None)
     assert loop.steps_gathered == loop.steps_done == args.steps + args.warmup
     stage[0] = "after the timed steps"
+    if args.dump_outputs and rank == 0:  # (before anything below runs the passes again)
+        stage[0] = "dump outputs"
+        ctx.sync()
+        dump_outputs(args.dump_outputs, gb, ev, d_acc.numpy()[last_slot[0]], int(d_mis.numpy()[0]))
+        stage[0] = "after the timed steps"
     gather_us = None
-    if collective:  # the gather alone: a few calls between device syncs (config 4's "RCCL gather over xGMI")
+    if collective and args.full:  # the gather alone: a few calls between device syncs (config 4's "RCCL gather over xGMI")
         ctx.sync()
         t0 = time.perf_counter()
         for _ in range(5):
@@ -452,9 +617,9 @@ def run(stage):
         ctx.sync()
         gather_us = (time.perf_counter() - t0) / 5 * 1e6
 
-    # per-pass device times (events on the engine stream) from a few extra, untimed-by-wall steps
+    # --full: per-pass device times (events on the engine stream) from a few extra, untimed-by-wall steps
     g_ms, e_ms = [], []
-    for _ in range(min(20, max(1, args.steps))):
+    for _ in range(min(20, max(1, args.steps)) if args.full else 0):
         gb.garble(key, d_rnd)
         g_ms.append(gb.last_ms)
         ev.select_inputs(gb, d_bits)
@@ -476,43 +641,8 @@ def run(stage):
     n_and = info.n_and
     total_and = n_and * batch * world * args.steps
     value = total_and / elapsed
-    algb = alg_bytes_per_instance(info)
-    g_avg = float(np.mean(g_ms))
-    e_avg = float(np.mean(e_ms))
     launches = gb.last_launches
-    # dominant kernel: the garble pass (schedule 1: ONE k_garble_flat launch; schedule 0: one
-    # k_garble_level launch per level).  Algorithmic bytes per launch = garble bytes per instance x batch
-    # / launches; launch duration from HIP events recorded on the engine's stream (gc_batch_last_ms).
-    achieved = algb * batch / (g_avg * 1e-3) / 1e9
-    kernel_name = {0: "k_garble_level", 1: "k_garble_flat", 2: "k_garble_lds"}[args.schedule]
     sched_name = {0: "level-launch", 1: "fused-flat", 2: "fused-levels"}[args.schedule]
-    blocks_g = sum(getattr(info, "n_" + k) * v[0] for k, v in AES_BLOCKS.items())
-    blocks_e = sum(getattr(info, "n_" + k) * v[1] for k, v in AES_BLOCKS.items())
-    # HBM traffic of the garble launch: PMC counters cannot be read from inside the run; the figure is the one
-    # scripts/profile.sh measured with rocprofv3 --pmc for this batch / schedule / key size AND this build of the
-    # kernels (profiles/latest_pmc.json carries the hash of the kernel sources) — null otherwise.
-    traffic, traffic_src = None, None
-    build_hash = kernel_build_hash(args.circuit)
-    pmc = os.path.join(ROOT, "profiles", "latest_pmc.json")
-    if os.path.exists(pmc):
-        try:
-            with open(pmc) as f:
-                pj = json.load(f)
-            if (pj.get("batch") == batch and pj.get("schedule") == args.schedule and pj.get("key_bytes") == args.key_bytes
-                    and pj.get("kernel_build_hash") == build_hash):
-                traffic = pj.get("garble_hbm_bytes_per_launch")
-                traffic_src = "profiles/latest_pmc.json (rocprofv3 --pmc, %s)" % pj.get("source", "scripts/profile.sh")
-            elif pj.get("kernel_build_hash") != build_hash:
-                traffic_src = "null: profiles/latest_pmc.json was measured on kernel build %s, this is %s" % (
-                    pj.get("kernel_build_hash"), build_hash)
-        except Exception:
-            traffic = None
-    read_b = sum(getattr(info, "n_" + k) * (v[0] + v[1]) for k, v in READ_BYTES.items())  # per instance, both passes
-    rounds = {16: 10, 24: 12, 32: 14}[args.key_bytes]
-    lookups_per_block = 16 * rounds
-    lds_g = blocks_g * batch * lookups_per_block / (g_avg * 1e-3) / LDS_B32_PEAK_LOOKUPS
-    lds_e = blocks_e * batch * lookups_per_block / (e_avg * 1e-3) / LDS_B32_PEAK_LOOKUPS
-    frac_read = value / world * (read_b / max(n_and, 1)) / 1e9 / HBM_PEAK_GBS
     res = {
         "metric": METRIC,
         "value": value,
@@ -543,51 +673,10 @@ def run(stage):
         # what the communicator itself says (gc_comm_nranks / gc_comm_version), not what the launcher promised
         "n_ranks_seen": comm.nranks if comm is not None else 1,
         "rccl_version": engine.comm_version() if comm is not None else None,
-        "garble_ms": g_avg,
-        "eval_ms": e_avg,
-        "and_gates_per_s_garble_only": n_and * batch / (g_avg * 1e-3),
-        "and_gates_per_s_eval_only": n_and * batch / (e_avg * 1e-3),
-        "hbm_alg_GBs_garble_plus_eval": 2 * algb * batch / ((g_avg + e_avg) * 1e-3) / 1e9,
-        "roofline": {
-            # what binds the dominant kernel: the T-table AES out of LDS (LDS array + VALU issue), not HBM — the wires
-            # never leave the CU.  achieved / peak / frac keep the contract's definition (SURVEY §8d algorithmic bytes of
-            # the garble launch over its HIP-event duration against the 8 TB/s HBM peak): a NOMINAL figure, restated as
-            # frac_nominal_model; frac_read is the north star's "HBM-read roofline" of the whole step; frac_bound prices
-            # the kernel against the resource that binds it.
-            "bound": "lds/valu-issue" if args.schedule != 0 else "hbm",
-            "kernel": kernel_name,
-            "achieved": achieved,
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS,
-            "frac_nominal_model": achieved / HBM_PEAK_GBS,
-            "frac_read": frac_read,
-            "frac_bound": lds_g,
-            "frac_bound_definition": "T-table look-ups/s of the garble launch over the LDS array's ds_read_b32 rate "
-                                     "(75 TB/s / 4 B, MI355X_MICROARCH.md)",
-            "traffic": traffic,
-            "traffic_source": traffic_src,
-            "kernel_build_hash": build_hash,
-            "alg_bytes_per_launch": algb * batch / max(launches, 1),
-            "avg_launch_us": g_avg * 1e3 / max(launches, 1),
-            "hbm_counter_GBs": (traffic / (g_avg * 1e-3) / 1e9) if traffic else None,  # what HBM really carried
-            "hbm_counter_frac": (traffic / (g_avg * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
-            "limiter": "LDS array + VALU issue of the T-table AES core (see aes_core); HBM is at hbm_counter_frac",
-        },
-        # what actually limits the kernels: AES blocks through the LDS T-table core (VALU issue + LDS address path)
-        "aes_core": {
-            "garble_blocks_per_s": blocks_g * batch / (g_avg * 1e-3),
-            "eval_blocks_per_s": blocks_e * batch / (e_avg * 1e-3),
-            "peak_blocks_per_s": AES_CORE_PEAK_BLOCKS,
-            "frac_garble": blocks_g * batch / (g_avg * 1e-3) / AES_CORE_PEAK_BLOCKS,
-            "frac_eval": blocks_e * batch / (e_avg * 1e-3) / AES_CORE_PEAK_BLOCKS,
-            "peak_source": "tools/aes_ubench: the production AES core alone, 16 waves/CU (own micro-benchmark)",
-            # against the hardware figure instead: table look-ups/s over the LDS array's ds_read_b32 rate
-            "lds_array_frac_garble": lds_g,
-            "lds_array_frac_eval": lds_e,
-            "lds_array_peak_lookups_per_s": LDS_B32_PEAK_LOOKUPS,
-        },
+        "full": args.full,
     }
+    if args.full:
+        res.update(pass_figures(args, info, batch, world, value, launches, g_ms, e_ms))
     if collective:
         # which GPU every rank really ran on (one process per GPU: each may see its own as device 0), as the ranks say
         # themselves: 96 bytes per rank through the communicator's own all-gather
@@ -628,7 +717,7 @@ def run(stage):
     for d in (d_rnd, d_bits, d_acc, d_mis, d_all):
         if d is not None:
             d.close()
-    if (world > 1 and comm is not None and not args.no_synthetic and args.circuit.endswith("aes_128.gcf")
+    if (args.full and world > 1 and comm is not None and not args.no_synthetic and args.circuit.endswith("aes_128.gcf")
             and not os.environ.get("GC_BENCH_ENGINE")):
         # north star: "AND-gates/sec on synthetic levelised circuits reported at 1/2/4/8 GPUs": every rank runs the five rows
         # of the N = 1 line on its own GPU (independent instances, 1 024 per GPU as there), the job's figure is the sum
@@ -643,7 +732,7 @@ def run(stage):
             r["and_gates_per_s_per_rank"] = [float(v) for v in allv[:, i, 0]]
             r["instances_per_gpu"] = 1024
         res["synthetic"] = rows
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         aes = args.circuit.endswith("aes_128.gcf")
         # how long each group of side rows took (the timed region of `value` is ms_per_step x steps; the rest of the run is these)
         side_wall = {}

@@ -15,11 +15,11 @@ NDEV=$(python -c "from mpc_amd import engine; print(engine.device_count())" 2>/d
 echo "devices visible: $NDEV" | tee $OUT/devices.txt
 rocm-smi --showtopo >> $OUT/devices.txt 2>&1
 timeout 900 python -m pytest tests/test_gpu_config4.py tests/test_gpu_two_ranks.py -q -m gpu > $OUT/tests.log 2>&1; echo "tests rc=$?" | tee -a $OUT/tests.log
-timeout 900 python bench.py --gpus 1 --steps $STEPS --warmup $WARMUP --no-stream --no-config3 --no-host-api > $OUT/n1.json 2> $OUT/n1.err; echo "N=1 rc=$?"
+timeout 900 python bench.py --full --gpus 1 --steps $STEPS --warmup $WARMUP --no-stream --no-config3 --no-host-api > $OUT/n1.json 2> $OUT/n1.err; echo "N=1 rc=$?"
 for N in 2 4 8; do
   [ "$N" -le "$NDEV" ] || continue
   timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) \
-      bench.py --gpus $N --steps $STEPS --warmup $WARMUP > $OUT/n$N.json 2> $OUT/n$N.err
+      bench.py --full --gpus $N --steps $STEPS --warmup $WARMUP > $OUT/n$N.json 2> $OUT/n$N.err
   echo "N=$N rc=$?"
 done
 python - "$OUT" <<'PY' | tee $OUT/summary.txt

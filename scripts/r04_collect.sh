@@ -16,7 +16,7 @@ bash scripts/profile_stream.sh r04s ssa23 ed25519like:1024 mixed > $OUT/profile_
 for p in ssa23 ed25519like mixed; do cp gpurun_out/prof_r04s/${p}_kernel_stats.csv $OUT/r04_stream_${p}_kernel_stats.csv; done
 bash scripts/profile_lanes.sh r04l ssa23 > $OUT/r04_stream_ssa23_lanes.txt 2>&1
 bash scripts/profile_lanes.sh r04m ed25519like:1024 > $OUT/r04_stream_ed25519like_lanes.txt 2>&1
-python bench.py > $OUT/r04_bench_b1024.json 2> $OUT/bench.err
+python bench.py --full > $OUT/r04_bench_b1024.json 2> $OUT/bench.err
 tail -c 300 $OUT/bench.err
 python - <<'PY'
 import json

@@ -22,7 +22,7 @@ bash scripts/profile_lanes.sh r05m ed25519like:1024 > $OUT/r05_stream_ed25519lik
 timeout 300 python scripts/probe_fixed_cost.py > $OUT/r05_fixed_cost_probe.json 2>&1
 timeout 2400 python tests/hostile_fuzz.py 10000 > $OUT/r05_hostile_fuzz.log 2>&1; echo "hostile fuzz rc=$?" >> $OUT/r05_hostile_fuzz.log
 timeout 1500 python tests/ext_fuzz.py 600 > $OUT/r05_fuzz.log 2>&1; echo "fuzz rc=$?" >> $OUT/r05_fuzz.log
-python bench.py > $OUT/r05_bench_b1024.json 2> $OUT/bench.err
+python bench.py --full > $OUT/r05_bench_b1024.json 2> $OUT/bench.err
 tail -c 300 $OUT/bench.err
 python - <<'PY'
 import json

@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/r05
 mkdir -p $OUT
 cd $REPO
-python bench.py > $OUT/r05_bench_b1024.json 2> $OUT/bench.err
+python bench.py --full > $OUT/r05_bench_b1024.json 2> $OUT/bench.err
 tail -c 300 $OUT/bench.err
 python - <<'PY'
 import json

@@ -14,7 +14,7 @@ cp gpurun_out/prof_r05f/latest_pmc.json $OUT/latest_pmc.json && cp $OUT/latest_p
 tail -n 3 $OUT/r05_flat_pmc_summary.txt
 timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/gpu_suite.log 2>&1; echo "gpu suite rc=$?" >> $OUT/gpu_suite.log
 tail -n 4 $OUT/gpu_suite.log
-timeout 900 python bench.py > $OUT/r05_bench_b1024.json 2> $OUT/bench.err
+timeout 900 python bench.py --full > $OUT/r05_bench_b1024.json 2> $OUT/bench.err
 tail -c 300 $OUT/bench.err
 python - <<'PY'
 import json

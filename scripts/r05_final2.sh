@@ -11,7 +11,7 @@ mkdir -p $OUT
 cd $REPO
 timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/r05b_gpu_suite.log 2>&1; echo "gpu suite rc=$?" >> $OUT/r05b_gpu_suite.log
 tail -n 3 $OUT/r05b_gpu_suite.log
-timeout 900 python bench.py > $OUT/r05b_bench_b1024.json 2> $OUT/bench.err
+timeout 900 python bench.py --full > $OUT/r05b_bench_b1024.json 2> $OUT/bench.err
 tail -c 300 $OUT/bench.err
 python - <<'PY'
 import json

@@ -22,7 +22,7 @@ tail -n 3 $OUT/${TAG}_gpu_suite.log
 # (the persistent-workgroup form of the dataflow experiment needs 16 hardware queues from the host: skipped in the suite above)
 GPU_MAX_HW_QUEUES=16 timeout 900 python -m pytest tests/test_gpu_dataflow.py -m gpu -q > $OUT/${TAG}_gpu_dataflow_hwq16.log 2>&1; echo "rc=$?" >> $OUT/${TAG}_gpu_dataflow_hwq16.log
 tail -n 2 $OUT/${TAG}_gpu_dataflow_hwq16.log
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench_b1024.json 2> $OUT/bench.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench_b1024.json 2> $OUT/bench.err
 tail -c 300 $OUT/bench.err
 python - "$OUT/${TAG}_bench_b1024.json" <<'PY'
 import json, sys

@@ -6,7 +6,7 @@ for i in 1 2; do
 done
 for i in 1 2; do
   t0=$SECONDS
-  timeout 600 python bench.py > /tmp/b$i.json 2> /tmp/b$i.err; rc=$?
+  timeout 600 python bench.py --full > /tmp/b$i.json 2> /tmp/b$i.err; rc=$?
   echo "bench $i rc=$rc wall $((SECONDS - t0)) s" >> $OUT
   python - /tmp/b$i.json >> $OUT 2>&1 <<'PY'
 import json, sys

@@ -15,6 +15,9 @@ Plan = _real.Plan
 EngineError = _real.EngineError
 COMM_ID_BYTES = 128
 
+if os.environ.get("GC_STUB_SLOW_RANK") == os.environ.get("RANK", "0"):  # (a rank still importing when the others move on)
+    time.sleep(2.0)
+
 
 class _Buf:
     def __init__(self, arr):
@@ -96,6 +99,19 @@ class Batch:
         Batch.step_counter += 1
         pat = ((np.arange(self.batch * nout) + 3 * rank + Batch.step_counter) & 1).astype(np.uint8)
         flat[off:off + self.batch * nout] = pat
+
+    def _labels(self, n, salt):  # (fixed bytes per call site: what bench.py --dump-outputs reads back)
+        a = np.random.default_rng(salt).integers(0, 1 << 63, (self.batch, n, 2), dtype=np.uint64)
+        return a.view(_real.LABEL).reshape(self.batch, n)
+
+    def read_outputs(self):
+        return self._labels(self.dc.circ.num_outputs, 1)
+
+    def read_r(self):
+        return self._labels(1, 2)[:, 0]
+
+    def read_slab(self):
+        return self._labels(self.dc.info.slab_rows, 3)
 
     def close(self):
         pass

@@ -76,10 +76,58 @@ def test_bench_missing_rank_ends_with_one_error_line(tmp_path):
 
 def test_bench_rank_that_dies_early_still_leaves_one_error_line(tmp_path):
     """rank 1 cannot open its device (what a 2-rank launch on a 1-GPU box does): it fails at once, the launcher sends SIGTERM
-    to rank 0 — which may be inside a C call —, and rank 0 still prints its ONE error line before it leaves"""
+    to rank 0 — which may be inside a C call, or still importing (GC_STUB_SLOW_RANK: before its watchdog exists) —, and
+    rank 0 still prints its ONE error line before it leaves"""
     t0 = time.time()
-    r = _launch(2, ["--init-timeout", "30"], {"GC_STUB_RANK_FAILS": "1"}, tmp_path, timeout=120)
+    r = _launch(2, ["--init-timeout", "30"], {"GC_STUB_RANK_FAILS": "1", "GC_STUB_SLOW_RANK": "0"}, tmp_path, timeout=120)
     assert time.time() - t0 < 60 and r.returncode != 0
     lines = _json_lines(r.stdout)
     assert len(lines) == 1 and lines[0].get("error") and lines[0]["n_gpus"] == 2, r.stdout[-2000:] + r.stderr[-2000:]
     assert "rank 1 failed at stage 'context'" in r.stderr
+
+
+def _single(args, timeout=240):
+    env = dict(os.environ, PYTHONPATH=ROOT, GC_BENCH_ENGINE="tests.stub_engine")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, capture_output=True, text=True,
+                       timeout=timeout)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = _json_lines(r.stdout)
+    assert len(lines) == 1, r.stdout[-2000:]
+    return lines[0]
+
+
+def test_bench_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """a plain run times exactly --steps steps and carries the headline alone (no per-pass figures, no side rows);
+    --dump-outputs writes the last step's arrays as float32 / float64 .npy files, the same bytes on a second run"""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        j = _single(["--gpus", "1", "--steps", "7", "--warmup", "2", "--batch", "64", "--dump-outputs", str(d)])
+        assert j["steps"] == 7 and j["warmup"] == 2 and j["full"] is False and j["config"]["outputs_ok"]
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in j, k
+        assert abs(j["value"] - 6400 * 64 * 7 / (j["ms_per_step"] * 7e-3)) < 1e-6 * j["value"]
+        for k in ("garble_ms", "roofline", "aes_core", "synthetic", "key16", "iknp", "host_api", "stream", "config3",
+                  "cpu_baseline", "side_rows_wall_s"):
+            assert k not in j, k
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1]))
+    assert {"decoded_outputs.npy", "output_labels.npy", "garbler_R.npy", "garbled_tables.npy", "instances.npy"} <= set(names)
+    assert sum(os.path.getsize(dirs[0] / n) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and a.shape == b.shape and (a == b).all(), n
+    dec = np.load(dirs[0] / "decoded_outputs.npy")
+    assert dec.shape == (64, 128) and set(np.unique(dec)) <= {0.0, 1.0}
+    # the stub's decode of the run's last step (tests/stub_engine.py): the step ahead of the capture, 100 pre-warm launches,
+    # then 2 + 7 steps
+    assert (dec.reshape(-1) == ((np.arange(64 * 128) + 1 + 100 + 9) & 1)).all()
+    assert np.load(dirs[0] / "output_labels.npy").shape == (64, 128, 4)
+    assert np.load(dirs[0] / "garbled_tables.npy").shape[0] == 16
+
+
+def test_bench_full_keeps_the_per_pass_figures(tmp_path):
+    j = _single(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "32", "--full", "--no-cpu-baseline", "--no-iknp",
+                 "--no-host-api", "--no-stream", "--no-config3", "--no-synthetic", "--no-extra-rows"])
+    assert j["full"] is True and j["garble_ms"] == 0.5 and j["roofline"]["kernel"] == "k_garble_flat"
+    assert "aes_core" in j and "side_rows_wall_s" in j and j["cpu_baseline"]["go_on_box"] is not None
