@@ -836,8 +836,9 @@ static int set_key(gc_batch *b, const uint8_t *key, size_t keylen) {
     return GC_OK;
 }
 
-// enqueue the level launches of one garble (eval == false) or eval pass
-static void enqueue_levels(gc_batch *b, bool eval, const uint4 *T, hipStream_t s) {
+// enqueue the level launches of one garble (eval == false) or eval pass; the first launch error (a geometry the launcher
+// refused, or what hipGetLastError() reports after the last launch)
+static hipError_t enqueue_levels(gc_batch *b, bool eval, const uint4 *T, hipStream_t s) {
     const Plan &p = b->circ->plan.p;
     LevelArgs a{};
     a.W = b->d_W;
@@ -851,9 +852,10 @@ static void enqueue_levels(gc_batch *b, bool eval, const uint4 *T, hipStream_t s
         a.count = st.count;
         a.nonfree = st.nonfree;
         a.out_slot0 = p.info.ninputs + st.first;
-        if (eval) launch_eval_level(a, b->g, s);
-        else launch_garble_level(a, b->g, s);
+        const hipError_t e = eval ? launch_eval_level(a, b->g, s) : launch_garble_level(a, b->g, s);
+        if (e != hipSuccess) return e;
     }
+    return hipGetLastError();
 }
 
 // does this batch run the flattened fused kernels?
@@ -1008,8 +1010,7 @@ static int run_levels(gc_batch *b, bool eval, const uint4 *T, const uint4 *rnd =
     }
     b->last_launches = (uint32_t)p.levels.size();
     if (!b->use_graph || p.levels.size() < 2 || live_contexts() > 1) {
-        enqueue_levels(b, eval, T, s);
-        GC_HIP(hipGetLastError());
+        GC_HIP(enqueue_levels(b, eval, T, s));
         return GC_OK;
     }
     // one captured graph per (pass, rounds, table pointer, schedule)
@@ -1026,18 +1027,20 @@ static int run_levels(gc_batch *b, bool eval, const uint4 *T, const uint4 *rnd =
         std::lock_guard<std::mutex> cap(capture_mu());
         e = hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed);
         if (e == hipSuccess) {
-            enqueue_levels(b, eval, T, s);
+            // a level whose launch was refused would be missing from the graph: such a capture is never kept
+            const hipError_t e_launch = enqueue_levels(b, eval, T, s);
             e = hipStreamEndCapture(s, &graph);
+            if (e == hipSuccess) e = e_launch;
         }
         if (e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     }
     if (graph) (void)hipGraphDestroy(graph);
     if (e != hipSuccess) {
-        // capture unsupported in this environment: fall back to direct launches (same kernels)
+        // capture unsupported in this environment, or a launch refused: direct launches of the same kernels (which report
+        // a refused launch)
         (void)hipGetLastError();
         b->use_graph = false;
-        enqueue_levels(b, eval, T, s);
-        GC_HIP(hipGetLastError());
+        GC_HIP(enqueue_levels(b, eval, T, s));
         return GC_OK;
     }
     b->graphs.push_back({eval, b->rounds, b->schedule, T, exec});

@@ -10,6 +10,7 @@
 #include "aes_device.h"
 #include "kernels.h"
 #include "level_gate.h"
+#include "split_grid.h"
 
 namespace gc {
 
@@ -128,19 +129,21 @@ __global__ __launch_bounds__(256) void k_garble_level_split(const GateDesc *__re
                                                             uint4 *__restrict__ W, const uint4 *__restrict__ Rv,
                                                             uint4 *__restrict__ T, const uint32_t *__restrict__ rk,
                                                             const uint32_t *__restrict__ g_te0, uint32_t chunks, uint32_t nb_hash,
-                                                            uint32_t gx_free) {
+                                                            uint32_t gx_free, uint32_t nblocks) {
     __shared__ uint32_t te[kTeWords];
     __shared__ uint4 xh[3][64];
-    if (blockIdx.x >= nb_hash) {  // the level's free gates: thread = (gate, instance)
-        const uint32_t b = blockIdx.x - nb_hash, bx = b % gx_free, by = b / gx_free;
-        const uint32_t gate = nonfree + bx * (256u >> lg) + (threadIdx.x >> lg);
-        const uint32_t inst = by * 256u + (threadIdx.x & ((1u << lg) - 1u));
+    const uint32_t bid = blockIdx.y * gridDim.x + blockIdx.x;  // list index (split_grid.h)
+    if (bid >= nblocks) return;
+    const SplitBlock sb = split_block(bid, chunks, nb_hash, gx_free);
+    if (!sb.hash) {  // the level's free gates: thread = (gate, instance)
+        const uint32_t gate = nonfree + sb.gate * (256u >> lg) + (threadIdx.x >> lg);
+        const uint32_t inst = sb.sub * 256u + (threadIdx.x & ((1u << lg) - 1u));
         if (gate >= count || inst >= batch) return;
         const GateDesc d = descs[gate];
         garble_one<NR>(d, inst, bstride, W, Rv[inst], T, W + (size_t)(out_slot0 + gate) * bstride + inst, rk, te);
         return;
     }
-    const uint32_t gate = blockIdx.x / chunks, chunk = blockIdx.x - gate * chunks;
+    const uint32_t gate = sb.gate, chunk = sb.sub;
     const uint32_t q = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
     const uint32_t inst = chunk * 64u + lane;
     const bool live = inst < batch;
@@ -206,19 +209,21 @@ __global__ __launch_bounds__(256) void k_eval_level_split(const GateDesc *__rest
                                                           uint32_t out_slot0, uint32_t batch, uint32_t bstride, uint32_t lg,
                                                           uint4 *__restrict__ W, const uint4 *__restrict__ T,
                                                           const uint32_t *__restrict__ rk, const uint32_t *__restrict__ g_te0,
-                                                          uint32_t chunks, uint32_t nb_hash, uint32_t gx_free) {
+                                                          uint32_t chunks, uint32_t nb_hash, uint32_t gx_free, uint32_t nblocks) {
     __shared__ uint32_t te[kTeWords];
     __shared__ uint4 xh[2][64];
-    if (blockIdx.x >= nb_hash) {
-        const uint32_t b = blockIdx.x - nb_hash, bx = b % gx_free, by = b / gx_free;
-        const uint32_t gate = nonfree + bx * (256u >> lg) + (threadIdx.x >> lg);
-        const uint32_t inst = by * 256u + (threadIdx.x & ((1u << lg) - 1u));
+    const uint32_t bid = blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    const SplitBlock sb = split_block(bid, chunks, nb_hash, gx_free);
+    if (!sb.hash) {
+        const uint32_t gate = nonfree + sb.gate * (256u >> lg) + (threadIdx.x >> lg);
+        const uint32_t inst = sb.sub * 256u + (threadIdx.x & ((1u << lg) - 1u));
         if (gate >= count || inst >= batch) return;
         const GateDesc d = descs[gate];
         eval_one<NR>(d, inst, bstride, W, T, W + (size_t)(out_slot0 + gate) * bstride + inst, rk, te);
         return;
     }
-    const uint32_t gate = blockIdx.x / chunks, chunk = blockIdx.x - gate * chunks;
+    const uint32_t gate = sb.gate, chunk = sb.sub;
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), sub = w >> 1, q = w & 1u, lane = threadIdx.x & 63u;
     const uint32_t inst = chunk * 128u + sub * 64u + lane;
     const bool live = inst < batch;
@@ -292,39 +297,41 @@ static bool level_whole_gates() {
         }                                                                                                  \
     } while (0)
 
+// the list of workgroups and its grid come from split_grid (split_grid.h): 64-bit block count, spread over grid.y past 2^24 - 1
 #define GC_DISPATCH_SPLIT(KERNEL, PER, ...)                                                                \
     do {                                                                                                   \
-        const uint32_t chunks = (g.batch + (PER) - 1) / (PER), nb_hash = a.nonfree * chunks;               \
-        const uint32_t nfree = a.count - a.nonfree, per_blk = 256u >> g.lg;                                \
-        const uint32_t gx_free = nfree ? (nfree + per_blk - 1) / per_blk : 1u;                             \
-        const dim3 grid(nb_hash + (nfree ? gx_free * g.yblocks : 0u)), block(256);                         \
+        const SplitGrid sg = split_grid(a.count, a.nonfree, g.batch, g.lg, (PER));                         \
+        if (!sg.ok) return hipErrorInvalidConfiguration;                                                   \
+        const dim3 grid(sg.gx, sg.gy), block(256);                                                         \
         switch (a.rounds) {                                                                                \
-        case 10: hipLaunchKernelGGL((KERNEL<10>), grid, block, 0, s, __VA_ARGS__, chunks, nb_hash, gx_free); break; \
-        case 12: hipLaunchKernelGGL((KERNEL<12>), grid, block, 0, s, __VA_ARGS__, chunks, nb_hash, gx_free); break; \
-        default: hipLaunchKernelGGL((KERNEL<14>), grid, block, 0, s, __VA_ARGS__, chunks, nb_hash, gx_free); break; \
+        case 10: hipLaunchKernelGGL((KERNEL<10>), grid, block, 0, s, __VA_ARGS__, sg.chunks, sg.nb_hash, sg.gx_free, sg.nblocks); break; \
+        case 12: hipLaunchKernelGGL((KERNEL<12>), grid, block, 0, s, __VA_ARGS__, sg.chunks, sg.nb_hash, sg.gx_free, sg.nblocks); break; \
+        default: hipLaunchKernelGGL((KERNEL<14>), grid, block, 0, s, __VA_ARGS__, sg.chunks, sg.nb_hash, sg.gx_free, sg.nblocks); break; \
         }                                                                                                  \
     } while (0)
 
-void launch_garble_level(const LevelArgs &a, const BatchGeom &g, hipStream_t s) {
-    if (a.count == 0) return;
+hipError_t launch_garble_level(const LevelArgs &a, const BatchGeom &g, hipStream_t s) {
+    if (a.count == 0) return hipSuccess;
     if (a.nonfree && !level_whole_gates()) {
         GC_DISPATCH_SPLIT(k_garble_level_split, 64u, a.descs, a.count, a.nonfree, a.out_slot0, g.batch, g.bstride, g.lg, a.W, a.R,
                           a.T, a.rk, a.te0);
-        return;
+        return hipSuccess;
     }
     GC_DISPATCH_LEVEL(k_garble_level, a.descs, a.count, a.nonfree, a.out_slot0, g.batch, g.bstride, g.lg, a.W, a.R,
                       a.T, a.rk, a.te0);
+    return hipSuccess;
 }
 
-void launch_eval_level(const LevelArgs &a, const BatchGeom &g, hipStream_t s) {
-    if (a.count == 0) return;
+hipError_t launch_eval_level(const LevelArgs &a, const BatchGeom &g, hipStream_t s) {
+    if (a.count == 0) return hipSuccess;
     if (a.nonfree && !level_whole_gates()) {
         GC_DISPATCH_SPLIT(k_eval_level_split, 128u, a.descs, a.count, a.nonfree, a.out_slot0, g.batch, g.bstride, g.lg, a.W,
                           (const uint4 *)a.T, a.rk, a.te0);
-        return;
+        return hipSuccess;
     }
     GC_DISPATCH_LEVEL(k_eval_level, a.descs, a.count, a.nonfree, a.out_slot0, g.batch, g.bstride, g.lg, a.W,
                       (const uint4 *)a.T, a.rk, a.te0);
+    return hipSuccess;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -57,8 +57,9 @@ struct LevelArgs {
     int rounds;
 };
 
-void launch_garble_level(const LevelArgs &a, const BatchGeom &g, hipStream_t s);
-void launch_eval_level(const LevelArgs &a, const BatchGeom &g, hipStream_t s);
+// hipErrorInvalidConfiguration (nothing launched) when a split level's workgroups fit no legal grid (split_grid.h)
+hipError_t launch_garble_level(const LevelArgs &a, const BatchGeom &g, hipStream_t s);
+hipError_t launch_eval_level(const LevelArgs &a, const BatchGeom &g, hipStream_t s);
 
 // Fused schedule: ONE launch walks all levels; a workgroup owns a tile of instances and
 // synchronises its own waves between levels (no inter-workgroup dependency at all).

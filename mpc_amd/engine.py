@@ -582,7 +582,11 @@ class Batch:
         self.h = lib().gc_batch_create(dcirc.h, batch, C.byref(st))
         if not self.h:
             raise EngineError(st.value, "gc_batch_create")
-        self.stride = lib().gc_batch_stride(self.h)
+
+    @property
+    def stride(self):
+        """instances per row of the device arrays (gc_batch_stride); set_schedule can change it"""
+        return int(lib().gc_batch_stride(self.h))
 
     @property
     def tile_instances(self):
