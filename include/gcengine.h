@@ -624,6 +624,72 @@ int gc_comm_allgather_all(gc_comm *const *comms, int n, const void *const *d_sen
 int gc_comm_allreduce_max(gc_comm *, double *value);
 int gc_comm_barrier(gc_comm *);
 
+
+/* ------------------------------------------------------------------------------------------
+ * GMW party engine (gmw/network.go, gmw/triples.go): the online phase of one party of the n-party GMW protocol over a
+ * BATCH of independent evaluations of one circuit by the same parties, plus the local folds of the Beaver-triple
+ * generation.  The p2p transport and the XOR of the opened values across peers (broadcastXORs, network.go:790-823) stay
+ * with the caller; with batch = 1 every buffer below is byte for byte the Go bit vector, so a Go peer cannot tell.
+ * All buffers are word-major u64: word index outside, instance inside ([words][batch]).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct gc_gmw gc_gmw;
+typedef struct gc_gmw_info {
+    uint32_t ngates, nwires, ninputs, noutputs;
+    uint32_t nlevels;         /* Stats[NumLevels] + 1 of AssignLevels(TargetGMW) (circuit.go:206-254) */
+    uint32_t n_and_levels;    /* levels with at least one AND = exchange rounds of a pass */
+    uint32_t triple_words;    /* TW = sum over levels of ceil(n_AND(level) / 64): whole words per level (triples.go:60-90) */
+    uint32_t max_level_words; /* max over levels of ceil(n_AND(level) / 64) */
+    uint32_t n_xor, n_xnor, n_and, n_inv;
+    uint32_t max_free_depth;  /* longest chain of free gates between two exchanges (workgroup barriers of one step) */
+} gc_gmw_info;
+
+/* Host-only plan introspection (no GPU): arrays sized by the caller, any of them may be NULL.
+ *  level_of_gate[ngates]      gate.Level of AssignLevels(TargetGMW)
+ *  and_index_of_gate[ngates]  AND gate: its bit index k in its level's vectors (network.go:680-700); others 0xffffffff
+ *  words_of_level[nlevels]    ceil(n_AND(level) / 64)
+ * Checks those of gc_plan_create; OR is GC_E_GATE ("gate OR not supported", network.go:609). */
+int gc_gmw_plan_describe(const gc_gate *gates, uint32_t ngates, uint32_t nwires, uint32_t ninputs, uint32_t noutputs,
+                         gc_gmw_info *info, uint32_t *level_of_gate, uint32_t *and_index_of_gate, uint32_t *words_of_level);
+
+/* One party (0 <= party < nparties, nparties >= 2) of `batch` instances; the handle keeps its own device state, so
+ * several handles may share a ctx.  A pass: gc_gmw_set_inputs, gc_gmw_set_triples, then gc_gmw_step until *words == 0,
+ * then gc_gmw_get_outputs.  Replaces the body of (*Network).run's level loop (network.go:563-618) and andBatchFlush
+ * (network.go:660-757). */
+gc_gmw *gc_gmw_create(gc_ctx *, const gc_gate *gates, uint32_t ngates, uint32_t nwires, uint32_t ninputs,
+                      uint32_t noutputs, uint32_t nparties, uint32_t party, uint32_t batch, int *status);
+void gc_gmw_free(gc_gmw *);
+int gc_gmw_get_info(const gc_gmw *, gc_gmw_info *out);
+/* inputs [ceil(ninputs/64)][batch]: this party's share of wires 0..ninputs-1 (the big.Int words of nw.wires after
+ * setWires, network.go:560-561).  Starts a new pass; the triples must be set again after it. */
+int gc_gmw_set_inputs(gc_gmw *, const uint64_t *inputs);
+int gc_gmw_set_inputs_dev(gc_gmw *, const void *d_inputs);
+/* a, b, c each [triple_words][batch]: level l uses words [W_l, W_l + w_l) (TriplePool.Get, triples.go:130-142).
+ * _dev: read in place during the pass (keep them alive until the last step); host form: copied. */
+int gc_gmw_set_triples(gc_gmw *, const uint64_t *a, const uint64_t *b, const uint64_t *c);
+int gc_gmw_set_triples_dev(gc_gmw *, const void *d_a, const void *d_b, const void *d_c);
+/* One exchange round.  (1) if an AND level is pending, close it: d, e = this party's message XOR the npeers received
+ * ones (peer_msgs [npeers][2][w][batch], the layout of msg_out), z = c ^ d&b ^ e&a (^ d&e on party 0)
+ * (network.go:735-756); (2) evaluate the free gates up to the next level that has ANDs, or to the end; (3) write that
+ * level's d then e to msg_out [2][*words][batch] (SendBitvec2, peer.go:131-163; padding bits past the level's ANDs carry
+ * the triples' a / b bits, network.go:695-721), *level = the level.  *words == 0: the pass is complete (*level = nlevels).
+ * npeers must be nparties - 1; peer_msgs may be NULL when nothing is pending.  _dev: device pointers, asynchronous on
+ * the ctx stream; host form: synchronous. */
+int gc_gmw_step(gc_gmw *, const uint64_t *peer_msgs, uint32_t npeers, uint64_t *msg_out, uint32_t *level, size_t *words);
+int gc_gmw_step_dev(gc_gmw *, const void *d_peer_msgs, uint32_t npeers, void *d_msg_out, uint32_t *level, size_t *words);
+/* [ceil(noutputs/64)][batch]: this party's share of the last noutputs wires (nw.output, network.go:622-624); only after
+ * the pass is complete */
+int gc_gmw_get_outputs(gc_gmw *, uint64_t *out);
+int gc_gmw_get_outputs_dev(gc_gmw *, void *d_out);
+uint32_t gc_gmw_last_launches(const gc_gmw *); /* kernel launches of the last pass, input load included */
+
+/* Local arithmetic of tripleBatch (triples.go:287-466) on device words (u64 [words]), asynchronous on the ctx stream;
+ * the bit-COT outputs come from gc_iknp_send_bits_dev / gc_iknp_receive_bits_dev. */
+int gc_gmw_triples_local_dev(gc_ctx *, const void *d_a, const void *d_b, void *d_c, size_t words);        /* c = a & b */
+int gc_gmw_triples_sender_u_dev(gc_ctx *, uint32_t delta_bit, const void *d_a, void *d_u, size_t words); /* u = a ^ (D0 ? ~0 : 0) */
+int gc_gmw_triples_sender_fold_dev(gc_ctx *, const void *d_s, const void *d_u, const void *d_v, void *d_c,
+                                   size_t words);                                                        /* c ^= s ^ (u & v) */
+int gc_gmw_triples_receiver_fold_dev(gc_ctx *, const void *d_r, void *d_c, size_t words);                /* c ^= r */
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,12 @@ class PlanInfo(C.Structure):
         "n_flat_outs", "n_flat_terms", "n_flat_steps", "n_flat_units")]
 
 
+class GmwInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in (
+        "ngates", "nwires", "ninputs", "noutputs", "nlevels", "n_and_levels", "triple_words", "max_level_words", "n_xor",
+        "n_xnor", "n_and", "n_inv", "max_free_depth")]
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -206,6 +212,23 @@ def lib():
         "gc_comm_allgather_all": (i32, [vp, i32, vp, vp, sz]),
         "gc_comm_allreduce_max": (i32, [vp, C.POINTER(C.c_double)]),
         "gc_comm_barrier": (i32, [vp]),
+        "gc_gmw_plan_describe": (i32, [vp, u32, u32, u32, u32, C.POINTER(GmwInfo), vp, vp, vp]),
+        "gc_gmw_create": (vp, [vp, vp, u32, u32, u32, u32, u32, u32, u32, ip]),
+        "gc_gmw_free": (None, [vp]),
+        "gc_gmw_get_info": (i32, [vp, C.POINTER(GmwInfo)]),
+        "gc_gmw_set_inputs": (i32, [vp, vp]),
+        "gc_gmw_set_inputs_dev": (i32, [vp, vp]),
+        "gc_gmw_set_triples": (i32, [vp, vp, vp, vp]),
+        "gc_gmw_set_triples_dev": (i32, [vp, vp, vp, vp]),
+        "gc_gmw_step": (i32, [vp, vp, u32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]),
+        "gc_gmw_step_dev": (i32, [vp, vp, u32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]),
+        "gc_gmw_get_outputs": (i32, [vp, vp]),
+        "gc_gmw_get_outputs_dev": (i32, [vp, vp]),
+        "gc_gmw_last_launches": (u32, [vp]),
+        "gc_gmw_triples_local_dev": (i32, [vp, vp, vp, vp, sz]),
+        "gc_gmw_triples_sender_u_dev": (i32, [vp, u32, vp, vp, sz]),
+        "gc_gmw_triples_sender_fold_dev": (i32, [vp, vp, vp, vp, vp, sz]),
+        "gc_gmw_triples_receiver_fold_dev": (i32, [vp, vp, vp, sz]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -1167,3 +1190,115 @@ def kos_sender_check(ctx, seed2, result, choice_vec, delta, x, t0, t1):
     _check(lib().gc_kos_sender_check(ctx.h, _p(_lab1(seed2)), _p(r) if len(r) else None, len(r), _p(cv), _p(_lab1(delta)),
                                      _p(_lab1(x)), _p(_lab1(t0)), _p(_lab1(t1)), C.byref(ok)), "gc_kos_sender_check")
     return bool(ok.value)
+
+
+# ---- GMW party engine (gmw/network.go, gmw/triples.go) ---------------------------------------
+
+
+def gmw_plan_describe(gates, nwires, ninputs, noutputs):
+    """host-only GMW plan (gc_gmw_plan_describe): (GmwInfo, level_of_gate, and_index_of_gate, words_of_level)"""
+    g = np.ascontiguousarray(gates, dtype=GATE)
+    info = GmwInfo()
+    _check(lib().gc_gmw_plan_describe(_p(g) if len(g) else None, len(g), nwires, ninputs, noutputs, C.byref(info), None, None,
+                                      None), "gc_gmw_plan_describe")
+    lv = np.zeros(max(len(g), 1), np.uint32)
+    ai = np.zeros(max(len(g), 1), np.uint32)
+    wl = np.zeros(max(info.nlevels, 1), np.uint32)
+    _check(lib().gc_gmw_plan_describe(_p(g) if len(g) else None, len(g), nwires, ninputs, noutputs, None, _p(lv), _p(ai), _p(wl)),
+           "gc_gmw_plan_describe")
+    return info, lv[: len(g)], ai[: len(g)], wl[: info.nlevels]
+
+
+class Gmw:
+    """One GMW party over `batch` instances (gc_gmw_*).  Buffers are u64 [words][batch] (word-major, instance inside);
+    host forms take / return numpy arrays, *_dev forms take device pointers and run asynchronously on the ctx stream."""
+
+    def __init__(self, ctx, circuit, nparties, party, batch):
+        self.ctx, self.batch, self.nparties, self.party = ctx, batch, nparties, party
+        g = np.ascontiguousarray(circuit.Gates, dtype=GATE)
+        st = C.c_int(0)
+        self.h = lib().gc_gmw_create(ctx.h, _p(g) if len(g) else None, len(g), circuit.NumWires, circuit.num_inputs,
+                                     circuit.num_outputs, nparties, party, batch, C.byref(st))
+        if not self.h:
+            raise EngineError(st.value, "gc_gmw_create")
+        self.info = GmwInfo()
+        _check(lib().gc_gmw_get_info(self.h, C.byref(self.info)), "gc_gmw_get_info")
+        self.in_words = (self.info.ninputs + 63) // 64
+        self.out_words = (self.info.noutputs + 63) // 64
+
+    def set_inputs(self, inputs):
+        a = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(self.in_words, self.batch)
+        _check(lib().gc_gmw_set_inputs(self.h, _p(a) if a.size else None), "gc_gmw_set_inputs")
+
+    def set_inputs_dev(self, d_inputs):
+        _check(lib().gc_gmw_set_inputs_dev(self.h, _dp(d_inputs)), "gc_gmw_set_inputs_dev")
+
+    def set_triples(self, a, b, c):
+        arrs = [np.ascontiguousarray(x, dtype=np.uint64).reshape(self.info.triple_words, self.batch) for x in (a, b, c)]
+        _check(lib().gc_gmw_set_triples(self.h, *[_p(x) if x.size else None for x in arrs]), "gc_gmw_set_triples")
+
+    def set_triples_dev(self, d_a, d_b, d_c):
+        _check(lib().gc_gmw_set_triples_dev(self.h, _dp(d_a), _dp(d_b), _dp(d_c)), "gc_gmw_set_triples_dev")
+
+    def step(self, peer_msgs=None):
+        """one exchange round (host form): peer_msgs [npeers][2][w][batch] of the pending level (None on the first step).
+        Returns (level, msg [2][w][batch]); w == 0 (an empty msg) when the pass is complete."""
+        npeers = self.nparties - 1
+        pm = None if peer_msgs is None else np.ascontiguousarray(peer_msgs, dtype=np.uint64)
+        out = np.zeros(2 * max(self.info.max_level_words, 1) * self.batch, np.uint64)
+        lv, w = C.c_uint32(0), C.c_size_t(0)
+        _check(lib().gc_gmw_step(self.h, _p(pm) if pm is not None and pm.size else None, npeers, _p(out), C.byref(lv),
+                                 C.byref(w)), "gc_gmw_step")
+        return lv.value, out[: 2 * w.value * self.batch].reshape(2, w.value, self.batch)
+
+    def step_dev(self, d_peer_msgs, d_msg_out, npeers=None):
+        """device form: returns (level, words)"""
+        lv, w = C.c_uint32(0), C.c_size_t(0)
+        _check(lib().gc_gmw_step_dev(self.h, None if d_peer_msgs is None else _dp(d_peer_msgs),
+                                     self.nparties - 1 if npeers is None else npeers,
+                                     None if d_msg_out is None else _dp(d_msg_out), C.byref(lv), C.byref(w)), "gc_gmw_step_dev")
+        return lv.value, w.value
+
+    def get_outputs(self):
+        out = np.zeros(max(self.out_words * self.batch, 1), np.uint64)
+        _check(lib().gc_gmw_get_outputs(self.h, _p(out)), "gc_gmw_get_outputs")
+        return out[: self.out_words * self.batch].reshape(self.out_words, self.batch)
+
+    def get_outputs_dev(self, d_out):
+        _check(lib().gc_gmw_get_outputs_dev(self.h, _dp(d_out)), "gc_gmw_get_outputs_dev")
+
+    @property
+    def last_launches(self):
+        return int(lib().gc_gmw_last_launches(self.h))
+
+    def close(self):
+        if self.h:
+            lib().gc_gmw_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def gmw_triples_local_dev(ctx, d_a, d_b, d_c, words):
+    """c = a & b (triples.go:312-315)"""
+    _check(lib().gc_gmw_triples_local_dev(ctx.h, _dp(d_a), _dp(d_b), _dp(d_c), words), "gc_gmw_triples_local_dev")
+
+
+def gmw_triples_sender_u_dev(ctx, delta_bit, d_a, d_u, words):
+    """u = a ^ (Delta.Bit(0) ? ~0 : 0) (triples.go:340-349)"""
+    _check(lib().gc_gmw_triples_sender_u_dev(ctx.h, int(delta_bit) & 1, _dp(d_a), _dp(d_u), words), "gc_gmw_triples_sender_u_dev")
+
+
+def gmw_triples_sender_fold_dev(ctx, d_s, d_u, d_v, d_c, words):
+    """c ^= s ^ (u & v) (triples.go:362-364)"""
+    _check(lib().gc_gmw_triples_sender_fold_dev(ctx.h, _dp(d_s), _dp(d_u), _dp(d_v), _dp(d_c), words),
+           "gc_gmw_triples_sender_fold_dev")
+
+
+def gmw_triples_receiver_fold_dev(ctx, d_r, d_c, words):
+    """c ^= r (triples.go:387-389)"""
+    _check(lib().gc_gmw_triples_receiver_fold_dev(ctx.h, _dp(d_r), _dp(d_c), words), "gc_gmw_triples_receiver_fold_dev")
