@@ -690,6 +690,23 @@ int gc_gmw_triples_sender_fold_dev(gc_ctx *, const void *d_s, const void *d_u, c
                                    size_t words);                                                        /* c ^= s ^ (u & v) */
 int gc_gmw_triples_receiver_fold_dev(gc_ctx *, const void *d_r, void *d_c, size_t words);                /* c ^= r */
 
+
+/* ------------------------------------------------------------------------------------------
+ * VOLE over packed IKNP (vole/vole.go, vole/prg.go).  p: the modulus, 32 bytes big-endian, odd, 3 <= p < 2^256
+ * (else GC_E_ARG).  Every value is 32 bytes big-endian, element i at [32i, 32i+32): the reference's messages as they are.
+ * Sender (Sender.Mul, vole.go:58-97): r_i = BE256(AES-128_{GetData(labels[i])}-CTR(zero IV, 32 zero bytes)) mod p,
+ * u_msg_i = (r_i + x_i * (BE256(y_msg_i) mod p)) mod p; labels = the sender's IKNP labels (gc_iknp_send_dev).
+ * Receiver (Receiver.Mul, vole.go:182-187): u_i = BE256(u_msg_i) mod p.  x, y and u_msg may be any value below 2^256.
+ * p is a host pointer in every form.  Host forms: synchronous, staged through device buffers.  _dev forms: device
+ * pointers, asynchronous on the ctx stream; d_u_out may be d_u_msg.  m = 0: GC_OK, nothing written.
+ * ------------------------------------------------------------------------------------------ */
+int gc_vole_sender_mul(gc_ctx *, const uint8_t *p, const gc_label *labels, const uint8_t *x, const uint8_t *y_msg,
+                       size_t m, uint8_t *r_out, uint8_t *u_msg_out);
+int gc_vole_sender_mul_dev(gc_ctx *, const uint8_t *p, const void *d_labels, const void *d_x, const void *d_y_msg,
+                           size_t m, void *d_r_out, void *d_u_msg_out);
+int gc_vole_receiver_reduce(gc_ctx *, const uint8_t *p, const uint8_t *u_msg, size_t m, uint8_t *u_out);
+int gc_vole_receiver_reduce_dev(gc_ctx *, const uint8_t *p, const void *d_u_msg, size_t m, void *d_u_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "plan.h"
+#include "vole_mod.h"
 
 namespace gc {
 
@@ -311,5 +312,12 @@ void launch_cot_send(uint4 seed, uint4 delta, const uint4 *data, const uint4 *wi
                      const uint32_t *te0, hipStream_t s);
 void launch_cot_recv(uint4 seed, const uint8_t *flags, const uint4 *sent, uint4 *result, size_t n,
                      const uint32_t *te0, hipStream_t s);
+
+// ---- VOLE kernels (vole_kernels.hip) ---------------------------------------------------------
+// every value 32 bytes big-endian (2 uint4 per element); labels: gc_label [m].  sender: r = BE256(AES-CTR_label(0^32))
+// mod p, u = (r + x * y) mod p; receiver: u_out = u_msg mod p (u_out may be u_msg)
+void launch_vole_sender(const VoleMod &mod, const uint4 *labels, const uint4 *x, const uint4 *y_msg, size_t m, uint4 *r_out,
+                        uint4 *u_out, const uint32_t *te0, hipStream_t s);
+void launch_vole_receiver(const VoleMod &mod, const uint4 *u_msg, size_t m, uint4 *u_out, hipStream_t s);
 
 }  // namespace gc

@@ -229,6 +229,10 @@ def lib():
         "gc_gmw_triples_sender_u_dev": (i32, [vp, u32, vp, vp, sz]),
         "gc_gmw_triples_sender_fold_dev": (i32, [vp, vp, vp, vp, vp, sz]),
         "gc_gmw_triples_receiver_fold_dev": (i32, [vp, vp, vp, sz]),
+        "gc_vole_sender_mul": (i32, [vp, vp, vp, vp, vp, sz, vp, vp]),
+        "gc_vole_sender_mul_dev": (i32, [vp, vp, vp, vp, vp, sz, vp, vp]),
+        "gc_vole_receiver_reduce": (i32, [vp, vp, vp, sz, vp]),
+        "gc_vole_receiver_reduce_dev": (i32, [vp, vp, vp, sz, vp]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -1302,3 +1306,60 @@ def gmw_triples_sender_fold_dev(ctx, d_s, d_u, d_v, d_c, words):
 def gmw_triples_receiver_fold_dev(ctx, d_r, d_c, words):
     """c ^= r (triples.go:387-389)"""
     _check(lib().gc_gmw_triples_receiver_fold_dev(ctx.h, _dp(d_r), _dp(d_c), words), "gc_gmw_triples_receiver_fold_dev")
+
+
+# ---- VOLE over packed IKNP (vole/vole.go, vole/prg.go) ----------------------------------------
+
+
+def vole_modulus(p):
+    """the modulus as the ABI takes it: 32 bytes big-endian, from an int or from 32 bytes.  A p that does not fit 32 bytes
+    is refused here (GC_E_ARG), as the library refuses an even p or p < 3."""
+    if isinstance(p, (bytes, bytearray, memoryview, np.ndarray)):
+        b = bytes(p)
+        if len(b) != 32:
+            raise EngineError(GC_E_ARG, "vole: the modulus takes 32 bytes, got %d" % len(b))
+    else:
+        p = int(p)
+        if p < 0 or p >= 1 << 256:
+            raise EngineError(GC_E_ARG, "vole: the modulus does not fit 32 bytes")
+        b = p.to_bytes(32, "big")
+    return np.frombuffer(b, np.uint8).copy()
+
+
+def _v32(a):
+    """values as the ABI takes them: uint8 [m, 32], element i = 32 bytes big-endian"""
+    return np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, 32)
+
+
+def vole_sender_mul(ctx, p, labels, x, y_msg):
+    """gc_vole_sender_mul: (*Sender).Mul's per-label work (vole/vole.go:58-97) -> (r, u_msg), uint8 [m, 32] each"""
+    lab = np.ascontiguousarray(labels, dtype=LABEL)
+    xs, ys = _v32(x), _v32(y_msg)
+    m = len(lab)
+    assert len(xs) == m and len(ys) == m
+    r, u = np.zeros((max(m, 1), 32), np.uint8), np.zeros((max(m, 1), 32), np.uint8)
+    _check(lib().gc_vole_sender_mul(ctx.h, _p(vole_modulus(p)), _p(lab) if m else None, _p(xs) if m else None,
+                                    _p(ys) if m else None, m, _p(r), _p(u)), "gc_vole_sender_mul")
+    return r[:m], u[:m]
+
+
+def vole_sender_mul_dev(ctx, p, d_labels, d_x, d_y_msg, m, d_r_out, d_u_msg_out):
+    """device pointers; asynchronous on the ctx stream"""
+    _check(lib().gc_vole_sender_mul_dev(ctx.h, _p(vole_modulus(p)), _dp(d_labels), _dp(d_x), _dp(d_y_msg), m, _dp(d_r_out),
+                                        _dp(d_u_msg_out)), "gc_vole_sender_mul_dev")
+
+
+def vole_receiver_reduce(ctx, p, u_msg):
+    """gc_vole_receiver_reduce: (*Receiver).Mul's reduction (vole/vole.go:182-187) -> us, uint8 [m, 32]"""
+    u = _v32(u_msg)
+    m = len(u)
+    out = np.zeros((max(m, 1), 32), np.uint8)
+    _check(lib().gc_vole_receiver_reduce(ctx.h, _p(vole_modulus(p)), _p(u) if m else None, m, _p(out)),
+           "gc_vole_receiver_reduce")
+    return out[:m]
+
+
+def vole_receiver_reduce_dev(ctx, p, d_u_msg, m, d_u_out):
+    """device pointers; asynchronous on the ctx stream; d_u_out may be d_u_msg"""
+    _check(lib().gc_vole_receiver_reduce_dev(ctx.h, _p(vole_modulus(p)), _dp(d_u_msg), m, _dp(d_u_out)),
+           "gc_vole_receiver_reduce_dev")
