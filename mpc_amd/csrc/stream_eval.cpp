@@ -8,67 +8,47 @@ using namespace gcs;
 
 namespace {
 
-int eval_launch_oldest(gc_stream_eval *e) {
-    if (e->win.open.empty()) return GC_OK;
-    const uint32_t seq = e->win.first_seq, slot = e->win.pop();
-    Slot &g = *e->slots[slot];
-    e->n_groups++;
-    e->n_group_blocks += g.jobs.size();
-    e->prof.lap(StageProf::kOther);
-    const int rc = launch_group(e->ctx, g, true, e->store, e->d_rk, nullptr, e->rounds, nullptr, e->deep, &e->fuse);
-    e->prof.lap(StageProf::kLaunch);
-    if (!g.chunk_refs.empty()) evdev_launched(e, g, slot);
-    e->win.note(seq, slot, g.launch_no);
-    if (rc == GC_OK) e->ctxq.pushed(slot, g.launch_no);
-    return rc;
-}
-int eval_close_group(gc_stream_eval *e) {
-    int rc = GC_OK;
-    while (!e->win.open.empty()) {
-        const int r = eval_launch_oldest(e);
-        if (rc == GC_OK) rc = r;
-    }
-    return rc;
-}
-
 // a slot for a new group of blocks: nothing comes back from an evaluator group, so a launched group's slot is free as
 // soon as its kernels have run; at most eight groups of the ctx stream in flight, then the oldest is waited for (deep
 // blocks on their lanes are bounded by kDeepInFlight and not counted: waiting for a 2 ms multiplier would idle the ctx stream)
-Slot *eval_slot(gc_stream_eval *e, uint32_t *index, bool big = false) {
+Slot *eval_slot(StreamCore &c, uint32_t *index, bool big) {
     auto done_with = [&](Slot &sl) {
         if (sl.deep_id) {
-            if (sl.error != GC_OK) (void)hipStreamSynchronize(e->deep.lanes[(size_t)sl.lane]);
-            e->deep.retire(sl.lane, sl.deep_id);
+            if (sl.error != GC_OK) (void)hipStreamSynchronize(c.deep.lanes[(size_t)sl.lane]);
+            c.deep.retire(sl.lane, sl.deep_id);
         }
         sl.reset();
     };
     uint32_t on_ctx = 0;
     bool any_free = false;
-    for (auto &sl : e->slots) any_free = any_free || (sl->kind == Slot::kFree && (sl->arena_cap >= ((size_t)2 << 20)) == big);
+    for (auto &sl : c.slots) any_free = any_free || (sl->kind == Slot::kFree && (sl->arena_cap >= ((size_t)2 << 20)) == big);
     if (!any_free) {  // (an event query is a microsecond or two: only when a slot is wanted)
-        for (uint32_t i = 0; i < e->slots.size(); i++) {
-            Slot &sl = *e->slots[i];
+        for (uint32_t i = 0; i < c.slots.size(); i++) {
+            Slot &sl = *c.slots[i];
             if (sl.kind == Slot::kGroup && sl.launched && (sl.error != GC_OK || hipEventQuery(sl.done) == hipSuccess)) done_with(sl);
             any_free = any_free || sl.kind == Slot::kFree;
         }
         (void)hipGetLastError();  // hipErrorNotReady of the queries
     }
-    for (auto &sl : e->slots)
+    for (auto &sl : c.slots)
         if (sl->kind == Slot::kGroup && sl->launched && !sl->deep_id) on_ctx++;
     if (on_ctx >= 8 && !any_free) {
         // the OLDEST launched group (the first one in slot order may be the newest: waiting for that one drains
         // everything queued, and the GPU then idles until the next group is ready — 136 us between the groups of the mixed
         // program)
         Slot *oldest = nullptr;
-        for (auto &sl : e->slots)
+        for (auto &sl : c.slots)
             if (sl->kind == Slot::kGroup && sl->launched && !sl->deep_id && (!oldest || sl->launch_no < oldest->launch_no)) oldest = sl.get();
         if (oldest) {
             (void)hipEventSynchronize(oldest->done);
             done_with(*oldest);
         }
     }
-    return slot_new(e->ctx, e->slots, index, big);
+    return slot_new(c.ctx, c.slots, index, big);
 }
+
+// (the core's hook: the chunks of the peer's stream that the jobs of a launched group gather their rows from)
+void eval_chunks_launched(StreamCore &c, Slot &g, uint32_t slot) { evdev_launched(static_cast<gc_stream_eval *>(&c), g, slot); }
 
 }  // namespace
 
@@ -83,6 +63,8 @@ gc_stream_eval *gc_stream_eval_create(gc_ctx *ctx, const uint8_t *key, size_t ke
     else if (!(e = new (std::nothrow) gc_stream_eval)) rc = GC_E_NOMEM;
     if (e) {
         e->ctx = ctx;
+        e->eval = true;
+        e->chunks_launched = eval_chunks_launched;
         e->key.assign(key, key + keylen);
         e->rounds = k.rounds;
         e->cache_budget = cache_budget_from_env();
@@ -137,7 +119,7 @@ void gc_stream_eval_free(gc_stream_eval *e) {
 
 int gc_stream_eval_set_wire(gc_stream_eval *e, uint32_t w, const gc_label *l) try {
     if (!e || !l) return GC_E_ARG;
-    int rc = eval_close_group(e);  // a queued block reads the wire's OLD label (the reference runs in program order)
+    int rc = close_group(*e);  // a queued block reads the wire's OLD label (the reference runs in program order)
     if (rc != GC_OK) return rc;
     if (e->deep.n_inflight) e->deep.drain();  // ... also a deep block on its lane
     e->store.set(w, *l);
@@ -161,30 +143,16 @@ int gc_stream_eval_dev_stats(const gc_stream_eval *e, uint64_t *blocks, uint64_t
 
 int gc_stream_eval_fuse_stats(const gc_stream_eval *e, uint64_t *fused_units, uint64_t *fused_blocks, uint64_t *plans_built,
                               uint64_t *unfit) {
-    if (!e) return GC_E_ARG;
-    if (fused_units) *fused_units = e->fuse.units;
-    if (fused_blocks) *fused_blocks = e->fuse.steps;
-    if (plans_built) *plans_built = e->fuse.built;
-    if (unfit) *unfit = e->fuse.unfit;
-    return GC_OK;
+    return fuse_stats(e, fused_units, fused_blocks, plans_built, unfit);
 }
 
-int gc_stream_eval_wait_stats(const gc_stream_eval *e, uint64_t *waiting_units) {
-    if (!e) return GC_E_ARG;
-    if (waiting_units) *waiting_units = e->fuse.waiting;
-    return GC_OK;
-}
+int gc_stream_eval_wait_stats(const gc_stream_eval *e, uint64_t *waiting_units) { return wait_stats(e, waiting_units); }
 
-int gc_stream_eval_deep_stats(const gc_stream_eval *e, uint64_t *deep_blocks, uint32_t *lanes) {
-    if (!e) return GC_E_ARG;
-    if (deep_blocks) *deep_blocks = e->deep.n_steps;
-    if (lanes) *lanes = e->deep.state > 0 ? (uint32_t)e->deep.lanes.size() : 0;
-    return GC_OK;
-}
+int gc_stream_eval_deep_stats(const gc_stream_eval *e, uint64_t *deep_blocks, uint32_t *lanes) { return deep_stats(e, deep_blocks, lanes); }
 
 int gc_stream_eval_get_wire(gc_stream_eval *e, uint32_t w, gc_label *l) try {
     if (!e || !l) return GC_E_ARG;
-    int rc = eval_close_group(e);  // a queued block may be the one that writes the wire
+    int rc = close_group(*e);  // a queued block may be the one that writes the wire
     if (rc != GC_OK) return rc;
     if (e->deep.n_inflight) e->deep.drain();  // ... or a deep block on its lane
     rc = e->store.get(e->ctx, w, l);
@@ -265,241 +233,19 @@ int eval_rows_buffer(gc_stream_eval *e, uint32_t ngates, bool *small_block_out, 
     return GC_OK;
 }
 
-// The block joins a group / takes a lane / runs as a pass of its own (see the head of stream_garble.cpp)
-int eval_schedule(gc_stream_eval *e, const BlockIn &in, size_t *consumed) {
+// a big block (or a small one without a one-workgroup plan: rare): its own launch sequence, behind everything queued
+static int eval_big_block(gc_stream_eval *e, const BlockIn &in, StreamTrace &tr, size_t *consumed) {
     CircEntry *ent = in.ent;
-    const uint32_t ngates = in.ngates, nin = in.nin, nout = in.nout, sb = in.sb;
+    const uint32_t nin = in.nin, nout = in.nout, sb = in.sb;
     const size_t nrows = in.nrows, pos = in.pos;
     const bool small_block = in.small_block;
     gc_label *slab = in.slab;
     const EvalSkel *rows_from = in.rows_from;
     const uint8_t *buf = in.buf;
     std::vector<uint32_t> &wr_ids = e->wr_ids;
-    StreamTrace tr;
-    ent->last_use = ++e->tick;
     gc_ctx *ctx = e->ctx;
-    // ---- a small block joins the open group: independent blocks are evaluated side by side in one launch sequence; a deep
-    //      block (a long one-workgroup pass, DeepLanes) takes a lane ----------------------------------------------------------
-    bool is_deep = entry_is_deep(ent, e->deep.min_steps, true) && e->deep.setup(ctx);
-    int follow_lane = -1;  // a short block that depends on a deep block in flight follows it onto its lane (see the garbler)
-    if (!is_deep && small_block && e->deep.n_inflight && e->deep.follow && entry_is_small(ent)) {
-        e->deep.ensure(e->store.host.size());
-        follow_lane = e->deep.lane_to_follow(e->deep.conflicts(e->io_host.data(), nin, wr_ids.data(), nout));
-        is_deep = follow_lane >= 0;
-    }
-    e->n_blocks_total++;
-    e->prof.lap(StageProf::kOther);
-    if (is_deep || (small_block && entry_is_small(ent))) {
-        if (!e->store.dirty.empty()) {  // host-set labels go up before the block's outputs are marked device-owned (and before
-            std::lock_guard<std::mutex> lk(ctx->mu);  // the block is put anywhere: a failure leaves nothing half-queued)
-            int rcs = e->store.flush(ctx);
-            if (rcs != GC_OK) return rcs;
-        }
-        e->win.ensure(e->store.host.size());
-        if (is_deep || e->deep.n_inflight) e->deep.ensure(e->store.host.size());
-        const size_t wbytes = up256((size_t)ent->job.w_tile * 16);
-        // chain fusion, as in the garbler (stream_garble.cpp: stream_begin): a short block whose conflicts with the latest group
-        // it has any with all sit in ONE launch unit is appended to that unit
-        uint32_t unit = kFuseNone;
-        uint32_t gi = fuse_enabled() ? e->win.place_fuse(e->io_host.data(), nin, wr_ids.data(), nout, &unit)
-                                     : e->win.place(e->io_host.data(), nin, wr_ids.data(), nout);
-        const bool may_fuse = fuse_enabled() && !is_deep && small_block && ent->uid != 0;
-        // conflicts with several units of that group (as in the garbler): appended to the latest if that one starts behind all
-        // the others, else a unit that waits
-        uint32_t dep_units[kUnitDeps], ndeps = 0;
-        const bool can_wait = fuse_enabled() && e->use_deps && !is_deep && small_block && gi > 0;
-        if (can_wait && unit == kFuseMulti) {
-            ndeps = e->win.conflict_units(e->io_host.data(), nin, wr_ids.data(), nout, e->win.first_seq + gi - 1, dep_units, kUnitDeps);
-            unit = wg_covering(*e->slots[e->win.open[gi - 1]], dep_units, ndeps);
-        } else if (can_wait) {
-            dep_units[0] = unit, ndeps = 1;
-        }
-        bool fuse = false;
-        uint64_t shape = 0;
-        uint32_t n_ext = 0;
-        if (may_fuse && gi > 0 && unit < kFuseMulti && ngates <= kFuseTailGates) {
-            const Slot &fg = *e->slots[e->win.open[gi - 1]];
-            const WgRec &w = fg.wgs[unit];
-            fuse = w.open && w.n < kFuseMembers && w.gates + ngates <= kFuseGates && w.slots + ent->job.zslot + 1 <= kFuseSlots &&
-                   w.inputs + nin <= kFuseInputs && fg.jobs.size() < kGroupSteps &&
-                   fg.arena_used + fg.up_used + 2 * wbytes + 2 * nrows * 16 <= kGroupBytes;
-            if (fuse) {  // input sources, and what chains of this shape say about their depth (as in the garbler)
-                const uint32_t seq = e->win.first_seq + gi - 1;
-                e->wiring_scratch.resize(nin);
-                for (uint32_t i = 0; i < nin; i++) {
-                    const GroupWindow::WireRec &r = e->win.rec[e->io_host[i]];
-                    if (r.wr == seq && r.wrj == unit) e->wiring_scratch[i] = (fg.jobs[r.wrm >> 20].member << 24) | (r.wrm & 0xfffffu);
-                    else e->wiring_scratch[i] = kFuseNone, n_ext++;
-                }
-                shape = fuse_shape(w.shape, ent, e->wiring_scratch.data());
-                const uint32_t hint = fuse_depth_hint(ctx, shape);
-                fuse = hint ? hint <= fuse_depth_cap() : w.depth_sum + ent->circ->plan.p.n_hash_phases <= 2 * fuse_depth_cap();
-            }
-        }
-        uint32_t slot_idx = 0;
-        auto full = [&](const Slot &g) {
-            return g.wgs.size() >= kGroupJobs || g.jobs.size() >= kGroupSteps ||
-                   g.arena_used + g.up_used + 2 * wbytes + 2 * nrows * 16 > kGroupBytes;
-        };
-        // not fused: the block still joins the group it conflicts with, as a unit that waits on the device for the units it
-        // conflicts with there (as in the garbler)
-        bool waits = false;
-        if (!fuse && can_wait && !full(*e->slots[e->win.open[gi - 1]])) {
-            waits = true;
-            gi--;
-        }
-        e->prof.lap(StageProf::kPlace);
-        if (fuse || waits) {
-            if (fuse) gi--;
-            slot_idx = e->win.open[gi];
-        } else if (is_deep) {
-            for (; gi > 0; gi--) {  // the open groups this block depends on go first
-                int rcq = eval_launch_oldest(e);
-                if (rcq != GC_OK) return rcq;
-            }
-            e->deep.poll();
-            if (e->deep.n_inflight >= kDeepInFlight) {
-                size_t l = 0;
-                for (size_t k = 1; k < e->deep.inflight.size(); k++)
-                    if (e->deep.inflight[k].size() > e->deep.inflight[l].size()) l = k;
-                (void)hipEventSynchronize(e->deep.inflight[l].front().ev);
-                e->deep.poll();
-            }
-            Slot *ng = eval_slot(e, &slot_idx, follow_lane < 0);
-            if (!ng) return GC_E_NOMEM;
-            ng->reset();
-            ng->kind = Slot::kGroup;
-            ng->deep_id = e->deep.new_id();
-            ng->lane = follow_lane >= 0 ? follow_lane : e->deep.pick();
-            ng->deps = e->deep.conflicts(e->io_host.data(), nin, wr_ids.data(), nout);
-            deep_after(e->win, e->slots, e->win.last_conflict(e->io_host.data(), nin, wr_ids.data(), nout), ng);
-        } else {
-            while (gi < e->win.open.size() && full(*e->slots[e->win.open[gi]])) gi++;
-            if (gi == e->win.open.size()) {
-                if (e->win.open.size() >= open_groups_limit((size_t)kOpenGroupsMax * 16)) {
-                    int rcq = eval_launch_oldest(e);
-                    if (rcq != GC_OK) return rcq;
-                    gi--;
-                }
-                uint32_t idx = 0;
-                Slot *ng = eval_slot(e, &idx);
-                tr.lap("eval: launch + free slot");
-                if (!ng) return GC_E_NOMEM;
-                ng->reset();
-                ng->kind = Slot::kGroup;
-                e->win.open.push_back(idx);
-            }
-            slot_idx = e->win.open[gi];
-        }
-        Slot &g = *e->slots[slot_idx];
-        // the rows of a block of many gates were parsed into the pinned ring: they go up from there (launch_group); the rows of
-        // a block the DEVICE matched are in device memory already: the launch sequence gathers them into the job's table array
-        const bool ext_rows = is_deep && !small_block;
-        const bool dev_rows = in.d_block != nullptr && !ext_rows;
-        const size_t io_bytes = up16(((size_t)nin + nout) * sizeof(uint32_t)), row_bytes = ext_rows || dev_rows ? 0 : up16(nrows * sizeof(gc_label));
-        hipError_t er = g.reserve_up(up16(g.up_used) - g.up_used + io_bytes + row_bytes + 16);
-        if (er != hipSuccess) {
-            set_error("gc_stream_eval_circuit (pinned)", er);
-            if (is_deep) g.reset();
-            return GC_E_NOMEM;
-        }
-        JobRec j;
-        j.ent = ent;
-        j.nin = nin, j.nout = nout;
-        g.up_used = up16(g.up_used);
-        j.off_io = g.up_used;
-        if (nin + nout) std::memcpy(g.h_up + g.up_used, e->io_host.data(), ((size_t)nin + nout) * sizeof(uint32_t));
-        g.up_used += io_bytes;
-        j.off_rows = g.up_used;
-        if (!ext_rows && !dev_rows && nrows) {
-            if (rows_from) rows_from->copy_rows(buf, (gc_label *)(g.h_up + g.up_used));
-            else std::memcpy(g.h_up + g.up_used, slab, nrows * sizeof(gc_label));
-        }
-        g.up_used += row_bytes;
-        j.off_w = g.arena_used;
-        g.arena_used += wbytes;
-        if (dev_rows) {
-            j.d_block = in.d_block, j.d_row_off = in.d_row_off, j.chunk = in.chunk;
-            j.off_t = g.arena_used;
-            g.arena_used += up256(nrows * sizeof(gc_label));
-            g.chunk_refs.push_back(in.chunk);
-            evdev_ref(e, in.chunk);
-        }
-        if (ext_rows) {
-            // the rows go up NOW, on the upload stream, from the pinned ring entry into the slot's arena: the entry is free
-            // again as soon as that copy has run (on the lane it would wait for the deep blocks queued there, and the parser
-            // for the entry)
-            j.rows_in_arena = true;
-            j.off_t = g.arena_used;
-            g.arena_used += up256(nrows * sizeof(gc_label));
-            std::lock_guard<std::mutex> lk(ctx->mu);
-            er = grow_dev(ctx, &g.d_arena, &g.arena_cap, g.arena_used);
-            if (er == hipSuccess && !e->up_stream) er = hipStreamCreateWithFlags(&e->up_stream, hipStreamNonBlocking);
-            if (er == hipSuccess && !e->up_ev[sb]) er = hipEventCreateWithFlags(&e->up_ev[sb], hipEventDisableTiming);
-            if (er == hipSuccess && nrows)
-                er = hipMemcpyAsync(g.d_arena + j.off_t, slab, nrows * sizeof(gc_label), hipMemcpyHostToDevice, e->up_stream);
-            if (er == hipSuccess) er = hipEventRecord(e->up_ev[sb], e->up_stream);
-            (void)hipEventRecord(e->slab_ev[sb], e->up_stream);
-            e->ring_batch[sb] = nullptr;
-            if (er != hipSuccess) {
-                set_error("gc_stream_eval_circuit (rows)", er);
-                (void)hipStreamSynchronize(e->up_stream);
-                g.reset();
-                return er == hipErrorOutOfMemory ? GC_E_NOMEM : GC_E_HIP;
-            }
-            g.rows_ev = e->up_ev[sb];
-        }
-        g.lds = std::max(g.lds, ent->lds);
-        g.has_or = g.has_or || ent->has_or;
-        j.nrows = (uint32_t)nrows;
-        const uint32_t step_idx = (uint32_t)g.jobs.size();
-        if (fuse) {  // the wiring goes with the block; outputs of earlier blocks of the unit that this one overwrites
-            const uint32_t seq = e->win.first_seq + gi;
-            j.off_wiring = g.wiring.size();
-            g.wiring.insert(g.wiring.end(), e->wiring_scratch.begin(), e->wiring_scratch.begin() + nin);
-            for (uint32_t k = 0; k < nout; k++) {
-                if (e->io_host[nin + k] == 0xffffffffu) continue;  // (superseded inside the block itself: not stored anyway)
-                const GroupWindow::WireRec &r = e->win.rec[wr_ids[k]];
-                if (r.wr == seq && r.wrj == unit) g.kills.emplace_back(r.wrm >> 20, r.wrm & 0xfffffu);
-            }
-            wg_append(g, unit, &j, ent, n_ext, shape);
-            e->fuse.appended++;
-        } else {
-            unit = wg_new(g, &j, ent, may_fuse);
-            if (waits) {
-                wg_wait(g, unit, dep_units, ndeps);
-                e->fuse.waiting++;
-            }
-        }
-        g.jobs.push_back(j);
-        e->prof.lap(StageProf::kQueue);
-        if (!is_deep) {
-            e->win.mark(gi, e->io_host.data(), nin, wr_ids.data(), nout, unit, step_idx);
-            if (e->deep.n_inflight) g.deps.merge(e->deep.conflicts(e->io_host.data(), nin, wr_ids.data(), nout));
-        }
-        if (is_deep) {  // launched at once, on its lane
-            int rcl = launch_group(ctx, g, true, e->store, e->d_rk, nullptr, e->rounds, nullptr, e->deep, &e->fuse);
-            if (!g.chunk_refs.empty()) evdev_launched(e, g, slot_idx);
-            hipStream_t lane = e->deep.lanes[(size_t)g.lane];
-            if (rcl != GC_OK) {
-                (void)hipStreamSynchronize(lane);
-                e->deep.retire(g.lane, g.deep_id);
-                g.reset();
-                return rcl;
-            }
-            e->deep.mark(g.deep_id, e->io_host.data(), nin, wr_ids.data(), nout);
-            e->n_groups++;
-            e->n_group_blocks++;
-        }
-        for (uint32_t k = 0; k < nout; k++) e->store.on_dev[wr_ids[k]] = 1;
-        e->prof.lap(StageProf::kMark);
-        tr.lap(is_deep ? "eval: launched on a lane" : "eval: queued in group");
-        *consumed = pos;
-        return GC_OK;
-    }
-    // ---- a big block: its own launch sequence, behind everything queued -------------------------------------------
     {
-        int rcq = eval_close_group(e);
+        int rcq = close_group(*e);
         if (rcq != GC_OK) return rcq;
         if (e->deep.n_inflight) {  // a pass on the ctx stream: behind every deep block in flight (DeepLanes)
             e->deep.poll();
@@ -508,7 +254,7 @@ int eval_schedule(gc_stream_eval *e, const BlockIn &in, size_t *consumed) {
         }
         {  // ... and later deep blocks must see what it reads and writes
             e->win.ensure(e->store.host.size());
-            e->win.mark_pass(e->io_host.data(), nin, wr_ids.data(), nout);
+            e->win.mark_pass(WireSet{e->io_host.data(), nin, wr_ids.data(), nout});
         }
     }
     gc_circ *circ = ent->circ;
@@ -604,6 +350,111 @@ int eval_schedule(gc_stream_eval *e, const BlockIn &in, size_t *consumed) {
     tr.lap("eval: enqueue");
     *consumed = pos;
     return GC_OK;
+}
+
+// a small block joins a group of independent blocks — evaluated side by side in one launch sequence —, a deep one takes a lane
+// (place_step)
+static int eval_queue_block(gc_stream_eval *e, const BlockIn &in, const WireSet &ws, bool is_deep, int follow_lane, StreamTrace &tr,
+                            size_t *consumed) {
+    CircEntry *ent = in.ent;
+    const uint32_t nin = in.nin, nout = in.nout, sb = in.sb;
+    const size_t nrows = in.nrows;
+    const bool small_block = in.small_block;
+    gc_ctx *ctx = e->ctx;
+    if (!e->store.dirty.empty()) {
+        int rcs = flush_store(*e);
+        if (rcs != GC_OK) return rcs;
+    }
+    // what the block takes of a group: its wire array and its rows — in the upload region and, for a chain, in the arena again
+    const size_t wbytes = up256((size_t)ent->job.w_tile * 16);
+    const PlaceArgs pa{2 * wbytes + 2 * nrows * 16, &Slot::up_used, small_block, small_block, (size_t)kOpenGroupsMax * 16, eval_slot};
+    Placement p;
+    int rcp = place_step(*e, ent, ws, in.ngates, is_deep, follow_lane, pa, &p);
+    if (rcp != GC_OK) return rcp;
+    Slot &g = *e->slots[p.slot];
+    // the rows of a block of many gates were parsed into the pinned ring: they go up from there (launch_group); the rows of
+    // a block the DEVICE matched are in device memory already: the launch sequence gathers them into the job's table array
+    const bool ext_rows = is_deep && !small_block;
+    const bool dev_rows = in.d_block != nullptr && !ext_rows;
+    const size_t io_bytes = up16(((size_t)nin + nout) * sizeof(uint32_t)), row_bytes = ext_rows || dev_rows ? 0 : up16(nrows * sizeof(gc_label));
+    hipError_t er = g.reserve_up(up16(g.up_used) - g.up_used + io_bytes + row_bytes + 16);
+    if (er != hipSuccess) {
+        set_error("gc_stream_eval_circuit (pinned)", er);
+        if (is_deep) g.reset();
+        return GC_E_NOMEM;
+    }
+    JobRec j;
+    j.ent = ent;
+    j.nin = nin, j.nout = nout;
+    g.up_used = up16(g.up_used);
+    j.off_io = g.up_used;
+    if (nin + nout) std::memcpy(g.h_up + g.up_used, e->io_host.data(), ((size_t)nin + nout) * sizeof(uint32_t));
+    g.up_used += io_bytes;
+    j.off_rows = g.up_used;
+    if (!ext_rows && !dev_rows && nrows) {
+        if (in.rows_from) in.rows_from->copy_rows(in.buf, (gc_label *)(g.h_up + g.up_used));
+        else std::memcpy(g.h_up + g.up_used, in.slab, nrows * sizeof(gc_label));
+    }
+    g.up_used += row_bytes;
+    j.off_w = g.arena_used;
+    g.arena_used += wbytes;
+    if (dev_rows) {
+        j.d_block = in.d_block, j.d_row_off = in.d_row_off, j.chunk = in.chunk;
+        j.off_t = g.arena_used;
+        g.arena_used += up256(nrows * sizeof(gc_label));
+        g.chunk_refs.push_back(in.chunk);
+        evdev_ref(e, in.chunk);
+    }
+    if (ext_rows) {
+        // the rows go up NOW, on the upload stream, from the pinned ring entry into the slot's arena: the entry is free
+        // again as soon as that copy has run (on the lane it would wait for the deep blocks queued there, and the parser
+        // for the entry)
+        j.rows_in_arena = true;
+        j.off_t = g.arena_used;
+        g.arena_used += up256(nrows * sizeof(gc_label));
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        er = grow_dev(ctx, &g.d_arena, &g.arena_cap, g.arena_used);
+        if (er == hipSuccess && !e->up_stream) er = hipStreamCreateWithFlags(&e->up_stream, hipStreamNonBlocking);
+        if (er == hipSuccess && !e->up_ev[sb]) er = hipEventCreateWithFlags(&e->up_ev[sb], hipEventDisableTiming);
+        if (er == hipSuccess && nrows)
+            er = hipMemcpyAsync(g.d_arena + j.off_t, in.slab, nrows * sizeof(gc_label), hipMemcpyHostToDevice, e->up_stream);
+        if (er == hipSuccess) er = hipEventRecord(e->up_ev[sb], e->up_stream);
+        (void)hipEventRecord(e->slab_ev[sb], e->up_stream);
+        e->ring_batch[sb] = nullptr;
+        if (er != hipSuccess) {
+            set_error("gc_stream_eval_circuit (rows)", er);
+            (void)hipStreamSynchronize(e->up_stream);
+            g.reset();
+            return er == hipErrorOutOfMemory ? GC_E_NOMEM : GC_E_HIP;
+        }
+        g.rows_ev = e->up_ev[sb];
+    }
+    g.lds = std::max(g.lds, ent->lds);
+    g.has_or = g.has_or || ent->has_or;
+    j.nrows = (uint32_t)nrows;
+    queue_step(*e, g, p, j, ws, e->io_host.data() + nin);
+    if (is_deep) {
+        int rcl = launch_deep(*e, g, p, ws);
+        if (rcl != GC_OK) return rcl;
+    }
+    for (uint32_t k = 0; k < nout; k++) e->store.on_dev[ws.wr[k]] = 1;
+    e->prof.lap(StageProf::kMark);
+    tr.lap(is_deep ? "eval: launched on a lane" : "eval: queued in group");
+    *consumed = in.pos;
+    return GC_OK;
+}
+
+// The block joins a group / takes a lane / runs as a pass of its own (see the head of stream_garble.cpp)
+int eval_schedule(gc_stream_eval *e, const BlockIn &in, size_t *consumed) {
+    StreamTrace tr;
+    in.ent->last_use = ++e->tick;
+    const WireSet ws{e->io_host.data(), in.nin, e->wr_ids.data(), in.nout};
+    int follow_lane = -1;  // a short block that depends on a deep block in flight follows it onto its lane
+    const bool is_deep = step_is_deep(*e, in.ent, ws, true, in.small_block, &follow_lane);
+    e->n_blocks_total++;
+    e->prof.lap(StageProf::kOther);
+    if (is_deep || (in.small_block && entry_is_small(in.ent))) return eval_queue_block(e, in, ws, is_deep, follow_lane, tr, consumed);
+    return eval_big_block(e, in, tr, consumed);
 }
 
 int eval_block(gc_stream_eval *e, uint32_t ngates, uint32_t ntmp, uint32_t nwires, const uint8_t *buf, size_t len,
@@ -836,7 +687,7 @@ int eval_block(gc_stream_eval *e, uint32_t ngates, uint32_t ntmp, uint32_t nwire
             // device memory without limit; the reference evaluator holds one block).  Least recently used circuits go,
             // with the byte skeletons that point at them; nothing may refer to them any more: launch what is queued and
             // drain the stream first (rare: once per budget's worth of NEW circuits).
-            int rcq = eval_close_group(e);
+            int rcq = close_group(*e);
             if (rcq != GC_OK) return rcq;
             GC_HIP(hipStreamSynchronize(e->ctx->stream));
             e->deep.drain();

@@ -559,8 +559,7 @@ int evdev_blocks(gc_stream_eval *e, const uint8_t *buf, size_t len, size_t *pos_
                         }
                         adopted = true;
                         if (e->win.rec.size() >= e->store.host.size()) {
-                            e->win.prefetch(e->io_host.data(), nin);
-                            e->win.prefetch(e->wr_ids.data(), nout);
+                            e->win.prefetch(WireSet{e->io_host.data(), nin, e->wr_ids.data(), nout});
                         }
                         if (o != sk) {  // most recently matched first: the next block of this key is guessed to be this layout
                             auto it = e->skels.find(sk->key);

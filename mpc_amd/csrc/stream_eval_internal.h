@@ -11,25 +11,8 @@ struct EvalDev;  // stream_eval_dev.cpp
 
 using namespace gcs;  // (internal header of the engine's own translation units)
 
-struct gc_stream_eval {
-    gc_ctx *ctx = nullptr;
-    std::vector<uint8_t> key;
-    int rounds = 0;
-    uint32_t *d_rk = nullptr;  // expanded key on the device (step groups)
-    DevStore store;  // StreamEval.wires (global store), device-resident
-    CircCache cache;
-    size_t cache_gates = 0, cache_budget = kCacheGatesDefault;
-    uint64_t tick = 0;
-    // step groups (see the head of this file): small blocks that share no global wire are evaluated by ONE launch sequence
-    std::vector<std::unique_ptr<Slot>> slots;
-    GroupWindow win;
-    CtxQueue ctxq;
-    DeepLanes deep;
+struct gc_stream_eval : StreamCore {  // (the core: what the evaluator shares with the garbler — store, cache, slots, window, lanes)
     std::vector<gc_label> rows_scratch;  // table rows of a small block while it is parsed
-    uint64_t n_groups = 0, n_group_blocks = 0;
-    FuseStats fuse;  // chain fusion (stream_fuse.cpp)
-    bool use_deps = deps_wanted();  // units that wait inside a launch (stream_internal.h: kUnitDeps)
-    std::vector<uint32_t> wiring_scratch;
     std::vector<uint32_t> io_host;  // indices of this block's inputs, then of its global outputs (0xffffffff: superseded)
     uint32_t *d_io = nullptr;
     size_t io_cap = 0;
@@ -65,14 +48,11 @@ struct gc_stream_eval {
     uint32_t slab_turn = 0;
     // The uploads of a big block (rows, wire maps) run on a stream of their own, under the kernels of the block before:
     // up_ev[i] = this entry's uploads done (the ctx stream waits for it); ring_batch[i] = the pooled batch whose table
-    // buffer they went into (an upload into it waits for slab_ev[i]: the pass that last read it); held = the batch of the
-    // last block, kept out of the pool until the next block has taken its own (two passes in flight, two table buffers)
+    // buffer they went into (an upload into it waits for slab_ev[i]: the pass that last read it); the core's held = the batch of
+    // the last block, kept out of the pool until the next block has taken its own (two passes in flight, two table buffers)
     hipStream_t up_stream = nullptr;
     hipEvent_t up_ev[kEvalRing] = {};
     gc_batch *ring_batch[kEvalRing] = {};
-    gc_circ *held_circ = nullptr;
-    gc_batch *held = nullptr;
-    StageProf prof;
     uint64_t n_blocks_total = 0;
     gcs::EvalDev *dev = nullptr;  // device-side match of the blocks of a read buffer (stream_eval_dev.cpp; created on first use)
 };

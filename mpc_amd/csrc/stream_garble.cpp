@@ -1,61 +1,50 @@
-// stream_engine.cpp — C ABI for the streaming garbler (circuit.Streaming, config 5).
+// stream_garble.cpp — C ABI for the streaming garbler (circuit.Streaming, config 5).
 //
-// Replaces the bodies of NewStreaming (circuit/stream_garble.go:41-75) and Streaming.Garble (:161-192).
-// The persistent wire store (stream.wires) stays on the host — it is touched only at circuit
-// boundaries; each Garble call (i) resolves the circuit's input wires through in[] (:131-141),
-// (ii) garbles the circuit on the device with the SAME kernels as Circuit.Garble (the tweak restarts
-// at 0 per circuit, :174, exactly like a fresh Circuit.Garble) and (iii) serialises the gates in the
-// reference's wire format (:391-446), byte for byte — ON THE DEVICE: per-gate byte sizes, a two-level exclusive
-// scan and a writer kernel that places header and rows at the gate's byte offset; the host copies the finished
-// byte string into the caller's buffer (the per-gate host loop was 4 ms for a 131 072-gate step, ten times the
-// garbling itself).  Circuits are cached by content, so an SSA instruction that repeats re-uses its levelised
-// plan and device buffers.
+// Replaces the bodies of NewStreaming (circuit/stream_garble.go:41-75) and Streaming.Garble (:161-192).  The wire store
+// (stream.wires) lives in HBM (DevStore): steps hand labels to each other on the device.  Each Garble call (i) resolves the
+// circuit's input wires through in[] (:131-141), (ii) garbles the circuit on the device with the SAME kernels as
+// Circuit.Garble (the tweak restarts at 0 per circuit, :174) and (iii) serialises the gates in the reference's wire format
+// (:391-446), byte for byte, ON THE DEVICE.  Circuits are cached by content; gc_stream_intern names one by a handle.
 //
-// Step-level parallelism (round 3).  A compiled program is a long sequence of SMALL circuits — one per SSA instruction
-// (compiler/ssa/streamer.go:412-524: 64-bit adders, comparators, multipliers ...) — most of which do not depend on
-// their immediate predecessors.  gc_stream_garble_begin QUEUES such a step; consecutive queued steps that share no
-// global wire (no read-after-write, write-after-write or write-after-read through in[] / out[]) form a GROUP that runs
-// as ONE launch sequence: host -> device copy of the group's job records, k_*_flat_jobs (workgroup j = step j: its own
-// circuit plan, input labels gathered from the device-resident wire store), k_stream_finish (output labels scattered
-// into the store, gates serialised into the step's byte slot), one copy of all the group's bytes back into pinned
-// memory.  A step that conflicts with the open group closes it (stream order then carries the dependency); the bytes
-// still leave in program order through gc_stream_garble_finish.  Steps of more than kSmallGates gates keep the
-// per-step path (level launches spread over the chip).  The evaluator groups its blocks the same way.
+// Queue.  gc_stream_garble_begin(_h) queues a step (at most kMaxPending in flight) and returns without waiting;
+// gc_stream_garble_finish hands out the bytes of the oldest: program order on the wire.
 //
-// Deep lanes (round 4).  A step whose one-workgroup pass is LONG (a 128- / 256-bit multiplier, a 256- / 512-bit adder: 0.5 -
-// 2 ms on one CU) runs on one of a few extra HIP streams of the ctx, beside the groups, ordered against them by events only
-// where two steps share a wire (DeepLanes below); short steps that depend on such a step follow it onto its lane.  The open
-// groups form a window of up to 16 (an add chain interleaved with independent products needs a group per link); the caller's
-// finish launches what is behind the group it waits for.  A circuit met in the middle of a stream gets its LDS plan from a
-// thread of its own while its first passes run on the kernels that need none (gc_circ_flat_poll).
+// Step groups.  A compiled program is a long sequence of SMALL circuits, one per SSA instruction
+// (compiler/ssa/streamer.go:412-524), most of which do not depend on their immediate predecessors.  A step whose one-instance
+// plan fits LDS is a job = one workgroup; jobs are list-scheduled into a window of open groups (GroupWindow: per global wire
+// the latest group and launch unit that reads / writes it; a job joins the earliest group behind everything it has a RAW /
+// WAW / WAR relation with).  A group is ONE launch sequence (stream_group.cpp: launch_group): pinned upload of job records and
+// wire maps, k_garble_flat_jobs (Get through in[] in the prologue, Set through out[] in the epilogue), and on the copy stream
+// the serialiser of the group (k_stream_serialise) + one copy of the bytes.  The window holds in_flight / 16 groups, between 4
+// and 6 with chain fusion on (open_groups_limit); a group goes to the GPU when the window is full or the caller reaches one of
+// its steps, and the groups behind it (kKeepQueued) go with it.
+//
+// Chain fusion (stream_fuse.cpp).  A short step whose conflicts with the latest group it conflicts with at all sit in ONE
+// launch unit of that group is appended to that unit: the chain runs as one job on a merged plan.
+//
+// Deep lanes.  A step whose one-workgroup pass is LONG (a 128- / 256-bit multiplier, a 256- / 512-bit adder: 0.5 - 2 ms on one
+// CU) runs on one of a few extra HIP streams of the ctx, beside the groups, ordered against them by events only where two
+// steps share a wire (DeepLanes); short steps that depend on such a step follow it onto its lane.
+//
+// Big steps (wide, or more than kSmallGates gates without a one-workgroup plan) keep a launch sequence of their own, behind
+// everything queued: the pass on the ctx stream, the serialiser on a stream of its own (garble_big_step).
+//
+// Where a step goes — group, chain, lane — is decided by ONE function for both sides (stream_group.cpp: place_step, over the
+// StreamCore that gc_stream and gc_stream_eval share); this file fills the step's job record and keeps the queue.  A circuit
+// met in the middle of a stream gets its LDS plan from a thread of its own while its first passes run on the kernels that need
+// none (gc_circ_flat_poll).
 #include "stream_internal.h"
 
 using namespace gcs;
 
-struct gc_stream {
-    gc_ctx *ctx = nullptr;
-    std::vector<uint8_t> key;
-    int rounds = 0;
+struct gc_stream : StreamCore {  // (the core: what the garbler shares with the evaluator — stream_internal.h)
     gc_label r{};
-    uint32_t *d_rk = nullptr;  // expanded key (60 words) and R on the device: the step groups' kernels read them
-    uint4 *d_R = nullptr;
-    DevStore store;               // global wire -> L0 (L1 = L0 ^ R)
-    CircCache cache;
-    size_t cache_gates = 0, cache_budget = kCacheGatesDefault;
-    uint64_t tick = 0;
     std::vector<uint32_t> alias_gen, alias_j;  // in[] / out[] aliasing check: stamp + index in out[] per global wire
     uint32_t gen = 0;
     std::vector<gc_gate> rewritten;            // gate list with aliased reads redirected (rare)
     std::vector<uint32_t> skip_scratch;        // out[] with 0xffffffff where nothing is stored
-    std::vector<uint32_t> wiring_scratch;      // chain fusion: the input sources of the step being queued
-    // circuits in flight (gc_stream_garble_begin / _finish), oldest first, and the slots that hold them
-    std::vector<std::unique_ptr<Slot>> slots;
-    std::deque<StepRef> queue;
-    GroupWindow win;              // the groups still accepting steps
-    CtxQueue ctxq;                // ... and the launched ones the ctx stream has not run yet
-    DeepLanes deep;               // long one-workgroup steps run beside the groups, on streams of their own
+    std::deque<StepRef> queue;    // circuits in flight (gc_stream_garble_begin / _finish), oldest first (their slots: the core's)
     std::vector<CircEntry *> handles;  // gc_stream_intern
-    hipStream_t copy_stream = nullptr;
     // Big steps: the serialiser (byte sizes, their scan, the total down, the bytes) runs on ser_stream behind the pass
     // (ev_pass) and under the pass of the NEXT step — which therefore gets another table buffer: the batch of the last big
     // step is held out of the pool until the next one has taken its own, and a pass into a table buffer waits for the
@@ -66,20 +55,16 @@ struct gc_stream {
     hipEvent_t ser_ev[2] = {nullptr, nullptr};
     gc_batch *ser_batch[2] = {nullptr, nullptr};
     uint32_t ser_turn = 0;
-    gc_circ *held_circ = nullptr;
-    gc_batch *held = nullptr;
-    uint64_t n_groups = 0, n_group_steps = 0, n_big_steps = 0;
+    uint64_t n_big_steps = 0;
     CopyPool copier;              // gc_stream_garble_finish_async: the copies into the caller's buffer, off this thread
-    FuseStats fuse;               // chain fusion: launch units of several steps, merged plans built
-    bool use_deps = deps_wanted();  // units that wait inside a launch (stream_internal.h: kUnitDeps)
-    Dataflow df;                    // units ordered by the versions of their wires, across launches (GC_STREAM_DATAFLOW)
-    StageProf prof;
+    Dataflow dataflow;            // units ordered by the versions of their wires, across launches (GC_STREAM_DATAFLOW; the core's df)
     uint64_t n_steps_total = 0;
     // gc_stream_garble_finish_view: the slot whose pinned bytes the caller is still reading (given back by the next finish),
     // and pinned staging for the bytes of a big step
     uint32_t view_slot = 0xffffffffu;
     uint8_t *view_buf = nullptr;
     size_t view_cap = 0;
+    gc_stream() { df = &dataflow; }
 };
 
 namespace {
@@ -94,30 +79,6 @@ inline void ensure(gc_stream *s, uint32_t max) {  // ensureWires, 64 Ki-wire pag
     s->store.ensure(((size_t)max / 0x10000 + 1) * 0x10000);
 }
 
-// the oldest open group leaves the window and is launched
-int launch_oldest(gc_stream *s, bool one_stream = false) {
-    if (s->win.open.empty()) return GC_OK;
-    const uint32_t seq = s->win.first_seq, slot = s->win.pop();
-    Slot &g = *s->slots[slot];
-    s->n_groups++;
-    s->n_group_steps += g.jobs.size();
-    s->prof.lap(StageProf::kOther);
-    const int rc = launch_group(s->ctx, g, false, s->store, s->d_rk, s->d_R, s->rounds, s->copy_stream, s->deep, &s->fuse, one_stream,
-                                &s->df);
-    s->prof.lap(StageProf::kLaunch);
-    s->win.note(seq, slot, g.launch_no);
-    if (rc == GC_OK) s->ctxq.pushed(slot, g.launch_no);
-    return rc;
-}
-// everything queued is launched, in order (a read-back, a big step or the caller's flush follows)
-int close_group(gc_stream *s) {
-    int rc = GC_OK;
-    while (!s->win.open.empty()) {
-        const int r = launch_oldest(s);
-        if (rc == GC_OK) rc = r;
-    }
-    return rc;
-}
 
 // the stream's cached device circuit for this gate list (cached by content; a new circuit is validated once:
 // garbleGate's checks, stream_garble.go:195-210)
@@ -137,7 +98,7 @@ int stream_find_or_load(gc_stream *s, const gc_gate *gates, uint32_t ngates, uin
             if (s->cache_gates + ngates + 1 > s->cache_budget && !s->cache.empty()) {
                 // over budget: least recently used circuits go.  Nothing may refer to them any more: launch what is queued
                 // and drain both streams first (rare: once per budget's worth of NEW circuits)
-                int rcq = close_group(s);
+                int rcq = close_group(*s);
                 if (rcq != GC_OK) return rcq;
                 GC_HIP(hipStreamSynchronize(st));
                 GC_HIP(hipStreamSynchronize(s->copy_stream));
@@ -209,8 +170,8 @@ gc_stream *gc_stream_create(gc_ctx *ctx, const uint8_t *key, size_t keylen, cons
         if (e == hipSuccess) e = hipMemcpy(s->d_rk, k.w, sizeof k.w, hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(s->d_R, &s->r, sizeof(gc_label), hipMemcpyHostToDevice);
         if (e == hipSuccess && dataflow_wanted() && fuse_enabled()) {  // (experiment: off unless GC_STREAM_DATAFLOW=1)
-            e = s->df.setup();
-            s->df.on = e == hipSuccess;
+            e = s->dataflow.setup();
+            s->dataflow.on = e == hipSuccess;
             // (GC_STREAM_DEPS=1 on top: steps that conflict with several units of an open group join it — units that depend on
             // one another inside a launch, in ticket order — instead of opening a later group)
         }
@@ -240,7 +201,7 @@ void gc_stream_free(gc_stream *s) {
         if (GroupTimeline::enabled()) group_timeline().print_and_clear();
     }
     s->deep.release();
-    s->df.release();
+    s->dataflow.release();
     if (s->copy_stream) {
         (void)hipStreamSynchronize(s->copy_stream);
         (void)hipStreamDestroy(s->copy_stream);
@@ -318,7 +279,7 @@ int gc_stream_garble_begin_h(gc_stream *s, uint32_t handle, const uint32_t *in, 
 
 int gc_stream_garble_flush(gc_stream *s) try {
     if (!s) return GC_E_ARG;
-    return close_group(s);
+    return close_group(*s);
 } catch (...) {
     return gc::on_exception();
 }
@@ -332,33 +293,19 @@ int gc_stream_stats(const gc_stream *s, uint64_t *groups, uint64_t *grouped_step
 }
 
 int gc_stream_fuse_stats(const gc_stream *s, uint64_t *fused_units, uint64_t *fused_steps, uint64_t *plans_built, uint64_t *unfit) {
-    if (!s) return GC_E_ARG;
-    if (fused_units) *fused_units = s->fuse.units;
-    if (fused_steps) *fused_steps = s->fuse.steps;
-    if (plans_built) *plans_built = s->fuse.built;
-    if (unfit) *unfit = s->fuse.unfit;
-    return GC_OK;
+    return fuse_stats(s, fused_units, fused_steps, plans_built, unfit);
 }
 
-int gc_stream_wait_stats(const gc_stream *s, uint64_t *waiting_units) {
-    if (!s) return GC_E_ARG;
-    if (waiting_units) *waiting_units = s->fuse.waiting;
-    return GC_OK;
-}
+int gc_stream_wait_stats(const gc_stream *s, uint64_t *waiting_units) { return wait_stats(s, waiting_units); }
 
-int gc_stream_deep_stats(const gc_stream *s, uint64_t *deep_steps, uint32_t *lanes) {
-    if (!s) return GC_E_ARG;
-    if (deep_steps) *deep_steps = s->deep.n_steps;
-    if (lanes) *lanes = s->deep.state > 0 ? (uint32_t)s->deep.lanes.size() : 0;
-    return GC_OK;
-}
+int gc_stream_deep_stats(const gc_stream *s, uint64_t *deep_steps, uint32_t *lanes) { return deep_stats(s, deep_steps, lanes); }
 
 int gc_stream_get_wire(gc_stream *s, uint32_t w, gc_wire *out) try {  // Streaming.GetInput (:117-119)
     if (!s || !out) return GC_E_ARG;
-    int rc = close_group(s);  // a queued step may be the one that sets the wire
+    int rc = close_group(*s);  // a queued step may be the one that sets the wire
     if (rc != GC_OK) return rc;
     if (s->deep.n_inflight) s->deep.drain();  // ... or a deep step on its lane
-    if (s->df.on) s->df.drain();              // ... or a group on one of the rotating streams (Dataflow)
+    if (s->dataflow.on) s->dataflow.drain();              // ... or a group on one of the rotating streams (Dataflow)
     gc_label l0;
     rc = s->store.get(s->ctx, w, &l0);
     if (rc != GC_OK) return rc;
@@ -386,314 +333,141 @@ int gc_stream_garble_begin(gc_stream *s, const gc_gate *gates, uint32_t ngates, 
 }  // extern "C"
 
 namespace {
-int stream_begin(gc_stream *s, const gc_gate *gates, uint32_t ngates, uint32_t nwires, const uint32_t *in,
-                 uint32_t nin, const uint32_t *out, uint32_t nout, CircEntry *known) {
-    if (!s || (nin && !in) || (nout && !out)) return GC_E_ARG;
-    s->prof.start();
-    s->n_steps_total++;
-    if (s->queue.size() >= kMaxPending) return GC_E_ARG;
-    // in[] and out[] may overlap (a circuit whose last wires are input wires): initCircuit (:102-114) takes both as they
-    // are, Get / Set resolve a wire through in[] first (:131-157), so such an output id is simply never written
-    if (nin > nwires || nout > nwires) return GC_E_ARG;
+// one step as stream_begin hands it on: the caller's wire maps and where the circuit's tmp / output wires start
+struct StepIo {
+    const uint32_t *in, *out;
+    uint32_t nin, nout, ngates, first_tmp, first_out;
+};
+
+// in[] / out[] naming the same GLOBAL wire (wire-id re-use, in-place update): the reference resolves
+// stream.wire(index) per gate (:131-157), so a gate that reads the input-mapped wire after the gate that Set the
+// output-mapped one sees the NEW label.  The device garbles from a snapshot of the inputs: redirect such reads to
+// the producing circuit wire (same global id and flags on the wire, so the serialised bytes do not change).
+// Returns whether the step is aliased: *gates is then the rewritten list (s->rewritten) and *known null.
+bool rewrite_aliased(gc_stream *s, const gc_gate **gates, uint32_t ngates, uint32_t nwires, const uint32_t *in, uint32_t nin,
+                     const uint32_t *out, uint32_t nout, CircEntry **known) {
     const uint32_t first_tmp = nin, first_out = nwires - nout;
-    // initCircuit (:102-114)
-    uint32_t mx = 0, in_hi = 0, out_lo = 0xffffffffu, out_hi = 0;
-    for (uint32_t i = 0; i < nin; i++) in_hi = std::max(in_hi, in[i]);
-    for (uint32_t i = 0; i < nout; i++) out_lo = std::min(out_lo, out[i]), out_hi = std::max(out_hi, out[i]);
-    mx = std::max(in_hi, out_hi);
-    ensure(s, mx);
-    // (in[] and out[] can only name a common wire if an input id lies inside the id range of the outputs: as a rule — results
-    // take fresh ids from the allocator, operands and constants lie elsewhere — none does, and the per-wire look of the
-    // aliasing check below, two passes over tables the size of the wire store, is skipped)
-    bool ranges_overlap = false;
-    for (uint32_t i = 0; i < nin && nout; i++) ranges_overlap |= in[i] >= out_lo && in[i] <= out_hi;
-    gc_ctx *ctx = s->ctx;
-    hipStream_t st = ctx->stream;
-    GC_HIP(hipSetDevice(ctx->device));
-    StreamTrace tr;
-
-    // in[] / out[] naming the same GLOBAL wire (wire-id re-use, in-place update): the reference resolves
-    // stream.wire(index) per gate (:131-157), so a gate that reads the input-mapped wire after the gate that Set the
-    // output-mapped one sees the NEW label.  The device garbles from a snapshot of the inputs: redirect such reads to
-    // the producing circuit wire (same global id and flags on the wire, so the serialised bytes do not change).
-    bool was_aliased = false;
-    if (ngates && ranges_overlap) {
-        if (s->alias_gen.size() < s->store.host.size()) {
-            s->alias_gen.resize(s->store.host.size(), 0);
-            s->alias_j.resize(s->store.host.size(), 0);
-        }
-        if (++s->gen == 0) {
-            std::fill(s->alias_gen.begin(), s->alias_gen.end(), 0);
-            s->gen = 1;
-        }
-        for (uint32_t j = 0; j < nout; j++)
-            if (first_out + j >= first_tmp) {
-                s->alias_gen[out[j]] = s->gen;
-                s->alias_j[out[j]] = j;
-            }
-        bool aliased = false;
-        for (uint32_t i = 0; i < nin && !aliased; i++) aliased = s->alias_gen[in[i]] == s->gen;
-        was_aliased = aliased;
-        if (aliased) {
-            std::vector<uint8_t> set(nout, 0);
-            if (known) {  // an interned circuit bound so that an output updates one of its inputs in place: rare, general path
-                s->rewritten.assign(ngates, gc_gate{});
-                for (uint32_t g = 0; g < ngates; g++) {
-                    const CircKey &k = known->gates[g];
-                    s->rewritten[g].in0 = k.in0, s->rewritten[g].in1 = k.in1, s->rewritten[g].out = k.out;
-                    s->rewritten[g].op = (uint8_t)k.op;
-                }
-                known = nullptr;
-            } else {
-                s->rewritten.assign(gates, gates + ngates);
-            }
-            for (uint32_t g = 0; g < ngates; g++) {
-                gc_gate &q = s->rewritten[g];
-                auto redirect = [&](uint32_t w) {
-                    if (w < nin && s->alias_gen[in[w]] == s->gen && set[s->alias_j[in[w]]]) return first_out + s->alias_j[in[w]];
-                    return w;
-                };
-                q.in0 = redirect(q.in0);
-                if (q.op != GC_INV) q.in1 = redirect(q.in1);
-                if (q.out >= first_out && q.out < nwires) set[q.out - first_out] = 1;
-            }
-            gates = s->rewritten.data();
-        }
+    if (s->alias_gen.size() < s->store.host.size()) {
+        s->alias_gen.resize(s->store.host.size(), 0);
+        s->alias_j.resize(s->store.host.size(), 0);
     }
+    if (++s->gen == 0) {
+        std::fill(s->alias_gen.begin(), s->alias_gen.end(), 0);
+        s->gen = 1;
+    }
+    for (uint32_t j = 0; j < nout; j++)
+        if (first_out + j >= first_tmp) {
+            s->alias_gen[out[j]] = s->gen;
+            s->alias_j[out[j]] = j;
+        }
+    bool aliased = false;
+    for (uint32_t i = 0; i < nin && !aliased; i++) aliased = s->alias_gen[in[i]] == s->gen;
+    if (!aliased) return false;
+    std::vector<uint8_t> set(nout, 0);
+    if (*known) {  // an interned circuit bound so that an output updates one of its inputs in place: rare, general path
+        s->rewritten.assign(ngates, gc_gate{});
+        for (uint32_t g = 0; g < ngates; g++) {
+            const CircKey &k = (*known)->gates[g];
+            s->rewritten[g].in0 = k.in0, s->rewritten[g].in1 = k.in1, s->rewritten[g].out = k.out;
+            s->rewritten[g].op = (uint8_t)k.op;
+        }
+        *known = nullptr;
+    } else {
+        s->rewritten.assign(*gates, *gates + ngates);
+    }
+    for (uint32_t g = 0; g < ngates; g++) {
+        gc_gate &q = s->rewritten[g];
+        auto redirect = [&](uint32_t w) {
+            if (w < nin && s->alias_gen[in[w]] == s->gen && set[s->alias_j[in[w]]]) return first_out + s->alias_j[in[w]];
+            return w;
+        };
+        q.in0 = redirect(q.in0);
+        if (q.op != GC_INV) q.in1 = redirect(q.in1);
+        if (q.out >= first_out && q.out < nwires) set[q.out - first_out] = 1;
+    }
+    *gates = s->rewritten.data();
+    return true;
+}
 
-    // device circuit (cached by content); a new circuit is validated once (garbleGate's checks, :195-210)
-    CircEntry *ent = known;
-    if (ngates && !ent) {
-        int rcl = stream_find_or_load(s, gates, ngates, nwires, nin, nout, &ent);
+Slot *garble_slot(StreamCore &c, uint32_t *index, bool big) { return slot_new(c.ctx, c.slots, index, big); }
+
+// a small step joins the earliest open group it has no dependency on (or behind); a deep one takes a lane (place_step)
+int queue_small_step(gc_stream *s, const StepIo &io, CircEntry *ent, bool is_deep, int follow_lane, bool fusable, StreamTrace &tr) {
+    const uint32_t *in = io.in, *out = io.out;
+    const uint32_t nin = io.nin, nout = io.nout;
+    if (!s->store.dirty.empty()) {
+        int rcs = flush_store(*s);
+        if (rcs != GC_OK) return rcs;
+    }
+    const WireSet ws{in, nin, s->skip_scratch.data(), nout};
+    // what the step takes of a group: its wire and table arrays and, an upper bound, its serialised bytes
+    const size_t wbytes = up256((size_t)ent->job.w_tile * 16) + up256((size_t)ent->job.t_tile * 16);
+    const PlaceArgs pa{wbytes + ent->ser_long, &Slot::down_used, fusable, true, s->queue.size(), garble_slot};
+    Placement p;
+    int rcp = place_step(*s, ent, ws, io.ngates, is_deep, follow_lane, pa, &p);
+    if (rcp != GC_OK) return rcp;
+    Slot &g = *s->slots[p.slot];
+    const size_t io_bytes = up16(((size_t)nin + 2 * (size_t)nout) * sizeof(uint32_t));
+    hipError_t e = g.reserve_up(up16(g.up_used) - g.up_used + io_bytes);
+    if (e != hipSuccess) {
+        set_error("gc_stream_garble (pinned)", e);
+        if (is_deep) g.reset();
+        return GC_E_NOMEM;
+    }
+    JobRec j;
+    j.ent = ent;
+    j.nin = nin, j.nout = nout, j.ngates = io.ngates, j.first_tmp = io.first_tmp, j.first_out = io.first_out;
+    g.up_used = up16(g.up_used);
+    j.off_io = g.up_used;
+    uint32_t *iow = (uint32_t *)(g.h_up + g.up_used);
+    if (nin) std::memcpy(iow, in, (size_t)nin * sizeof(uint32_t));
+    if (nout) {
+        std::memcpy(iow + nin, out, (size_t)nout * sizeof(uint32_t));
+        std::memcpy(iow + nin + nout, ws.wr, (size_t)nout * sizeof(uint32_t));
+    }
+    g.up_used += io_bytes;
+    j.off_w = g.arena_used;
+    g.arena_used += up256((size_t)ent->job.w_tile * 16);
+    j.off_t = g.arena_used;
+    g.arena_used += up256((size_t)ent->job.t_tile * 16);
+    j.off_bytes = g.down_used;
+    g.down_used += up16((size_t)ent->ser_long);
+    g.lds = std::max(g.lds, ent->lds);
+    g.has_or = g.has_or || ent->has_or;
+    queue_step(*s, g, p, j, ws, ws.wr);
+    if (is_deep) {
+        int rcl = launch_deep(*s, g, p, ws);
         if (rcl != GC_OK) return rcl;
     }
-    if (ent) ent->last_use = ++s->tick;
-    tr.lap("alias + hash + cache");
+    for (uint32_t k = 0; k < nout; k++)
+        if (ws.wr[k] != 0xffffffffu) s->store.on_dev[out[k]] = 1;
+    s->queue.push_back(StepRef{p.slot, (uint32_t)g.jobs.size() - 1});
+    s->prof.lap(StageProf::kMark);
+    tr.lap(is_deep ? "launched on a lane" : "queued in group");
+    return GC_OK;
+}
 
-    // out[] with "no store" marks (an output wire that is an input wire has no gate: no Set)
-    s->skip_scratch.resize(nout);
-    for (uint32_t j = 0; j < nout; j++) s->skip_scratch[j] = first_out + j >= first_tmp ? out[j] : 0xffffffffu;
-
-    if (ngates && s->win.rec.size() >= s->store.host.size()) {
-        s->win.prefetch(in, nin);
-        s->win.prefetch(out, nout);
-    }
-    s->prof.lap(StageProf::kGuess);  // (alias check, look-up, skip marks)
-    // ---- a small step joins the earliest open group it has no dependency on (or behind); a deep one takes a lane ---------
-    bool is_deep = ngates && entry_is_deep(ent, s->deep.min_steps, known == nullptr) && s->deep.setup(ctx);
-    // A SHORT step that reads or overwrites what a deep step in flight writes or reads FOLLOWS that step onto its lane (as a
-    // deep step of its own: a group of one job, ordered by the lane).  In a group it would make the ctx stream wait for the
-    // deep step — with every group behind it, whether they have anything to do with it or not (an in-order stream); on the
-    // lane only the chain that really depends on the long step waits for it (ssa23: the 256- and 512-bit values chain among
-    // themselves; the ctx stream idled 74 of 286 ms behind multipliers before).
-    int follow_lane = -1;
-    if (!is_deep && ngates && s->deep.n_inflight && s->deep.follow && entry_is_small(ent)) {
-        s->deep.ensure(s->store.host.size());
-        follow_lane = s->deep.lane_to_follow(s->deep.conflicts(in, nin, s->skip_scratch.data(), nout));
-        is_deep = follow_lane >= 0;
-    }
-    if (is_deep || (ngates && entry_is_small(ent))) {
-        // labels the host has set and not uploaded yet go up BEFORE this step's outputs are marked device-owned (the
-        // upload skips device-owned wires: an output that overwrites a host-set input of the same step would lose it) —
-        // and before the step is put anywhere: a failure here leaves nothing half-queued
-        if (!s->store.dirty.empty()) {
-            std::lock_guard<std::mutex> lk(ctx->mu);
-            if (s->df.on) GC_HIP(s->df.join(ctx->stream));  // (the upload overwrites store entries: behind every group launched so far)
-            if (s->df.persist && s->store.host.size() > s->store.cap) s->df.drain();  // (a growing store moves behind a device-wide wait)
-            int rcs = s->store.flush(ctx);
-            if (rcs != GC_OK) return rcs;
-        }
-        s->win.ensure(s->store.host.size());
-        if (is_deep || s->deep.n_inflight) s->deep.ensure(s->store.host.size());
-        const size_t wbytes = up256((size_t)ent->job.w_tile * 16) + up256((size_t)ent->job.t_tile * 16);
-        // Chain fusion (stream_fuse.cpp): when everything the step conflicts with in the latest group it conflicts with at all
-        // (group gi - 1) is ONE launch unit, a short step is appended to that unit — the chain runs as one planned job — instead
-        // of waiting for that whole group in a later one.
-        uint32_t unit = kFuseNone;
-        const uint32_t *skip = s->skip_scratch.data();
-        uint32_t gi = fuse_enabled() ? s->win.place_fuse(in, nin, skip, nout, &unit) : s->win.place(in, nin, skip, nout);
-        const bool may_fuse = fuse_enabled() && !is_deep && !was_aliased && ent->uid != 0 && first_out >= first_tmp;
-        // conflicts with SEVERAL units of that group: which ones (stream_internal.h: kUnitDeps) — a step can still be appended
-        // to the latest of them if that one starts behind all the others, else it joins the group as a unit that waits
-        uint32_t dep_units[kUnitDeps], ndeps = 0;
-        const bool can_wait = fuse_enabled() && s->use_deps && !is_deep && gi > 0;
-        if (can_wait && unit == kFuseMulti) {
-            ndeps = s->win.conflict_units(in, nin, skip, nout, s->win.first_seq + gi - 1, dep_units, kUnitDeps);
-            unit = wg_covering(*s->slots[s->win.open[gi - 1]], dep_units, ndeps);
-        } else if (can_wait) {
-            dep_units[0] = unit, ndeps = 1;
-        }
-        bool fuse = false;
-        uint64_t shape = 0;
-        uint32_t n_ext = 0;
-        if (may_fuse && gi > 0 && unit < kFuseMulti && ngates <= kFuseTailGates) {
-            const Slot &fg = *s->slots[s->win.open[gi - 1]];
-            const WgRec &w = fg.wgs[unit];
-            fuse = w.open && w.n < kFuseMembers && w.gates + ngates <= kFuseGates && w.slots + ent->job.zslot + 1 <= kFuseSlots &&
-                   w.inputs + nin <= kFuseInputs && fg.jobs.size() < kGroupSteps &&
-                   fg.arena_used + fg.down_used + wbytes + ent->ser_long <= kGroupBytes;
-            if (fuse) {
-                // where every input comes from: an earlier step of the unit (the window's record of the wire names it) or the
-                // wire store; and is a chain of this shape known to run too long for one workgroup?
-                const uint32_t seq = s->win.first_seq + gi - 1;
-                s->wiring_scratch.resize(nin);
-                for (uint32_t i = 0; i < nin; i++) {
-                    const GroupWindow::WireRec &r = s->win.rec[in[i]];
-                    if (r.wr == seq && r.wrj == unit) s->wiring_scratch[i] = (fg.jobs[r.wrm >> 20].member << 24) | (r.wrm & 0xfffffu);
-                    else s->wiring_scratch[i] = kFuseNone, n_ext++;
-                }
-                shape = fuse_shape(w.shape, ent, s->wiring_scratch.data());
-                const uint32_t hint = fuse_depth_hint(ctx, shape);
-                fuse = hint ? hint <= fuse_depth_cap() : w.depth_sum + ent->circ->plan.p.n_hash_phases <= 2 * fuse_depth_cap();
-            }
-        }
-        uint32_t slot_idx = 0;
-        auto full = [&](const Slot &g) {
-            return g.wgs.size() >= kGroupJobs || g.jobs.size() >= kGroupSteps ||
-                   g.arena_used + g.down_used + wbytes + ent->ser_long > kGroupBytes;
-        };
-        // not fused: the step still joins the group it conflicts with, as a unit that waits on the device for the units it
-        // conflicts with there (stream_internal.h: kUnitDeps) — where that group has room
-        bool waits = false;
-        if (!fuse && can_wait && !full(*s->slots[s->win.open[gi - 1]])) {
-            waits = true;
-            gi--;
-        }
-        s->prof.lap(StageProf::kPlace);
-        if (fuse || waits) {
-            if (fuse) gi--;
-            slot_idx = s->win.open[gi];
-        } else if (is_deep) {
-            // the open groups this step depends on go to the GPU first (place(): every conflict sits in a group before gi)
-            for (; gi > 0; gi--) {
-                int rcq = launch_oldest(s);
-                if (rcq != GC_OK) return rcq;
-            }
-            s->deep.poll();
-            if (s->deep.n_inflight >= kDeepInFlight) {  // bounded: wait for the oldest deep step of the fullest lane
-                size_t l = 0;
-                for (size_t k = 1; k < s->deep.inflight.size(); k++)
-                    if (s->deep.inflight[k].size() > s->deep.inflight[l].size()) l = k;
-                (void)hipEventSynchronize(s->deep.inflight[l].front().ev);
-                s->deep.poll();
-            }
-            Slot *ng = slot_new(ctx, s->slots, &slot_idx, follow_lane < 0);
-            if (!ng) return GC_E_NOMEM;
-            ng->reset();
-            ng->kind = Slot::kGroup;
-            ng->deep_id = s->deep.new_id();
-            ng->lane = follow_lane >= 0 ? follow_lane : s->deep.pick();
-            ng->deps = s->deep.conflicts(in, nin, s->skip_scratch.data(), nout);
-            deep_after(s->win, s->slots, s->win.last_conflict(in, nin, s->skip_scratch.data(), nout), ng);
-        } else {
-            while (gi < s->win.open.size() && full(*s->slots[s->win.open[gi]])) gi++;
-            if (gi == s->win.open.size()) {  // behind every open group: a new one (the oldest goes to the GPU when the window is full)
-                if (s->win.open.size() >= open_groups_limit(s->queue.size())) {
-                    int rcq = launch_oldest(s);
-                    if (rcq != GC_OK) return rcq;
-                    gi--;
-                }
-                uint32_t idx = 0;
-                Slot *ng = slot_new(ctx, s->slots, &idx);
-                if (!ng) return GC_E_NOMEM;
-                ng->reset();
-                ng->kind = Slot::kGroup;
-                s->win.open.push_back(idx);
-            }
-            slot_idx = s->win.open[gi];
-        }
-        Slot &g = *s->slots[slot_idx];
-        const size_t io_bytes = up16(((size_t)nin + 2 * (size_t)nout) * sizeof(uint32_t));
-        hipError_t e = g.reserve_up(up16(g.up_used) - g.up_used + io_bytes);
-        if (e != hipSuccess) {
-            set_error("gc_stream_garble (pinned)", e);
-            if (is_deep) g.reset();
-            return GC_E_NOMEM;
-        }
-        JobRec j;
-        j.ent = ent;
-        j.nin = nin, j.nout = nout, j.ngates = ngates, j.first_tmp = first_tmp, j.first_out = first_out;
-        g.up_used = up16(g.up_used);
-        j.off_io = g.up_used;
-        uint32_t *io = (uint32_t *)(g.h_up + g.up_used);
-        if (nin) std::memcpy(io, in, (size_t)nin * sizeof(uint32_t));
-        if (nout) {
-            std::memcpy(io + nin, out, (size_t)nout * sizeof(uint32_t));
-            std::memcpy(io + nin + nout, s->skip_scratch.data(), (size_t)nout * sizeof(uint32_t));
-        }
-        g.up_used += io_bytes;
-        j.off_w = g.arena_used;
-        g.arena_used += up256((size_t)ent->job.w_tile * 16);
-        j.off_t = g.arena_used;
-        g.arena_used += up256((size_t)ent->job.t_tile * 16);
-        j.off_bytes = g.down_used;
-        g.down_used += up16((size_t)ent->ser_long);
-        g.lds = std::max(g.lds, ent->lds);
-        g.has_or = g.has_or || ent->has_or;
-        const uint32_t step_idx = (uint32_t)g.jobs.size();
-        if (fuse) {
-            // the wiring goes with the step; outputs of earlier steps of the unit that this one overwrites: their stores are
-            // dropped (launch_group)
-            const uint32_t seq = s->win.first_seq + gi;
-            j.off_wiring = g.wiring.size();
-            g.wiring.insert(g.wiring.end(), s->wiring_scratch.begin(), s->wiring_scratch.begin() + nin);
-            for (uint32_t k = 0; k < nout; k++) {
-                if (skip[k] == 0xffffffffu) continue;
-                const GroupWindow::WireRec &r = s->win.rec[out[k]];
-                if (r.wr == seq && r.wrj == unit) g.kills.emplace_back(r.wrm >> 20, r.wrm & 0xfffffu);
-            }
-            wg_append(g, unit, &j, ent, n_ext, shape);
-            s->fuse.appended++;
-        } else {
-            unit = wg_new(g, &j, ent, may_fuse);
-            if (waits) {
-                wg_wait(g, unit, dep_units, ndeps);
-                s->fuse.waiting++;
-            }
-        }
-        g.jobs.push_back(j);
-        s->prof.lap(StageProf::kQueue);
-        if (!is_deep) {
-            s->win.mark(gi, in, nin, s->skip_scratch.data(), nout, unit, step_idx);
-            // a deep step in flight that this one must follow: the group waits for it (and for the older ones of its lane)
-            if (s->deep.n_inflight) g.deps.merge(s->deep.conflicts(in, nin, s->skip_scratch.data(), nout));
-        }
-        if (is_deep) {  // launched at once, on its lane
-            int rcl = launch_group(ctx, g, false, s->store, s->d_rk, s->d_R, s->rounds, s->copy_stream, s->deep, &s->fuse, false, &s->df);
-            if (rcl != GC_OK) {
-                (void)hipStreamSynchronize(s->deep.lanes[(size_t)g.lane]);
-                s->deep.retire(g.lane, g.deep_id);
-                g.reset();
-                return rcl;
-            }
-            s->deep.mark(g.deep_id, in, nin, s->skip_scratch.data(), nout);
-            s->n_groups++;
-            s->n_group_steps++;
-        }
-        for (uint32_t k = 0; k < nout; k++)
-            if (s->skip_scratch[k] != 0xffffffffu) s->store.on_dev[out[k]] = 1;
-        s->queue.push_back(StepRef{slot_idx, (uint32_t)g.jobs.size() - 1});
-        s->prof.lap(StageProf::kMark);
-        tr.lap(is_deep ? "launched on a lane" : "queued in group");
-        return GC_OK;
-    }
-
-    // ---- a big (or empty) step: its own launch sequence, behind everything queued ------------------------------
+// a big (or empty) step: its own launch sequence — the pass on the ctx stream, the serialiser on its own — behind everything queued
+int garble_big_step(gc_stream *s, const StepIo &io, CircEntry *ent, StreamTrace &tr) {
+    const uint32_t *in = io.in, *out = io.out;
+    const uint32_t nin = io.nin, nout = io.nout, ngates = io.ngates, first_tmp = io.first_tmp, first_out = io.first_out;
+    gc_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
     {
-        int rcq = close_group(s);
+        int rcq = close_group(*s);
         if (rcq != GC_OK) return rcq;
         if (s->deep.n_inflight) {  // a pass on the ctx stream: behind every deep step in flight (DeepLanes)
             s->deep.poll();
             std::lock_guard<std::mutex> lk(ctx->mu);
             GC_HIP(s->deep.wait_all(st));
         }
-        if (s->df.on) {  // ... and behind every group on the rotating streams (Dataflow)
+        if (s->dataflow.on) {  // ... and behind every group on the rotating streams (Dataflow)
             std::lock_guard<std::mutex> lk(ctx->mu);
-            GC_HIP(s->df.join(st));
+            GC_HIP(s->dataflow.join(st));
         }
         if (ngates) {  // ... and later deep steps must see what it reads and writes
             s->win.ensure(s->store.host.size());
-            s->win.mark_pass(in, nin, s->skip_scratch.data(), nout);
+            s->win.mark_pass(WireSet{in, nin, s->skip_scratch.data(), nout});
         }
     }
     uint32_t idx = 0;
@@ -782,17 +556,17 @@ int stream_begin(gc_stream *s, const gc_gate *gates, uint32_t ngates, uint32_t n
     int rc = gc_pass_dev(circ, false, s->key.data(), s->key.size(), &s->r, s->store.d, b.d_io, b.d_io + nin + nout, nullptr, 0, &bt,
                          (const gc::StoreXchg *)(b.d_io + x_off));
     if (rc != GC_OK) return rc;
-    if (s->df.on) {
+    if (s->dataflow.on) {
         // dataflow across launches: the pass has read in[] and written the stored outputs — the wires' counts follow, on the device
         // behind the pass and in the host's mirrors, and every later group launch waits for this point of the ctx stream
         std::lock_guard<std::mutex> lk(ctx->mu);
-        GC_HIP(s->df.ensure(s->store.cap));
-        launch_df_bump(s->df.d_ver, s->df.d_rd, b.d_io, nin, b.d_io + nin + nout, nout, st);
+        GC_HIP(s->dataflow.ensure(s->store.cap));
+        launch_df_bump(s->dataflow.d_ver, s->dataflow.d_rd, b.d_io, nin, b.d_io + nin + nout, nout, st);
         GC_HIP(hipGetLastError());
-        for (uint32_t i = 0; i < nin; i++) s->df.vr[in[i]].rd++;
+        for (uint32_t i = 0; i < nin; i++) s->dataflow.vr[in[i]].rd++;
         for (uint32_t j = 0; j < nout; j++)
-            if (s->skip_scratch[j] != 0xffffffffu) s->df.vr[out[j]].ver++;
-        GC_HIP(s->df.fence_from(st));
+            if (s->skip_scratch[j] != 0xffffffffu) s->dataflow.vr[out[j]].ver++;
+        GC_HIP(s->dataflow.fence_from(st));
     }
     for (uint32_t j = 0; j < nout; j++)
         if (first_out + j >= first_tmp) s->store.on_dev[out[j]] = 1;
@@ -838,6 +612,54 @@ int stream_begin(gc_stream *s, const gc_gate *gates, uint32_t ngates, uint32_t n
     tr.lap("enqueue pass + serialiser");
     return rc;
 }
+
+int stream_begin(gc_stream *s, const gc_gate *gates, uint32_t ngates, uint32_t nwires, const uint32_t *in,
+                 uint32_t nin, const uint32_t *out, uint32_t nout, CircEntry *known) {
+    if (!s || (nin && !in) || (nout && !out)) return GC_E_ARG;
+    s->prof.start();
+    s->n_steps_total++;
+    if (s->queue.size() >= kMaxPending) return GC_E_ARG;
+    // in[] and out[] may overlap (a circuit whose last wires are input wires): initCircuit (:102-114) takes both as they
+    // are, Get / Set resolve a wire through in[] first (:131-157), so such an output id is simply never written
+    if (nin > nwires || nout > nwires) return GC_E_ARG;
+    const uint32_t first_tmp = nin, first_out = nwires - nout;
+    // initCircuit (:102-114)
+    uint32_t mx = 0, in_hi = 0, out_lo = 0xffffffffu, out_hi = 0;
+    for (uint32_t i = 0; i < nin; i++) in_hi = std::max(in_hi, in[i]);
+    for (uint32_t i = 0; i < nout; i++) out_lo = std::min(out_lo, out[i]), out_hi = std::max(out_hi, out[i]);
+    mx = std::max(in_hi, out_hi);
+    ensure(s, mx);
+    // (in[] and out[] can only name a common wire if an input id lies inside the id range of the outputs: as a rule — results
+    // take fresh ids from the allocator, operands and constants lie elsewhere — none does, and the per-wire look of the
+    // aliasing check, two passes over tables the size of the wire store, is skipped)
+    bool ranges_overlap = false;
+    for (uint32_t i = 0; i < nin && nout; i++) ranges_overlap |= in[i] >= out_lo && in[i] <= out_hi;
+    GC_HIP(hipSetDevice(s->ctx->device));
+    StreamTrace tr;
+    const bool was_aliased = ngates && ranges_overlap && rewrite_aliased(s, &gates, ngates, nwires, in, nin, out, nout, &known);
+
+    // device circuit (cached by content); a new circuit is validated once (garbleGate's checks, :195-210)
+    CircEntry *ent = known;
+    if (ngates && !ent) {
+        int rcl = stream_find_or_load(s, gates, ngates, nwires, nin, nout, &ent);
+        if (rcl != GC_OK) return rcl;
+    }
+    if (ent) ent->last_use = ++s->tick;
+    tr.lap("alias + hash + cache");
+
+    // out[] with "no store" marks (an output wire that is an input wire has no gate: no Set)
+    s->skip_scratch.resize(nout);
+    for (uint32_t j = 0; j < nout; j++) s->skip_scratch[j] = first_out + j >= first_tmp ? out[j] : 0xffffffffu;
+
+    if (ngates && s->win.rec.size() >= s->store.host.size()) s->win.prefetch(WireSet{in, nin, out, nout});
+    s->prof.lap(StageProf::kGuess);  // (alias check, look-up, skip marks)
+    const StepIo io{in, out, nin, nout, ngates, first_tmp, first_out};
+    int follow_lane = -1;
+    const bool is_deep = ngates && step_is_deep(*s, ent, WireSet{in, nin, s->skip_scratch.data(), nout}, known == nullptr, true, &follow_lane);
+    if (is_deep || (ngates && entry_is_small(ent)))
+        return queue_small_step(s, io, ent, is_deep, follow_lane, !was_aliased && first_out >= first_tmp, tr);
+    return garble_big_step(s, io, ent, tr);
+}
 }  // namespace
 
 extern "C" {
@@ -875,7 +697,7 @@ static int stream_finish(gc_stream *s, uint8_t *buf, size_t cap, size_t *written
     Slot &g = *s->slots[ref.slot];
     while (g.kind == Slot::kGroup && !g.launched) {  // the oldest step sits in an open group: launch up to that one
         // (the only step queued, in the only open group: the caller garbles one instruction at a time — launch_group)
-        int rc = launch_oldest(s, s->queue.size() == 1 && s->win.open.size() == 1);
+        int rc = launch_oldest(*s, s->queue.size() == 1 && s->win.open.size() == 1);
         if (rc != GC_OK && g.error == GC_OK && g.launched) g.error = rc;
         if (s->win.open.empty()) break;
     }
@@ -892,7 +714,7 @@ static int stream_finish(gc_stream *s, uint8_t *buf, size_t cap, size_t *written
         // leave the GPU with nothing behind it until the caller reaches the NEXT group — and sits through that one's whole
         // kernel, serialiser and copy.)
         while (!s->win.open.empty() && s->ctxq.hungry(s->slots)) {
-            int rcq = launch_oldest(s);
+            int rcq = launch_oldest(*s);
             if (rcq != GC_OK) break;
         }
         (void)hipGetLastError();

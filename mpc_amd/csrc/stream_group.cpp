@@ -1,5 +1,6 @@
-// stream_group.cpp — shared by the streaming garbler and evaluator: the per-stream circuit cache, which circuits one
-// workgroup can run (small / deep), launch slots, and the launch sequence of a step group (see stream_garble.cpp's head).
+// stream_group.cpp — shared by the streaming garbler and evaluator (StreamCore): the per-stream circuit cache, which circuits one
+// workgroup can run (small / deep), launch slots, where a step goes (place_step: group, chain or lane) and the launch sequence
+// of a step group (see stream_garble.cpp's head).
 #include "stream_internal.h"
 
 namespace gcs {
@@ -252,10 +253,17 @@ void launch_df_bump(uint32_t *d_ver, uint32_t *d_rd, const uint32_t *d_in_idx, u
     hipLaunchKernelGGL(k_df_bump, dim3((nin + nout + 255) / 256), dim3(256), 0, st, d_ver, d_rd, d_in_idx, nin, d_out_idx, nout);
 }
 
-int launch_group(gc_ctx *ctx, Slot &g, bool eval, DevStore &store, const uint32_t *d_rk, const uint4 *d_R, int rounds,
-                 hipStream_t copy_stream, DeepLanes &deep, FuseStats *fstats, bool one_stream, Dataflow *df) {
+int launch_group(StreamCore &c, Slot &g, bool one_stream) {
+    gc_ctx *ctx = c.ctx;
+    const bool eval = c.eval;
+    DevStore &store = c.store;
+    DeepLanes &deep = c.deep;
+    const uint32_t *d_rk = c.d_rk;
+    const uint4 *d_R = c.d_R;
+    const int rounds = c.rounds;
+    hipStream_t copy_stream = c.copy_stream;
     const bool on_lane = g.deep_id != 0;
-    if (df && (!df->on || eval)) df = nullptr;
+    Dataflow *df = c.df && c.df->on && !eval ? c.df : nullptr;
     // dataflow across launches (stream_internal.h: Dataflow): the group goes to the next of the rotating streams — nothing orders
     // it against the groups before it but the versions of the wires its units read and write
     uint32_t df_k = 0;
@@ -283,11 +291,9 @@ int launch_group(gc_ctx *ctx, Slot &g, bool eval, DevStore &store, const uint32_
                 mem.push_back(FuseMember{g.jobs[(size_t)k].ent, mem.empty() ? nullptr : g.wiring.data() + g.jobs[(size_t)k].off_wiring});
             bool built = false;
             const FusedPlan *fp = fuse_plan(ctx, eval, mem.data(), (uint32_t)mem.size(), &built);
-            if (fstats) {
-                fstats->units++;
-                fstats->steps += w.n;
-                fstats->built += built;
-            }
+            c.fuse.units++;
+            c.fuse.steps += w.n;
+            c.fuse.built += built;
             if (fp && fp->circ) {
                 plans[u] = fp;
                 nrec++;
@@ -298,7 +304,7 @@ int launch_group(gc_ctx *ctx, Slot &g, bool eval, DevStore &store, const uint32_
                 has_or = has_or || fp->has_or;
             } else {
                 nrec += w.n;
-                if (fstats) (fp ? fstats->unfit : fstats->unplanned)++;
+                (fp ? c.fuse.unfit : c.fuse.unplanned)++;
             }
         }
     }
@@ -705,6 +711,183 @@ int launch_group(gc_ctx *ctx, Slot &g, bool eval, DevStore &store, const uint32_
     }
     if (tl) tl->h_l1 = group_timeline().now();
     if (e != hipSuccess) return fail("launch_group", e);
+    return GC_OK;
+}
+
+int launch_oldest(StreamCore &c, bool one_stream) {
+    if (c.win.open.empty()) return GC_OK;
+    const uint32_t seq = c.win.first_seq, slot = c.win.pop();
+    Slot &g = *c.slots[slot];
+    c.n_groups++;
+    c.n_group_steps += g.jobs.size();
+    c.prof.lap(StageProf::kOther);
+    const int rc = launch_group(c, g, one_stream);
+    c.prof.lap(StageProf::kLaunch);
+    if (c.chunks_launched && !g.chunk_refs.empty()) c.chunks_launched(c, g, slot);
+    c.win.note(seq, slot, g.launch_no);
+    if (rc == GC_OK) c.ctxq.pushed(slot, g.launch_no);
+    return rc;
+}
+int close_group(StreamCore &c) {
+    int rc = GC_OK;
+    while (!c.win.open.empty()) {
+        const int r = launch_oldest(c);
+        if (rc == GC_OK) rc = r;
+    }
+    return rc;
+}
+
+// BEFORE a step's outputs are marked device-owned (the upload skips device-owned wires: an output that overwrites a host-set
+// input of the same step would lose it) — and before the step is put anywhere: a failure here leaves nothing half-queued
+int flush_store(StreamCore &c) {
+    std::lock_guard<std::mutex> lk(c.ctx->mu);
+    if (c.df && c.df->on) GC_HIP(c.df->join(c.ctx->stream));  // (the upload overwrites store entries: behind every group launched so far)
+    if (c.df && c.df->persist && c.store.host.size() > c.store.cap) c.df->drain();  // (a growing store moves behind a device-wide wait)
+    return c.store.flush(c.ctx);
+}
+
+int place_step(StreamCore &c, CircEntry *ent, const WireSet &ws, uint32_t ngates, bool is_deep, int follow_lane, const PlaceArgs &a,
+               Placement *p) {
+    c.win.ensure(c.store.host.size());
+    if (is_deep || c.deep.n_inflight) c.deep.ensure(c.store.host.size());
+    p->deep = is_deep;
+    // Chain fusion (stream_fuse.cpp): when everything the step conflicts with in the latest group it conflicts with at all
+    // (group gi - 1) is ONE launch unit, a short step is appended to that unit — the chain runs as one planned job — instead
+    // of waiting for that whole group in a later one.
+    uint32_t unit = kFuseNone;
+    uint32_t gi = fuse_enabled() ? c.win.place_fuse(ws, &unit) : c.win.place(ws);
+    const bool may_fuse = p->may_fuse = fuse_enabled() && !is_deep && a.fusable && ent->uid != 0;
+    // conflicts with SEVERAL units of that group: which ones (stream_internal.h: kUnitDeps) — a step can still be appended
+    // to the latest of them if that one starts behind all the others, else it joins the group as a unit that waits
+    const bool can_wait = fuse_enabled() && c.use_deps && !is_deep && a.waitable && gi > 0;
+    if (can_wait && unit == kFuseMulti) {
+        p->ndeps = c.win.conflict_units(ws, c.win.first_seq + gi - 1, p->dep_units, kUnitDeps);
+        unit = wg_covering(*c.slots[c.win.open[gi - 1]], p->dep_units, p->ndeps);
+    } else if (can_wait) {
+        p->dep_units[0] = unit, p->ndeps = 1;
+    }
+    auto full = [&](const Slot &g) {
+        return g.wgs.size() >= kGroupJobs || g.jobs.size() >= kGroupSteps || g.arena_used + g.*a.beside_arena + a.group_bytes > kGroupBytes;
+    };
+    bool fuse = false;
+    if (may_fuse && gi > 0 && unit < kFuseMulti && ngates <= kFuseTailGates) {
+        const Slot &fg = *c.slots[c.win.open[gi - 1]];
+        const WgRec &w = fg.wgs[unit];
+        fuse = w.open && w.n < kFuseMembers && w.gates + ngates <= kFuseGates && w.slots + ent->job.zslot + 1 <= kFuseSlots &&
+               w.inputs + ws.nrd <= kFuseInputs && fg.jobs.size() < kGroupSteps &&
+               fg.arena_used + fg.*a.beside_arena + a.group_bytes <= kGroupBytes;
+        if (fuse) {
+            // where every input comes from: an earlier step of the unit (the window's record of the wire names it) or the
+            // wire store; and is a chain of this shape known to run too long for one workgroup?
+            const uint32_t seq = c.win.first_seq + gi - 1;
+            c.wiring_scratch.resize(ws.nrd);
+            for (uint32_t i = 0; i < ws.nrd; i++) {
+                const GroupWindow::WireRec &r = c.win.rec[ws.rd[i]];
+                if (r.wr == seq && r.wrj == unit) c.wiring_scratch[i] = (fg.jobs[r.wrm >> 20].member << 24) | (r.wrm & 0xfffffu);
+                else c.wiring_scratch[i] = kFuseNone, p->n_ext++;
+            }
+            p->shape = fuse_shape(w.shape, ent, c.wiring_scratch.data());
+            const uint32_t hint = fuse_depth_hint(c.ctx, p->shape);
+            fuse = hint ? hint <= fuse_depth_cap() : w.depth_sum + ent->circ->plan.p.n_hash_phases <= 2 * fuse_depth_cap();
+        }
+    }
+    // not fused: the step still joins the group it conflicts with, as a unit that waits on the device for the units it
+    // conflicts with there (stream_internal.h: kUnitDeps) — where that group has room
+    bool waits = false;
+    if (!fuse && can_wait && !full(*c.slots[c.win.open[gi - 1]])) {
+        waits = true;
+        gi--;
+    }
+    c.prof.lap(StageProf::kPlace);
+    if (fuse || waits) {
+        if (fuse) gi--;
+        p->slot = c.win.open[gi];
+    } else if (is_deep) {
+        // the open groups this step depends on go to the GPU first (place(): every conflict sits in a group before gi)
+        for (; gi > 0; gi--) {
+            int rcq = launch_oldest(c);
+            if (rcq != GC_OK) return rcq;
+        }
+        c.deep.poll();
+        if (c.deep.n_inflight >= kDeepInFlight) {  // bounded: wait for the oldest deep step of the fullest lane
+            size_t l = 0;
+            for (size_t k = 1; k < c.deep.inflight.size(); k++)
+                if (c.deep.inflight[k].size() > c.deep.inflight[l].size()) l = k;
+            (void)hipEventSynchronize(c.deep.inflight[l].front().ev);
+            c.deep.poll();
+        }
+        Slot *ng = a.take_slot(c, &p->slot, follow_lane < 0);
+        if (!ng) return GC_E_NOMEM;
+        ng->reset();
+        ng->kind = Slot::kGroup;
+        ng->deep_id = c.deep.new_id();
+        ng->lane = follow_lane >= 0 ? follow_lane : c.deep.pick();
+        ng->deps = c.deep.conflicts(ws);
+        deep_after(c.win, c.slots, c.win.last_conflict(ws), ng);
+    } else {
+        while (gi < c.win.open.size() && full(*c.slots[c.win.open[gi]])) gi++;
+        if (gi == c.win.open.size()) {  // behind every open group: a new one (the oldest goes to the GPU when the window is full)
+            if (c.win.open.size() >= open_groups_limit(a.in_flight)) {
+                int rcq = launch_oldest(c);
+                if (rcq != GC_OK) return rcq;
+                gi--;
+            }
+            uint32_t idx = 0;
+            Slot *ng = a.take_slot(c, &idx, false);
+            if (!ng) return GC_E_NOMEM;
+            ng->reset();
+            ng->kind = Slot::kGroup;
+            c.win.open.push_back(idx);
+        }
+        p->slot = c.win.open[gi];
+    }
+    p->gi = gi, p->unit = unit, p->fused = fuse, p->waits = waits;
+    return GC_OK;
+}
+
+void queue_step(StreamCore &c, Slot &g, Placement &p, JobRec &j, const WireSet &ws, const uint32_t *stored) {
+    const uint32_t step_idx = (uint32_t)g.jobs.size();
+    if (p.fused) {
+        // the wiring goes with the step; outputs of earlier steps of the unit that this one overwrites: their stores are
+        // dropped (launch_group)
+        const uint32_t seq = c.win.first_seq + p.gi;
+        j.off_wiring = g.wiring.size();
+        g.wiring.insert(g.wiring.end(), c.wiring_scratch.begin(), c.wiring_scratch.begin() + ws.nrd);
+        for (uint32_t k = 0; k < ws.nwr; k++) {
+            if (stored[k] == 0xffffffffu) continue;
+            const GroupWindow::WireRec &r = c.win.rec[ws.wr[k]];
+            if (r.wr == seq && r.wrj == p.unit) g.kills.emplace_back(r.wrm >> 20, r.wrm & 0xfffffu);
+        }
+        wg_append(g, p.unit, &j, j.ent, p.n_ext, p.shape);
+        c.fuse.appended++;
+    } else {
+        p.unit = wg_new(g, &j, j.ent, p.may_fuse);
+        if (p.waits) {
+            wg_wait(g, p.unit, p.dep_units, p.ndeps);
+            c.fuse.waiting++;
+        }
+    }
+    g.jobs.push_back(j);
+    c.prof.lap(StageProf::kQueue);
+    if (!p.deep) {
+        c.win.mark(p.gi, ws, p.unit, step_idx);
+        // a deep step in flight that this one must follow: the group waits for it (and for the older ones of its lane)
+        if (c.deep.n_inflight) g.deps.merge(c.deep.conflicts(ws));
+    }
+}
+
+int launch_deep(StreamCore &c, Slot &g, const Placement &p, const WireSet &ws) {
+    const int rc = launch_group(c, g, false);
+    if (c.chunks_launched && !g.chunk_refs.empty()) c.chunks_launched(c, g, p.slot);
+    if (rc != GC_OK) {
+        (void)hipStreamSynchronize(c.deep.lanes[(size_t)g.lane]);
+        c.deep.retire(g.lane, g.deep_id);
+        g.reset();
+        return rc;
+    }
+    c.deep.mark(g.deep_id, ws);
+    c.n_groups++;
+    c.n_group_steps++;
     return GC_OK;
 }
 

@@ -763,6 +763,14 @@ struct Dataflow {
 void launch_df_bump(uint32_t *d_ver, uint32_t *d_rd, const uint32_t *d_in_idx, uint32_t nin, const uint32_t *d_out_idx, uint32_t nout,
                     hipStream_t st);
 
+// the global wires a step reads and writes (writes may hold 0xffffffff: nothing stored)
+struct WireSet {
+    const uint32_t *rd;
+    uint32_t nrd;
+    const uint32_t *wr;
+    uint32_t nwr;
+};
+
 struct GroupWindow {
     std::deque<uint32_t> open;      // slots of the open groups, oldest first
     uint32_t first_seq = 1;         // sequence number of open.front()
@@ -778,20 +786,22 @@ struct GroupWindow {
     }
     // the records of these wires on their way into the cache (a step names a few hundred wires spread over a table of tens of
     // megabytes: the look-ups below are a chain of cache misses unless the loads are in flight together)
-    void prefetch(const uint32_t *wires, uint32_t n) const {
-        for (uint32_t i = 0; i < n; i += 3)  // (consecutive ids share cache lines: every third record is enough)
-            if (wires[i] < rec.size()) __builtin_prefetch(&rec[wires[i]]);
+    void prefetch(const WireSet &ws) const {
+        for (uint32_t i = 0; i < ws.nrd; i += 3)  // (consecutive ids share cache lines: every third record is enough)
+            if (ws.rd[i] < rec.size()) __builtin_prefetch(&rec[ws.rd[i]]);
+        for (uint32_t j = 0; j < ws.nwr; j += 3)
+            if (ws.wr[j] < rec.size()) __builtin_prefetch(&rec[ws.wr[j]]);
     }
     // index into `open` of the earliest group the step may join (== open.size(): it needs a new group)
-    uint32_t place(const uint32_t *reads, uint32_t nr, const uint32_t *writes, uint32_t nw) const {
+    uint32_t place(const WireSet &ws) const {
         uint32_t lo = first_seq;
-        for (uint32_t i = 0; i < nr; i++) {
-            const uint32_t w = rec[reads[i]].wr;
+        for (uint32_t i = 0; i < ws.nrd; i++) {
+            const uint32_t w = rec[ws.rd[i]].wr;
             if (w >= lo) lo = w + 1;  // read after write
         }
-        for (uint32_t j = 0; j < nw; j++) {
-            if (writes[j] == 0xffffffffu) continue;
-            const uint32_t w = rec[writes[j]].wr, r = rec[writes[j]].rd;
+        for (uint32_t j = 0; j < ws.nwr; j++) {
+            if (ws.wr[j] == 0xffffffffu) continue;
+            const uint32_t w = rec[ws.wr[j]].wr, r = rec[ws.wr[j]].rd;
             if (w >= lo) lo = w + 1;  // write after write
             if (r >= lo) lo = r + 1;  // write after read
         }
@@ -800,20 +810,20 @@ struct GroupWindow {
     // place(), and chain fusion's question in the same walk: do ALL the step's conflicts with the latest open group it has any
     // with (the group before the one place() names) sit in ONE launch unit?  *unit = that unit, kFuseMulti if there are
     // several, kFuseNone if the step conflicts with nothing in the window.
-    uint32_t place_fuse(const uint32_t *reads, uint32_t nr, const uint32_t *writes, uint32_t nw, uint32_t *unit) const {
+    uint32_t place_fuse(const WireSet &ws, uint32_t *unit) const {
         uint32_t best = 0, bj = kFuseNone;
         auto consider = [&](uint32_t seq, uint32_t job) {
             if (seq < first_seq) return;
             if (seq > best) best = seq, bj = job;
             else if (seq == best && job != bj) bj = kFuseMulti;
         };
-        for (uint32_t i = 0; i < nr; i++) {
-            const WireRec &r = rec[reads[i]];
+        for (uint32_t i = 0; i < ws.nrd; i++) {
+            const WireRec &r = rec[ws.rd[i]];
             consider(r.wr, r.wrj);
         }
-        for (uint32_t j = 0; j < nw; j++) {
-            if (writes[j] == 0xffffffffu) continue;
-            const WireRec &r = rec[writes[j]];
+        for (uint32_t j = 0; j < ws.nwr; j++) {
+            if (ws.wr[j] == 0xffffffffu) continue;
+            const WireRec &r = rec[ws.wr[j]];
             consider(r.wr, r.wrj);
             consider(r.rd, r.rdj);
         }
@@ -823,8 +833,7 @@ struct GroupWindow {
     // The units of the open group with sequence number `seq` that the step conflicts with (distinct, at most `max`), for a
     // step that joins that group as a unit that waits for them.  Returns their number, or kDepsAllEarlier where the records
     // cannot name them (a wire several units read; more than `max`).
-    uint32_t conflict_units(const uint32_t *reads, uint32_t nr, const uint32_t *writes, uint32_t nw, uint32_t seq, uint32_t *units,
-                            uint32_t max) const {
+    uint32_t conflict_units(const WireSet &ws, uint32_t seq, uint32_t *units, uint32_t max) const {
         uint32_t n = 0;
         bool all = false;
         auto add = [&](uint32_t u) {
@@ -837,30 +846,29 @@ struct GroupWindow {
             if (n < max) units[n++] = u;
             else all = true;
         };
-        for (uint32_t i = 0; i < nr && !all; i++) {
-            const WireRec &r = rec[reads[i]];
+        for (uint32_t i = 0; i < ws.nrd && !all; i++) {
+            const WireRec &r = rec[ws.rd[i]];
             if (r.wr == seq) add(r.wrj);
         }
-        for (uint32_t j = 0; j < nw && !all; j++) {
-            if (writes[j] == 0xffffffffu) continue;
-            const WireRec &r = rec[writes[j]];
+        for (uint32_t j = 0; j < ws.nwr && !all; j++) {
+            if (ws.wr[j] == 0xffffffffu) continue;
+            const WireRec &r = rec[ws.wr[j]];
             if (r.wr == seq) add(r.wrj);
             if (r.rd == seq) add(r.rdj);
         }
         return all ? kDepsAllEarlier : n;
     }
     // unit / step: the launch unit of the group that the step is (part of), and its index among the group's steps
-    void mark(uint32_t index, const uint32_t *reads, uint32_t nr, const uint32_t *writes, uint32_t nw, uint32_t unit = 0,
-              uint32_t step = 0) {
+    void mark(uint32_t index, const WireSet &ws, uint32_t unit = 0, uint32_t step = 0) {
         const uint32_t seq = first_seq + index;
-        for (uint32_t i = 0; i < nr; i++) {
-            WireRec &r = rec[reads[i]];
+        for (uint32_t i = 0; i < ws.nrd; i++) {
+            WireRec &r = rec[ws.rd[i]];
             if (r.rd < seq) r.rd = seq, r.rdj = unit;
             else if (r.rd == seq && r.rdj != unit) r.rdj = kFuseMulti;
         }
-        for (uint32_t j = 0; j < nw; j++)
-            if (writes[j] != 0xffffffffu) {
-                WireRec &r = rec[writes[j]];
+        for (uint32_t j = 0; j < ws.nwr; j++)
+            if (ws.wr[j] != 0xffffffffu) {
+                WireRec &r = rec[ws.wr[j]];
                 r.wr = seq, r.wrj = unit, r.wrm = (step << 20) | j;
                 // (who read the wire before this write is of no interest any more: whoever conflicts with them conflicts
                 // with this writer, which is behind them)
@@ -878,17 +886,17 @@ struct GroupWindow {
     void note(uint32_t seq, uint32_t slot, uint64_t launch_no) { ring[seq & 63u] = Launched{seq, slot, launch_no}; }
     // sequence number of the latest group — open, launched or long gone — with a step that the step with these reads / writes
     // must follow (0: none)
-    uint32_t last_conflict(const uint32_t *reads, uint32_t nr, const uint32_t *writes, uint32_t nw) const {
+    uint32_t last_conflict(const WireSet &ws) const {
         uint32_t q = 0;
-        for (uint32_t i = 0; i < nr; i++) q = std::max(q, rec[reads[i]].wr);
-        for (uint32_t j = 0; j < nw; j++)
-            if (writes[j] != 0xffffffffu) q = std::max(q, std::max(rec[writes[j]].wr, rec[writes[j]].rd));
+        for (uint32_t i = 0; i < ws.nrd; i++) q = std::max(q, rec[ws.rd[i]].wr);
+        for (uint32_t j = 0; j < ws.nwr; j++)
+            if (ws.wr[j] != 0xffffffffu) q = std::max(q, std::max(rec[ws.wr[j]].wr, rec[ws.wr[j]].rd));
         return q;
     }
     // a pass of the ctx stream that is no group (the window is empty: everything queued was launched in front of it) takes a
     // sequence number of its own, so that later deep steps see what it reads and writes
-    void mark_pass(const uint32_t *reads, uint32_t nr, const uint32_t *writes, uint32_t nw) {
-        mark(0, reads, nr, writes, nw);
+    void mark_pass(const WireSet &ws) {
+        mark(0, ws);
         note(first_seq, 0xffffffffu, 0);
         first_seq++;
     }
@@ -1019,23 +1027,23 @@ struct DeepLanes {
         return f;
     }
     // the deep steps in flight that a step with these reads / writes depends on
-    DeepDeps conflicts(const uint32_t *reads, uint32_t nr, const uint32_t *writes, uint32_t nw) const {
+    DeepDeps conflicts(const WireSet &ws) const {
         DeepDeps d;
         if (n_inflight == 0 || rd.empty()) return d;
         const uint32_t fl = floor();
-        for (uint32_t i = 0; i < nr; i++)
-            if (wr[reads[i]] > fl) d.add(wr[reads[i]]);  // read after write
-        for (uint32_t j = 0; j < nw; j++) {
-            if (writes[j] == 0xffffffffu) continue;
-            if (wr[writes[j]] > fl) d.add(wr[writes[j]]);                                      // write after write
-            if (rd[writes[j]] > fl && rd[writes[j]] > wr[writes[j]]) d.upto = std::max(d.upto, rd[writes[j]]);  // write after read
+        for (uint32_t i = 0; i < ws.nrd; i++)
+            if (wr[ws.rd[i]] > fl) d.add(wr[ws.rd[i]]);  // read after write
+        for (uint32_t j = 0; j < ws.nwr; j++) {
+            if (ws.wr[j] == 0xffffffffu) continue;
+            if (wr[ws.wr[j]] > fl) d.add(wr[ws.wr[j]]);                                      // write after write
+            if (rd[ws.wr[j]] > fl && rd[ws.wr[j]] > wr[ws.wr[j]]) d.upto = std::max(d.upto, rd[ws.wr[j]]);  // write after read
         }
         return d;
     }
-    void mark(uint32_t id, const uint32_t *reads, uint32_t nr, const uint32_t *writes, uint32_t nw) {
-        for (uint32_t i = 0; i < nr; i++) rd[reads[i]] = id;
-        for (uint32_t j = 0; j < nw; j++)
-            if (writes[j] != 0xffffffffu) wr[writes[j]] = id;
+    void mark(uint32_t id, const WireSet &ws) {
+        for (uint32_t i = 0; i < ws.nrd; i++) rd[ws.rd[i]] = id;
+        for (uint32_t j = 0; j < ws.nwr; j++)
+            if (ws.wr[j] != 0xffffffffu) wr[ws.wr[j]] = id;
     }
     // steps whose kernels have run leave the lists (cheap: one query per lane head)
     void poll() {
@@ -1287,8 +1295,111 @@ void wg_wait(Slot &g, uint32_t unit, const uint32_t *units, uint32_t n);
 bool entry_is_small(CircEntry *e);
 bool entry_is_deep(CircEntry *e, uint32_t min_steps, bool in_stream);
 Slot *slot_new(gc_ctx *ctx, std::vector<std::unique_ptr<Slot>> &slots, uint32_t *index, bool big = false);
+
+// ---- what the streaming garbler and evaluator share: state, launches, the placement of a step (stream_group.cpp) ---------
+// gc_stream and gc_stream_eval derive from it and add what is theirs (the queue of steps in flight, serialiser streams and
+// alias scratch there; parser scratch, skeletons, the pinned ring and the device-side match here).
+struct StreamCore {
+    gc_ctx *ctx = nullptr;
+    bool eval = false;            // the evaluator: table rows go up with a group and nothing comes back
+    std::vector<uint8_t> key;
+    int rounds = 0;
+    uint32_t *d_rk = nullptr;     // expanded key (60 words) on the device: the step groups' kernels read it
+    uint4 *d_R = nullptr;         // garbler: R on the device
+    DevStore store;               // global wire -> label (garbler: L0, L1 = L0 ^ R), device-resident
+    CircCache cache;
+    size_t cache_gates = 0, cache_budget = kCacheGatesDefault;
+    uint64_t tick = 0;
+    std::vector<std::unique_ptr<Slot>> slots;
+    GroupWindow win;              // the groups still accepting steps
+    CtxQueue ctxq;                // ... and the launched ones the ctx stream has not run yet
+    DeepLanes deep;               // long one-workgroup steps run beside the groups, on streams of their own
+    FuseStats fuse;               // chain fusion (stream_fuse.cpp): launch units of several steps, merged plans built
+    bool use_deps = deps_wanted();         // units that wait inside a launch (kUnitDeps)
+    std::vector<uint32_t> wiring_scratch;  // chain fusion: the input sources of the step being queued
+    hipStream_t copy_stream = nullptr;     // garbler: serialiser and bytes of a group, beside the next group's kernel
+    Dataflow *df = nullptr;       // garbler: units ordered by the versions of their wires (GC_STREAM_DATAFLOW); null: the evaluator
+    StageProf prof;
+    uint64_t n_groups = 0, n_group_steps = 0;
+    // big steps: the batch (table buffer) of the last one is held out of its circuit's pool until the next has taken its own
+    gc_circ *held_circ = nullptr;
+    gc_batch *held = nullptr;
+    // per-GROUP hook, after the launch of a group whose jobs gather rows from chunks of the peer's stream (Slot::chunk_refs;
+    // the evaluator's device-side match) — also after a launch that failed; null: the garbler
+    void (*chunks_launched)(StreamCore &c, Slot &g, uint32_t slot) = nullptr;
+};
+
 void deep_after(const GroupWindow &win, const std::vector<std::unique_ptr<Slot>> &slots, uint32_t cs, Slot *ng);
-int launch_group(gc_ctx *ctx, Slot &g, bool eval, DevStore &store, const uint32_t *d_rk, const uint4 *d_R, int rounds,
-                 hipStream_t copy_stream, DeepLanes &deep, FuseStats *fstats, bool one_stream = false, Dataflow *df = nullptr);
+int launch_group(StreamCore &c, Slot &g, bool one_stream);
+// the oldest open group leaves the window and is launched; close_group: everything queued, in order (a read-back, a big step
+// or the caller's flush follows)
+int launch_oldest(StreamCore &c, bool one_stream = false);
+int close_group(StreamCore &c);
+// labels the host has set and not uploaded yet (store.dirty) go up (Dataflow: behind every group launched so far)
+int flush_store(StreamCore &c);
+
+// Is the step deep (a lane of its own), or — may_follow — a short one that FOLLOWS a deep step in flight onto its lane
+// (*follow_lane >= 0)?  in_stream: entry_is_deep.
+// A SHORT step that reads or overwrites what a deep step in flight writes or reads FOLLOWS that step onto its lane (as a
+// deep step of its own: a group of one job, ordered by the lane).  In a group it would make the ctx stream wait for the
+// deep step — with every group behind it, whether they have anything to do with it or not (an in-order stream); on the
+// lane only the chain that really depends on the long step waits for it (ssa23: the 256- and 512-bit values chain among
+// themselves; the ctx stream idled 74 of 286 ms behind multipliers before).
+inline bool step_is_deep(StreamCore &c, CircEntry *ent, const WireSet &ws, bool in_stream, bool may_follow, int *follow_lane) {
+    if (entry_is_deep(ent, c.deep.min_steps, in_stream) && c.deep.setup(c.ctx)) return true;
+    if (may_follow && c.deep.n_inflight && c.deep.follow && entry_is_small(ent)) {
+        c.deep.ensure(c.store.host.size());
+        *follow_lane = c.deep.lane_to_follow(c.deep.conflicts(ws));
+    }
+    return *follow_lane >= 0;
+}
+
+// Where the two sides differ in placing a small or deep step
+struct PlaceArgs {
+    size_t group_bytes;          // what the step adds to a group's kGroupBytes: arrays in the arena + ...
+    size_t Slot::*beside_arena;  // ... what the group holds beside the arena (garbler: bytes down, evaluator: rows up)
+    bool fusable, waitable;      // may be appended to a chain / join a group as a unit that waits (beyond what holds on both sides)
+    size_t in_flight;            // what open_groups_limit sizes the window by
+    Slot *(*take_slot)(StreamCore &c, uint32_t *index, bool big);  // a free slot (per group, and per deep step)
+};
+struct Placement {
+    uint32_t slot = 0, gi = 0;   // the slot of the group (deep: of the step) and the group's index in the window
+    bool fused = false, waits = false, deep = false, may_fuse = false;
+    uint32_t unit = kFuseNone;   // fused: the unit it is appended to
+    uint32_t dep_units[kUnitDeps], ndeps = 0;  // waits: the units it waits for
+    uint64_t shape = 0;          // fused: the unit's shape with this step, and how many of its inputs come from the wire store
+    uint32_t n_ext = 0;
+};
+// The step joins the earliest open group it has no dependency on (or behind), is appended to the one unit it depends on
+// (chain fusion), joins that unit's group as a unit that waits, or — deep — takes a lane: the open groups it depends on are
+// launched, a slot of its own is set up.  c.wiring_scratch holds a fused step's input sources.  Nothing is queued yet.
+int place_step(StreamCore &c, CircEntry *ent, const WireSet &ws, uint32_t ngates, bool is_deep, int follow_lane, const PlaceArgs &a,
+               Placement *p);
+// The step (its JobRec filled but for the unit) becomes part of group g as placed: wiring and dropped stores of a fused step,
+// its launch unit, the window's records.  stored[k] == 0xffffffff: output k is not stored.
+void queue_step(StreamCore &c, Slot &g, Placement &p, JobRec &j, const WireSet &ws, const uint32_t *stored);
+// a deep step, queued: launched at once, on its lane (a failure leaves the lane drained and the slot free)
+int launch_deep(StreamCore &c, Slot &g, const Placement &p, const WireSet &ws);
+
+// the stats getters of the two C ABIs
+inline int fuse_stats(const StreamCore *c, uint64_t *units, uint64_t *steps, uint64_t *built, uint64_t *unfit) {
+    if (!c) return GC_E_ARG;
+    if (units) *units = c->fuse.units;
+    if (steps) *steps = c->fuse.steps;
+    if (built) *built = c->fuse.built;
+    if (unfit) *unfit = c->fuse.unfit;
+    return GC_OK;
+}
+inline int wait_stats(const StreamCore *c, uint64_t *waiting_units) {
+    if (!c) return GC_E_ARG;
+    if (waiting_units) *waiting_units = c->fuse.waiting;
+    return GC_OK;
+}
+inline int deep_stats(const StreamCore *c, uint64_t *deep_steps, uint32_t *lanes) {
+    if (!c) return GC_E_ARG;
+    if (deep_steps) *deep_steps = c->deep.n_steps;
+    if (lanes) *lanes = c->deep.state > 0 ? (uint32_t)c->deep.lanes.size() : 0;
+    return GC_OK;
+}
 
 }  // namespace gcs
