@@ -1,12 +1,15 @@
 """GMW party engine on the GPU (gc_gmw_*, mpc_amd/csrc/gmw_engine.cpp + gmw_kernels.hip) against the plain-Python
 restatement of the reference (tests/py_gmw_reference.py): every step's message (padding bits included), the output shares,
-the plaintext result, the launch count; the Beaver-triple folds on real bit-COT outputs; an end-to-end AES pass on
-device-made triples; misuse."""
+the plaintext result, the launch count, for every instance of the batch; the circuits of tests/gmw_cases.py (the ones the
+host walk of tests/test_gmw_plan_walk.py runs on the CPU); several passes on one handle, abandoned ones and misuse between
+them; 2^20 instances of aes_128; the Beaver-triple folds on real bit-COT outputs and past one sweep of their grid; an
+end-to-end AES pass on device-made triples; misuse."""
 import numpy as np
 import pytest
 
 import oracle
 from mpc_amd import engine
+from tests import gmw_cases as G
 from tests import py_gmw_reference as R
 from tests.test_gpu_ot import base_setup
 
@@ -40,29 +43,43 @@ def _round_words(c):
     return [int(w) for w in wl if w]
 
 
-def _run_host(parties, inputs, triples):
-    """one pass of every party through the host forms; returns (msgs[p] = [(level, [2][w][batch])], outs[p])"""
+def _host_steps(parties, msgs, cur, limit=None):
+    """host-form steps of every party, round by round, until the pass ends (True) or `limit` rounds were made (False);
+    msgs[p] grows by (level, [2][w][batch]) per round, cur holds the last round's messages"""
     P = len(parties)
-    for g, x, t in zip(parties, inputs, triples):
-        g.set_inputs(x)
-        g.set_triples(*t)
-    msgs = [[] for _ in range(P)]
-    cur = [None] * P
-    while True:
+    done = 0
+    while limit is None or done < limit:
         new = []
         for p, g in enumerate(parties):
             peers = None if cur[0] is None else np.stack([cur[q] for q in range(P) if q != p])
             new.append(g.step(peers))
         if new[0][1].shape[1] == 0:
             assert all(m.shape[1] == 0 for _, m in new)
-            break
+            return True
         for p in range(P):
             msgs[p].append(new[p])
-        cur = [m for _, m in new]
+        cur[:] = [m for _, m in new]
+        done += 1
+    return False
+
+
+def _run_host(parties, inputs, triples, limit=None):
+    """one pass of every party through the host forms; returns (msgs[p] = [(level, [2][w][batch])], outs[p]).  With `limit`
+    the pass is left after that many rounds: (msgs, None)."""
+    P = len(parties)
+    for g, x, t in zip(parties, inputs, triples):
+        g.set_inputs(x)
+        g.set_triples(*t)
+    msgs = [[] for _ in range(P)]
+    cur = [None] * P
+    if limit is not None:
+        assert not _host_steps(parties, msgs, cur, limit)
+        return msgs, None
+    assert _host_steps(parties, msgs, cur)
     return msgs, [g.get_outputs() for g in parties]
 
 
-def _run_dev(ctx, c, parties, inputs, triples):
+def _run_dev(ctx, c, parties, inputs, triples, limit=None):
     """the same through the _dev forms, messages passed device-side through a double-buffered exchange area: party p writes
     slot p, slots 0 .. P-2 are copied behind slot P-1, so party p's peers are the P-1 slots after its own"""
     P, batch = len(parties), parties[0].batch
@@ -78,7 +95,7 @@ def _run_dev(ctx, c, parties, inputs, triples):
         g.set_triples_dev(*t)
     msgs = [[] for _ in range(P)]
     r = 0
-    while True:
+    while limit is None or r < limit:
         w_prev = ws[r - 1] if r else 0
         w = ws[r] if r < len(ws) else 0
         src, dst = xch[(r + 1) & 1], xch[r & 1]
@@ -98,8 +115,11 @@ def _run_dev(ctx, c, parties, inputs, triples):
         for p in range(P):
             msgs[p].append((level, host[p]))
         r += 1
-    outs = []
+    outs = [] if limit is None else None
     for p, g in enumerate(parties):
+        if limit is not None:  # the pass is left here; the handle's triple pointers die with the buffers below
+            assert r == limit
+            break
         g.get_outputs_dev(d_out[p])
         outs.append(d_out[p].download(np.uint64, None, 0, outw * batch * 8).reshape(outw, batch))
     for b in d_in + [x for t in d_t for x in t] + xch + d_out:
@@ -108,21 +128,27 @@ def _run_dev(ctx, c, parties, inputs, triples):
 
 
 def _check_pass(c, P, batch, seed, msgs, outs, bits, shares, trip, launches):
-    rng = np.random.default_rng(seed + 1)
-    idx = _sample(batch, rng)
-    ref_msgs, ref_outs = R.run_parties(c, [s[:, idx] for s in shares], [tuple(x[:, idx] for x in t) for t in trip])
+    """every instance of the batch: the messages of every level (whole words, padding bits included) and the output shares
+    against R.run_parties (vectorised over the batch), the XOR of the output shares against the plaintext in the bucketed
+    order, (level, words) of every round, and the launch count"""
+    ref_msgs, ref_outs = R.run_parties(c, shares, trip)
+    w_of = R.triple_words(c)[0]
     for p in range(P):
         assert [lv for lv, _ in msgs[p]] == [lv for lv, _ in ref_msgs[p]]
         for (lv, m), (_, rm) in zip(msgs[p], ref_msgs[p]):
-            assert (m[:, :, idx] == rm).all(), "party %d level %d: message differs from the reference's" % (p, lv)
-        assert (outs[p][:, idx] == ref_outs[p]).all()
+            assert m.shape == rm.shape == (2, w_of[lv], batch)
+            assert (m == rm).all(), "party %d level %d: message differs from the reference's" % (p, lv)
+        assert outs[p].shape == ref_outs[p].shape and (outs[p] == ref_outs[p]).all()
     x = np.bitwise_xor.reduce(np.stack(outs), axis=0)
-    ob = R.unpack(x[:, idx], c.num_outputs)
-    for k, i in enumerate(idx[:24]):
-        assert (ob[:, k] == R.plain_bucketed(c, bits[i])).all()
+    ob = R.unpack(x, c.num_outputs)
+    assert (ob == G.plain_bucketed_batch(c, bits)).all()
+    rng = np.random.default_rng(seed + 1)
+    for i in _sample(batch, rng)[:24]:  # the batched plaintext above against the restatement's own, instance by instance
+        assert (ob[:, i] == R.plain_bucketed(c, bits[i])).all()
     ands, _ = R.buckets(c)
     n_and_levels = sum(1 for a in ands if a)
     assert launches <= n_and_levels + 2
+    return n_and_levels
 
 
 @pytest.mark.parametrize("batch", [1, 63, 64, 65, 1000, 4096])
@@ -145,6 +171,253 @@ def test_online_phase_bit_for_bit(ctx, aes_circ, add64_circ, name, P, batch):
     assert all(g.last_launches == parties[0].last_launches for g in parties)
     for g in parties:
         g.close()
+
+
+def _make(ctx, c, P, batch):
+    parties = [engine.Gmw(ctx, c, P, p, batch) for p in range(P)]
+    assert parties[0].info.triple_words == R.triple_words(c)[2]
+    return parties
+
+
+def _one_pass(ctx, c, parties, batch, seed, dev):
+    """a full pass on the given handles with the inputs and triples of `seed`, every instance checked; returns the number of
+    AND levels"""
+    P = len(parties)
+    bits, shares, trip = G.pass_data(c, P, batch, seed)
+    msgs, outs = _run_dev(ctx, c, parties, shares, trip) if dev else _run_host(parties, shares, trip)
+    n_and_levels = _check_pass(c, P, batch, seed, msgs, outs, bits, shares, trip, parties[0].last_launches)
+    assert all(g.last_launches == parties[0].last_launches for g in parties)
+    return n_and_levels
+
+
+DIRECTED = G.directed()
+
+
+@pytest.mark.parametrize("batch", [1, 65, 130])
+@pytest.mark.parametrize("k", range(len(DIRECTED)), ids=[c.name for c, _ in DIRECTED])
+def test_directed_circuits_through_the_engine(ctx, k, batch):
+    """the directed circuits of tests/gmw_cases.py (what each pins is written there), 2 .. 5 parties in turn; every circuit
+    runs in the host form at one batch and in the _dev form at another"""
+    c, status = DIRECTED[k]
+    P = G.directed_parties(k)
+    if status:
+        with pytest.raises(engine.EngineError) as e:
+            engine.Gmw(ctx, c, P, 0, batch)
+        assert e.value.code == status == engine.GC_E_WIRE
+        return
+    parties = _make(ctx, c, P, batch)
+    _one_pass(ctx, c, parties, batch, 1000 * batch + k, dev=(k + batch) % 2 == 1)
+    for g in parties:
+        g.close()
+
+
+@pytest.mark.parametrize("seed,batch,dev", G.GPU_FUZZ)
+def test_fuzz_circuits_through_the_engine(ctx, seed, batch, dev):
+    """seeded circuits of the host walk's set: 2 .. 5 parties (P = 5 in both forms: four peers behind `peers`), reuse up to
+    0.6, p_and 0 .. 0.9"""
+    c, P = G.fuzz_case(seed)
+    assert P == 2 + seed % 4
+    parties = _make(ctx, c, P, batch)
+    _one_pass(ctx, c, parties, batch, 50000 + seed, dev)
+    for g in parties:
+        g.close()
+
+
+def test_fuzz_set_covers_parties_batches_and_forms():
+    cases = [(2 + seed % 4, batch, dev) for seed, batch, dev in G.GPU_FUZZ]
+    assert len(cases) >= 24
+    assert {P for P, _, _ in cases} == {2, 3, 4, 5} and {b for _, b, _ in cases} == {1, 63, 64, 65, 257, 1000}
+    assert {dev for P, _, dev in cases if P == 5} == {False, True}
+    assert 8 <= sum(1 for _, _, dev in cases if dev) <= len(cases) - 8
+
+
+def _arg_error(fn, *args):
+    with pytest.raises(engine.EngineError) as e:
+        fn(*args)
+    assert e.value.code == engine.GC_E_ARG
+
+
+@pytest.mark.parametrize("name,P,batch", [("aes", 2, 130), ("fuzz3", 3, 257)])
+def test_handles_are_reused_over_passes(ctx, aes_circ, add64_circ, name, P, batch):
+    """One set of handles, pass after pass with new inputs and triples, each checked for every instance and with the launch
+    count of that pass: host form, _dev form, host form; a host pass left after two rounds, then a full _dev pass; a _dev pass
+    left after two rounds, then a host pass with misuse in it (outputs and a step between the restart and the triples,
+    triples after the first step, outputs in mid-pass: GC_E_ARG each, and the pass goes on); a last _dev pass."""
+    c = _circuit(name, aes_circ, add64_circ)
+    parties = _make(ctx, c, P, batch)
+    g0 = parties[0]
+    seed = 31000 + batch
+    for k, dev in enumerate((False, True, False)):
+        n = _one_pass(ctx, c, parties, batch, seed + k, dev)
+        assert g0.last_launches == n + 2  # the input load and R + 1 steps: the count starts again with every pass
+    assert n >= 3
+    # a host pass left after two rounds; the next set_inputs starts over
+    _, shares, trip = G.pass_data(c, P, batch, seed + 10)
+    msgs, outs = _run_host(parties, shares, trip, limit=2)
+    assert outs is None and len(msgs[0]) == 2
+    assert _one_pass(ctx, c, parties, batch, seed + 11, True) == n and g0.last_launches == n + 2
+    # a _dev pass left after two rounds, then a host pass with misuse in it
+    _, shares, trip = G.pass_data(c, P, batch, seed + 12)
+    msgs, outs = _run_dev(ctx, c, parties, shares, trip, limit=2)
+    assert outs is None and len(msgs[0]) == 2
+    bits, shares, trip = G.pass_data(c, P, batch, seed + 13)
+    for g, x in zip(parties, shares):
+        g.set_inputs(x)
+    d_buf = ctx.zeros(max(2 * g0.info.max_level_words, g0.out_words, 1) * batch * 8)
+    _arg_error(g0.get_outputs)                 # between the restart and the end of the pass
+    _arg_error(g0.get_outputs_dev, d_buf)
+    _arg_error(g0.step)                        # a step straight after the restart: the triples must be set again
+    _arg_error(g0.step_dev, None, d_buf)
+    for g, t in zip(parties, trip):
+        g.set_triples(*t)
+    msgs, cur = [[] for _ in range(P)], [None] * P
+    assert not _host_steps(parties, msgs, cur, 1)
+    _arg_error(g0.set_triples, *trip[0])       # after the first step
+    _arg_error(g0.set_triples_dev, d_buf, d_buf, d_buf)
+    _arg_error(g0.get_outputs)                 # in mid-pass
+    assert _host_steps(parties, msgs, cur)
+    outs = [g.get_outputs() for g in parties]
+    assert _check_pass(c, P, batch, seed + 13, msgs, outs, bits, shares, trip, g0.last_launches) == n
+    assert all(g.last_launches == n + 2 for g in parties)
+    _arg_error(g0.step, np.stack(cur[1:]))  # a step after the end
+    assert _one_pass(ctx, c, parties, batch, seed + 14, True) == n and g0.last_launches == n + 2
+    d_buf.close()
+    for g in parties:
+        g.close()
+
+
+def test_2_20_instances_of_aes_on_real_triples(ctx, aes_circ):
+    """aes_128, 2 parties, 2^20 instances through the _dev forms with valid random triples: the slot store is 36 919 x 16 384
+    words per party, so byte offsets pass 2^32.  300 distinct (key, plaintext) pairs are tiled over the batch, instance 0 the
+    FIPS-197 C.1 vector: the XOR of the two output buffers is compared for all 2^20 instances with the tiled plaintext
+    results; every message and the output shares are compared with R.run_parties on 256 sampled instances (the first and
+    last 64 and both sides of three instance-word boundaries).  Device memory ~17.6 GB (arithmetic, not measured): slots
+    2 x 36 919 x 16 384 x 8 B = 9.68 GB, triples 6 x 130 x 2^20 x 8 B = 6.54 GB, four message buffers of
+    2 x max_level_words x 2^20 x 8 B, inputs and outputs 0.1 GB.  Host memory: three triple arrays of 1.09 GB at a time."""
+    c, P, batch, K = aes_circ, 2, 1 << 20, 300
+    tw = R.triple_words(c)[2]
+    ws = _round_words(c)
+    rng = np.random.default_rng(2020)
+
+    def rand(rows):
+        return rng.integers(0, 0xFFFFFFFFFFFFFFFF, (rows, batch), dtype=np.uint64, endpoint=True)
+
+    small = rng.integers(0, 2, (K, c.num_inputs)).astype(np.uint8)
+    key = int.from_bytes(bytes(range(16)), "big")
+    pt = int.from_bytes(bytes.fromhex("00112233445566778899aabbccddeeff"), "big")
+    small[0] = [(key >> i) & 1 for i in range(128)] + [(pt >> i) & 1 for i in range(128)]
+    plain = G.plain_bucketed_batch(c, small)  # [128][K]
+    ct = sum(int(v) << i for i, v in enumerate(plain[:, 0]))
+    assert ct.to_bytes(16, "big").hex() == "69c4e0d86a7b0430d8cdb78070b4c55a"
+    assert (plain[:, 1] == c.compute_bits(small[1])[c.NumWires - c.num_outputs:]).all()
+    reps = -(-batch // K)
+    want = np.tile(R.pack(plain), (1, reps))[:, :batch]
+    ranges = [(0, 64), (333 * 64 - 16, 333 * 64 + 16), ((1 << 19) - 32, (1 << 19) + 32),
+              (batch - (1 << 16) - 16, batch - (1 << 16) + 16), (batch - 64, batch)]
+    idx = np.concatenate([np.arange(lo, hi) for lo, hi in ranges])
+    assert len(idx) == 256
+
+    s0 = rand((c.num_inputs + 63) // 64)
+    shares = [s0, s0 ^ np.tile(R.pack(small.T), (1, reps))[:, :batch]]
+    d_in = [ctx.to_device(x) for x in shares]
+    s_in = [x[:, idx].copy() for x in shares]
+    del s0, shares
+    # triples, one array at a time: upload, keep the sampled columns, fold into c1 = (a0 ^ a1) & (b0 ^ b1) ^ c0
+    d_t = [[None] * 3 for _ in range(P)]
+    s_t = [[None] * 3 for _ in range(P)]
+
+    def put(p, k, arr):
+        d_t[p][k] = ctx.to_device(arr)
+        s_t[p][k] = arr[:, idx].copy()
+
+    acc = rand(tw)
+    put(0, 0, acc)
+    x = rand(tw)
+    put(1, 0, x)
+    acc ^= x  # a0 ^ a1
+    xb = rand(tw)
+    put(0, 1, xb)
+    x = rand(tw)
+    put(1, 1, x)
+    xb ^= x  # b0 ^ b1
+    acc &= xb
+    del xb
+    x = rand(tw)
+    put(0, 2, x)
+    acc ^= x
+    put(1, 2, acc)
+    del x, acc
+
+    parties = _make(ctx, c, P, batch)
+    assert parties[0].info.ninputs + parties[0].info.ngates == 36919
+    assert 36919 * ((batch + 63) // 64) * 8 > 1 << 32
+    maxw = max(ws)
+    mb = [[ctx.empty(2 * maxw * batch * 8) for _ in range(P)] for _ in range(2)]
+    d_out = [ctx.empty(2 * batch * 8) for _ in range(P)]
+    for g, d, t in zip(parties, d_in, d_t):
+        g.set_inputs_dev(d)
+        g.set_triples_dev(*t)
+    msgs = [[] for _ in range(P)]
+    r = 0
+    while True:
+        w_prev = ws[r - 1] if r else 0
+        w = ws[r] if r < len(ws) else 0
+        res = [g.step_dev(mb[(r - 1) & 1][1 - p] if w_prev else None, mb[r & 1][p] if w else None) for p, g in enumerate(parties)]
+        assert res[0] == res[1] and res[0][1] == w
+        if not w:
+            assert res[0][0] == len(R.buckets(c)[0])
+            break
+        for p in range(P):
+            rows = [np.concatenate([mb[r & 1][p].download(np.uint64, None, (row * batch + lo) * 8, (hi - lo) * 8) for lo, hi in ranges])
+                    for row in range(2 * w)]
+            msgs[p].append((res[0][0], np.stack(rows).reshape(2, w, len(idx))))
+        r += 1
+    outs = []
+    for p, g in enumerate(parties):
+        g.get_outputs_dev(d_out[p])
+        outs.append(d_out[p].download(np.uint64, (2, batch)))
+    assert all(g.last_launches == len(ws) + 2 == 62 for g in parties)
+    assert np.array_equal(outs[0] ^ outs[1], want)  # all 2^20 instances
+    ref_msgs, ref_outs = R.run_parties(c, s_in, [tuple(t) for t in s_t])
+    for p in range(P):
+        assert [lv for lv, _ in msgs[p]] == [lv for lv, _ in ref_msgs[p]] and len(msgs[p]) == 60
+        for (lv, m), (_, rm) in zip(msgs[p], ref_msgs[p]):
+            assert m.shape == rm.shape and (m == rm).all(), "party %d level %d: message differs from the reference's" % (p, lv)
+        assert (outs[p][:, idx] == ref_outs[p]).all()
+    for g in parties:
+        g.close()
+    for b in d_in + [x for t in d_t for x in t] + mb[0] + mb[1] + d_out:
+        b.close()
+    ctx.sync()
+
+
+@pytest.mark.parametrize("words", [1, 255, 256, 257, (1 << 24) + 3])
+def test_triple_folds_whole_buffers(ctx, words):
+    """each of the four folds against numpy over the whole buffer, and the word after the end of the written buffer
+    untouched.  One sweep of k_gmw_fold's grid is 65 536 blocks x 256 threads = 2^24 words: at 2^24 + 3 the grid-stride
+    loop goes round for three threads.  Device memory at that size: 4 x 134 MB = 0.54 GB."""
+    rng = np.random.default_rng(words)
+    x, y, z, c0 = (rng.integers(0, 0xFFFFFFFFFFFFFFFF, words + 1, dtype=np.uint64, endpoint=True) for _ in range(4))
+    d_x, d_y, d_z, d_c = (ctx.to_device(v) for v in (x, y, z, c0))
+
+    def check(want):
+        got = d_c.download(np.uint64)
+        assert got[words] == c0[words], "the word after the end was written"
+        assert np.array_equal(got[:words], want[:words])
+        d_c.upload(c0)
+
+    engine.gmw_triples_local_dev(ctx, d_x, d_y, d_c, words)
+    check(x & y)
+    engine.gmw_triples_sender_u_dev(ctx, 0, d_x, d_c, words)
+    check(x)
+    engine.gmw_triples_sender_u_dev(ctx, 1, d_x, d_c, words)
+    check(~x)
+    engine.gmw_triples_sender_fold_dev(ctx, d_x, d_y, d_z, d_c, words)
+    check(c0 ^ x ^ (y & z))
+    engine.gmw_triples_receiver_fold_dev(ctx, d_x, d_c, words)
+    check(c0 ^ x)
+    for b in (d_x, d_y, d_z, d_c):
+        b.close()
 
 
 def _device_triples(ctx, P, words, seed):
