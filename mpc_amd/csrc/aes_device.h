@@ -142,6 +142,10 @@ __device__ __forceinline__ void aes_encrypt_repl(uint32_t (&s)[N][4], const uint
 //     col = Te0[b3(a0)] ^ Te2[b1(a2)] ^ rotr8(Te0[b2(a1)] ^ Te2[b0(a3)]) ^ rk
 // -> 8 VALU (4 perm, xor3 with the key, xor, alignbit, xor) + 4 ds_read_b32 per column: 32 + 16 per round
 // versus ~70 + 16 for the classic form.
+// The last XOR, the rotate and the NEXT round's four byte extracts fuse further (te_addr_xor below): with
+// u = Te0[..] ^ Te2[..] ^ rk and v = Te0[..] ^ Te2[..] the next state word is u ^ rotr8(v), so its byte b is
+// u.byte[b] ^ v.byte[(b+1)&3] — one SDWA XOR that writes byte 1 of a register whose byte 0 keeps the lane offset, i.e.
+// the next look-up address itself.  6 VALU per column (xor3, xor, 4 SDWA XORs): 24 + 16 per round.
 constexpr int kTeDualBytes = 256 * 256;
 
 __device__ __forceinline__ void te_dual_check(const uint32_t *te);
@@ -195,11 +199,88 @@ __device__ __forceinline__ void te_round_addrs(const uint32_t (&a)[4], uint32_t 
     }
 }
 
+// ad.byte1 = u.byte[B0] ^ v.byte[B1]; the other bytes of ad (lane offset in byte 0, zeros above) stay.  There is no
+// builtin for an SDWA operation with a preserved destination, hence inline assembly.
+// USAGE CONSTRAINT: the compiler's hazard recognizer does not decode inline assembly, so nothing guards the dst_sel
+// forwarding hazard of gfx940+ (a VALU instruction that reads ad straight after this partial write).  The only readers of
+// ad may be ds_reads (LDS addresses are not subject to it) and the next GC_TE_ADDR_XOR of the same register, which is a
+// whole round of look-ups away.  Do not feed ad to a VALU instruction (a plain XOR, a perm, a DPP move) without another
+// instruction in between.
+#define GC_TE_ADDR_XOR(ad, u, v, B0, B1)                                                                          \
+    asm("v_xor_b32_sdwa %0, %1, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_" #B0 " src1_sel:BYTE_" #B1 \
+        : "+v"(ad)                                                                                                \
+        : "v"(u), "v"(v))
+
+// u_c = t0 ^ t1 ^ rk, v_c = t2 ^ t3 of a round's four columns.  ORDERED: an empty volatile statement per column keeps
+// the columns' combines apart and in column order.  The statements order only each other, not the loads, so what the
+// batch kernels get (k_eval_flat<14,false,false>) is: the four plain XORs (v_c) run under the tail of the batch, one per
+// wait (lgkmcnt 12, 8, 4, 0); the four xor3 (u_c) and the SDWA XORs follow lgkmcnt(0).  Without the statements all
+// eight combines sink below one lgkmcnt(0), which costs a lone wave 8 "cycles" per round (tools/aes_model_ubench.hip,
+// variants 9 / 10).
+template <bool ORDERED>
+__device__ __forceinline__ void te_round_uv(const uint32_t (&t)[16], uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3,
+                                            uint32_t (&u)[4], uint32_t (&v)[4]) {
+    const uint32_t k[4] = {k0, k1, k2, k3};
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        u[c] = xor3(t[4 * c], t[4 * c + 1], k[c]);
+        v[c] = t[4 * c + 2] ^ t[4 * c + 3];
+        if constexpr (ORDERED) asm volatile("" : "+v"(u[c]), "+v"(v[c]));
+    }
+}
+
+// The sixteen addresses of the next round from this round's u_j = t0 ^ t1 ^ rk and v_j = t2 ^ t3 (state word
+// s_j = u_j ^ rotr8(v_j)).  LAST = false: slot order of te_round_addrs (Te0[b3(s_c)], Te2[b1(s_c+2)], Te0[b2(s_c+1)],
+// Te2[b0(s_c+3)]); LAST = true: the final round's order (b3(s_c), b2(s_c+1), b1(s_c+2), b0(s_c+3)).  Which half of a
+// row a slot reads is the load's immediate offset (te_slot_off), not part of the address.
+template <bool LAST>
+__device__ __forceinline__ void te_next_addrs(const uint32_t (&u)[4], const uint32_t (&v)[4], uint32_t (&ad)[16]) {
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const int j1 = LAST ? (c + 1) & 3 : (c + 2) & 3, j2 = LAST ? (c + 2) & 3 : (c + 1) & 3, j3 = (c + 3) & 3;
+        GC_TE_ADDR_XOR(ad[4 * c + 0], u[c], v[c], 3, 0);
+        if constexpr (LAST) {
+            GC_TE_ADDR_XOR(ad[4 * c + 1], u[j1], v[j1], 2, 3);
+            GC_TE_ADDR_XOR(ad[4 * c + 2], u[j2], v[j2], 1, 2);
+        } else {
+            GC_TE_ADDR_XOR(ad[4 * c + 1], u[j1], v[j1], 1, 2);
+            GC_TE_ADDR_XOR(ad[4 * c + 2], u[j2], v[j2], 2, 3);
+        }
+        GC_TE_ADDR_XOR(ad[4 * c + 3], u[j3], v[j3], 0, 1);
+    }
+}
+// word offset of the Te2 half for slot i of a column's four look-ups: slots 1 and 3 in a full round, 0 and 3 in the last
+template <bool LAST>
+__device__ __forceinline__ constexpr int te_slot_off(int i) {
+    return ((i & 3) == 3 || (i & 3) == (LAST ? 0 : 1)) ? 32 : 0;
+}
+
+// The final round's combine (no MixColumns): S[x] is bytes 2,1 of Te0[x] and bytes 3,0 of Te2[x], so a column is byte 3
+// of t0, byte 2 of t1, byte 1 of t2, byte 0 of t3: three bit-selects (v_bitop3 0xCA = m ? a : b), then the last round key
+// and, with FEED, the feed-forward in one three-input XOR.
+template <int NR, int N, int FEED>
+__device__ __forceinline__ void te_final_combine(const uint32_t (&t)[N][16], const uint32_t (&rk)[4 * (NR + 1)],
+                                                 const uint32_t (&fin)[FEED ? N : 1][4], uint32_t (&s)[N][4]) {
+#pragma unroll
+    for (int k = 0; k < N; k++)
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const uint32_t hi = __builtin_amdgcn_bitop3_b32(0xff000000u, t[k][4 * c], t[k][4 * c + 1], 0xCA);
+            const uint32_t lo = __builtin_amdgcn_bitop3_b32(0x0000ff00u, t[k][4 * c + 2], t[k][4 * c + 3], 0xCA);
+            const uint32_t sb = __builtin_amdgcn_bitop3_b32(0xffff0000u, hi, lo, 0xCA);
+            if constexpr (FEED) s[k][c] = xor3(sb, rk[4 * NR + c], fin[k][c]);
+            else s[k][c] = sb ^ rk[4 * NR + c];
+        }
+}
+
 // rk: NR+1 round keys as big-endian words, expected in SGPRs (see load_round_keys)
 // FEED = 1: the caller wants pi(K) ^ K (the fixed-key hash): the last AddRoundKey and the feed-forward of the input
 // block become one three-input XOR per word.  FEED = 2: as 1, and the input is already whitened (s = K ^ rk[0..3],
 // whiten_half / whiten_k) with the last round key folded (fold_last_round_key): pi(K) ^ K = SB ^ (rk_last ^ rk_0) ^ s.
-template <int NR, int N, int FEED = 0>
+// FUSED = true (default): the sixteen addresses are registers that live for the whole block, set once from the
+// whitened input with v_perm and rewritten in place by te_next_addrs — 24 VALU per round.  FUSED = false keeps the
+// 32-VALU round (perm per look-up, alignbit + xor per column) for comparison (tools/aes_ubench.hip).
+template <int NR, int N, int FEED = 0, bool FUSED = true>
 __device__ __forceinline__ void aes_encrypt_dual(uint32_t (&s)[N][4], const uint32_t (&rk)[4 * (NR + 1)],
                                                  const uint32_t *te, uint32_t lo0) {
     uint32_t fin[FEED ? N : 1][4];
@@ -210,7 +291,6 @@ __device__ __forceinline__ void aes_encrypt_dual(uint32_t (&s)[N][4], const uint
             for (int c = 0; c < 4; c++) fin[k][c] = s[k][c];
     }
     (void)te;  // the table sits at LDS offset 0 (te_dual_check)
-    const uint32_t lo2 = lo0 + 128u;
     if constexpr (FEED != 2) {
 #pragma unroll
         for (int k = 0; k < N; k++) {
@@ -220,54 +300,74 @@ __device__ __forceinline__ void aes_encrypt_dual(uint32_t (&s)[N][4], const uint
             s[k][3] ^= rk[3];
         }
     }
-#pragma unroll
-    for (int r = 1; r < NR; r++) {
+    if constexpr (FUSED) {
         uint32_t ad[N][16], t[N][16];
 #pragma unroll
-        for (int k = 0; k < N; k++) te_round_addrs(s[k], lo0, lo2, ad[k]);
-        __builtin_amdgcn_sched_barrier(0);
+        for (int k = 0; k < N; k++) te_round_addrs(s[k], lo0, lo0, ad[k]);
 #pragma unroll
-        for (int k = 0; k < N; k++)
+        for (int r = 1; r < NR; r++) {
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int i = 0; i < 16; i++) t[k][i] = *(lds_u32 *)(uintptr_t)ad[k][i];
-        __builtin_amdgcn_sched_barrier(0);
+            for (int k = 0; k < N; k++)
 #pragma unroll
-        for (int k = 0; k < N; k++)
+                for (int i = 0; i < 16; i++) t[k][i] = ((lds_u32 *)(uintptr_t)ad[k][i])[te_slot_off<false>(i)];
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int c = 0; c < 4; c++)
-                s[k][c] = xor3(t[k][4 * c], t[k][4 * c + 1], rk[4 * r + c]) ^ rotr32(t[k][4 * c + 2] ^ t[k][4 * c + 3], 8);
-    }
-    // final round (no MixColumns): S[x] is bytes 2,1 of Te0[x] and bytes 3,0 of Te2[x]; same byte positions as above
-    // but the roles of the two table halves are swapped for the first and last byte
-    {
-        const uint32_t sel0 = GC_PERM_SEL(0), sel1 = GC_PERM_SEL(1), sel2 = GC_PERM_SEL(2), sel3 = GC_PERM_SEL(3);
-        uint32_t ad[N][16], t[N][16];
-#pragma unroll
-        for (int k = 0; k < N; k++)
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                ad[k][4 * c + 0] = __builtin_amdgcn_perm(s[k][c], lo2, sel3);
-                ad[k][4 * c + 1] = __builtin_amdgcn_perm(s[k][(c + 1) & 3], lo0, sel2);
-                ad[k][4 * c + 2] = __builtin_amdgcn_perm(s[k][(c + 2) & 3], lo0, sel1);
-                ad[k][4 * c + 3] = __builtin_amdgcn_perm(s[k][(c + 3) & 3], lo2, sel0);
+            for (int k = 0; k < N; k++) {
+                uint32_t u[4], v[4];
+                te_round_uv<true>(t[k], rk[4 * r], rk[4 * r + 1], rk[4 * r + 2], rk[4 * r + 3], u, v);
+                if (r < NR - 1) te_next_addrs<false>(u, v, ad[k]);
+                else te_next_addrs<true>(u, v, ad[k]);
             }
+        }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int k = 0; k < N; k++)
 #pragma unroll
-            for (int i = 0; i < 16; i++) t[k][i] = *(lds_u32 *)(uintptr_t)ad[k][i];
+            for (int i = 0; i < 16; i++) t[k][i] = ((lds_u32 *)(uintptr_t)ad[k][i])[te_slot_off<true>(i)];
         __builtin_amdgcn_sched_barrier(0);
+        te_final_combine<NR, N, FEED>(t, rk, fin, s);
+    } else {
+        const uint32_t lo2 = lo0 + 128u;
 #pragma unroll
-        for (int k = 0; k < N; k++)
+        for (int r = 1; r < NR; r++) {
+            uint32_t ad[N][16], t[N][16];
 #pragma unroll
-            for (int c = 0; c < 4; c++)
-            {  // byte 3 of t0, byte 2 of t1, byte 1 of t2, byte 0 of t3: three bit-selects (v_bitop3 0xCA = m ? a : b)
-                const uint32_t hi = __builtin_amdgcn_bitop3_b32(0xff000000u, t[k][4 * c], t[k][4 * c + 1], 0xCA);
-                const uint32_t lo = __builtin_amdgcn_bitop3_b32(0x0000ff00u, t[k][4 * c + 2], t[k][4 * c + 3], 0xCA);
-                const uint32_t sb = __builtin_amdgcn_bitop3_b32(0xffff0000u, hi, lo, 0xCA);
-                if constexpr (FEED) s[k][c] = xor3(sb, rk[4 * NR + c], fin[k][c]);
-                else s[k][c] = sb ^ rk[4 * NR + c];
-            }
+            for (int k = 0; k < N; k++) te_round_addrs(s[k], lo0, lo2, ad[k]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < N; k++)
+#pragma unroll
+                for (int i = 0; i < 16; i++) t[k][i] = *(lds_u32 *)(uintptr_t)ad[k][i];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < N; k++)
+#pragma unroll
+                for (int c = 0; c < 4; c++)
+                    s[k][c] = xor3(t[k][4 * c], t[k][4 * c + 1], rk[4 * r + c]) ^ rotr32(t[k][4 * c + 2] ^ t[k][4 * c + 3], 8);
+        }
+        // final round: same byte positions as above, but the roles of the two table halves are swapped for the first
+        // and last byte (te_final_combine)
+        {
+            const uint32_t sel0 = GC_PERM_SEL(0), sel1 = GC_PERM_SEL(1), sel2 = GC_PERM_SEL(2), sel3 = GC_PERM_SEL(3);
+            uint32_t ad[N][16], t[N][16];
+#pragma unroll
+            for (int k = 0; k < N; k++)
+#pragma unroll
+                for (int c = 0; c < 4; c++) {
+                    ad[k][4 * c + 0] = __builtin_amdgcn_perm(s[k][c], lo2, sel3);
+                    ad[k][4 * c + 1] = __builtin_amdgcn_perm(s[k][(c + 1) & 3], lo0, sel2);
+                    ad[k][4 * c + 2] = __builtin_amdgcn_perm(s[k][(c + 2) & 3], lo0, sel1);
+                    ad[k][4 * c + 3] = __builtin_amdgcn_perm(s[k][(c + 3) & 3], lo2, sel0);
+                }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < N; k++)
+#pragma unroll
+                for (int i = 0; i < 16; i++) t[k][i] = *(lds_u32 *)(uintptr_t)ad[k][i];
+            __builtin_amdgcn_sched_barrier(0);
+            te_final_combine<NR, N, FEED>(t, rk, fin, s);
+        }
     }
 }
 
@@ -344,19 +444,19 @@ __device__ __forceinline__ void fold_last_round_key(uint32_t (&rk)[4 * (NR + 1)]
 #pragma unroll
     for (int c = 0; c < 4; c++) rk[4 * NR + c] ^= rk[c];
 }
-template <int NR>
+template <int NR, bool FUSED = true>
 __device__ __forceinline__ uint4 hash_dual_whitened(const uint32_t (&s0)[4], const uint32_t (&rk)[4 * (NR + 1)],
                                                     const uint32_t *te, uint32_t lo0) {
     uint32_t s[1][4] = {{s0[0], s0[1], s0[2], s0[3]}};
-    aes_encrypt_dual<NR, 1, 2>(s, rk, te, lo0);
+    aes_encrypt_dual<NR, 1, 2, FUSED>(s, rk, te, lo0);
     return make_uint4(s[0][1], s[0][0], s[0][3], s[0][2]);
 }
 
 // ---- column-sliced form: the four lanes of a quad hold the four state columns of ONE block ----------------------
 // For hash phases with so little work that the phase IS the latency of a lone wave's AES (deep, narrow circuits:
 // sha256xor x 256 has ~13 ANDs per phase; a chain of ANDs has one): a lane looks up the four bytes of ITS column and
-// the quad exchanges the table values with DPP quad permutes (fused into the XORs) — 4 look-ups + 10 VALU per round
-// and lane instead of 16 + 32, four times the lanes.  Round keys come from LDS (keyaddr = byte address of word
+// the quad exchanges the table values with DPP quad permutes (fused into the XORs) — 4 look-ups + 8 VALU per round
+// and lane (two XORs, two DPP XORs/moves, four SDWA address XORs) instead of 16 + 24, four times the lanes.  Round keys come from LDS (keyaddr = byte address of word
 // [round 0][column of this lane], 16 bytes per round; the last round key is folded, fold_last_round_key).
 // s0 = the lane's column of K ^ rk_0; returns the lane's column of pi(K) ^ K.
 constexpr int GC_QROT1 = 0x39;  // quad_perm [1,2,3,0]: value of the next column's lane
@@ -368,26 +468,27 @@ __device__ __forceinline__ uint32_t quad_from(uint32_t v) {
 }
 template <int NR>
 __device__ __forceinline__ uint32_t hash_col_whitened(uint32_t s0, uint32_t keyaddr, uint32_t lo0) {
-    const uint32_t lo2 = lo0 + 128u;
     const uint32_t sel0 = GC_PERM_SEL(0), sel1 = GC_PERM_SEL(1), sel2 = GC_PERM_SEL(2), sel3 = GC_PERM_SEL(3);
-    uint32_t s = s0;
+    // the lane's four addresses live for the whole block: byte 0 = lane offset, byte 1 = b3, b2, b1, b0 of its column
+    uint32_t a0 = __builtin_amdgcn_perm(s0, lo0, sel3), a1 = __builtin_amdgcn_perm(s0, lo0, sel2);
+    uint32_t a2 = __builtin_amdgcn_perm(s0, lo0, sel1), a3 = __builtin_amdgcn_perm(s0, lo0, sel0);
 #pragma unroll
     for (int r = 1; r < NR; r++) {
         // column c: Te0[b3(a_c)] ^ Te1[b2(a_c+1)] ^ Te2[b1(a_c+2)] ^ Te3[b0(a_c+3)], Te1/Te3 = rotr8(Te0/Te2)
-        const uint32_t a0 = __builtin_amdgcn_perm(s, lo0, sel3), a1 = __builtin_amdgcn_perm(s, lo0, sel2);
-        const uint32_t a2 = __builtin_amdgcn_perm(s, lo2, sel1), a3 = __builtin_amdgcn_perm(s, lo2, sel0);
         const uint32_t A = *(lds_u32 *)(uintptr_t)a0, B = *(lds_u32 *)(uintptr_t)a1;
-        const uint32_t C = *(lds_u32 *)(uintptr_t)a2, D = *(lds_u32 *)(uintptr_t)a3;
+        const uint32_t C = ((lds_u32 *)(uintptr_t)a2)[32], D = ((lds_u32 *)(uintptr_t)a3)[32];
         const uint32_t k = *(lds_u32 *)(uintptr_t)(keyaddr + 16u * r);
-        const uint32_t x = (A ^ k) ^ quad_from<GC_QROT2>(C);
-        const uint32_t y = quad_from<GC_QROT1>(B) ^ quad_from<GC_QROT3>(D);
-        s = x ^ rotr32(y, 8);
+        const uint32_t u = (A ^ k) ^ quad_from<GC_QROT2>(C);
+        const uint32_t v = quad_from<GC_QROT1>(B) ^ quad_from<GC_QROT3>(D);
+        // next column = u ^ rotr8(v): its four bytes go straight into the addresses (te_next_addrs)
+        GC_TE_ADDR_XOR(a0, u, v, 3, 0);
+        GC_TE_ADDR_XOR(a1, u, v, 2, 3);
+        GC_TE_ADDR_XOR(a2, u, v, 1, 2);
+        GC_TE_ADDR_XOR(a3, u, v, 0, 1);
     }
     // last round: byte 3 = S[b3(a_c)] (Te2), byte 2 = S[b2(a_c+1)] (Te0), byte 1 = S[b1(a_c+2)] (Te0), byte 0 (Te2)
-    const uint32_t a0 = __builtin_amdgcn_perm(s, lo2, sel3), a1 = __builtin_amdgcn_perm(s, lo0, sel2);
-    const uint32_t a2 = __builtin_amdgcn_perm(s, lo0, sel1), a3 = __builtin_amdgcn_perm(s, lo2, sel0);
-    const uint32_t A = *(lds_u32 *)(uintptr_t)a0, B = *(lds_u32 *)(uintptr_t)a1;
-    const uint32_t C = *(lds_u32 *)(uintptr_t)a2, D = *(lds_u32 *)(uintptr_t)a3;
+    const uint32_t A = ((lds_u32 *)(uintptr_t)a0)[32], B = *(lds_u32 *)(uintptr_t)a1;
+    const uint32_t C = *(lds_u32 *)(uintptr_t)a2, D = ((lds_u32 *)(uintptr_t)a3)[32];
     const uint32_t k = *(lds_u32 *)(uintptr_t)(keyaddr + 16u * NR);
     const uint32_t hi = __builtin_amdgcn_bitop3_b32(0xff000000u, A, quad_from<GC_QROT1>(B), 0xCA);
     const uint32_t lo = __builtin_amdgcn_bitop3_b32(0x0000ff00u, quad_from<GC_QROT2>(C), quad_from<GC_QROT3>(D), 0xCA);

@@ -571,7 +571,10 @@ __device__ __forceinline__ void garble_flat_body(const FlArgs &a) {
                 whiten_half(x, d.tweak + (HAS_OR ? (second ? 1u : 0u) : (q >> 1)), rkr, k);
             }
             GC_FPROF(6)  // debug profile: slot 6 = operand fetch + key set-up, slot 7 = AES, slot 1 = combine + stores
-            const uint4 h = hash_dual_whitened<NR>(k, rkr, te, lo);
+            // The profiling build of the garbler is out of registers (it spills already): the sixteen persistent
+            // addresses of the fused round would cost it two more spilled VGPRs around every hash, so it keeps the
+            // 32-VALU round.  Its slot 7 therefore overstates the production AES by the eight VALU per round.
+            const uint4 h = hash_dual_whitened<NR, !PROF>(k, rkr, te, lo);
             GC_FPROF(7)
             // 32-bit byte offset into the tile's table rows (launch_fused_flat checks that a tile's rows stay below
             // 4 GiB): scalar base + one VGPR offset instead of 64-bit address arithmetic per lane

@@ -9,6 +9,9 @@
 //   4: 1 perm + 2, 4 reads at immediate offsets                  = 3   (LDS-dominated)
 //   5: variant 0 without the LDS reads (value = address)         = 9 VALU, 0 LDS
 //   6: variant 4 with 8 reads per column                          = LDS only, twice the reads
+//   8: variant 1 with the round's 16 look-ups as one batch        = 8   (production core before the fused addresses)
+//   9: variant 8 with persistent addresses rewritten by SDWA XORs = 6   (te_next_addrs), one wait per round
+//  10: variant 9 with the columns combined in look-up order        = 6   (production core: waits count down)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include "../mpc_amd/csrc/aes_device.h"
@@ -76,6 +79,20 @@ __device__ __forceinline__ void round_batched(const uint32_t *te, uint32_t &a0, 
     a0 = n[0], a1 = n[1], a2 = n[2], a3 = n[3];
 }
 
+// variant 9: the addresses are the loop-carried state (byte 0 = lane offset, byte 1 = index); xor3 + xor per column, then
+// sixteen SDWA XORs write the next round's indices (no perm, no alignbit, no last xor)
+template <bool ORDERED>
+__device__ __forceinline__ void round_fused(uint32_t (&ad)[16], const uint32_t *rk4) {
+    __builtin_amdgcn_sched_barrier(0);
+    uint32_t t[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) t[i] = ((lds_u32 *)(uintptr_t)ad[i])[te_slot_off<false>(i)];
+    __builtin_amdgcn_sched_barrier(0);
+    uint32_t u[4], v[4];
+    te_round_uv<ORDERED>(t, rk4[0], rk4[1], rk4[2], rk4[3], u, v);
+    te_next_addrs<false>(u, v, ad);
+}
+
 template <int V>
 __global__ __launch_bounds__(1024) void k_bench(const uint32_t *rk, const uint32_t *te0, uint4 *out, int iters) {
     extern __shared__ uint4 smem[];
@@ -86,6 +103,18 @@ __global__ __launch_bounds__(1024) void k_bench(const uint32_t *rk, const uint32
     __syncthreads();
     const uint32_t lo0 = te_lane_off(), lo2 = lo0 + 128;
     uint32_t a0 = threadIdx.x * 7, a1 = blockIdx.x, a2 = 0x1234567, a3 = threadIdx.x;
+    if (V == 9 || V == 10) {
+        const uint32_t s[4] = {a0, a1, a2, a3};
+        uint32_t ad[16];
+        te_round_addrs(s, lo0, lo0, ad);
+        for (int it = 0; it < iters; it++) {
+#pragma unroll
+            for (int r = 1; r < 14; r++) round_fused<V == 10>(ad, &rkr[4 * r]);
+        }
+        out[blockIdx.x * blockDim.x + threadIdx.x] = make_uint4(ad[0] ^ ad[4] ^ ad[8] ^ ad[12], ad[1] ^ ad[5] ^ ad[9] ^ ad[13],
+                                                                ad[2] ^ ad[6] ^ ad[10] ^ ad[14], ad[3] ^ ad[7] ^ ad[11] ^ ad[15]);
+        return;
+    }
     for (int it = 0; it < iters; it++) {
 #pragma unroll
         for (int r = 1; r < 14; r++) {
@@ -146,6 +175,8 @@ int main() {
         run<6>(threads, d_rk, d_te, d_out);
         run<7>(threads, d_rk, d_te, d_out);
         run<8>(threads, d_rk, d_te, d_out);
+        run<9>(threads, d_rk, d_te, d_out);
+        run<10>(threads, d_rk, d_te, d_out);
     }
     return 0;
 }

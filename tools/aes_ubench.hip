@@ -14,7 +14,7 @@ template <int ILP, int MODE>
 __global__ void k_bench(const uint32_t *rk, const uint32_t *te0, uint4 *out, int iters) {
     extern __shared__ uint4 smem[];
     uint32_t *te = (uint32_t *)smem;
-    if (MODE == 0) load_te_dual(te, te0);
+    if (MODE == 0 || MODE == 3) load_te_dual(te, te0);
     else if (MODE == 1) load_te_replicated(te, te0);
     else load_te_tables(te, te0);
     uint32_t rkr[60];
@@ -30,6 +30,7 @@ __global__ void k_bench(const uint32_t *rk, const uint32_t *te0, uint4 *out, int
     }
     for (int it = 0; it < iters; it++) {
         if (MODE == 0) aes_encrypt_dual<14, ILP>(s, rkr, te, lo);
+        else if (MODE == 3) aes_encrypt_dual<14, ILP, 0, false>(s, rkr, te, lo);  // the 32-VALU round, for comparison
         else if (MODE == 1) aes_encrypt_repl<14, ILP>(s, rk, te, lo);
         else aes_encrypt_n<14, ILP>(s, rk, te);
     }
@@ -41,7 +42,7 @@ __global__ void k_bench(const uint32_t *rk, const uint32_t *te0, uint4 *out, int
 template <int ILP, int MODE>
 void run(const char *name, int threads, int blocks_per_cu, const uint32_t *d_rk, const uint32_t *d_te, uint4 *d_out) {
     const int cus = 256, iters = 200;
-    size_t lds = MODE == 0 ? 65536 : MODE == 1 ? 32768 : 4096;
+    size_t lds = (MODE == 0 || MODE == 3) ? 65536 : MODE == 1 ? 32768 : 4096;
     hipFuncSetAttribute((const void *)k_bench<ILP, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipEvent_t e0, e1;
     hipEventCreate(&e0);
@@ -81,6 +82,11 @@ int main() {
     run<2, 0>("dual", 1024, 1, d_rk, d_te, d_out);
     run<4, 0>("dual", 256, 1, d_rk, d_te, d_out);
     run<4, 0>("dual", 1024, 1, d_rk, d_te, d_out);
+    run<1, 3>("dual-perm", 64, 1, d_rk, d_te, d_out);
+    run<1, 0>("dual", 64, 1, d_rk, d_te, d_out);
+    run<1, 3>("dual-perm", 256, 1, d_rk, d_te, d_out);
+    run<1, 3>("dual-perm", 1024, 1, d_rk, d_te, d_out);
+    run<2, 3>("dual-perm", 1024, 1, d_rk, d_te, d_out);
     run<1, 1>("repl32k", 1024, 1, d_rk, d_te, d_out);
     run<1, 1>("repl32k", 1024, 2, d_rk, d_te, d_out);
     run<2, 1>("repl32k", 1024, 2, d_rk, d_te, d_out);

@@ -93,6 +93,11 @@ VALU_KERNEL(k_addf, I_ADDF)
 VALU_KERNEL(k_pkadd16, I_PKADD16)
 VALU_KERNEL(k_mov, I_MOV)
 VALU_KERNEL(k_sdwa, I_SDWA)
+// the fused AES round's address update: one byte of each source, result into byte 1, the rest of the destination kept
+#define I_SDWA_XOR(A) "v_xor_b32_sdwa " A ", %8, %9 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_3 src1_sel:BYTE_0\n"
+#define I_SDWA_XOR2(A) "v_xor_b32_sdwa " A ", %9, %8 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_1 src1_sel:BYTE_2\n"
+VALU_KERNEL(k_sdwa_xor, I_SDWA_XOR)
+VALU_KERNEL(k_sdwa_xor2, I_SDWA_XOR2)
 
 // ---- LDS reads: 16 loads per batch, one s_waitcnt per batch -------------------------------------------------------
 // MODE: address shape (see main); the 16 addresses of a batch differ by an XOR with the batch's previous data so that
@@ -245,7 +250,8 @@ int main() {
               {"v_or_b32", k_or}, {"v_xor_b32 (literal)", k_xor_c},
               {"v_mov_b32_dpp quad_perm", k_movdpp}, {"v_xor_b32_dpp quad_perm", k_xordpp}, {"v_fma_f32", k_fma},
               {"v_add_f32", k_addf},              {"v_pk_add_u16", k_pkadd16},        {"v_mov_b32", k_mov},
-              {"v_lshlrev_b32_sdwa BYTE_1", k_sdwa}};
+              {"v_lshlrev_b32_sdwa BYTE_1", k_sdwa},
+              {"v_xor_b32_sdwa B1<-B3^B0 preserve", k_sdwa_xor}, {"v_xor_b32_sdwa B1<-B1^B2 preserve", k_sdwa_xor2}};
     const int iters = 2000;
     // ns = wall clock of the launch / instructions per SIMD (launch overhead included: ~10 us of ~0.1-1 ms)
     for (auto &v : vs) {
