@@ -45,7 +45,8 @@ enum {
     GC_E_ARG = -5,     /* NULL / size mismatch */
     GC_E_HIP = -6,     /* HIP runtime failure (no device, launch error); see gc_last_error() */
     GC_E_NOMEM = -7,   /* device or host allocation failed */
-    GC_E_WIRE = -8     /* gate reads a wire that no input/gate has written, or wire id >= nwires */
+    GC_E_WIRE = -8,    /* gate reads a wire that no input/gate has written, or wire id >= nwires */
+    GC_E_POINT = -9    /* ot.ErrPointNotOnCurve: "ot: point not on curve" (co_helpers.go:17, :179-188) */
 };
 
 const char *gc_strerror(int status);
@@ -706,6 +707,53 @@ int gc_vole_sender_mul_dev(gc_ctx *, const uint8_t *p, const void *d_labels, con
                            size_t m, void *d_r_out, void *d_u_msg_out);
 int gc_vole_receiver_reduce(gc_ctx *, const uint8_t *p, const uint8_t *u_msg, size_t m, uint8_t *u_out);
 int gc_vole_receiver_reduce_dev(gc_ctx *, const uint8_t *p, const void *d_u_msg, size_t m, void *d_u_out);
+
+/* ------------------------------------------------------------------------------------------
+ * Chou-Orlandi base OT on P-256 (ot/co.go, ot/co_helpers.go).  The per-OT work of ONE session (one sender scalar a, one
+ * point A), bit-exact with the reference.  crand.Int, the framing and the p2p messages stay with the caller, who passes
+ * the scalars it drew.  Other curves, several sessions per call and ot.RSA are not covered.
+ *   gc_p256_point  an affine point, x and y as 32 big-endian bytes each (the caller pads big.Int.Bytes() to that width);
+ *                  64 zero bytes are the point at infinity, crypto/elliptic's (0, 0).  A point is VALID when 0 <= x, y < p
+ *                  and y^2 = x^3 - 3x + b (curve.IsOnCurve): an encoding >= p is refused, not reduced, and so is infinity.
+ *   scalars        32 bytes big-endian, any value below 2^256, taken mod N as the curve code does; b = 0 mod N gives
+ *                  the point at infinity.
+ *   mask(P, id)    deriveMask (co_helpers.go:222-235): SHA-256(x.Bytes() || y.Bytes() || BE64(id))[:16] with
+ *                  minimal-length coordinates (infinity: two empty strings).  The id of OT i is id0 + i, so that a caller
+ *                  may split a session into chunks.
+ * Sender setup (GenerateCOSenderSetup, co_helpers.go:77-101), host only: A = a * G, AaInv = (x(a * A), p - y(a * A)); a = 0 mod N is
+ *   GC_E_ARG.
+ * Sender encrypt (EncryptCOCiphertexts, co_helpers.go:104-137): S = a * B_i, T = S + AaInv (a complete addition: S = AaInv doubles,
+ *   S = -AaInv gives infinity), ct[i] = mask(S, id) ^ GetData(L0) || mask(T, id) ^ GetData(L1), 32 bytes per OT.  A B_i that
+ *   is not VALID gets 32 zero bytes.  Host form: GC_E_POINT and *bad_index = the lowest such i (bad_index may be NULL; ct
+ *   is written for every good point all the same).  _dev form: d_status is two uint64 in device memory that the call itself
+ *   resets and the kernel fills: {number of bad points, lowest bad index (all ones: none)}; read it after gc_ctx_sync.
+ *   a = 0 mod N or an AaInv that is not VALID: GC_E_ARG.  wires: the gc_wire array that is also gc_iknp_receiver_create's base.
+ * Receiver choices (BuildCOChoices, co_helpers.go:140-177): B_i = b_i * G, + A when choice[i] != 0 (one byte per OT, as gc_iknp_receive).
+ * Receiver decrypt (DecryptCOCiphertexts, co_helpers.go:191-219): labels_out[i] = SetData(mask(b_i * A, id) ^ (choice[i] ? ct1 : ct0));
+ *   labels_out is gc_iknp_sender_create's k0.  An A that is not VALID: GC_E_POINT, in both receiver calls.
+ * a, A and AaInv are host pointers in every form.  Host forms: synchronous, staged through device buffers.  _dev forms:
+ * device pointers (16-byte aligned, as gc_dev_alloc returns them), asynchronous on the ctx stream.  n = 0: GC_OK, nothing
+ * written.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct gc_p256_point { uint8_t x[32], y[32]; } gc_p256_point;
+
+/* GenerateCOSenderSetup, ot/co_helpers.go:77-101 (host only) */
+int gc_co_sender_setup(const uint8_t *a, gc_p256_point *A_out, gc_p256_point *AaInv_out);
+/* EncryptCOCiphertexts, ot/co_helpers.go:104-137, deriveMask ot/co_helpers.go:222-235; ct: 32 bytes per OT */
+int gc_co_sender_encrypt(gc_ctx *, const uint8_t *a, const gc_p256_point *AaInv, const gc_p256_point *points,
+                         const gc_wire *wires, size_t n, uint64_t id0, uint8_t *ct, size_t *bad_index);
+int gc_co_sender_encrypt_dev(gc_ctx *, const uint8_t *a, const gc_p256_point *AaInv, const void *d_points,
+                             const void *d_wires, size_t n, uint64_t id0, void *d_ct, void *d_status);
+/* BuildCOChoices, ot/co_helpers.go:140-177 */
+int gc_co_receiver_choices(gc_ctx *, const gc_p256_point *A, const uint8_t *scalars, const uint8_t *choice, size_t n,
+                           gc_p256_point *points_out);
+int gc_co_receiver_choices_dev(gc_ctx *, const gc_p256_point *A, const void *d_scalars, const void *d_choice, size_t n,
+                               void *d_points_out);
+/* DecryptCOCiphertexts, ot/co_helpers.go:191-219, deriveMask ot/co_helpers.go:222-235 */
+int gc_co_receiver_decrypt(gc_ctx *, const gc_p256_point *A, const uint8_t *scalars, const uint8_t *choice,
+                           const uint8_t *ct, size_t n, uint64_t id0, gc_label *labels_out);
+int gc_co_receiver_decrypt_dev(gc_ctx *, const gc_p256_point *A, const void *d_scalars, const void *d_choice,
+                               const void *d_ct, size_t n, uint64_t id0, void *d_labels_out);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,224 @@
+// co_engine.cpp — C ABI of the Chou-Orlandi base OT on P-256 (gcengine.h: gc_co_*): the per-OT work of ot/co_helpers.go
+// (GenerateCOSenderSetup :77-101, EncryptCOCiphertexts :104-137, BuildCOChoices :140-177, DecryptCOCiphertexts :191-219).
+// crand.Int, the framing and the p2p messages stay with the caller, who passes the scalars it drew; co_kernels.hip is the
+// device side.  The session constants (a, A, AaInv) are host pointers in every form and are prepared here, on the host, with
+// the arithmetic of p256.h that the kernels run: gc_co_sender_setup is two scalar multiplications per SESSION, not worth a
+// launch.
+#include <cstring>
+#include <new>
+
+#include "engine.h"
+
+using namespace gc;
+
+namespace {
+
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+};
+
+// n OTs of at most 64 bytes per array: refuse an n whose byte count does not fit size_t
+bool bytes_fit(size_t n) { return n <= SIZE_MAX / 64; }
+
+Fe load_fe(const uint8_t *b) {
+    Fe f;
+    vole_load_be(b, f.v);
+    return f;
+}
+
+// a point of the boundary -> Montgomery affine; false: not on the curve (infinity included)
+bool load_point(const gc_p256_point *pt, Aff *q) { return pt_on_curve(load_fe(pt->x), load_fe(pt->y), *q); }
+
+void store_point(const Jac &p, gc_p256_point *out) {
+    Fe x, y;
+    pt_to_affine(p, fe_inv(p.z), x, y);
+    vole_store_be(x.v, out->x);
+    vole_store_be(y.v, out->y);
+}
+
+Aff generator() {
+    Aff g;
+    g.x = fe_to_mont(p256_gx());
+    g.y = fe_to_mont(p256_gy());
+    g.inf = 0;
+    return g;
+}
+
+// the sender's scalar mod N; false: a = 0 mod N
+bool load_sender_scalar(const uint8_t *a, Fe *k) {
+    *k = sc_reduce(load_fe(a));
+    return !fe_is_zero(*k);
+}
+
+int sender_session(const uint8_t *a, const gc_p256_point *ainv, CoSender *ses) {
+    Fe k;
+    if (!load_sender_scalar(a, &k)) return GC_E_ARG;
+    if (!load_point(ainv, &ses->ainv)) return GC_E_ARG;  // the caller's own constant, not a peer's point
+    for (int j = 0; j < kVoleLimbs; j++) ses->a[j] = k.v[j];
+    return GC_OK;
+}
+
+int receiver_session(const gc_p256_point *A, CoBase *base) {
+    base->g = generator();
+    return load_point(A, &base->a) ? GC_OK : GC_E_POINT;  // ensureOnCurve(Ax, Ay), co_helpers.go:144
+}
+
+// the status block of gc_co_sender_encrypt_dev before the kernel: {0, ~0}
+hipError_t reset_status(void *d_status, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(d_status, 0, 8, s);
+    if (e != hipSuccess) return e;
+    return hipMemsetAsync((uint8_t *)d_status + 8, 0xff, 8, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gc_co_sender_setup(const uint8_t *a, gc_p256_point *A_out, gc_p256_point *AaInv_out) {
+    if (!a || !A_out || !AaInv_out) return GC_E_ARG;
+    Fe k;
+    if (!load_sender_scalar(a, &k)) return GC_E_ARG;
+    store_point(pt_mul(k, generator()), A_out);  // A = a * G
+    Aff A;
+    if (!load_point(A_out, &A)) return GC_E_ARG;  // (cannot be: a != 0 mod N)
+    const Jac aa = pt_mul(k, A);                  // a * A
+    Fe x, y;
+    pt_to_affine(aa, fe_inv(aa.z), x, y);
+    vole_store_be(x.v, AaInv_out->x);
+    vole_store_be(fe_neg(y).v, AaInv_out->y);     // p - y (co_helpers.go:90-91); y != 0 on a curve of odd order
+    return GC_OK;
+}
+
+int gc_co_sender_encrypt_dev(gc_ctx *ctx, const uint8_t *a, const gc_p256_point *AaInv, const void *d_points,
+                             const void *d_wires, size_t n, uint64_t id0, void *d_ct, void *d_status) {
+    if (!ctx || !a || !AaInv || (n && (!d_points || !d_wires || !d_ct || !d_status)) || !bytes_fit(n)) return GC_E_ARG;
+    CoSender ses;
+    const int rc = sender_session(a, AaInv, &ses);
+    if (rc != GC_OK) return rc;
+    if (n == 0) return GC_OK;
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_HIP(reset_status(d_status, ctx->stream));
+    launch_co_encrypt(ses, (const uint4 *)d_points, (const uint4 *)d_wires, n, id0, (uint4 *)d_ct,
+                      (unsigned long long *)d_status, ctx->stream);
+    GC_HIP(hipGetLastError());
+    return GC_OK;
+}
+
+int gc_co_receiver_choices_dev(gc_ctx *ctx, const gc_p256_point *A, const void *d_scalars, const void *d_choice, size_t n,
+                               void *d_points_out) {
+    if (!ctx || !A || (n && (!d_scalars || !d_choice || !d_points_out)) || !bytes_fit(n)) return GC_E_ARG;
+    CoBase base;
+    const int rc = receiver_session(A, &base);
+    if (rc != GC_OK) return rc;
+    if (n == 0) return GC_OK;
+    GC_HIP(hipSetDevice(ctx->device));
+    launch_co_choices(base, (const uint4 *)d_scalars, (const uint8_t *)d_choice, n, (uint4 *)d_points_out, ctx->stream);
+    GC_HIP(hipGetLastError());
+    return GC_OK;
+}
+
+int gc_co_receiver_decrypt_dev(gc_ctx *ctx, const gc_p256_point *A, const void *d_scalars, const void *d_choice,
+                               const void *d_ct, size_t n, uint64_t id0, void *d_labels_out) {
+    if (!ctx || !A || (n && (!d_scalars || !d_choice || !d_ct || !d_labels_out)) || !bytes_fit(n)) return GC_E_ARG;
+    CoBase base;
+    const int rc = receiver_session(A, &base);
+    if (rc != GC_OK) return rc;
+    if (n == 0) return GC_OK;
+    GC_HIP(hipSetDevice(ctx->device));
+    launch_co_decrypt(base, (const uint4 *)d_scalars, (const uint8_t *)d_choice, (const uint4 *)d_ct, n, id0,
+                      (uint4 *)d_labels_out, ctx->stream);
+    GC_HIP(hipGetLastError());
+    return GC_OK;
+}
+
+int gc_co_sender_encrypt(gc_ctx *ctx, const uint8_t *a, const gc_p256_point *AaInv, const gc_p256_point *points,
+                         const gc_wire *wires, size_t n, uint64_t id0, uint8_t *ct, size_t *bad_index) try {
+    if (!ctx || !a || !AaInv || (n && (!points || !wires || !ct)) || !bytes_fit(n)) return GC_E_ARG;
+    CoSender ses;
+    const int rc = sender_session(a, AaInv, &ses);
+    if (rc != GC_OK) return rc;
+    if (n == 0) return GC_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    DevBuf d_pts, d_wires, d_ct, d_status;
+    GC_HIP(d_pts.alloc(n * 64));
+    GC_HIP(d_wires.alloc(n * 32));
+    GC_HIP(d_ct.alloc(n * 32));
+    GC_HIP(d_status.alloc(16));
+    hipStream_t s = ctx->stream;
+    GC_HIP(hipMemcpyAsync(d_pts.p, points, n * 64, hipMemcpyHostToDevice, s));
+    GC_HIP(hipMemcpyAsync(d_wires.p, wires, n * 32, hipMemcpyHostToDevice, s));
+    GC_HIP(reset_status(d_status.p, s));
+    launch_co_encrypt(ses, (const uint4 *)d_pts.p, (const uint4 *)d_wires.p, n, id0, (uint4 *)d_ct.p,
+                      (unsigned long long *)d_status.p, s);
+    GC_HIP(hipGetLastError());
+    uint64_t status[2] = {0, 0};
+    GC_HIP(hipMemcpyAsync(ct, d_ct.p, n * 32, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipMemcpyAsync(status, d_status.p, 16, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipStreamSynchronize(s));
+    if (status[0]) {  // ErrPointNotOnCurve (co_helpers.go:119-121)
+        if (bad_index) *bad_index = (size_t)status[1];
+        return GC_E_POINT;
+    }
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_co_receiver_choices(gc_ctx *ctx, const gc_p256_point *A, const uint8_t *scalars, const uint8_t *choice, size_t n,
+                           gc_p256_point *points_out) try {
+    if (!ctx || !A || (n && (!scalars || !choice || !points_out)) || !bytes_fit(n)) return GC_E_ARG;
+    CoBase base;
+    const int rc = receiver_session(A, &base);
+    if (rc != GC_OK) return rc;
+    if (n == 0) return GC_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    DevBuf d_sc, d_ch, d_out;
+    GC_HIP(d_sc.alloc(n * 32));
+    GC_HIP(d_ch.alloc(n));
+    GC_HIP(d_out.alloc(n * 64));
+    hipStream_t s = ctx->stream;
+    GC_HIP(hipMemcpyAsync(d_sc.p, scalars, n * 32, hipMemcpyHostToDevice, s));
+    GC_HIP(hipMemcpyAsync(d_ch.p, choice, n, hipMemcpyHostToDevice, s));
+    launch_co_choices(base, (const uint4 *)d_sc.p, (const uint8_t *)d_ch.p, n, (uint4 *)d_out.p, s);
+    GC_HIP(hipGetLastError());
+    GC_HIP(hipMemcpyAsync(points_out, d_out.p, n * 64, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipStreamSynchronize(s));
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_co_receiver_decrypt(gc_ctx *ctx, const gc_p256_point *A, const uint8_t *scalars, const uint8_t *choice,
+                           const uint8_t *ct, size_t n, uint64_t id0, gc_label *labels_out) try {
+    if (!ctx || !A || (n && (!scalars || !choice || !ct || !labels_out)) || !bytes_fit(n)) return GC_E_ARG;
+    CoBase base;
+    const int rc = receiver_session(A, &base);
+    if (rc != GC_OK) return rc;
+    if (n == 0) return GC_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    DevBuf d_sc, d_ch, d_ct, d_out;
+    GC_HIP(d_sc.alloc(n * 32));
+    GC_HIP(d_ch.alloc(n));
+    GC_HIP(d_ct.alloc(n * 32));
+    GC_HIP(d_out.alloc(n * 16));
+    hipStream_t s = ctx->stream;
+    GC_HIP(hipMemcpyAsync(d_sc.p, scalars, n * 32, hipMemcpyHostToDevice, s));
+    GC_HIP(hipMemcpyAsync(d_ch.p, choice, n, hipMemcpyHostToDevice, s));
+    GC_HIP(hipMemcpyAsync(d_ct.p, ct, n * 32, hipMemcpyHostToDevice, s));
+    launch_co_decrypt(base, (const uint4 *)d_sc.p, (const uint8_t *)d_ch.p, (const uint4 *)d_ct.p, n, id0, (uint4 *)d_out.p, s);
+    GC_HIP(hipGetLastError());
+    GC_HIP(hipMemcpyAsync(labels_out, d_out.p, n * 16, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipStreamSynchronize(s));
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+}  // extern "C"

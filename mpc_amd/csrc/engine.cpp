@@ -252,6 +252,7 @@ const char *gc_strerror(int status) {
     case GC_E_HIP: return "HIP runtime error";
     case GC_E_NOMEM: return "out of memory";
     case GC_E_WIRE: return "gate input wire not set";
+    case GC_E_POINT: return "ot: point not on curve";
     default: return "unknown status";
     }
 }

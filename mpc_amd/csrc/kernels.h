@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "p256.h"
 #include "plan.h"
 #include "vole_mod.h"
 
@@ -319,5 +320,24 @@ void launch_cot_recv(uint4 seed, const uint8_t *flags, const uint4 *sent, uint4 
 void launch_vole_sender(const VoleMod &mod, const uint4 *labels, const uint4 *x, const uint4 *y_msg, size_t m, uint4 *r_out,
                         uint4 *u_out, const uint32_t *te0, hipStream_t s);
 void launch_vole_receiver(const VoleMod &mod, const uint4 *u_msg, size_t m, uint4 *u_out, hipStream_t s);
+
+// ---- Chou-Orlandi base OT kernels (co_kernels.hip) -------------------------------------------
+// The constants of one session, passed by value (uniform across the grid).  a: the sender's scalar mod N, non-zero, limbs
+// least significant first; ainv: AaInv = -(a * A); g, a: the generator and the sender's point A; points in Montgomery form.
+struct CoSender {
+    uint32_t a[kVoleLimbs];
+    Aff ainv;
+};
+struct CoBase {
+    Aff g, a;
+};
+// points: gc_p256_point [n] (4 uint4 each); wires: gc_wire [n]; ct: [n][2] of 16 bytes; scalars: 32 bytes big-endian each;
+// choice: one byte per OT; status: {bad points (added to), lowest bad index (min-ed into)}; every pointer 16-byte aligned
+void launch_co_encrypt(const CoSender &ses, const uint4 *points, const uint4 *wires, size_t n, uint64_t id0, uint4 *ct,
+                       unsigned long long *status, hipStream_t s);
+void launch_co_choices(const CoBase &base, const uint4 *scalars, const uint8_t *choice, size_t n, uint4 *points_out,
+                       hipStream_t s);
+void launch_co_decrypt(const CoBase &base, const uint4 *scalars, const uint8_t *choice, const uint4 *ct, size_t n, uint64_t id0,
+                       uint4 *labels_out, hipStream_t s);
 
 }  // namespace gc

@@ -18,8 +18,8 @@ LIB_PATH = os.environ.get("GC_LIB") or os.path.join(CSRC, "libgcengine.so")  # G
 HEADER = os.path.join(os.path.dirname(HERE), "include", "gcengine.h")
 
 ABI_VERSION = 2  # GC_ABI_VERSION of include/gcengine.h
-GC_OK, GC_E_KEYSIZE, GC_E_RAND, GC_E_GATE, GC_E_ROWS, GC_E_ARG, GC_E_HIP, GC_E_NOMEM, GC_E_WIRE = (
-    0, -1, -2, -3, -4, -5, -6, -7, -8)
+GC_OK, GC_E_KEYSIZE, GC_E_RAND, GC_E_GATE, GC_E_ROWS, GC_E_ARG, GC_E_HIP, GC_E_NOMEM, GC_E_WIRE, GC_E_POINT = (
+    0, -1, -2, -3, -4, -5, -6, -7, -8, -9)
 
 
 class EngineError(RuntimeError):
@@ -233,6 +233,13 @@ def lib():
         "gc_vole_sender_mul_dev": (i32, [vp, vp, vp, vp, vp, sz, vp, vp]),
         "gc_vole_receiver_reduce": (i32, [vp, vp, vp, sz, vp]),
         "gc_vole_receiver_reduce_dev": (i32, [vp, vp, vp, sz, vp]),
+        "gc_co_sender_setup": (i32, [vp, vp, vp]),
+        "gc_co_sender_encrypt": (i32, [vp, vp, vp, vp, vp, sz, C.c_uint64, vp, C.POINTER(C.c_size_t)]),
+        "gc_co_sender_encrypt_dev": (i32, [vp, vp, vp, vp, vp, sz, C.c_uint64, vp, vp]),
+        "gc_co_receiver_choices": (i32, [vp, vp, vp, vp, sz, vp]),
+        "gc_co_receiver_choices_dev": (i32, [vp, vp, vp, vp, sz, vp]),
+        "gc_co_receiver_decrypt": (i32, [vp, vp, vp, vp, vp, sz, C.c_uint64, vp]),
+        "gc_co_receiver_decrypt_dev": (i32, [vp, vp, vp, vp, vp, sz, C.c_uint64, vp]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -1363,3 +1370,129 @@ def vole_receiver_reduce_dev(ctx, p, d_u_msg, m, d_u_out):
     """device pointers; asynchronous on the ctx stream; d_u_out may be d_u_msg"""
     _check(lib().gc_vole_receiver_reduce_dev(ctx.h, _p(vole_modulus(p)), _dp(d_u_msg), m, _dp(d_u_out)),
            "gc_vole_receiver_reduce_dev")
+
+
+# ---- Chou-Orlandi base OT on P-256 (ot/co.go, ot/co_helpers.go) --------------------------------
+
+
+class CoPointError(EngineError):
+    """GC_E_POINT of gc_co_sender_encrypt: .bad_index = the lowest index of a point that is not on the curve, .ct = the
+    ciphertexts all the same (zeros at the bad points)"""
+
+    def __init__(self, what, bad_index, ct):
+        super().__init__(GC_E_POINT, what)
+        self.bad_index, self.ct = bad_index, ct
+
+
+def _b32(v):
+    """a scalar as the ABI takes it: 32 bytes big-endian, from an int below 2^256 or from 32 bytes"""
+    if isinstance(v, (bytes, bytearray, memoryview, np.ndarray)):
+        b = bytes(v)
+        if len(b) != 32:
+            raise EngineError(GC_E_ARG, "co: a scalar takes 32 bytes, got %d" % len(b))
+        return np.frombuffer(b, np.uint8).copy()
+    v = int(v)
+    if v < 0 or v >= 1 << 256:
+        raise EngineError(GC_E_ARG, "co: the scalar does not fit 32 bytes")
+    return np.frombuffer(v.to_bytes(32, "big"), np.uint8).copy()
+
+
+def _scalars(a):
+    """scalars as the ABI takes them: uint8 [n, 32] from such an array or from a sequence of ints"""
+    if isinstance(a, np.ndarray):
+        return _v32(a)
+    a = list(a)
+    if not a:
+        return np.zeros((0, 32), np.uint8)
+    return np.stack([_b32(v) for v in a])
+
+
+def co_point(pt):
+    """gc_p256_point (uint8 [64]) from 64 bytes or from an (x, y) pair of ints below 2^256"""
+    if isinstance(pt, (tuple, list)):
+        pt = int(pt[0]).to_bytes(32, "big") + int(pt[1]).to_bytes(32, "big")
+    b = bytes(pt)
+    if len(b) != 64:
+        raise EngineError(GC_E_ARG, "co: a point takes 64 bytes, got %d" % len(b))
+    return np.frombuffer(b, np.uint8).copy()
+
+
+def _points(a):
+    if isinstance(a, np.ndarray):
+        return np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, 64)
+    a = list(a)
+    if not a:
+        return np.zeros((0, 64), np.uint8)
+    return np.stack([co_point(p) for p in a])
+
+
+def co_sender_setup(a):
+    """gc_co_sender_setup (GenerateCOSenderSetup, ot/co_helpers.go:77-101) -> (A, AaInv), uint8 [64] each; host only"""
+    A, ainv = np.zeros(64, np.uint8), np.zeros(64, np.uint8)
+    _check(lib().gc_co_sender_setup(_p(_b32(a)), _p(A), _p(ainv)), "gc_co_sender_setup")
+    return A, ainv
+
+
+def co_sender_encrypt(ctx, a, AaInv, points, wires, id0=0):
+    """gc_co_sender_encrypt (EncryptCOCiphertexts, :104-137) -> ct, uint8 [n, 2, 16]; raises CoPointError when a point is
+    not on the curve"""
+    pts = _points(points)
+    w = np.ascontiguousarray(wires, dtype=WIRE)
+    n = len(pts)
+    assert len(w) == n
+    ct = np.zeros((max(n, 1), 2, 16), np.uint8)
+    bad = C.c_size_t(0)
+    rc = lib().gc_co_sender_encrypt(ctx.h, _p(_b32(a)), _p(co_point(AaInv)), _p(pts) if n else None, _p(w) if n else None, n,
+                                    id0, _p(ct), C.byref(bad))
+    if rc == GC_E_POINT:
+        raise CoPointError("gc_co_sender_encrypt", bad.value, ct[:n])
+    _check(rc, "gc_co_sender_encrypt")
+    return ct[:n]
+
+
+def co_sender_encrypt_dev(ctx, a, AaInv, d_points, d_wires, n, id0, d_ct, d_status):
+    """device pointers; asynchronous on the ctx stream; d_status: uint64 [2] = {bad points, lowest bad index}"""
+    _check(lib().gc_co_sender_encrypt_dev(ctx.h, _p(_b32(a)), _p(co_point(AaInv)), _dp(d_points), _dp(d_wires), n, id0,
+                                          _dp(d_ct), _dp(d_status)), "gc_co_sender_encrypt_dev")
+
+
+def _choices(choice, n):
+    c = np.ascontiguousarray(choice, dtype=np.uint8).reshape(-1)
+    assert len(c) == n
+    return c
+
+
+def co_receiver_choices(ctx, A, scalars, choice):
+    """gc_co_receiver_choices (BuildCOChoices, :140-177) -> points, uint8 [n, 64]"""
+    sc = _scalars(scalars)
+    n = len(sc)
+    ch = _choices(choice, n)
+    out = np.zeros((max(n, 1), 64), np.uint8)
+    _check(lib().gc_co_receiver_choices(ctx.h, _p(co_point(A)), _p(sc) if n else None, _p(ch) if n else None, n, _p(out)),
+           "gc_co_receiver_choices")
+    return out[:n]
+
+
+def co_receiver_choices_dev(ctx, A, d_scalars, d_choice, n, d_points_out):
+    """device pointers; asynchronous on the ctx stream"""
+    _check(lib().gc_co_receiver_choices_dev(ctx.h, _p(co_point(A)), _dp(d_scalars), _dp(d_choice), n, _dp(d_points_out)),
+           "gc_co_receiver_choices_dev")
+
+
+def co_receiver_decrypt(ctx, A, scalars, choice, ct, id0=0):
+    """gc_co_receiver_decrypt (DecryptCOCiphertexts, :191-219) -> labels [n]"""
+    sc = _scalars(scalars)
+    n = len(sc)
+    ch = _choices(choice, n)
+    c = np.ascontiguousarray(ct, dtype=np.uint8).reshape(-1, 32)
+    assert len(c) == n
+    out = np.zeros(max(n, 1), LABEL)
+    _check(lib().gc_co_receiver_decrypt(ctx.h, _p(co_point(A)), _p(sc) if n else None, _p(ch) if n else None,
+                                        _p(c) if n else None, n, id0, _p(out)), "gc_co_receiver_decrypt")
+    return out[:n]
+
+
+def co_receiver_decrypt_dev(ctx, A, d_scalars, d_choice, d_ct, n, id0, d_labels_out):
+    """device pointers; asynchronous on the ctx stream"""
+    _check(lib().gc_co_receiver_decrypt_dev(ctx.h, _p(co_point(A)), _dp(d_scalars), _dp(d_choice), _dp(d_ct), n, id0,
+                                            _dp(d_labels_out)), "gc_co_receiver_decrypt_dev")
