@@ -24,9 +24,6 @@ namespace gc {
 
 namespace {
 
-constexpr int kCoThreads = 256;
-constexpr int kCoGrid = 2048;  // grid-stride beyond 2048 workgroups (8 per CU)
-
 // 32 big-endian bytes as two 16-byte loads <-> limbs
 __device__ __forceinline__ Fe load_be_fe(const uint4 *p) {
     const uint4 a = p[0], b = p[1];

@@ -24,7 +24,7 @@ namespace gc {
 
 namespace {
 
-constexpr int IKT = 1024;
+constexpr int IKT = kIknpThreads;
 constexpr uint32_t kKeyBytes = 128 * 176;  // [column][11 round keys][16 bytes]
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -280,7 +280,7 @@ __global__ __launch_bounds__(IKT) void k_iknp_fused(const uint32_t *__restrict__
                                                     uint8_t *__restrict__ u_out, uint4 *__restrict__ labels,
                                                     const uint32_t *__restrict__ g_te0) {
     extern __shared__ uint4 smem[];
-    constexpr uint32_t NCH = RECV ? 4 : 8;                    // chunks per workgroup step
+    constexpr uint32_t NCH = RECV ? kIknpRecvChunks : kIknpSendChunks;  // chunks per workgroup step
     constexpr uint32_t kKey0 = kTeDualBytes, kKey1 = kKey0 + kKeyBytes;
     constexpr uint32_t kBuf = RECV ? kKey1 + kKeyBytes : kKey1;  // byte address of chunk buffer 0
     load_te_dual((uint32_t *)smem, g_te0);
@@ -394,9 +394,9 @@ hipError_t launch_iknp_fused(bool recv, const uint32_t *rk0, const uint32_t *rk1
                              const uint32_t *te0, hipStream_t s) {
     if (n == 0) return hipSuccess;
     const size_t chunks = (n + 511) / 512;
-    const uint32_t nch = recv ? 4 : 8;
+    const uint32_t nch = recv ? kIknpRecvChunks : kIknpSendChunks;
     const size_t groups = (chunks + nch - 1) / nch;
-    const unsigned grid = (unsigned)(groups < 256 ? groups : 256);
+    const unsigned grid = (unsigned)(groups < kIknpGrid ? groups : kIknpGrid);
     const size_t lds = kTeDualBytes + (recv ? 2 : 1) * kKeyBytes + (size_t)nch * kChunkBuf;
     const bool mis = (pos0 & 15u) != 0;
     // every counter this launch encrypts below 2^32 blocks (64 GiB of keystream per column): the cheaper first round

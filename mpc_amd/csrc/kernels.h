@@ -290,6 +290,14 @@ void launch_slab_be(uint4 *T, const Layout &lt, uint32_t rows, uint32_t batch, u
                     hipStream_t s);
 
 // ---- OT kernels (ot_kernels.hip) -------------------------------------------------------------
+// Launch shapes of the persistent OT kernels.  Every one of them caps its grid and loops over the rest of its work; the
+// sweep tests (tests/test_gpu_ot_sweeps.py) read these values from this file and size themselves past one trip.
+constexpr int kIknpThreads = 1024;    // k_iknp_fused: lanes per workgroup (8 slices x 128 columns)
+constexpr int kIknpGrid = 256;        // ... at most this many workgroups, each walking groups of chunks (grp += gridDim.x)
+constexpr int kIknpRecvChunks = 4;    // ... chunks of 512 OTs per group and trip as receiver (4 chunks x 2 streams)
+constexpr int kIknpSendChunks = 8;    // ... and as sender
+constexpr int kCotThreads = 1024;     // k_cot_dual, k_kos_accumulate: one lane = one OT per trip
+constexpr int kCotGrid = 256;         // ... at most this many workgroups (j += gridDim.x * kCotThreads)
 // IKNP OT extension, fused (iknp_fused_kernels.hip): column AES-128-CTR PRG + u-matrix / delta fold + createLabels.
 // rk0/rk1: [128][44] expanded column keys (big-endian words); pos0: bytes every column stream has already
 // produced; n OTs in chunks of 512.
@@ -324,6 +332,8 @@ void launch_vole_receiver(const VoleMod &mod, const uint4 *u_msg, size_t m, uint
 // ---- Chou-Orlandi base OT kernels (co_kernels.hip) -------------------------------------------
 // The constants of one session, passed by value (uniform across the grid).  a: the sender's scalar mod N, non-zero, limbs
 // least significant first; ainv: AaInv = -(a * A); g, a: the generator and the sender's point A; points in Montgomery form.
+constexpr int kCoThreads = 256;  // one lane = one OT per trip
+constexpr int kCoGrid = 2048;    // grid-stride beyond 2048 workgroups (8 per CU)
 struct CoSender {
     uint32_t a[kVoleLimbs];
     Aff ainv;

@@ -196,7 +196,7 @@ void launch_cot_recv_classic(uint4 seed, const uint8_t *flags, const uint4 *sent
 // only on round key r - 1 and are issued together with the 16 (or 32) state look-ups of round r.
 // The first version (k_mitccrh / k_cot_send / k_cot_recv above, kept as GC_COT_CLASSIC=1) used a 4 KiB classic
 // T-table per 256-thread block: ~3.5-way bank conflicts on every look-up and a table reload per 256 OTs.
-constexpr int kCotThreads = 1024;
+// (kCotThreads lanes, at most kCotGrid workgroups: kernels.h)
 
 // MODE 0: blks[j*h + t] ^= AES_key(j)(blks[j*h + t]), h = 1 or 2 (mitccrh.go:107-127)
 // MODE 1: COT.Send pads   (cot.go:160-181): out[2j] = H_j(x_j) ^ L0_j, out[2j+1] = H_j(x_j ^ delta) ^ L1_j;
@@ -261,7 +261,7 @@ template <typename K>
 static void launch_cot_dual(K kern, size_t n, hipStream_t s, uint4 seed, uint4 delta, uint64_t gid0, const uint4 *data,
                             const uint4 *wires, const uint8_t *flags, uint4 *out, const uint32_t *te0) {
     (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kTeDualBytes);
-    const unsigned grid = (unsigned)std::min<size_t>(256, (n + kCotThreads - 1) / kCotThreads);
+    const unsigned grid = (unsigned)std::min<size_t>(kCotGrid, (n + kCotThreads - 1) / kCotThreads);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kCotThreads), kTeDualBytes, s, seed, delta, gid0, data, wires, flags, out, n, te0);
 }
 
@@ -352,7 +352,7 @@ void launch_kos_accumulate(const uint32_t *rk, uint64_t idx0, const uint4 *v, co
                            unsigned long long *acc, const uint32_t *te0, hipStream_t s) {
     if (n == 0) return;
     (void)hipFuncSetAttribute((const void *)k_kos_accumulate, hipFuncAttributeMaxDynamicSharedMemorySize, kTeDualBytes);
-    const unsigned grid = (unsigned)std::min<size_t>(256, (n + kCotThreads - 1) / kCotThreads);
+    const unsigned grid = (unsigned)std::min<size_t>(kCotGrid, (n + kCotThreads - 1) / kCotThreads);
     hipLaunchKernelGGL(k_kos_accumulate, dim3(grid), dim3(kCotThreads), kTeDualBytes, s, rk, idx0, v, bits, n, acc, te0);
 }
 

@@ -15,11 +15,14 @@ from mpc_amd.circuit import LABEL, WIRE
 from tests import go_transcript as gt
 from tests import py_co_reference as co
 from tests.test_py_co_reference import go_session, round2_hash
-from tests.util import drbg
+from tests.util import drbg, kernel_constants
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [0, 1, 63, 64, 65, 257]  # wave and workgroup edges, one ragged grid-stride pass
+SIZES = [0, 1, 63, 64, 65, 257]  # wave and workgroup edges, a second, ragged workgroup (the grid-stride loops make one trip)
+CO_THREADS, CO_GRID = kernel_constants("kCoThreads", "kCoGrid")
+CO_SWEEP = CO_GRID * CO_THREADS  # OTs of one trip of the capped grid
+N_CO = CO_SWEEP + CO_THREADS + 37  # the second trip has a full workgroup and one with 37 live lanes
 ID0S = [0, (1 << 32) + 5]
 POOL = 257
 TOP = 1 << 256
@@ -168,6 +171,69 @@ def test_byte_parity(ctx, pool, n, id0, form):
     for i in range(n):  # decrypt(encrypt) = L_choice
         if i not in want_bad:
             assert label_raw(labels[i:i + 1])[0] == pool["pairs"][i][pool["choice"][i]], i
+
+
+def test_past_one_grid_sweep(ctx):
+    """N_CO OTs through the device-pointer forms: every lane of the first CO_THREADS + 37 makes a second trip of its
+    grid-stride loop.  decrypt(encrypt(choices)) = L_choice for every OT, and point, ciphertext and label equal the
+    restatement's bytes at 24 indices (both sides of the sweep edge among them).  Then the sender meets two hostile points,
+    one in each trip."""
+    n, id0 = N_CO, (1 << 32) - 7  # the id carries into its high word at OT 7
+    assert n > CO_SWEEP + CO_THREADS and (n - CO_SWEEP) % CO_THREADS != 0
+    rng = np.random.default_rng(20240607)
+    a = int.from_bytes(drbg("co/sweep/a", 32), "big")
+    A, AaInv = co.sender_setup(a)
+    Ab, AaInvb = co.point_bytes(A), co.point_bytes(AaInv)
+    scalars = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    choice = rng.integers(0, 2, n).astype(np.uint8)
+    wires = np.zeros(n, WIRE)
+    for half in ("l0", "l1"):
+        wires[half]["d0"] = rng.integers(0, 1 << 64, n, dtype=np.uint64)
+        wires[half]["d1"] = rng.integers(0, 1 << 64, n, dtype=np.uint64)
+    d_sc, d_ch, d_w = ctx.to_device(scalars), ctx.to_device(choice), ctx.to_device(wires)
+    sentinel = 0xA5
+    d_pts, d_ct, d_lab = ctx.empty((n, 64)).zero(sentinel), ctx.empty((n, 32)).zero(sentinel), ctx.empty((n, 16)).zero(sentinel)
+    d_status = ctx.empty(2, np.uint64).zero(sentinel)
+    engine.co_receiver_choices_dev(ctx, Ab, d_sc, d_ch, n, d_pts)
+    engine.co_sender_encrypt_dev(ctx, a, AaInvb, d_pts, d_w, n, id0, d_ct, d_status)
+    engine.co_receiver_decrypt_dev(ctx, Ab, d_sc, d_ch, d_ct, n, id0, d_lab)
+    ctx.sync()
+    pts, ct = d_pts.numpy(), d_ct.numpy()
+    labels = np.frombuffer(d_lab.numpy().tobytes(), LABEL)
+    assert [int(v) for v in d_status.numpy()] == [0, (1 << 64) - 1]
+    want = pick(wires, choice)
+    bad = np.flatnonzero(labels != want)
+    assert bad.size == 0, "decrypt(encrypt) != L_choice at %d OTs, the first %d" % (bad.size, bad[0])
+    idx = {0, 1, n - 2, n - 1} | set(range(CO_SWEEP - 4, CO_SWEEP + 4))
+    while len(idx) < 24:
+        idx.add(int(rng.integers(0, n)))
+    for i in sorted(idx):
+        b, c = int.from_bytes(bytes(scalars[i]), "big"), int(choice[i])
+        pair = (label_raw(wires["l0"][i:i + 1])[0], label_raw(wires["l1"][i:i + 1])[0])
+        B = co.receiver_choices(A, [b], [c])
+        assert bytes(pts[i]) == co.point_bytes(B[0]), "choice point %d" % i
+        cts, none_bad = co.sender_encrypt(a, AaInv, B, [pair], id0 + i)
+        assert not none_bad and bytes(ct[i]) == cts[0], "ciphertext %d" % i
+        assert label_raw(labels[i:i + 1]) == co.receiver_decrypt(A, [b], [c], cts, id0 + i) == [pair[c]], "label %d" % i
+    # a second encrypt of the same points, two of them hostile: one off the curve in the second trip, x = p in the first
+    off, xp = CO_SWEEP + 12, 700
+    assert xp < CO_SWEEP < off < n
+    x, y = co.point_from_bytes(bytes(pts[off]))
+    hostile = {off: (x, (y + 1) % co.P), xp: HOSTILE["x_equals_p"]}
+    for at, p in hostile.items():
+        assert not co.valid_point(p)
+        d_pts.upload(np.frombuffer(co.point_bytes(p), np.uint8), 64 * at)
+    d_ct2 = ctx.empty((n, 32)).zero(sentinel)
+    engine.co_sender_encrypt_dev(ctx, a, AaInvb, d_pts, d_w, n, id0, d_ct2, d_status)
+    ctx.sync()
+    assert [int(v) for v in d_status.numpy()] == [2, xp]
+    ct2 = d_ct2.numpy()
+    for at in hostile:
+        assert not ct2[at].any(), "the ciphertexts of a refused point are zero"
+        assert (ct2[at + 1:at + 3] == ct[at + 1:at + 3]).all(), "the OTs behind a refused point are untouched by it"
+    rest = np.ones(n, bool)
+    rest[list(hostile)] = False
+    assert (ct2[rest] == ct[rest]).all()
 
 
 def test_short_coordinates(ctx):

@@ -268,17 +268,31 @@ def test_bitcot_device_resident_matches_host(ctx, n):
 
 def test_cot_tuned_and_classic_kernels_agree(ctx, monkeypatch):
     """the dual-table persistent COT kernels (default) and the first, 4 KiB-table form (GC_COT_CLASSIC) are both the
-    MITCCRH of ot/mitccrh.go: the reference's own vectors on each, ragged sizes"""
-    import subprocess, sys, os
+    MITCCRH of ot/mitccrh.go: each child's bytes are the oracle's for the same inputs (key indices from gid0 = 5 on, a ragged
+    size), and so each other's"""
+    import hashlib, subprocess, sys, os
     code = ("import numpy as np, oracle; from mpc_amd import engine; from tests.test_gpu_ot import labels; from tests.util import drbg;"
             "ctx = engine.Context(0); seed = oracle.label_from_bytes(drbg('cls', 16)); x = labels('clsx', 3001);"
-            "out = engine.mitccrh_hash(ctx, seed, 5, x, 1); m = oracle.MITCCRH(seed, 1);"
+            "out = engine.mitccrh_hash(ctx, seed, 5, x, 1);"
             "import hashlib; print(hashlib.sha256(out.tobytes()).hexdigest())")
     env = dict(os.environ, PYTHONPATH=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     a = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     b = subprocess.run([sys.executable, "-c", code], env=dict(env, GC_COT_CLASSIC="1"), capture_output=True, text=True, timeout=300)
     assert a.returncode == 0 and b.returncode == 0, a.stderr + b.stderr
     assert a.stdout.strip().splitlines()[-1] == b.stdout.strip().splitlines()[-1]
+    # the oracle's MITCCRH object with its key counter preset to 5, 8 keys per call (cot.go:160-171)
+    seed, want = oracle.label_from_bytes(drbg("cls", 16)), labels("clsx", 3001)
+    m = oracle.MITCCRH(seed, 8)
+    m.s.gid = 5
+    for i in range(0, 3001, 8):
+        k = min(8, 3001 - i)
+        pad = np.zeros(8, LABEL)
+        pad[:k] = want[i:i + k]
+        m.hash(pad, 8, 1)
+        want[i:i + k] = pad[:k]
+    digest = hashlib.sha256(want.tobytes()).hexdigest()
+    assert a.stdout.strip().splitlines()[-1] == digest, "the tuned kernel's bytes are not the oracle's"
+    assert b.stdout.strip().splitlines()[-1] == digest, "the classic kernel's bytes are not the oracle's"
 
 
 @pytest.mark.parametrize("n", [0, 1, 7, 8, 9, 1000, 4097])

@@ -153,3 +153,35 @@ def test_rot_pads_pair_up_and_hit_the_reference_vectors():
     r = oracle.rot_receive((0, 0), z)
     for i in range(8):
         assert oracle.label_to_bytes(w[i]["l0"]).hex() == MITCCRH_BLOCKS[i] == oracle.label_to_bytes(r[i]).hex()
+
+
+@pytest.mark.parametrize("gid0", [(1 << 32) - 4, (1 << 64) - 4])
+def test_mitccrh_key_index_carries_and_wraps(gid0):
+    """mitccrh.go:70-89 with the key counter started elsewhere than 0: 16 keys that cross the carry from the low 32-bit key
+    word into the high one (2^32 - 4) and the wrap of Go's uint64 (2^64 - 4), h = 2.  The C oracle, the Python restatement
+    (both with `gid` preset) and AES_key(gid)(x) ^ x spelled out per block agree: the GPU tests lean on the first two."""
+    from tests import py_ot_reference as po
+    from tests.py_reference import AES, label_bytes, label_from_bytes, lxor
+    keys, h = 16, 2
+    seed = oracle.label_from_bytes(drbg("carry/seed", 16))
+    blks = labels("carry/blks", keys * h)
+    x = [(int(b["d0"]), int(b["d1"])) for b in blks]
+    m = oracle.MITCCRH(seed, 8)
+    m.s.gid = gid0
+    got = blks.copy()
+    for i in range(0, keys, 8):
+        m.hash(got[i * h:(i + 8) * h], 8, h)
+    end = (gid0 + keys) % (1 << 64)  # 2^32 + 12, or 12 behind the wrap
+    assert int(m.s.gid) == end
+    pm = po.Mitccrh(seed)
+    pm.gid = gid0
+    py = []
+    for i in range(0, keys, 8):
+        py += pm.hash(x[i * h:(i + 8) * h], 8, h)
+    assert pm.gid == end
+    direct = []
+    for j in range(keys):
+        aes = AES(label_bytes(lxor(((gid0 + j) % (1 << 64), 0), seed)))
+        direct += [lxor(b, label_from_bytes(aes.encrypt(label_bytes(b)))) for b in x[j * h:(j + 1) * h]]
+    assert [(int(b["d0"]), int(b["d1"])) for b in got] == py == direct
+    assert len(set(direct)) == keys * h

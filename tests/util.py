@@ -1,5 +1,7 @@
 """Shared helpers for the tests: deterministic byte streams and bit packing."""
 import hashlib
+import os
+import re
 
 import numpy as np
 
@@ -13,6 +15,20 @@ def drbg(seed, n):
         out += hashlib.sha256(s + ctr.to_bytes(8, "big")).digest()
         ctr += 1
     return bytes(out[:n])
+
+
+def kernel_constants(*names):
+    """integer `constexpr` values of mpc_amd/csrc/kernels.h by name (the launch shapes of the persistent kernels): tests that
+    have to get past one trip of a capped grid size themselves from these, so a changed cap moves them along"""
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mpc_amd", "csrc", "kernels.h")
+    with open(path) as f:
+        text = f.read()
+    out = []
+    for name in names:
+        m = re.findall(r"^\s*constexpr\s+(?:int|unsigned|uint32_t|size_t)\s+%s\s*=\s*(\d+)\s*;" % re.escape(name), text, re.M)
+        assert len(m) == 1, "kernels.h: %d definitions of %s" % (len(m), name)
+        out.append(int(m[0]))
+    return out[0] if len(out) == 1 else tuple(out)
 
 
 def bits_lsb(value, nbits):
