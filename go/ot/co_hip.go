@@ -17,7 +17,8 @@ import (
 )
 
 // SOURCE ONLY (no Go toolchain in the build image).  Drop-in bodies of (*CO).Send and (*CO).Receive (ot/co.go:263-361)
-// with the per-OT elliptic-curve and SHA-256 work on MI355X (gcengine.h: gc_co_*).  The scalars are drawn here with
+// with the per-OT elliptic-curve and SHA-256 work on MI355X (gcengine.h: gc_co_*; the receiver goes through a gc_co_base
+// handle, which owns the window table of the session's A).  The scalars are drawn here with
 // crand.Int exactly as GenerateCOSenderSetup (co_helpers.go:83) and BuildCOChoices (:151) draw them — one per OT, in
 // order, from co.rand — and every SendData / ReceiveData / Flush is the reference's, so a Go peer sees the same bytes.
 // A maintainer replaces
@@ -132,6 +133,16 @@ func (co *CO) receiveHIP(ctx *C.gc_ctx, flags []bool, result []Label) error {
 	if !coPoint(Ax, Ay, &A) {
 		return ErrPointNotOnCurve
 	}
+	// The session's handle: A is checked once (ensureOnCurve, co_helpers.go:144) and its fixed-base window table is built
+	// and owned by the handle; both receiver calls below sum b*G and b*A from tables instead of walking the ladder.  With
+	// the create included the handle is the faster way from a single OT on (DESIGN.md section 11), so it is used for
+	// every n.  The deferred free runs on every exit path.
+	var st C.int
+	base := C.gc_co_base_create(ctx, &A, &st)
+	if base == nil {
+		return coErr(st)
+	}
+	defer C.gc_co_base_free(base)
 
 	// BuildCOChoices (co_helpers.go:140-177): one crand.Int per OT, in order
 	n := len(flags)
@@ -149,7 +160,7 @@ func (co *CO) receiveHIP(ctx *C.gc_ctx, flags []bool, result []Label) error {
 		}
 	}
 	points := make([]C.gc_p256_point, n+1)
-	st := C.gc_co_receiver_choices(ctx, &A, (*C.uint8_t)(unsafe.Pointer(&scalars[0])), (*C.uint8_t)(unsafe.Pointer(&choice[0])),
+	st = C.gc_co_base_choices(base, (*C.uint8_t)(unsafe.Pointer(&scalars[0])), (*C.uint8_t)(unsafe.Pointer(&choice[0])),
 		C.size_t(n), &points[0])
 	if st != C.GC_OK {
 		return coErr(st)
@@ -183,7 +194,7 @@ func (co *CO) receiveHIP(ctx *C.gc_ctx, flags []bool, result []Label) error {
 
 	// DecryptCOCiphertexts (co_helpers.go:191-219)
 	labels := make([]Label, n+1)
-	st = C.gc_co_receiver_decrypt(ctx, &A, (*C.uint8_t)(unsafe.Pointer(&scalars[0])), (*C.uint8_t)(unsafe.Pointer(&choice[0])),
+	st = C.gc_co_base_decrypt(base, (*C.uint8_t)(unsafe.Pointer(&scalars[0])), (*C.uint8_t)(unsafe.Pointer(&choice[0])),
 		(*C.uint8_t)(unsafe.Pointer(&ct[0])), C.size_t(n), C.uint64_t(0), (*C.gc_label)(unsafe.Pointer(&labels[0])))
 	if st != C.GC_OK {
 		return coErr(st)

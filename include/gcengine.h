@@ -755,6 +755,25 @@ int gc_co_receiver_decrypt(gc_ctx *, const gc_p256_point *A, const uint8_t *scal
 int gc_co_receiver_decrypt_dev(gc_ctx *, const gc_p256_point *A, const void *d_scalars, const void *d_choice,
                                const void *d_ct, size_t n, uint64_t id0, void *d_labels_out);
 
+/* The receiver's side of ONE session behind a handle: the two receiver calls above, byte for byte (scalars mod N, b = 0
+ * mod N gives infinity, one choice byte per OT, the id of OT i is id0 + i, host forms synchronous, _dev forms asynchronous
+ * on the ctx stream, n = 0: GC_OK and nothing written), with b_i * G and b_i * A summed from fixed-base window tables in
+ * device memory instead of walked by double-and-add.  gc_co_base_create checks A (not VALID: NULL and *status =
+ * GC_E_POINT), builds A's table on the host (61 440 bytes) and uploads it; the first handle of a ctx also uploads G's table
+ * (built once per process), which is freed with the ctx.  Create is synchronous and not allowed between
+ * gc_ctx_capture_begin and _end.  Several handles may live on one ctx, one per session, each for any number of calls; free
+ * them before the ctx.  A NULL handle or NULL pointer: GC_E_ARG.  The tables are indexed by digits of b_i (as the AES
+ * tables are by secret bytes); a caller who does not want that keeps the calls above. */
+typedef struct gc_co_base gc_co_base;
+gc_co_base *gc_co_base_create(gc_ctx *, const gc_p256_point *A, int *status);
+void gc_co_base_free(gc_co_base *); /* waits for the ctx stream first; NULL is a no-op */
+int gc_co_base_choices(gc_co_base *, const uint8_t *scalars, const uint8_t *choice, size_t n, gc_p256_point *points_out);
+int gc_co_base_choices_dev(gc_co_base *, const void *d_scalars, const void *d_choice, size_t n, void *d_points_out);
+int gc_co_base_decrypt(gc_co_base *, const uint8_t *scalars, const uint8_t *choice, const uint8_t *ct, size_t n,
+                       uint64_t id0, gc_label *labels_out);
+int gc_co_base_decrypt_dev(gc_co_base *, const void *d_scalars, const void *d_choice, const void *d_ct, size_t n,
+                           uint64_t id0, void *d_labels_out);
+
 #ifdef __cplusplus
 }
 #endif

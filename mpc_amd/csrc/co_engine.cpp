@@ -4,8 +4,17 @@
 // device side.  The session constants (a, A, AaInv) are host pointers in every form and are prepared here, on the host, with
 // the arithmetic of p256.h that the kernels run: gc_co_sender_setup is two scalar multiplications per SESSION, not worth a
 // launch.
+//
+// gc_co_base_*: the receiver's side of one session behind a handle that owns A's window table (co_table.h).  The tables are
+// built here, on the host, for the reason above: the 252 dependent doublings of a table are a lone wave's work on the
+// device, about 2 ms, and a fraction of that on a CPU core.  G's table is built once per process and uploaded once per ctx.
+#define GC_CO_TABLE_BUILD 1  // co_table.h: the host-side table build as well
+
 #include <cstring>
+#include <memory>
+#include <mutex>
 #include <new>
+#include <vector>
 
 #include "engine.h"
 
@@ -74,9 +83,162 @@ hipError_t reset_status(void *d_status, hipStream_t s) {
     return hipMemsetAsync((uint8_t *)d_status + 8, 0xff, 8, s);
 }
 
+// the generator's table, built by the first handle of the process
+const std::vector<CoTabEntry> &g_table() {
+    static std::vector<CoTabEntry> tab;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        std::vector<CoTabEntry> t(co_tab_entries(kCoTabWidthG));
+        co_tab_build<kCoTabWidthG>(generator(), t.data());
+        tab.swap(t);
+    });
+    return tab;
+}
+
+// a table into device memory, complete when the call returns (the source is pageable host memory)
+int upload_table(gc_ctx *ctx, const std::vector<CoTabEntry> &tab, CoTabEntry **d_out) {
+    void *d = nullptr;
+    GC_HIP(hipMalloc(&d, tab.size() * sizeof(CoTabEntry)));
+    hipError_t e = hipMemcpyAsync(d, tab.data(), tab.size() * sizeof(CoTabEntry), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        GC_HIP(e);
+    }
+    *d_out = (CoTabEntry *)d;
+    return GC_OK;
+}
+
+}  // namespace
+
+struct gc_co_base {
+    gc_ctx *ctx = nullptr;
+    Aff a;                      // the sender's point, for B = b * G + A
+    CoTabEntry *d_tab = nullptr;  // A's table, width kCoTabWidthA
+};
+
+namespace {
+
+int co_base_init(gc_co_base *h, gc_ctx *ctx) {
+    std::vector<CoTabEntry> tab(co_tab_entries(kCoTabWidthA));
+    co_tab_build<kCoTabWidthA>(h->a, tab.data());
+    const std::vector<CoTabEntry> &g = g_table();
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    if (!ctx->d_co_g_tab) {
+        const int rc = upload_table(ctx, g, &ctx->d_co_g_tab);
+        if (rc != GC_OK) return rc;
+    }
+    h->ctx = ctx;
+    return upload_table(ctx, tab, &h->d_tab);
+}
+
+bool base_args(const gc_co_base *h, size_t n, bool pointers) { return h && (n == 0 || pointers) && bytes_fit(n); }
+
 }  // namespace
 
 extern "C" {
+
+gc_co_base *gc_co_base_create(gc_ctx *ctx, const gc_p256_point *A, int *status) try {
+    int rc = GC_OK;
+    std::unique_ptr<gc_co_base> h;
+    if (!ctx || !A) {
+        rc = GC_E_ARG;
+    } else if (ctx->capturing) {
+        rc = GC_E_ARG;  // allocates and waits for the stream: not between gc_ctx_capture_begin and _end
+    } else {
+        h.reset(new gc_co_base);
+        if (!load_point(A, &h->a)) rc = GC_E_POINT;  // ensureOnCurve(Ax, Ay), co_helpers.go:144
+        if (rc == GC_OK) rc = co_base_init(h.get(), ctx);
+    }
+    if (status) *status = rc;
+    return rc == GC_OK ? h.release() : nullptr;
+} catch (...) {
+    const int rc__ = gc::on_exception();
+    if (status) *status = rc__;
+    return nullptr;
+}
+
+void gc_co_base_free(gc_co_base *h) {
+    if (!h) return;
+    if (h->ctx) {
+        (void)hipSetDevice(h->ctx->device);
+        (void)hipStreamSynchronize(h->ctx->stream);  // a _dev call may still read the table
+    }
+    if (h->d_tab) (void)hipFree(h->d_tab);
+    delete h;
+}
+
+int gc_co_base_choices_dev(gc_co_base *h, const void *d_scalars, const void *d_choice, size_t n, void *d_points_out) {
+    if (!base_args(h, n, d_scalars && d_choice && d_points_out)) return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    gc_ctx *ctx = h->ctx;
+    GC_HIP(hipSetDevice(ctx->device));
+    launch_co_choices_tab(ctx->d_co_g_tab, h->a, (const uint4 *)d_scalars, (const uint8_t *)d_choice, n, (uint4 *)d_points_out,
+                          ctx->stream);
+    GC_HIP(hipGetLastError());
+    return GC_OK;
+}
+
+int gc_co_base_decrypt_dev(gc_co_base *h, const void *d_scalars, const void *d_choice, const void *d_ct, size_t n,
+                           uint64_t id0, void *d_labels_out) {
+    if (!base_args(h, n, d_scalars && d_choice && d_ct && d_labels_out)) return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    gc_ctx *ctx = h->ctx;
+    GC_HIP(hipSetDevice(ctx->device));
+    launch_co_decrypt_tab(h->d_tab, (const uint4 *)d_scalars, (const uint8_t *)d_choice, (const uint4 *)d_ct, n, id0,
+                          (uint4 *)d_labels_out, ctx->stream);
+    GC_HIP(hipGetLastError());
+    return GC_OK;
+}
+
+int gc_co_base_choices(gc_co_base *h, const uint8_t *scalars, const uint8_t *choice, size_t n, gc_p256_point *points_out) try {
+    if (!base_args(h, n, scalars && choice && points_out)) return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    gc_ctx *ctx = h->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    DevBuf d_sc, d_ch, d_out;
+    GC_HIP(d_sc.alloc(n * 32));
+    GC_HIP(d_ch.alloc(n));
+    GC_HIP(d_out.alloc(n * 64));
+    hipStream_t s = ctx->stream;
+    GC_HIP(hipMemcpyAsync(d_sc.p, scalars, n * 32, hipMemcpyHostToDevice, s));
+    GC_HIP(hipMemcpyAsync(d_ch.p, choice, n, hipMemcpyHostToDevice, s));
+    launch_co_choices_tab(ctx->d_co_g_tab, h->a, (const uint4 *)d_sc.p, (const uint8_t *)d_ch.p, n, (uint4 *)d_out.p, s);
+    GC_HIP(hipGetLastError());
+    GC_HIP(hipMemcpyAsync(points_out, d_out.p, n * 64, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipStreamSynchronize(s));
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_co_base_decrypt(gc_co_base *h, const uint8_t *scalars, const uint8_t *choice, const uint8_t *ct, size_t n, uint64_t id0,
+                       gc_label *labels_out) try {
+    if (!base_args(h, n, scalars && choice && ct && labels_out)) return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    gc_ctx *ctx = h->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    DevBuf d_sc, d_ch, d_ct, d_out;
+    GC_HIP(d_sc.alloc(n * 32));
+    GC_HIP(d_ch.alloc(n));
+    GC_HIP(d_ct.alloc(n * 32));
+    GC_HIP(d_out.alloc(n * 16));
+    hipStream_t s = ctx->stream;
+    GC_HIP(hipMemcpyAsync(d_sc.p, scalars, n * 32, hipMemcpyHostToDevice, s));
+    GC_HIP(hipMemcpyAsync(d_ch.p, choice, n, hipMemcpyHostToDevice, s));
+    GC_HIP(hipMemcpyAsync(d_ct.p, ct, n * 32, hipMemcpyHostToDevice, s));
+    launch_co_decrypt_tab(h->d_tab, (const uint4 *)d_sc.p, (const uint8_t *)d_ch.p, (const uint4 *)d_ct.p, n, id0,
+                          (uint4 *)d_out.p, s);
+    GC_HIP(hipGetLastError());
+    GC_HIP(hipMemcpyAsync(labels_out, d_out.p, n * 16, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipStreamSynchronize(s));
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
 
 int gc_co_sender_setup(const uint8_t *a, gc_p256_point *A_out, gc_p256_point *AaInv_out) {
     if (!a || !A_out || !AaInv_out) return GC_E_ARG;

@@ -306,6 +306,7 @@ void gc_ctx_destroy(gc_ctx *c) {
         (void)hipStreamDestroy(c->stream);
     }
     if (c->d_te0) (void)hipFree(c->d_te0);
+    if (c->d_co_g_tab) (void)hipFree(c->d_co_g_tab);
     if (c->d_coop) (void)hipFree(c->d_coop);
     if (c->h_coop_err) (void)hipHostFree(c->h_coop_err);
     for (int b = 0; b < 2; b++) {

@@ -32,6 +32,7 @@ struct gc_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     uint32_t *d_te0 = nullptr;  // Te0 (1 KiB), L2-resident source of the LDS tables
+    gc::CoTabEntry *d_co_g_tab = nullptr;  // the generator's window table (co_table.h), uploaded by the first gc_co_base_create
     std::mutex mu;              // serialises host-buffer calls sharing this ctx's stream
     bool capturing = false;     // between gc_ctx_capture_begin / _end: launches are recorded, not run
     // host-buffer calls on PINNED caller memory (gc_host_alloc / gc_host_register): the DMA runs on its own stream,

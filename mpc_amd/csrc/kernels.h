@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "co_table.h"
 #include "p256.h"
 #include "plan.h"
 #include "vole_mod.h"
@@ -349,5 +350,19 @@ void launch_co_choices(const CoBase &base, const uint4 *scalars, const uint8_t *
                        hipStream_t s);
 void launch_co_decrypt(const CoBase &base, const uint4 *scalars, const uint8_t *choice, const uint4 *ct, size_t n, uint64_t id0,
                        uint4 *labels_out, hipStream_t s);
+
+// ---- Chou-Orlandi receiver over fixed-base window tables (co_base_kernels.hip, co_table.h) -----
+// The same two receiver loops with b_i * G and b_i * A taken from tables in device memory (CoTabEntry [co_tab_entries(w)],
+// built on the host by co_tab_build) instead of the ladder: one plain mixed addition per window and no doubling.  G's table
+// is built once per process, where a wider window pays; A's is built per session.
+constexpr int kCoTabThreads = 256;  // one lane = one OT per trip
+constexpr int kCoTabGrid = 2048;    // grid-stride beyond 2048 workgroups
+constexpr int kCoTabWidthA = 4;     // 64 windows x 15 entries = 61 440 bytes per session
+constexpr int kCoTabWidthG = 8;     // 32 windows x 255 entries = 522 240 bytes per ctx (EXPERIMENTS.md: measured against 4)
+// a: the sender's point A (Montgomery form), added when the choice is set
+void launch_co_choices_tab(const CoTabEntry *g_tab, const Aff &a, const uint4 *scalars, const uint8_t *choice, size_t n,
+                           uint4 *points_out, hipStream_t s);
+void launch_co_decrypt_tab(const CoTabEntry *a_tab, const uint4 *scalars, const uint8_t *choice, const uint4 *ct, size_t n,
+                           uint64_t id0, uint4 *labels_out, hipStream_t s);
 
 }  // namespace gc

@@ -240,6 +240,12 @@ def lib():
         "gc_co_receiver_choices_dev": (i32, [vp, vp, vp, vp, sz, vp]),
         "gc_co_receiver_decrypt": (i32, [vp, vp, vp, vp, vp, sz, C.c_uint64, vp]),
         "gc_co_receiver_decrypt_dev": (i32, [vp, vp, vp, vp, vp, sz, C.c_uint64, vp]),
+        "gc_co_base_create": (vp, [vp, vp, ip]),
+        "gc_co_base_free": (None, [vp]),
+        "gc_co_base_choices": (i32, [vp, vp, vp, sz, vp]),
+        "gc_co_base_choices_dev": (i32, [vp, vp, vp, sz, vp]),
+        "gc_co_base_decrypt": (i32, [vp, vp, vp, vp, sz, C.c_uint64, vp]),
+        "gc_co_base_decrypt_dev": (i32, [vp, vp, vp, vp, sz, C.c_uint64, vp]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -1496,3 +1502,52 @@ def co_receiver_decrypt_dev(ctx, A, d_scalars, d_choice, d_ct, n, id0, d_labels_
     """device pointers; asynchronous on the ctx stream"""
     _check(lib().gc_co_receiver_decrypt_dev(ctx.h, _p(co_point(A)), _dp(d_scalars), _dp(d_choice), _dp(d_ct), n, id0,
                                             _dp(d_labels_out)), "gc_co_receiver_decrypt_dev")
+
+
+class CoBase:
+    """gc_co_base: the receiver's side of one session.  The handle checks A once and owns its fixed-base window table; the
+    calls are co_receiver_choices / co_receiver_decrypt byte for byte, without their double-and-add ladder"""
+
+    def __init__(self, ctx, A):
+        st = C.c_int(0)
+        self.ctx = ctx  # gc_co_base_free waits for this ctx's stream: the handle has to go first
+        self.h = lib().gc_co_base_create(ctx.h, _p(co_point(A)), C.byref(st))
+        if not self.h:
+            raise EngineError(st.value, "gc_co_base_create")
+
+    def choices(self, scalars, choice):
+        """gc_co_base_choices -> points, uint8 [n, 64]"""
+        sc = _scalars(scalars)
+        n = len(sc)
+        ch = _choices(choice, n)
+        out = np.zeros((max(n, 1), 64), np.uint8)
+        _check(lib().gc_co_base_choices(self.h, _p(sc) if n else None, _p(ch) if n else None, n, _p(out)), "gc_co_base_choices")
+        return out[:n]
+
+    def choices_dev(self, d_scalars, d_choice, n, d_points_out):
+        """device pointers; asynchronous on the ctx stream"""
+        _check(lib().gc_co_base_choices_dev(self.h, _dp(d_scalars), _dp(d_choice), n, _dp(d_points_out)), "gc_co_base_choices_dev")
+
+    def decrypt(self, scalars, choice, ct, id0=0):
+        """gc_co_base_decrypt -> labels [n]"""
+        sc = _scalars(scalars)
+        n = len(sc)
+        ch = _choices(choice, n)
+        c = np.ascontiguousarray(ct, dtype=np.uint8).reshape(-1, 32)
+        assert len(c) == n
+        out = np.zeros(max(n, 1), LABEL)
+        _check(lib().gc_co_base_decrypt(self.h, _p(sc) if n else None, _p(ch) if n else None, _p(c) if n else None, n, id0,
+                                        _p(out)), "gc_co_base_decrypt")
+        return out[:n]
+
+    def decrypt_dev(self, d_scalars, d_choice, d_ct, n, id0, d_labels_out):
+        """device pointers; asynchronous on the ctx stream"""
+        _check(lib().gc_co_base_decrypt_dev(self.h, _dp(d_scalars), _dp(d_choice), _dp(d_ct), n, id0, _dp(d_labels_out)),
+               "gc_co_base_decrypt_dev")
+
+    def close(self):
+        if self.h:
+            if self.ctx.h is None:  # the stream the free would wait for is gone with the ctx
+                raise EngineError(GC_E_ARG, "CoBase.close: close the handle before its Context")
+            lib().gc_co_base_free(self.h)
+            self.h = None
