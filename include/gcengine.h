@@ -711,7 +711,8 @@ int gc_vole_receiver_reduce_dev(gc_ctx *, const uint8_t *p, const void *d_u_msg,
 /* ------------------------------------------------------------------------------------------
  * Chou-Orlandi base OT on P-256 (ot/co.go, ot/co_helpers.go).  The per-OT work of ONE session (one sender scalar a, one
  * point A), bit-exact with the reference.  crand.Int, the framing and the p2p messages stay with the caller, who passes
- * the scalars it drew.  Other curves, several sessions per call and ot.RSA are not covered.
+ * the scalars it drew.  Several sessions per call are the gc_co_multi_* calls at the end of this section.  Other curves
+ * and ot.RSA are not covered.
  *   gc_p256_point  an affine point, x and y as 32 big-endian bytes each (the caller pads big.Int.Bytes() to that width);
  *                  64 zero bytes are the point at infinity, crypto/elliptic's (0, 0).  A point is VALID when 0 <= x, y < p
  *                  and y^2 = x^3 - 3x + b (curve.IsOnCurve): an encoding >= p is refused, not reduced, and so is infinity.
@@ -773,6 +774,45 @@ int gc_co_base_decrypt(gc_co_base *, const uint8_t *scalars, const uint8_t *choi
                        uint64_t id0, gc_label *labels_out);
 int gc_co_base_decrypt_dev(gc_co_base *, const void *d_scalars, const void *d_choice, const void *d_ct, size_t n,
                            uint64_t id0, void *d_labels_out);
+
+/* S independent sessions in one call: what a caller has who runs S CO.Send / CO.Receive pairs of equal length at once (S
+ * instances of a two-party run, S IKNP set-ups, the set-ups of the parties of a GMW network).  Session-major: OT j of
+ * session s is element i = s * per + j of every per-OT array (the arrays of the one-session calls), and its id is id0 + j,
+ * since Go numbers every session from 0.  Sessions of unequal length are padded by the caller.  The session constants are
+ * arrays: a [S][32] bytes big-endian, any value below 2^256; A and AaInv [S] gc_p256_point.  Byte for byte, session s of a
+ * multi call is the one-session call on that session alone.
+ *   Setup: A_s = a_s * G, AaInv_s = (x, p - y) of a_s * A_s, on the device, one lane per session, from G's window table.
+ *   A BAD SESSION gets zero bytes in all its outputs, and its OTs are not counted as bad points.  Sender calls: a_s = 0 mod
+ *   N, or (encrypt) an AaInv_s that is not VALID.  Receiver calls: an A_s that is not VALID.  A bad point (B_i not VALID) in
+ *   a good session is what it is in gc_co_sender_encrypt: 32 zero bytes and a count.
+ *   d_status: four uint64 in device memory, {bad points, lowest bad OT index i, bad sessions, lowest bad session}, which the
+ *   call itself resets on the stream to {0, ~0, 0, ~0} and the kernel fills; a session is counted once.  Read it after
+ *   gc_ctx_sync.
+ * _dev forms: device pointers for EVERY array, the session constants included (16-byte aligned), asynchronous on the ctx
+ * stream, one kernel per call.  Host forms: host pointers, synchronous, staged; a bad session returns GC_E_ARG from the
+ * sender calls and GC_E_POINT from the receiver calls with *bad_session = the lowest one, a bad point GC_E_POINT with
+ * *bad_index = the lowest i; a bad session wins when both occur; every good output is written all the same (bad_index and
+ * bad_session may be NULL).  S = 0 or per = 0: GC_OK, nothing written, the status included.  A NULL ctx, a NULL array with
+ * S * per > 0, or an S * per * 64 that does not fit size_t: GC_E_ARG.  Setup and choices read G's table: the first such call
+ * of a ctx uploads it as gc_co_base_create does (synchronously), and returns GC_E_ARG between gc_ctx_capture_begin and
+ * _end.  The receiver's decrypt walks the ladder; choices index G's table by digits of b_i, as gc_co_base_choices does. */
+int gc_co_multi_sender_setup(gc_ctx *, const uint8_t *a, size_t S, gc_p256_point *A_out, gc_p256_point *AaInv_out,
+                             size_t *bad_session);
+int gc_co_multi_sender_setup_dev(gc_ctx *, const void *d_a, size_t S, void *d_A_out, void *d_AaInv_out, void *d_status);
+int gc_co_multi_sender_encrypt(gc_ctx *, const uint8_t *a, const gc_p256_point *AaInv, const gc_p256_point *points,
+                               const gc_wire *wires, size_t S, size_t per, uint64_t id0, uint8_t *ct, size_t *bad_index,
+                               size_t *bad_session);
+int gc_co_multi_sender_encrypt_dev(gc_ctx *, const void *d_a, const void *d_AaInv, const void *d_points, const void *d_wires,
+                                   size_t S, size_t per, uint64_t id0, void *d_ct, void *d_status);
+int gc_co_multi_receiver_choices(gc_ctx *, const gc_p256_point *A, const uint8_t *scalars, const uint8_t *choice, size_t S,
+                                 size_t per, gc_p256_point *points_out, size_t *bad_session);
+int gc_co_multi_receiver_choices_dev(gc_ctx *, const void *d_A, const void *d_scalars, const void *d_choice, size_t S,
+                                     size_t per, void *d_points_out, void *d_status);
+int gc_co_multi_receiver_decrypt(gc_ctx *, const gc_p256_point *A, const uint8_t *scalars, const uint8_t *choice,
+                                 const uint8_t *ct, size_t S, size_t per, uint64_t id0, gc_label *labels_out,
+                                 size_t *bad_session);
+int gc_co_multi_receiver_decrypt_dev(gc_ctx *, const void *d_A, const void *d_scalars, const void *d_choice, const void *d_ct,
+                                     size_t S, size_t per, uint64_t id0, void *d_labels_out, void *d_status);
 
 #ifdef __cplusplus
 }

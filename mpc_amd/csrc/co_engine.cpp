@@ -8,6 +8,9 @@
 // gc_co_base_*: the receiver's side of one session behind a handle that owns A's window table (co_table.h).  The tables are
 // built here, on the host, for the reason above: the 252 dependent doublings of a table are a lone wave's work on the
 // device, about 2 ms, and a fraction of that on a CPU core.  G's table is built once per process and uploaded once per ctx.
+//
+// gc_co_multi_*: S sessions per call (co_multi_kernels.hip).  The session constants are ARRAYS in device memory there, and
+// the sender's setup runs on the device, one lane per session, from G's table.
 #define GC_CO_TABLE_BUILD 1  // co_table.h: the host-side table build as well
 
 #include <cstring>
@@ -109,6 +112,13 @@ int upload_table(gc_ctx *ctx, const std::vector<CoTabEntry> &tab, CoTabEntry **d
     return GC_OK;
 }
 
+// G's table in the memory of this ctx: uploaded by the first caller (ctx->mu held, the device set), then kept until the ctx
+// goes.  g: g_table(), built before the lock is taken
+int ensure_g_table(gc_ctx *ctx, const std::vector<CoTabEntry> &g) {
+    if (ctx->d_co_g_tab) return GC_OK;
+    return upload_table(ctx, g, &ctx->d_co_g_tab);
+}
+
 }  // namespace
 
 struct gc_co_base {
@@ -125,10 +135,8 @@ int co_base_init(gc_co_base *h, gc_ctx *ctx) {
     const std::vector<CoTabEntry> &g = g_table();
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    if (!ctx->d_co_g_tab) {
-        const int rc = upload_table(ctx, g, &ctx->d_co_g_tab);
-        if (rc != GC_OK) return rc;
-    }
+    const int rc = ensure_g_table(ctx, g);
+    if (rc != GC_OK) return rc;
     h->ctx = ctx;
     return upload_table(ctx, tab, &h->d_tab);
 }
@@ -379,6 +387,254 @@ int gc_co_receiver_decrypt(gc_ctx *ctx, const gc_p256_point *A, const uint8_t *s
     GC_HIP(hipMemcpyAsync(labels_out, d_out.p, n * 16, hipMemcpyDeviceToHost, s));
     GC_HIP(hipStreamSynchronize(s));
     return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+}  // extern "C"
+
+// ---- several sessions per call (gc_co_multi_*, co_multi_kernels.hip) ----------------------------------------------------
+
+namespace {
+
+// the constants of the group order N, for the a^2 mod N of k_co_multi_setup
+const VoleMod &order_mod() {
+    static const VoleMod mod = [] {
+        uint8_t n_be[32];
+        vole_store_be(p256_n().v, n_be);
+        VoleMod m;
+        (void)vole_mod_init(n_be, &m);  // N is odd and above 2
+        return m;
+    }();
+    return mod;
+}
+
+// S sessions of per OTs each: false when S * per, or its byte count at 64 bytes per OT, does not fit size_t
+bool multi_count(size_t S, size_t per, size_t *n) {
+    if (per && S > SIZE_MAX / per) return false;
+    *n = S * per;
+    return bytes_fit(*n);
+}
+
+// the status block of the gc_co_multi_*_dev calls before the kernel: {0, ~0, 0, ~0}
+hipError_t reset_status4(void *d_status, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(d_status, 0, 32, s);
+    if (e == hipSuccess) e = hipMemsetAsync((uint8_t *)d_status + 8, 0xff, 8, s);
+    if (e == hipSuccess) e = hipMemsetAsync((uint8_t *)d_status + 24, 0xff, 8, s);
+    return e;
+}
+
+// G's table for a multi call, ctx->mu held and the device set: the first such call of a ctx uploads it, synchronously, which
+// cannot happen between gc_ctx_capture_begin and _end
+int multi_g_table_locked(gc_ctx *ctx, const std::vector<CoTabEntry> &g) {
+    if (!ctx->d_co_g_tab && ctx->capturing) return GC_E_ARG;
+    return ensure_g_table(ctx, g);
+}
+int multi_g_table(gc_ctx *ctx) {
+    const std::vector<CoTabEntry> &g = g_table();
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    return multi_g_table_locked(ctx, g);
+}
+
+// the status block of a host form -> its return code.  A bad session wins over a bad point.
+int multi_status(const uint64_t (&st)[4], int session_code, size_t *bad_index, size_t *bad_session) {
+    if (st[0] && bad_index) *bad_index = (size_t)st[1];
+    if (st[2]) {
+        if (bad_session) *bad_session = (size_t)st[3];
+        return session_code;
+    }
+    return st[0] ? GC_E_POINT : GC_OK;  // ErrPointNotOnCurve (co_helpers.go:119-121)
+}
+
+}  // namespace
+
+extern "C" {
+
+int gc_co_multi_sender_setup_dev(gc_ctx *ctx, const void *d_a, size_t S, void *d_A_out, void *d_AaInv_out, void *d_status) try {
+    if (!ctx || (S && (!d_a || !d_A_out || !d_AaInv_out || !d_status)) || !bytes_fit(S)) return GC_E_ARG;
+    if (S == 0) return GC_OK;
+    const int rc = multi_g_table(ctx);
+    if (rc != GC_OK) return rc;
+    GC_HIP(reset_status4(d_status, ctx->stream));
+    launch_co_multi_setup(order_mod(), ctx->d_co_g_tab, (const uint4 *)d_a, S, (uint4 *)d_A_out, (uint4 *)d_AaInv_out,
+                          (unsigned long long *)d_status, ctx->stream);
+    GC_HIP(hipGetLastError());
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_co_multi_sender_encrypt_dev(gc_ctx *ctx, const void *d_a, const void *d_AaInv, const void *d_points, const void *d_wires,
+                                   size_t S, size_t per, uint64_t id0, void *d_ct, void *d_status) {
+    size_t n = 0;
+    if (!ctx || !multi_count(S, per, &n) || (n && (!d_a || !d_AaInv || !d_points || !d_wires || !d_ct || !d_status)))
+        return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_HIP(reset_status4(d_status, ctx->stream));
+    launch_co_multi_encrypt((const uint4 *)d_a, (const uint4 *)d_AaInv, (const uint4 *)d_points, (const uint4 *)d_wires, S, per,
+                            id0, (uint4 *)d_ct, (unsigned long long *)d_status, ctx->stream);
+    GC_HIP(hipGetLastError());
+    return GC_OK;
+}
+
+int gc_co_multi_receiver_choices_dev(gc_ctx *ctx, const void *d_A, const void *d_scalars, const void *d_choice, size_t S,
+                                     size_t per, void *d_points_out, void *d_status) try {
+    size_t n = 0;
+    if (!ctx || !multi_count(S, per, &n) || (n && (!d_A || !d_scalars || !d_choice || !d_points_out || !d_status)))
+        return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    const int rc = multi_g_table(ctx);
+    if (rc != GC_OK) return rc;
+    GC_HIP(reset_status4(d_status, ctx->stream));
+    launch_co_multi_choices(ctx->d_co_g_tab, (const uint4 *)d_A, (const uint4 *)d_scalars, (const uint8_t *)d_choice, S, per,
+                            (uint4 *)d_points_out, (unsigned long long *)d_status, ctx->stream);
+    GC_HIP(hipGetLastError());
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_co_multi_receiver_decrypt_dev(gc_ctx *ctx, const void *d_A, const void *d_scalars, const void *d_choice, const void *d_ct,
+                                     size_t S, size_t per, uint64_t id0, void *d_labels_out, void *d_status) {
+    size_t n = 0;
+    if (!ctx || !multi_count(S, per, &n) || (n && (!d_A || !d_scalars || !d_choice || !d_ct || !d_labels_out || !d_status)))
+        return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_HIP(reset_status4(d_status, ctx->stream));
+    launch_co_multi_decrypt((const uint4 *)d_A, (const uint4 *)d_scalars, (const uint8_t *)d_choice, (const uint4 *)d_ct, S, per,
+                            id0, (uint4 *)d_labels_out, (unsigned long long *)d_status, ctx->stream);
+    GC_HIP(hipGetLastError());
+    return GC_OK;
+}
+
+int gc_co_multi_sender_setup(gc_ctx *ctx, const uint8_t *a, size_t S, gc_p256_point *A_out, gc_p256_point *AaInv_out,
+                             size_t *bad_session) try {
+    if (!ctx || (S && (!a || !A_out || !AaInv_out)) || !bytes_fit(S)) return GC_E_ARG;
+    if (S == 0) return GC_OK;
+    const std::vector<CoTabEntry> &g = g_table();
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    const int rc = multi_g_table_locked(ctx, g);
+    if (rc != GC_OK) return rc;
+    DevBuf d_a, d_A, d_ainv, d_status;
+    GC_HIP(d_a.alloc(S * 32));
+    GC_HIP(d_A.alloc(S * 64));
+    GC_HIP(d_ainv.alloc(S * 64));
+    GC_HIP(d_status.alloc(32));
+    hipStream_t s = ctx->stream;
+    GC_HIP(hipMemcpyAsync(d_a.p, a, S * 32, hipMemcpyHostToDevice, s));
+    GC_HIP(reset_status4(d_status.p, s));
+    launch_co_multi_setup(order_mod(), ctx->d_co_g_tab, (const uint4 *)d_a.p, S, (uint4 *)d_A.p, (uint4 *)d_ainv.p,
+                          (unsigned long long *)d_status.p, s);
+    GC_HIP(hipGetLastError());
+    uint64_t status[4] = {0, 0, 0, 0};
+    GC_HIP(hipMemcpyAsync(A_out, d_A.p, S * 64, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipMemcpyAsync(AaInv_out, d_ainv.p, S * 64, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipMemcpyAsync(status, d_status.p, 32, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipStreamSynchronize(s));
+    return multi_status(status, GC_E_ARG, nullptr, bad_session);
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_co_multi_sender_encrypt(gc_ctx *ctx, const uint8_t *a, const gc_p256_point *AaInv, const gc_p256_point *points,
+                               const gc_wire *wires, size_t S, size_t per, uint64_t id0, uint8_t *ct, size_t *bad_index,
+                               size_t *bad_session) try {
+    size_t n = 0;
+    if (!ctx || !multi_count(S, per, &n) || (n && (!a || !AaInv || !points || !wires || !ct))) return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    DevBuf d_a, d_ainv, d_pts, d_wires, d_ct, d_status;
+    GC_HIP(d_a.alloc(S * 32));
+    GC_HIP(d_ainv.alloc(S * 64));
+    GC_HIP(d_pts.alloc(n * 64));
+    GC_HIP(d_wires.alloc(n * 32));
+    GC_HIP(d_ct.alloc(n * 32));
+    GC_HIP(d_status.alloc(32));
+    hipStream_t s = ctx->stream;
+    GC_HIP(hipMemcpyAsync(d_a.p, a, S * 32, hipMemcpyHostToDevice, s));
+    GC_HIP(hipMemcpyAsync(d_ainv.p, AaInv, S * 64, hipMemcpyHostToDevice, s));
+    GC_HIP(hipMemcpyAsync(d_pts.p, points, n * 64, hipMemcpyHostToDevice, s));
+    GC_HIP(hipMemcpyAsync(d_wires.p, wires, n * 32, hipMemcpyHostToDevice, s));
+    GC_HIP(reset_status4(d_status.p, s));
+    launch_co_multi_encrypt((const uint4 *)d_a.p, (const uint4 *)d_ainv.p, (const uint4 *)d_pts.p, (const uint4 *)d_wires.p, S,
+                            per, id0, (uint4 *)d_ct.p, (unsigned long long *)d_status.p, s);
+    GC_HIP(hipGetLastError());
+    uint64_t status[4] = {0, 0, 0, 0};
+    GC_HIP(hipMemcpyAsync(ct, d_ct.p, n * 32, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipMemcpyAsync(status, d_status.p, 32, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipStreamSynchronize(s));
+    return multi_status(status, GC_E_ARG, bad_index, bad_session);
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_co_multi_receiver_choices(gc_ctx *ctx, const gc_p256_point *A, const uint8_t *scalars, const uint8_t *choice, size_t S,
+                                 size_t per, gc_p256_point *points_out, size_t *bad_session) try {
+    size_t n = 0;
+    if (!ctx || !multi_count(S, per, &n) || (n && (!A || !scalars || !choice || !points_out))) return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    const std::vector<CoTabEntry> &g = g_table();
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    const int rc = multi_g_table_locked(ctx, g);
+    if (rc != GC_OK) return rc;
+    DevBuf d_A, d_sc, d_ch, d_out, d_status;
+    GC_HIP(d_A.alloc(S * 64));
+    GC_HIP(d_sc.alloc(n * 32));
+    GC_HIP(d_ch.alloc(n));
+    GC_HIP(d_out.alloc(n * 64));
+    GC_HIP(d_status.alloc(32));
+    hipStream_t s = ctx->stream;
+    GC_HIP(hipMemcpyAsync(d_A.p, A, S * 64, hipMemcpyHostToDevice, s));
+    GC_HIP(hipMemcpyAsync(d_sc.p, scalars, n * 32, hipMemcpyHostToDevice, s));
+    GC_HIP(hipMemcpyAsync(d_ch.p, choice, n, hipMemcpyHostToDevice, s));
+    GC_HIP(reset_status4(d_status.p, s));
+    launch_co_multi_choices(ctx->d_co_g_tab, (const uint4 *)d_A.p, (const uint4 *)d_sc.p, (const uint8_t *)d_ch.p, S, per,
+                            (uint4 *)d_out.p, (unsigned long long *)d_status.p, s);
+    GC_HIP(hipGetLastError());
+    uint64_t status[4] = {0, 0, 0, 0};
+    GC_HIP(hipMemcpyAsync(points_out, d_out.p, n * 64, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipMemcpyAsync(status, d_status.p, 32, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipStreamSynchronize(s));
+    return multi_status(status, GC_E_POINT, nullptr, bad_session);
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_co_multi_receiver_decrypt(gc_ctx *ctx, const gc_p256_point *A, const uint8_t *scalars, const uint8_t *choice,
+                                 const uint8_t *ct, size_t S, size_t per, uint64_t id0, gc_label *labels_out,
+                                 size_t *bad_session) try {
+    size_t n = 0;
+    if (!ctx || !multi_count(S, per, &n) || (n && (!A || !scalars || !choice || !ct || !labels_out))) return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    DevBuf d_A, d_sc, d_ch, d_ct, d_out, d_status;
+    GC_HIP(d_A.alloc(S * 64));
+    GC_HIP(d_sc.alloc(n * 32));
+    GC_HIP(d_ch.alloc(n));
+    GC_HIP(d_ct.alloc(n * 32));
+    GC_HIP(d_out.alloc(n * 16));
+    GC_HIP(d_status.alloc(32));
+    hipStream_t s = ctx->stream;
+    GC_HIP(hipMemcpyAsync(d_A.p, A, S * 64, hipMemcpyHostToDevice, s));
+    GC_HIP(hipMemcpyAsync(d_sc.p, scalars, n * 32, hipMemcpyHostToDevice, s));
+    GC_HIP(hipMemcpyAsync(d_ch.p, choice, n, hipMemcpyHostToDevice, s));
+    GC_HIP(hipMemcpyAsync(d_ct.p, ct, n * 32, hipMemcpyHostToDevice, s));
+    GC_HIP(reset_status4(d_status.p, s));
+    launch_co_multi_decrypt((const uint4 *)d_A.p, (const uint4 *)d_sc.p, (const uint8_t *)d_ch.p, (const uint4 *)d_ct.p, S, per,
+                            id0, (uint4 *)d_out.p, (unsigned long long *)d_status.p, s);
+    GC_HIP(hipGetLastError());
+    uint64_t status[4] = {0, 0, 0, 0};
+    GC_HIP(hipMemcpyAsync(labels_out, d_out.p, n * 16, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipMemcpyAsync(status, d_status.p, 32, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipStreamSynchronize(s));
+    return multi_status(status, GC_E_POINT, nullptr, bad_session);
 } catch (...) {
     return gc::on_exception();
 }

@@ -365,4 +365,21 @@ void launch_co_choices_tab(const CoTabEntry *g_tab, const Aff &a, const uint4 *s
 void launch_co_decrypt_tab(const CoTabEntry *a_tab, const uint4 *scalars, const uint8_t *choice, const uint4 *ct, size_t n,
                            uint64_t id0, uint4 *labels_out, hipStream_t s);
 
+// ---- Chou-Orlandi base OT, several sessions per call (co_multi_kernels.hip, co_multi.h) -------
+// S sessions of `per` OTs each, session-major: OT j of session s is element i = s * per + j of every per-OT array and its
+// id is id0 + j.  The session constants are arrays in device memory: a [S][32] bytes big-endian, A and AaInv [S]
+// gc_p256_point.  status: four words {bad points (added to), lowest bad OT index (min-ed into), bad sessions (added to, once
+// per session), lowest bad session (min-ed into)}.  Every pointer 16-byte aligned; S * per does not overflow.
+constexpr int kCoMultiThreads = 256;  // one lane = one OT (setup: one session) per trip
+constexpr int kCoMultiGrid = 2048;    // grid-stride beyond 2048 workgroups
+// modn: the constants of the group order N (vole_mod_init); g_tab: G's table of width kCoTabWidthG
+void launch_co_multi_setup(const VoleMod &modn, const CoTabEntry *g_tab, const uint4 *a, size_t S, uint4 *A_out,
+                           uint4 *AaInv_out, unsigned long long *status, hipStream_t s);
+void launch_co_multi_encrypt(const uint4 *a, const uint4 *ainv, const uint4 *points, const uint4 *wires, size_t S, size_t per,
+                             uint64_t id0, uint4 *ct, unsigned long long *status, hipStream_t s);
+void launch_co_multi_choices(const CoTabEntry *g_tab, const uint4 *A, const uint4 *scalars, const uint8_t *choice, size_t S,
+                             size_t per, uint4 *points_out, unsigned long long *status, hipStream_t s);
+void launch_co_multi_decrypt(const uint4 *A, const uint4 *scalars, const uint8_t *choice, const uint4 *ct, size_t S,
+                             size_t per, uint64_t id0, uint4 *labels_out, unsigned long long *status, hipStream_t s);
+
 }  // namespace gc

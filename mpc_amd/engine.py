@@ -246,6 +246,15 @@ def lib():
         "gc_co_base_choices_dev": (i32, [vp, vp, vp, sz, vp]),
         "gc_co_base_decrypt": (i32, [vp, vp, vp, vp, sz, C.c_uint64, vp]),
         "gc_co_base_decrypt_dev": (i32, [vp, vp, vp, vp, sz, C.c_uint64, vp]),
+        "gc_co_multi_sender_setup": (i32, [vp, vp, sz, vp, vp, C.POINTER(C.c_size_t)]),
+        "gc_co_multi_sender_setup_dev": (i32, [vp, vp, sz, vp, vp, vp]),
+        "gc_co_multi_sender_encrypt": (i32, [vp, vp, vp, vp, vp, sz, sz, C.c_uint64, vp, C.POINTER(C.c_size_t),
+                                             C.POINTER(C.c_size_t)]),
+        "gc_co_multi_sender_encrypt_dev": (i32, [vp, vp, vp, vp, vp, sz, sz, C.c_uint64, vp, vp]),
+        "gc_co_multi_receiver_choices": (i32, [vp, vp, vp, vp, sz, sz, vp, C.POINTER(C.c_size_t)]),
+        "gc_co_multi_receiver_choices_dev": (i32, [vp, vp, vp, vp, sz, sz, vp, vp]),
+        "gc_co_multi_receiver_decrypt": (i32, [vp, vp, vp, vp, vp, sz, sz, C.c_uint64, vp, C.POINTER(C.c_size_t)]),
+        "gc_co_multi_receiver_decrypt_dev": (i32, [vp, vp, vp, vp, vp, sz, sz, C.c_uint64, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -1551,3 +1560,124 @@ class CoBase:
                 raise EngineError(GC_E_ARG, "CoBase.close: close the handle before its Context")
             lib().gc_co_base_free(self.h)
             self.h = None
+
+
+# ---- several sessions per call (gc_co_multi_*): S sessions of `per` OTs each, session-major ----
+
+
+class CoSessionError(EngineError):
+    """a bad session of a gc_co_multi_* host call (GC_E_ARG from the sender calls, GC_E_POINT from the receiver calls):
+    .bad_session = the lowest one, .out = the outputs all the same (zeros in the bad sessions), .bad_index = the lowest bad
+    point's OT index when the sender met one as well, else None"""
+
+    def __init__(self, code, what, bad_session, out, bad_index=None):
+        super().__init__(code, what)
+        self.bad_session, self.out, self.bad_index = bad_session, out, bad_index
+
+
+def _multi(S, per, *arrays):
+    S, per = int(S), int(per)
+    n = S * per
+    for a in arrays:
+        assert len(a) == n, (len(a), S, per)
+    return S, per, n
+
+
+_NONE = C.c_size_t(-1).value  # what *bad_session and *bad_index hold when the call did not set them
+
+
+def _bad(v):
+    return None if v.value == _NONE else v.value
+
+
+def co_multi_sender_setup(ctx, a):
+    """gc_co_multi_sender_setup: a = S scalars -> (A, AaInv), uint8 [S, 64] each; raises CoSessionError (.out = (A, AaInv))
+    when an a_s is 0 mod N"""
+    sc = _scalars(a)
+    S = len(sc)
+    A, ainv = np.zeros((max(S, 1), 64), np.uint8), np.zeros((max(S, 1), 64), np.uint8)
+    bad_s = C.c_size_t(_NONE)
+    rc = lib().gc_co_multi_sender_setup(ctx.h, _p(sc) if S else None, S, _p(A), _p(ainv), C.byref(bad_s))
+    if rc == GC_E_ARG and _bad(bad_s) is not None:
+        raise CoSessionError(rc, "gc_co_multi_sender_setup", bad_s.value, (A[:S], ainv[:S]))
+    _check(rc, "gc_co_multi_sender_setup")
+    return A[:S], ainv[:S]
+
+
+def co_multi_sender_setup_dev(ctx, d_a, S, d_A_out, d_AaInv_out, d_status):
+    """device pointers; asynchronous on the ctx stream; d_status: uint64 [4] = {bad points, lowest bad OT index, bad
+    sessions, lowest bad session}"""
+    _check(lib().gc_co_multi_sender_setup_dev(ctx.h, _dp(d_a), S, _dp(d_A_out), _dp(d_AaInv_out), _dp(d_status)),
+           "gc_co_multi_sender_setup_dev")
+
+
+def co_multi_sender_encrypt(ctx, a, AaInv, points, wires, S, per, id0=0):
+    """gc_co_multi_sender_encrypt -> ct, uint8 [S * per, 2, 16]; raises CoSessionError (.out = ct) when a session is bad,
+    else CoPointError when a point is not on the curve"""
+    sc, ai, pts = _scalars(a), _points(AaInv), _points(points)
+    w = np.ascontiguousarray(wires, dtype=WIRE)
+    S, per, n = _multi(S, per, pts, w)
+    assert len(sc) == S and len(ai) == S
+    ct = np.zeros((max(n, 1), 2, 16), np.uint8)
+    bad, bad_s = C.c_size_t(_NONE), C.c_size_t(_NONE)
+    rc = lib().gc_co_multi_sender_encrypt(ctx.h, _p(sc) if n else None, _p(ai) if n else None, _p(pts) if n else None,
+                                          _p(w) if n else None, S, per, id0, _p(ct), C.byref(bad), C.byref(bad_s))
+    if rc == GC_E_ARG and _bad(bad_s) is not None:
+        raise CoSessionError(rc, "gc_co_multi_sender_encrypt", bad_s.value, ct[:n], _bad(bad))
+    if rc == GC_E_POINT:
+        raise CoPointError("gc_co_multi_sender_encrypt", bad.value, ct[:n])
+    _check(rc, "gc_co_multi_sender_encrypt")
+    return ct[:n]
+
+
+def co_multi_sender_encrypt_dev(ctx, d_a, d_AaInv, d_points, d_wires, S, per, id0, d_ct, d_status):
+    """device pointers, the session constants included; asynchronous on the ctx stream"""
+    _check(lib().gc_co_multi_sender_encrypt_dev(ctx.h, _dp(d_a), _dp(d_AaInv), _dp(d_points), _dp(d_wires), S, per, id0,
+                                                _dp(d_ct), _dp(d_status)), "gc_co_multi_sender_encrypt_dev")
+
+
+def co_multi_receiver_choices(ctx, A, scalars, choice, S, per):
+    """gc_co_multi_receiver_choices -> points, uint8 [S * per, 64]; raises CoSessionError (.out = points) when an A_s is not
+    on the curve"""
+    As, sc = _points(A), _scalars(scalars)
+    S, per, n = _multi(S, per, sc)
+    ch = _choices(choice, n)
+    assert len(As) == S
+    out = np.zeros((max(n, 1), 64), np.uint8)
+    bad_s = C.c_size_t(_NONE)
+    rc = lib().gc_co_multi_receiver_choices(ctx.h, _p(As) if n else None, _p(sc) if n else None, _p(ch) if n else None, S, per,
+                                            _p(out), C.byref(bad_s))
+    if rc == GC_E_POINT:
+        raise CoSessionError(rc, "gc_co_multi_receiver_choices", _bad(bad_s), out[:n])
+    _check(rc, "gc_co_multi_receiver_choices")
+    return out[:n]
+
+
+def co_multi_receiver_choices_dev(ctx, d_A, d_scalars, d_choice, S, per, d_points_out, d_status):
+    """device pointers, the session constants included; asynchronous on the ctx stream"""
+    _check(lib().gc_co_multi_receiver_choices_dev(ctx.h, _dp(d_A), _dp(d_scalars), _dp(d_choice), S, per, _dp(d_points_out),
+                                                  _dp(d_status)), "gc_co_multi_receiver_choices_dev")
+
+
+def co_multi_receiver_decrypt(ctx, A, scalars, choice, ct, S, per, id0=0):
+    """gc_co_multi_receiver_decrypt -> labels [S * per]; raises CoSessionError (.out = labels) when an A_s is not on the
+    curve"""
+    As, sc = _points(A), _scalars(scalars)
+    S, per, n = _multi(S, per, sc)
+    ch = _choices(choice, n)
+    c = np.ascontiguousarray(ct, dtype=np.uint8).reshape(-1, 32)
+    assert len(As) == S and len(c) == n
+    out = np.zeros(max(n, 1), LABEL)
+    bad_s = C.c_size_t(_NONE)
+    rc = lib().gc_co_multi_receiver_decrypt(ctx.h, _p(As) if n else None, _p(sc) if n else None, _p(ch) if n else None,
+                                            _p(c) if n else None, S, per, id0, _p(out), C.byref(bad_s))
+    if rc == GC_E_POINT:
+        raise CoSessionError(rc, "gc_co_multi_receiver_decrypt", _bad(bad_s), out[:n])
+    _check(rc, "gc_co_multi_receiver_decrypt")
+    return out[:n]
+
+
+def co_multi_receiver_decrypt_dev(ctx, d_A, d_scalars, d_choice, d_ct, S, per, id0, d_labels_out, d_status):
+    """device pointers, the session constants included; asynchronous on the ctx stream"""
+    _check(lib().gc_co_multi_receiver_decrypt_dev(ctx.h, _dp(d_A), _dp(d_scalars), _dp(d_choice), _dp(d_ct), S, per, id0,
+                                                  _dp(d_labels_out), _dp(d_status)), "gc_co_multi_receiver_decrypt_dev")
