@@ -27,6 +27,11 @@ import (
 // BuildCOChoices (:151) draw them, and Go numbers the OTs of every session from 0 (id0 = 0).  Layout: session-major, OT j
 // of session s is element s*per + j.
 
+// coMultiBaseMinPer is the session length from which ReceiveMultiHIP decrypts through a gc_co_multi_base handle: the
+// smallest measured per at S = 1 024 from which building the tables and decrypting from them took less time than the
+// ladder decrypt (profiles/co_multi_base_bench.jsonl, the row named in DESIGN.md section 11).
+const coMultiBaseMinPer = 8
+
 func coMultiCheck(cos []*CO, per int, lens func(s int) int) error {
 	for s := range cos {
 		if lens(s) != per {
@@ -167,6 +172,18 @@ func ReceiveMultiHIP(ctx *C.gc_ctx, cos []*CO, flags [][]bool, result [][]Label)
 		}
 	}
 
+	// Sessions of coMultiBaseMinPer OTs or more decrypt through a handle whose per-session window tables are built on the
+	// device now, while this side still draws its scalars (gcengine.h: gc_co_multi_base_*); shorter ones keep the ladder call
+	var base *C.gc_co_multi_base
+	if per >= coMultiBaseMinPer {
+		var status C.int
+		base = C.gc_co_multi_base_create(ctx, &A[0], C.size_t(S), &status)
+		if base == nil {
+			return coErr(status)
+		}
+		defer C.gc_co_multi_base_free(base)
+	}
+
 	// BuildCOChoices (co_helpers.go:140-177): one crand.Int per OT, in order, from the session's own rand
 	n := S * per
 	scalars := make([]byte, 32*n+1)
@@ -222,9 +239,15 @@ func ReceiveMultiHIP(ctx *C.gc_ctx, cos []*CO, flags [][]bool, result [][]Label)
 
 	// DecryptCOCiphertexts (co_helpers.go:191-219) of every session
 	labels := make([]Label, n+1)
-	st = C.gc_co_multi_receiver_decrypt(ctx, &A[0], (*C.uint8_t)(unsafe.Pointer(&scalars[0])),
-		(*C.uint8_t)(unsafe.Pointer(&choice[0])), (*C.uint8_t)(unsafe.Pointer(&ct[0])), C.size_t(S), C.size_t(per),
-		C.uint64_t(0), (*C.gc_label)(unsafe.Pointer(&labels[0])), &badSession)
+	if base != nil {
+		st = C.gc_co_multi_base_decrypt(base, (*C.uint8_t)(unsafe.Pointer(&scalars[0])),
+			(*C.uint8_t)(unsafe.Pointer(&choice[0])), (*C.uint8_t)(unsafe.Pointer(&ct[0])), C.size_t(per), C.uint64_t(0),
+			(*C.gc_label)(unsafe.Pointer(&labels[0])), &badSession)
+	} else {
+		st = C.gc_co_multi_receiver_decrypt(ctx, &A[0], (*C.uint8_t)(unsafe.Pointer(&scalars[0])),
+			(*C.uint8_t)(unsafe.Pointer(&choice[0])), (*C.uint8_t)(unsafe.Pointer(&ct[0])), C.size_t(S), C.size_t(per),
+			C.uint64_t(0), (*C.gc_label)(unsafe.Pointer(&labels[0])), &badSession)
+	}
 	if st != C.GC_OK {
 		return coErr(st)
 	}

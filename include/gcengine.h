@@ -795,7 +795,8 @@ int gc_co_base_decrypt_dev(gc_co_base *, const void *d_scalars, const void *d_ch
  * bad_session may be NULL).  S = 0 or per = 0: GC_OK, nothing written, the status included.  A NULL ctx, a NULL array with
  * S * per > 0, or an S * per * 64 that does not fit size_t: GC_E_ARG.  Setup and choices read G's table: the first such call
  * of a ctx uploads it as gc_co_base_create does (synchronously), and returns GC_E_ARG between gc_ctx_capture_begin and
- * _end.  The receiver's decrypt walks the ladder; choices index G's table by digits of b_i, as gc_co_base_choices does. */
+ * _end.  The receiver's decrypt walks the ladder (gc_co_multi_base_* below reads per-session tables instead); choices index
+ * G's table by digits of b_i, as gc_co_base_choices does. */
 int gc_co_multi_sender_setup(gc_ctx *, const uint8_t *a, size_t S, gc_p256_point *A_out, gc_p256_point *AaInv_out,
                              size_t *bad_session);
 int gc_co_multi_sender_setup_dev(gc_ctx *, const void *d_a, size_t S, void *d_A_out, void *d_AaInv_out, void *d_status);
@@ -813,6 +814,38 @@ int gc_co_multi_receiver_decrypt(gc_ctx *, const gc_p256_point *A, const uint8_t
                                  size_t *bad_session);
 int gc_co_multi_receiver_decrypt_dev(gc_ctx *, const void *d_A, const void *d_scalars, const void *d_choice, const void *d_ct,
                                      size_t S, size_t per, uint64_t id0, void *d_labels_out, void *d_status);
+
+/* The receiver's decrypt of S sessions behind a handle: gc_co_multi_receiver_decrypt / _dev byte for byte and status word for
+ * status word (session-major, the id of OT j of a session is id0 + j, scalars mod N, b = 0 mod N gives infinity), with
+ * b_i * A_s summed from a fixed-base window table of A_s instead of walked by double-and-add.  S is fixed at create; per and
+ * id0 are arguments of each call, so one handle serves any number of calls.
+ *   Create checks every A_s (VALID as above: x, y >= p and (0, 0) are refused) and builds the tables of the good sessions ON
+ *   THE DEVICE, on the ctx stream: one lane per session walks the 252 doublings, one lane per (session, window) fills the 15
+ *   entries of a window and converts them with one inversion.  A handle holds 61 440 bytes of device memory per session
+ *   (S * 61 440 + S * 4); while create runs, a workspace of 6 144 bytes per session and 61 440 bytes for each of up to 1 024
+ *   sessions is held as well and freed before create returns.  A BAD SESSION does not make create fail: the handle remembers
+ *   it, gc_co_multi_base_info reports the count and the lowest one (all ones: none), and every decrypt gives its OTs zero
+ *   labels, counts it once in status words 2 and 3 and does not count its OTs as bad points.  Create is synchronous and not
+ *   allowed between gc_ctx_capture_begin and _end (GC_E_ARG).  _create_dev reads d_A (S gc_p256_point in device memory,
+ *   16-byte aligned) behind what is queued on the ctx stream.  S = 0, a NULL ctx or pointer, or an S * 61 440 that does not
+ *   fit size_t: NULL and *status = GC_E_ARG; allocation failure: NULL and GC_E_NOMEM (status may be NULL).  Several handles may
+ *   live on one ctx; free them before the ctx.
+ *   Decrypt, _dev form: asynchronous on the ctx stream, one kernel; d_status is the four uint64 of the gc_co_multi_*_dev
+ *   calls, reset by the call itself on the stream to {0, ~0, 0, ~0}.  Host form: synchronous, staged; a bad session returns
+ *   GC_E_POINT with *bad_session = the lowest one (bad_session may be NULL) and every good label is written all the same.
+ *   per = 0: GC_OK, nothing written, the status block included.  A NULL handle, a NULL array with S * per > 0, or an
+ *   S * per * 64 that does not fit size_t: GC_E_ARG.
+ * There is no choices call: gc_co_multi_receiver_choices reads G's table already.  The tables are indexed by digits of b_i
+ * (as the AES tables are by secret bytes); a caller who does not want that keeps gc_co_multi_receiver_decrypt. */
+typedef struct gc_co_multi_base gc_co_multi_base;
+gc_co_multi_base *gc_co_multi_base_create(gc_ctx *, const gc_p256_point *A, size_t S, int *status);
+gc_co_multi_base *gc_co_multi_base_create_dev(gc_ctx *, const void *d_A, size_t S, int *status);
+void gc_co_multi_base_free(gc_co_multi_base *); /* waits for the ctx stream first; NULL is a no-op */
+int gc_co_multi_base_info(const gc_co_multi_base *, size_t *S, size_t *bad_sessions, size_t *lowest_bad);
+int gc_co_multi_base_decrypt(gc_co_multi_base *, const uint8_t *scalars, const uint8_t *choice, const uint8_t *ct, size_t per,
+                             uint64_t id0, gc_label *labels_out, size_t *bad_session);
+int gc_co_multi_base_decrypt_dev(gc_co_multi_base *, const void *d_scalars, const void *d_choice, const void *d_ct, size_t per,
+                                 uint64_t id0, void *d_labels_out, void *d_status);
 
 #ifdef __cplusplus
 }

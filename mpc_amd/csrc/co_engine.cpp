@@ -640,3 +640,181 @@ int gc_co_multi_receiver_decrypt(gc_ctx *ctx, const gc_p256_point *A, const uint
 }
 
 }  // extern "C"
+
+// ---- the multi receiver behind a handle: per-session window tables built on the device (gc_co_multi_base_*,
+// co_multi_base_kernels.hip) ------------------------------------------------------------------------------------------------
+
+struct gc_co_multi_base {
+    gc_ctx *ctx = nullptr;
+    size_t S = 0;
+    CoTabEntry *d_tabs = nullptr;  // [S][960], width kCoTabWidthA; a bad session's part is never written or read
+    uint32_t *d_good = nullptr;    // [S]: 1 = A_s is a point of the curve
+    size_t bad = 0, lowest_bad = SIZE_MAX;
+};
+
+namespace {
+
+constexpr size_t kTabBytes = co_tab_entries(kCoTabWidthA) * sizeof(CoTabEntry);  // 61 440 per session
+
+void multi_base_release(gc_co_multi_base *h) {
+    if (h->d_tabs) (void)hipFree(h->d_tabs);
+    if (h->d_good) (void)hipFree(h->d_good);
+    delete h;
+}
+
+int multi_base_alloc(void **p, size_t bytes) {
+    GC_HIP(hipMalloc(p, bytes));  // (out of memory: GC_E_NOMEM)
+    return GC_OK;
+}
+
+// A: S points in host memory (d_A NULL) or in device memory; the tables of the good sessions, complete on return
+int multi_base_build(gc_co_multi_base *h, gc_ctx *ctx, const gc_p256_point *A, const void *d_A, size_t S) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    h->ctx = ctx;
+    h->S = S;
+    int rc = multi_base_alloc((void **)&h->d_tabs, S * kTabBytes);
+    if (rc == GC_OK) rc = multi_base_alloc((void **)&h->d_good, S * sizeof(uint32_t));
+    if (rc != GC_OK) return rc;
+    const size_t chunk = std::min<size_t>(S, kCoMultiTabChunk);
+    DevBuf d_pts, d_bases, d_zs;  // the build's workspace: freed before create returns
+    void **ws[3] = {&d_bases.p, &d_zs.p, &d_pts.p};
+    const size_t ws_bytes[3] = {S * co_tab_windows(kCoTabWidthA) * sizeof(CoTabBase),
+                                chunk * co_tab_entries(kCoTabWidthA) * sizeof(CoTabZ), d_A ? 0 : S * sizeof(gc_p256_point)};
+    for (int k = 0; k < 3; k++) {
+        if (!ws_bytes[k]) continue;
+        rc = multi_base_alloc(ws[k], ws_bytes[k]);
+        if (rc != GC_OK) return rc;
+    }
+    hipStream_t s = ctx->stream;
+    if (!d_A) {
+        GC_HIP(hipMemcpyAsync(d_pts.p, A, S * sizeof(gc_p256_point), hipMemcpyHostToDevice, s));
+        d_A = d_pts.p;
+    }
+    launch_co_multi_tab_bases((const uint4 *)d_A, S, h->d_good, (CoTabBase *)d_bases.p, s);
+    GC_HIP(hipGetLastError());
+    for (size_t s0 = 0; s0 < S; s0 += chunk) {  // (the launches of one stream run in order: one chunk's workspace serves all)
+        launch_co_multi_tab_rows(h->d_good, (const CoTabBase *)d_bases.p, s0, std::min(chunk, S - s0), h->d_tabs,
+                                 (CoTabZ *)d_zs.p, s);
+        GC_HIP(hipGetLastError());
+    }
+    std::vector<uint32_t> good(S);
+    GC_HIP(hipMemcpyAsync(good.data(), h->d_good, S * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    GC_HIP(hipStreamSynchronize(s));
+    for (size_t k = S; k-- > 0;)
+        if (!good[k]) {
+            h->bad++;
+            h->lowest_bad = k;
+        }
+    return GC_OK;
+}
+
+gc_co_multi_base *multi_base_create(gc_ctx *ctx, const gc_p256_point *A, const void *d_A, size_t S, int *status) try {
+    int rc = GC_OK;
+    gc_co_multi_base *h = nullptr;
+    if (!ctx || (!A && !d_A) || S == 0 || S > SIZE_MAX / kTabBytes) {
+        rc = GC_E_ARG;
+    } else if (ctx->capturing) {
+        rc = GC_E_ARG;  // allocates and waits for the stream: not between gc_ctx_capture_begin and _end
+    } else {
+        h = new gc_co_multi_base;
+        try {
+            rc = multi_base_build(h, ctx, A, d_A, S);
+        } catch (...) {
+            multi_base_release(h);
+            throw;
+        }
+        if (rc != GC_OK) {
+            (void)hipStreamSynchronize(ctx->stream);  // a build kernel may be queued on what is freed next
+            multi_base_release(h);
+            h = nullptr;
+        }
+    }
+    if (status) *status = rc;
+    return h;
+} catch (...) {
+    const int rc__ = gc::on_exception();
+    if (status) *status = rc__;
+    return nullptr;
+}
+
+// the arguments of a decrypt; *n = S * per
+bool multi_base_args(const gc_co_multi_base *h, size_t per, bool pointers, size_t *n) {
+    return h && multi_count(h->S, per, n) && (*n == 0 || pointers);
+}
+
+}  // namespace
+
+extern "C" {
+
+gc_co_multi_base *gc_co_multi_base_create(gc_ctx *ctx, const gc_p256_point *A, size_t S, int *status) {
+    return multi_base_create(ctx, A, nullptr, S, status);
+}
+
+gc_co_multi_base *gc_co_multi_base_create_dev(gc_ctx *ctx, const void *d_A, size_t S, int *status) {
+    return multi_base_create(ctx, nullptr, d_A, S, status);
+}
+
+void gc_co_multi_base_free(gc_co_multi_base *h) {
+    if (!h) return;
+    if (h->ctx) {
+        (void)hipSetDevice(h->ctx->device);
+        (void)hipStreamSynchronize(h->ctx->stream);  // a _dev call may still read the tables
+    }
+    multi_base_release(h);
+}
+
+int gc_co_multi_base_info(const gc_co_multi_base *h, size_t *S, size_t *bad_sessions, size_t *lowest_bad) {
+    if (!h) return GC_E_ARG;
+    if (S) *S = h->S;
+    if (bad_sessions) *bad_sessions = h->bad;
+    if (lowest_bad) *lowest_bad = h->lowest_bad;  // all ones: none
+    return GC_OK;
+}
+
+int gc_co_multi_base_decrypt_dev(gc_co_multi_base *h, const void *d_scalars, const void *d_choice, const void *d_ct, size_t per,
+                                 uint64_t id0, void *d_labels_out, void *d_status) {
+    size_t n = 0;
+    if (!multi_base_args(h, per, d_scalars && d_choice && d_ct && d_labels_out && d_status, &n)) return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    gc_ctx *ctx = h->ctx;
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_HIP(reset_status4(d_status, ctx->stream));
+    launch_co_multi_decrypt_tab(h->d_tabs, h->d_good, (const uint4 *)d_scalars, (const uint8_t *)d_choice, (const uint4 *)d_ct,
+                                h->S, per, id0, (uint4 *)d_labels_out, (unsigned long long *)d_status, ctx->stream);
+    GC_HIP(hipGetLastError());
+    return GC_OK;
+}
+
+int gc_co_multi_base_decrypt(gc_co_multi_base *h, const uint8_t *scalars, const uint8_t *choice, const uint8_t *ct, size_t per,
+                             uint64_t id0, gc_label *labels_out, size_t *bad_session) try {
+    size_t n = 0;
+    if (!multi_base_args(h, per, scalars && choice && ct && labels_out, &n)) return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    gc_ctx *ctx = h->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    DevBuf d_sc, d_ch, d_ct, d_out, d_status;
+    GC_HIP(d_sc.alloc(n * 32));
+    GC_HIP(d_ch.alloc(n));
+    GC_HIP(d_ct.alloc(n * 32));
+    GC_HIP(d_out.alloc(n * 16));
+    GC_HIP(d_status.alloc(32));
+    hipStream_t s = ctx->stream;
+    GC_HIP(hipMemcpyAsync(d_sc.p, scalars, n * 32, hipMemcpyHostToDevice, s));
+    GC_HIP(hipMemcpyAsync(d_ch.p, choice, n, hipMemcpyHostToDevice, s));
+    GC_HIP(hipMemcpyAsync(d_ct.p, ct, n * 32, hipMemcpyHostToDevice, s));
+    GC_HIP(reset_status4(d_status.p, s));
+    launch_co_multi_decrypt_tab(h->d_tabs, h->d_good, (const uint4 *)d_sc.p, (const uint8_t *)d_ch.p, (const uint4 *)d_ct.p, h->S,
+                                per, id0, (uint4 *)d_out.p, (unsigned long long *)d_status.p, s);
+    GC_HIP(hipGetLastError());
+    uint64_t status[4] = {0, 0, 0, 0};
+    GC_HIP(hipMemcpyAsync(labels_out, d_out.p, n * 16, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipMemcpyAsync(status, d_status.p, 32, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipStreamSynchronize(s));
+    return multi_status(status, GC_E_POINT, nullptr, bad_session);
+} catch (...) {
+    return gc::on_exception();
+}
+
+}  // extern "C"

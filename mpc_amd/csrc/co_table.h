@@ -94,12 +94,9 @@ GC_P256_FN Jac pt_mul_tab(const Fe &k, const CoTabEntry *tab, LOAD load) {
     return acc;
 }
 
-// ---- host only: building a table.  Compiled only where GC_CO_TABLE_BUILD is defined before the first include
-// (co_engine.cpp, the host test), so the kernels' translation units see the half above alone. ----
-#if defined(GC_CO_TABLE_BUILD)
-
-// Jacobian + Jacobian, 12M + 4S, for distinct finite points that are not each other's negative (the table build only)
-inline Jac pt_add_distinct(const Jac &p, const Jac &q) {
+// Jacobian + Jacobian, 12M + 4S, for distinct finite points that are not each other's negative (the table builds only:
+// co_tab_build below on the host, co_multi_table.h on the device)
+GC_P256_FN Jac pt_add_distinct(const Jac &p, const Jac &q) {
     const Fe z1z1 = fe_sqr(p.z), z2z2 = fe_sqr(q.z);
     const Fe u1 = fe_mul(p.x, z2z2), u2 = fe_mul(q.x, z1z1);
     const Fe s1 = fe_mul(p.y, fe_mul(q.z, z2z2)), s2 = fe_mul(q.y, fe_mul(p.z, z1z1));
@@ -111,6 +108,10 @@ inline Jac pt_add_distinct(const Jac &p, const Jac &q) {
     o.z = fe_mul(fe_mul(p.z, q.z), h);
     return o;
 }
+
+// ---- host only: building a table.  Compiled only where GC_CO_TABLE_BUILD is defined before the first include
+// (co_engine.cpp, the host test), so the kernels' translation units see the half above alone. ----
+#if defined(GC_CO_TABLE_BUILD)
 
 // The table of a finite point P of order N, on the host: every entry in Jacobian coordinates (window i + 1 starts from W
 // doublings of window i's first entry; d * B = (d - 1) * B + B, a doubling at d = 2 and distinct points beyond, since

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "co_multi_table.h"
 #include "co_table.h"
 #include "p256.h"
 #include "plan.h"
@@ -381,5 +382,24 @@ void launch_co_multi_choices(const CoTabEntry *g_tab, const uint4 *A, const uint
                              size_t per, uint4 *points_out, unsigned long long *status, hipStream_t s);
 void launch_co_multi_decrypt(const uint4 *A, const uint4 *scalars, const uint8_t *choice, const uint4 *ct, size_t S,
                              size_t per, uint64_t id0, uint4 *labels_out, unsigned long long *status, hipStream_t s);
+
+// ---- Chou-Orlandi multi receiver over per-session window tables (co_multi_base_kernels.hip, co_multi_table.h) ----
+// tabs: [S][co_tab_entries(kCoTabWidthA)] CoTabEntry, session s at entry s * 960, built ON THE DEVICE from A [S]
+// gc_p256_point: launch_co_multi_tab_bases for all S sessions (good: one word per session, 1 = A_s is a point of the curve;
+// bases: [S][64] CoTabBase, 6 KiB per session), then launch_co_multi_tab_rows per chunk of at most kCoMultiTabChunk sessions
+// s0 .. s0 + count - 1 (zs: [count][960] CoTabZ, the workspace of one chunk).  Neither build launch has a grid-stride loop:
+// the grid is sized to the lanes.  launch_co_multi_decrypt_tab is launch_co_multi_decrypt from the tables; a session whose
+// good word is zero gets zero labels and one count in status[2], and its table is never read.
+constexpr int kCoMultiTabBaseThreads = 64;  // one lane = one session: a wave per workgroup spreads the chains over the CUs
+constexpr int kCoMultiTabRowThreads = 256;  // one lane = one (session, window)
+constexpr int kCoMultiTabChunk = 1024;      // sessions per rows launch: 1 024 x 61 440 bytes of Z / prefix workspace
+constexpr int kCoMultiTabThreads = 256;     // decrypt: one lane = one OT per trip
+constexpr int kCoMultiTabGrid = 2048;       // decrypt: grid-stride beyond 2048 workgroups
+void launch_co_multi_tab_bases(const uint4 *A, size_t S, uint32_t *good, CoTabBase *bases, hipStream_t s);
+void launch_co_multi_tab_rows(const uint32_t *good, const CoTabBase *bases, size_t s0, size_t count, CoTabEntry *tabs,
+                              CoTabZ *zs, hipStream_t s);
+void launch_co_multi_decrypt_tab(const CoTabEntry *tabs, const uint32_t *good, const uint4 *scalars, const uint8_t *choice,
+                                 const uint4 *ct, size_t S, size_t per, uint64_t id0, uint4 *labels_out,
+                                 unsigned long long *status, hipStream_t s);
 
 }  // namespace gc

@@ -255,6 +255,12 @@ def lib():
         "gc_co_multi_receiver_choices_dev": (i32, [vp, vp, vp, vp, sz, sz, vp, vp]),
         "gc_co_multi_receiver_decrypt": (i32, [vp, vp, vp, vp, vp, sz, sz, C.c_uint64, vp, C.POINTER(C.c_size_t)]),
         "gc_co_multi_receiver_decrypt_dev": (i32, [vp, vp, vp, vp, vp, sz, sz, C.c_uint64, vp, vp]),
+        "gc_co_multi_base_create": (vp, [vp, vp, sz, ip]),
+        "gc_co_multi_base_create_dev": (vp, [vp, vp, sz, ip]),
+        "gc_co_multi_base_free": (None, [vp]),
+        "gc_co_multi_base_info": (i32, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+        "gc_co_multi_base_decrypt": (i32, [vp, vp, vp, vp, sz, C.c_uint64, vp, C.POINTER(C.c_size_t)]),
+        "gc_co_multi_base_decrypt_dev": (i32, [vp, vp, vp, vp, sz, C.c_uint64, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -1681,3 +1687,59 @@ def co_multi_receiver_decrypt_dev(ctx, d_A, d_scalars, d_choice, d_ct, S, per, i
     """device pointers, the session constants included; asynchronous on the ctx stream"""
     _check(lib().gc_co_multi_receiver_decrypt_dev(ctx.h, _dp(d_A), _dp(d_scalars), _dp(d_choice), _dp(d_ct), S, per, id0,
                                                   _dp(d_labels_out), _dp(d_status)), "gc_co_multi_receiver_decrypt_dev")
+
+
+class CoMultiBase:
+    """gc_co_multi_base: the receiver's decrypt of S sessions.  The handle checks every A_s once and owns one fixed-base
+    window table per good session, built on the device (61 440 bytes each); decrypt is co_multi_receiver_decrypt byte for
+    byte, without its double-and-add ladder.  A: S points (host), or a device buffer of S gc_p256_point with S given"""
+
+    def __init__(self, ctx, A, S=None):
+        st = C.c_int(0)
+        self.ctx = ctx  # gc_co_multi_base_free waits for this ctx's stream: the handle has to go first
+        if S is None:
+            As = _points(A)
+            self.S = len(As)
+            self.h = lib().gc_co_multi_base_create(ctx.h, _p(As) if self.S else None, self.S, C.byref(st))
+            what = "gc_co_multi_base_create"
+        else:
+            self.S = int(S)
+            self.h = lib().gc_co_multi_base_create_dev(ctx.h, _dp(A), self.S, C.byref(st))
+            what = "gc_co_multi_base_create_dev"
+        if not self.h:
+            raise EngineError(st.value, what)
+
+    def info(self):
+        """gc_co_multi_base_info -> (S, bad sessions, the lowest bad session or None)"""
+        S, bad, low = C.c_size_t(0), C.c_size_t(0), C.c_size_t(_NONE)
+        _check(lib().gc_co_multi_base_info(self.h, C.byref(S), C.byref(bad), C.byref(low)), "gc_co_multi_base_info")
+        return S.value, bad.value, _bad(low)
+
+    def decrypt(self, scalars, choice, ct, per, id0=0):
+        """gc_co_multi_base_decrypt -> labels [S * per]; raises CoSessionError (.out = labels) when an A_s was not on the
+        curve"""
+        sc = _scalars(scalars)
+        S, per, n = _multi(self.S, per, sc)
+        ch = _choices(choice, n)
+        c = np.ascontiguousarray(ct, dtype=np.uint8).reshape(-1, 32)
+        assert len(c) == n
+        out = np.zeros(max(n, 1), LABEL)
+        bad_s = C.c_size_t(_NONE)
+        rc = lib().gc_co_multi_base_decrypt(self.h, _p(sc) if n else None, _p(ch) if n else None, _p(c) if n else None, per, id0,
+                                            _p(out), C.byref(bad_s))
+        if rc == GC_E_POINT:
+            raise CoSessionError(rc, "gc_co_multi_base_decrypt", _bad(bad_s), out[:n])
+        _check(rc, "gc_co_multi_base_decrypt")
+        return out[:n]
+
+    def decrypt_dev(self, d_scalars, d_choice, d_ct, per, id0, d_labels_out, d_status):
+        """device pointers; asynchronous on the ctx stream; d_status: uint64 [4] as the gc_co_multi_*_dev calls fill it"""
+        _check(lib().gc_co_multi_base_decrypt_dev(self.h, _dp(d_scalars), _dp(d_choice), _dp(d_ct), per, id0, _dp(d_labels_out),
+                                                  _dp(d_status)), "gc_co_multi_base_decrypt_dev")
+
+    def close(self):
+        if self.h:
+            if self.ctx.h is None:  # the stream the free would wait for is gone with the ctx
+                raise EngineError(GC_E_ARG, "CoMultiBase.close: close the handle before its Context")
+            lib().gc_co_multi_base_free(self.h)
+            self.h = None

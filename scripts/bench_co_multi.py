@@ -12,7 +12,17 @@ end in gc_ctx_sync, k sized once (after a warm-up) so that a window lasts at lea
 The yardsticks do the same number of OTs with ONE session's constants, so `ratio` = multi / single is what per-lane
 constants and the divergence of a wave that spans sessions cost.  With --sequential S (default 8) the script also times
 what a caller without the multi calls does for S sessions of `per` OTs: S one-session sender sequences (host setup +
-encrypt) and S gc_co_base receiver sequences (create + choices + decrypt + free), each ending in gc_ctx_sync."""
+encrypt) and S gc_co_base receiver sequences (create + choices + decrypt + free), each ending in gc_ctx_sync.
+
+With --base-shapes the script times the receiver handle over S sessions instead (gc_co_multi_base_*: per-session window tables
+built on the device), by the same method and on the same buffers, the three calls alternating in one process:
+
+  base_create     gc_co_multi_base_create_dev + gc_co_multi_base_free: the build of S tables, its allocations included
+  base_decrypt    gc_co_multi_base_decrypt_dev through a handle that exists
+  ladder_decrypt  gc_co_multi_receiver_decrypt_dev, the call the handle replaces
+
+one line per shape, with `create_plus_decrypt_ms` and `speedup` = ladder / (create + decrypt): what a caller gains who builds
+the tables for ONE decrypt, as ReceiveMultiHIP does."""
 import argparse
 import json
 import os
@@ -29,6 +39,54 @@ from mpc_amd import engine  # noqa: E402
 from scripts.bench_co import calls_for, timed  # noqa: E402
 
 SHAPES = [(8, 128), (1024, 128), (1024, 127), (131072, 1)]
+BASE_SHAPES = [(8, 128), (1024, 128), (1024, 127), (8192, 128), (1024, 8), (1024, 16), (1024, 32), (1024, 64), (1024, 256)]
+
+
+def shapes_of(text):
+    return [tuple(int(v) for v in s.split("x")) for s in text.split(",") if s]
+
+
+def bench_base(ctx, a, emit):
+    """the rows of the receiver handle; the labels of the two decrypts are compared once per shape"""
+    rng = np.random.default_rng(11)
+    for S, per in shapes_of(a.base_shapes):
+        n = S * per
+        d_a = ctx.to_device(rng.integers(0, 256, (S, 32), dtype=np.uint8))
+        d_A, d_ainv, d_st, d_st1 = ctx.zeros((S, 64)), ctx.zeros((S, 64)), ctx.zeros(4, np.uint64), ctx.zeros(4, np.uint64)
+        d_sc, d_ch, d_ct = ctx.random_u8((n, 32), seed=1), ctx.random_u8(n, high=2, seed=2), ctx.random_u8((n, 32), seed=4)
+        d_lab, d_lab1 = ctx.zeros((n, 16)), ctx.zeros((n, 16))
+        engine.co_multi_sender_setup_dev(ctx, d_a, S, d_A, d_ainv, d_st)
+        ctx.sync()
+        h = engine.CoMultiBase(ctx, d_A, S)
+        assert h.info() == (S, 0, None)
+
+        def create():
+            engine.CoMultiBase(ctx, d_A, S).close()
+
+        fns = {"base_create": create,
+               "base_decrypt": lambda: h.decrypt_dev(d_sc, d_ch, d_ct, per, 0, d_lab, d_st),
+               "ladder_decrypt": lambda: engine.co_multi_receiver_decrypt_dev(ctx, d_A, d_sc, d_ch, d_ct, S, per, 0, d_lab1, d_st1)}
+        ks = {name: calls_for(ctx, fn, a.window) for name, fn in fns.items()}
+        times = {name: [] for name in fns}
+        for _ in range(a.reps):  # alternating
+            for name, fn in fns.items():
+                times[name].append(timed(ctx, fn, ks[name]))
+        clean = [0, (1 << 64) - 1, 0, (1 << 64) - 1]
+        assert [int(v) for v in d_st.numpy()] == clean and [int(v) for v in d_st1.numpy()] == clean
+        assert (d_lab.numpy() == d_lab1.numpy()).all(), "the handle's labels differ from the ladder's"
+        med = {name: statistics.median(t) for name, t in times.items()}
+        both = med["base_create"] + med["base_decrypt"]
+        emit(dict(bench="co_multi_base", S=S, per=per, n=n, reps=a.reps, calls_per_window=ks,
+                  create_ms=round(med["base_create"] * 1e3, 4), create_ms_all=[round(t * 1e3, 4) for t in times["base_create"]],
+                  decrypt_ms=round(med["base_decrypt"] * 1e3, 4), decrypt_ms_all=[round(t * 1e3, 4) for t in times["base_decrypt"]],
+                  ladder_ms=round(med["ladder_decrypt"] * 1e3, 4),
+                  ladder_ms_all=[round(t * 1e3, 4) for t in times["ladder_decrypt"]],
+                  create_plus_decrypt_ms=round(both * 1e3, 4), speedup=round(med["ladder_decrypt"] / both, 3),
+                  decrypt_speedup=round(med["ladder_decrypt"] / med["base_decrypt"], 3),
+                  create_us_per_session=round(med["base_create"] * 1e6 / S, 3), table_bytes=S * 61440))
+        h.close()
+        for d in (d_a, d_A, d_ainv, d_st, d_st1, d_sc, d_ch, d_ct, d_lab, d_lab1):
+            d.close()
 
 
 def main():
@@ -37,6 +95,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.2)
     ap.add_argument("--sequential", type=int, default=8, help="S of the sequential one-session comparison (0: skip)")
+    ap.add_argument("--base-shapes", default=None, nargs="?", const=",".join("%dx%d" % s for s in BASE_SHAPES),
+                    help="time the receiver handle (gc_co_multi_base_*) at these shapes INSTEAD of the rows above")
     ap.add_argument("--out", default=None, help="also append the lines to this file")
     a = ap.parse_args()
     ctx = engine.Context(0)
@@ -46,8 +106,10 @@ def main():
         lines.append(json.dumps(row))
         print(lines[-1], flush=True)
 
+    if a.base_shapes:
+        bench_base(ctx, a, emit)
     rng = np.random.default_rng(7)
-    for S, per in [tuple(int(v) for v in s.split("x")) for s in a.shapes.split(",")]:
+    for S, per in [] if a.base_shapes else shapes_of(a.shapes):
         n = S * per
         a_host = rng.integers(0, 256, (S, 32), dtype=np.uint8)
         d_a = ctx.to_device(a_host)
