@@ -1,0 +1,227 @@
+//go:build gchip
+
+// Package ot — S IKNP sessions of equal length per device call (gc_iknp_multi_*, gc_cot_multi_*): S instances of a
+// two-party run whose 128 base OTs each came out of the gc_co_multi_* calls (co_multi_hip.go).
+// SOURCE ONLY here (no Go toolchain in the build image); see INTEGRATION.md.
+//
+// Every session keeps its own ot.IO and is framed on it exactly as iknp.go:499 / :203 frame one session, so each of the S
+// peers may be an unmodified Go party.  Arrays are session-major: OT j of session s is element s*per + j.
+package ot
+
+/*
+#cgo CFLAGS: -I${SRCDIR}/../../include
+#cgo LDFLAGS: -L${SRCDIR}/../../mpc_amd/csrc -lgcengine -Wl,-rpath,${SRCDIR}/../../mpc_amd/csrc
+#include "gcengine.h"
+*/
+import "C"
+
+import (
+	"fmt"
+	"unsafe"
+)
+
+// hipIKNPMulti holds the base labels of S sessions and the one stream position they share.
+type hipIKNPMulti struct {
+	ctx *C.gc_ctx
+	h   *C.gc_iknp_multi
+	s   int
+}
+
+func multiErr(st C.int) error {
+	return fmt.Errorf("gcengine: %s", C.GoString(C.gc_strerror(st)))
+}
+
+// after base.Send(wires[:]) of every session (iknp.go:337-356): wires holds S * K pairs
+func newHipMultiReceiver(ctx *C.gc_ctx, wires []Wire) (*hipIKNPMulti, error) {
+	if len(wires) == 0 || len(wires)%K != 0 {
+		return nil, fmt.Errorf("invalid base wire count: %v", len(wires))
+	}
+	var st C.int
+	h := C.gc_iknp_multi_receiver_create(ctx, (*C.gc_wire)(unsafe.Pointer(&wires[0])), C.size_t(len(wires)/K), &st)
+	if h == nil {
+		return nil, multiErr(st)
+	}
+	return &hipIKNPMulti{ctx: ctx, h: h, s: len(wires) / K}, nil
+}
+
+// after base.Receive(flags[:], k0[:]) of every session (iknp.go:112-122): one delta and K labels per session
+func newHipMultiSender(ctx *C.gc_ctx, deltas []Label, k0 []Label) (*hipIKNPMulti, error) {
+	if len(deltas) == 0 || len(k0) != len(deltas)*K {
+		return nil, fmt.Errorf("invalid base label count: %v for %v sessions", len(k0), len(deltas))
+	}
+	var st C.int
+	h := C.gc_iknp_multi_sender_create(ctx, (*C.gc_label)(unsafe.Pointer(&deltas[0])),
+		(*C.gc_label)(unsafe.Pointer(&k0[0])), C.size_t(len(deltas)), &st)
+	if h == nil {
+		return nil, multiErr(st)
+	}
+	return &hipIKNPMulti{ctx: ctx, h: h, s: len(deltas)}, nil
+}
+
+// the base labels straight from device memory: dK0 is the d_labels_out of gc_co_multi_receiver_decrypt_dev /
+// gc_co_multi_base_decrypt_dev at per = K (co_multi_hip.go), dDelta S labels; copied behind what the ctx stream holds
+func newHipMultiSenderDev(ctx *C.gc_ctx, dDelta, dK0 unsafe.Pointer, sessions int) (*hipIKNPMulti, error) {
+	var st C.int
+	h := C.gc_iknp_multi_sender_create_dev(ctx, dDelta, dK0, C.size_t(sessions), &st)
+	if h == nil {
+		return nil, multiErr(st)
+	}
+	return &hipIKNPMulti{ctx: ctx, h: h, s: sessions}, nil
+}
+
+// dBase: the S * K gc_wire that gc_co_multi_sender_encrypt_dev read as d_wires
+func newHipMultiReceiverDev(ctx *C.gc_ctx, dBase unsafe.Pointer, sessions int) (*hipIKNPMulti, error) {
+	var st C.int
+	h := C.gc_iknp_multi_receiver_create_dev(ctx, dBase, C.size_t(sessions), &st)
+	if h == nil {
+		return nil, multiErr(st)
+	}
+	return &hipIKNPMulti{ctx: ctx, h: h, s: sessions}, nil
+}
+
+func (m *hipIKNPMulti) free() {
+	C.gc_iknp_multi_free(m.h)
+	m.h = nil
+}
+
+// position reports the bytes every column stream of every session has given out
+func (m *hipIKNPMulti) position() (uint64, error) {
+	var sessions C.size_t
+	var receiver C.int
+	var pos C.uint64_t
+	if st := C.gc_iknp_multi_info(m.h, &sessions, &receiver, &pos); st != C.GC_OK {
+		return 0, multiErr(st)
+	}
+	return uint64(pos), nil
+}
+
+// receive runs (*IKNPReceiver).receive (iknp.go:468-511) for every session: b and result hold S * per elements, and
+// session s sends its u-matrix on ios[s] in the messages of iknp.go:499
+func (m *hipIKNPMulti) receive(ios []IO, b []bool, per int, result []Label) error {
+	if len(ios) != m.s || len(b) != m.s*per || len(result) != len(b) {
+		panic("len(b) != len(result)")
+	}
+	if per == 0 {
+		for _, io := range ios {
+			if err := io.Flush(); err != nil {
+				return err
+			}
+		}
+		return nil
+	}
+	ub := int(C.gc_iknp_u_bytes(C.size_t(per)))
+	u := make([]byte, m.s*ub)
+	// []bool is one byte per element (0/1): it crosses cgo as the choice array
+	st := C.gc_iknp_multi_receive(m.h, (*C.uint8_t)(unsafe.Pointer(&b[0])), C.size_t(per),
+		(*C.uint8_t)(unsafe.Pointer(&u[0])), (*C.gc_label)(unsafe.Pointer(&result[0])))
+	if st != C.GC_OK {
+		return multiErr(st)
+	}
+	for s, io := range ios {
+		us := u[s*ub : (s+1)*ub]
+		for ofs := 0; ofs < len(us); ofs += chunkSize { // same framing as iknp.go:499
+			end := ofs + chunkSize
+			if end > len(us) {
+				end = len(us)
+			}
+			if err := io.SendData(us[ofs:end]); err != nil {
+				return err
+			}
+		}
+		if err := io.Flush(); err != nil {
+			return err
+		}
+	}
+	return nil
+}
+
+// send runs (*IKNPSender).send (iknp.go:197-226) for every session: session s reads its u-matrix from ios[s]
+func (m *hipIKNPMulti) send(ios []IO, per int) ([]Label, error) {
+	if len(ios) != m.s {
+		panic("len(ios) != sessions")
+	}
+	result := make([]Label, m.s*per)
+	ub := int(C.gc_iknp_u_bytes(C.size_t(per)))
+	u := make([]byte, 0, m.s*ub)
+	for s, io := range ios {
+		for len(u) < (s+1)*ub {
+			chunk, err := io.ReceiveData()
+			if err != nil {
+				return nil, err
+			}
+			if len(chunk)%K != 0 || len(u)+len(chunk) > (s+1)*ub {
+				return nil, fmt.Errorf("invalid chunk size: %v", len(chunk))
+			}
+			u = append(u, chunk...)
+		}
+	}
+	if per == 0 {
+		return result, nil
+	}
+	st := C.gc_iknp_multi_send(m.h, (*C.uint8_t)(unsafe.Pointer(&u[0])), C.size_t(len(u)), C.size_t(per),
+		(*C.gc_label)(unsafe.Pointer(&result[0])))
+	if st != C.GC_OK {
+		return nil, multiErr(st) // (the lengths were checked above: a wrong u_len cannot be the cause)
+	}
+	return result, nil
+}
+
+// device-resident forms: every array stays in HBM (d_* as in gcengine.h), asynchronous on the ctx stream
+func (m *hipIKNPMulti) receiveDev(dChoicePacked unsafe.Pointer, per int, dU, dLabels unsafe.Pointer) error {
+	if st := C.gc_iknp_multi_receive_dev(m.h, dChoicePacked, C.size_t(per), dU, dLabels); st != C.GC_OK {
+		return multiErr(st)
+	}
+	return nil
+}
+
+func (m *hipIKNPMulti) sendDev(dU unsafe.Pointer, per int, dLabels unsafe.Pointer) error {
+	if st := C.gc_iknp_multi_send_dev(m.h, dU, C.size_t(per), dLabels); st != C.GC_OK {
+		return multiErr(st)
+	}
+	return nil
+}
+
+// pad loop of COT.Send (cot.go:155-182) for S sessions: seeds and deltas hold one label per session, data and wires
+// S * per elements; out = the 2 * per labels every session puts on its wire, session after session
+func cotMultiSendPads(ctx *C.gc_ctx, seeds, deltas []Label, data []Label, wires []Wire, per int) ([]Label, error) {
+	out := make([]Label, 2*len(wires))
+	if len(wires) == 0 {
+		return out, nil
+	}
+	st := C.gc_cot_multi_send_pads(ctx, (*C.gc_label)(unsafe.Pointer(&seeds[0])), (*C.gc_label)(unsafe.Pointer(&deltas[0])),
+		(*C.gc_label)(unsafe.Pointer(&data[0])), (*C.gc_wire)(unsafe.Pointer(&wires[0])), C.size_t(len(seeds)),
+		C.size_t(per), (*C.gc_label)(unsafe.Pointer(&out[0])))
+	if st != C.GC_OK {
+		return nil, multiErr(st)
+	}
+	return out, nil
+}
+
+// unpad loop of COT.Receive (cot.go:200-232) for S sessions: result holds the receivers' IKNP labels in, the chosen wire
+// labels out
+func cotMultiReceiveUnpad(ctx *C.gc_ctx, seeds []Label, flags []bool, sent []Label, result []Label, per int) error {
+	if len(flags) == 0 {
+		return nil
+	}
+	st := C.gc_cot_multi_receive_unpad(ctx, (*C.gc_label)(unsafe.Pointer(&seeds[0])),
+		(*C.uint8_t)(unsafe.Pointer(&flags[0])), (*C.gc_label)(unsafe.Pointer(&sent[0])),
+		(*C.gc_label)(unsafe.Pointer(&result[0])), C.size_t(len(seeds)), C.size_t(per))
+	if st != C.GC_OK {
+		return multiErr(st)
+	}
+	return nil
+}
+
+func cotMultiSendPadsDev(ctx *C.gc_ctx, dSeeds, dDeltas, dData, dWires unsafe.Pointer, sessions, per int, dOut unsafe.Pointer) error {
+	if st := C.gc_cot_multi_send_pads_dev(ctx, dSeeds, dDeltas, dData, dWires, C.size_t(sessions), C.size_t(per), dOut); st != C.GC_OK {
+		return multiErr(st)
+	}
+	return nil
+}
+
+func cotMultiReceiveUnpadDev(ctx *C.gc_ctx, dSeeds, dFlags, dSent, dResult unsafe.Pointer, sessions, per int) error {
+	if st := C.gc_cot_multi_receive_unpad_dev(ctx, dSeeds, dFlags, dSent, dResult, C.size_t(sessions), C.size_t(per)); st != C.GC_OK {
+		return multiErr(st)
+	}
+	return nil
+}

@@ -847,6 +847,54 @@ int gc_co_multi_base_decrypt(gc_co_multi_base *, const uint8_t *scalars, const u
 int gc_co_multi_base_decrypt_dev(gc_co_multi_base *, const void *d_scalars, const void *d_choice, const void *d_ct, size_t per,
                                  uint64_t id0, void *d_labels_out, void *d_status);
 
+/* ------------------------------------------------------------------------------------------
+ * IKNP extension and COT pads for several sessions per call (ot/iknp.go:197-226, ot/iknp.go:468-511, ot/cot.go:136-235; additive)
+ * S sessions of `per` OTs each in one call and one kernel: S instances of a two-party run whose base OTs came out of the
+ * gc_co_multi_* calls.  Byte for byte, session s of a multi call is gc_iknp_receive / gc_iknp_send / gc_cot_send_pads /
+ * gc_cot_receive_unpad on that session alone.  Conventions are those of gc_co_multi_*: session-major (OT j of session s is
+ * element s * per + j of every per-OT array), the session constants are arrays, a _dev form takes device pointers for EVERY
+ * array (16-byte aligned) and is asynchronous on the ctx stream with one kernel per call, a host form takes host pointers
+ * and is synchronous and staged.  Sessions of unequal length, bit-COT, ROT and a KOS check over the handle are not offered:
+ * gc_kos_*_dev runs per session on slices of the session-major label arrays.
+ *   The handle holds copies of the base labels in device memory (sender: delta [S] and k0 [S][128], 2 KiB + 16 bytes per
+ *   session; receiver: base [S][128] gc_wire, 4 KiB per session) and no round keys: the kernel expands a column's key in the
+ *   lane.  It holds ONE stream position: sessions of equal length advance in lock step, every call advances it by what
+ *   gc_iknp_receive advances its own for `per` OTs, and a handle serves any number of calls.  _create_dev copies behind what
+ *   is queued on the ctx stream, so d_k0 may be the d_labels_out of gc_co_multi_receiver_decrypt_dev /
+ *   gc_co_multi_base_decrypt_dev at per = 128 (and d_base the d_wires of gc_co_multi_sender_encrypt_dev); the host forms of
+ *   create are synchronous.  Several handles may live on one ctx; free them before the ctx.
+ *   Layouts: u of session s is at byte s * gc_iknp_u_bytes(per), inside a session as gc_iknp_receive has it; the packed
+ *   choice bits of session s (_dev form) are at byte s * 64 * ceil(per / 512), LSB first, zero-padded to whole chunks of 64
+ *   bytes.  The padding is READ: the kernel loads a chunk's choice bytes as 16-byte words whatever the chunk's length, so
+ *   d_choice_packed must be 16-byte aligned and hold all S * 64 * ceil(per / 512) bytes (gc_iknp_receive_dev reads a
+ *   ragged chunk byte by byte and asks for less); what the padding holds does not reach any output.  The host form takes one byte per OT, [S][per]; labels are [S][per].  gc_cot_multi_*: seed and delta [S], data /
+ *   flags / result [S][per], wires [S][per] gc_wire, out / sent [S][per][2] gc_label; the MITCCRH key index restarts at 0 in
+ *   every session.
+ *   Errors: per = 0 returns GC_OK and writes nothing (the position stays).  S = 0, a NULL handle, ctx or array, the wrong
+ *   role, a u_len other than S * gc_iknp_u_bytes(per), or a size that does not fit size_t: GC_E_ARG (create: NULL and
+ *   *status, which may be NULL).  Create and every gc_iknp_multi_receive / _send call, _dev or not, return GC_E_ARG between
+ *   gc_ctx_capture_begin and _end (the position is a kernel argument); gc_cot_multi_*_dev may be captured.  Allocation
+ *   failure: GC_E_NOMEM.  GC_IKNP_GENERIC=1 has the meaning it has for gc_iknp_*. */
+typedef struct gc_iknp_multi gc_iknp_multi;
+gc_iknp_multi *gc_iknp_multi_sender_create(gc_ctx *, const gc_label *delta, const gc_label *k0, size_t S, int *status);
+gc_iknp_multi *gc_iknp_multi_sender_create_dev(gc_ctx *, const void *d_delta, const void *d_k0, size_t S, int *status);
+gc_iknp_multi *gc_iknp_multi_receiver_create(gc_ctx *, const gc_wire *base, size_t S, int *status);
+gc_iknp_multi *gc_iknp_multi_receiver_create_dev(gc_ctx *, const void *d_base, size_t S, int *status);
+void gc_iknp_multi_free(gc_iknp_multi *); /* waits for the ctx stream first; NULL is a no-op */
+int gc_iknp_multi_info(const gc_iknp_multi *, size_t *S, int *receiver, uint64_t *pos);
+int gc_iknp_multi_receive(gc_iknp_multi *, const uint8_t *choice, size_t per, uint8_t *u_out, gc_label *labels_out);
+int gc_iknp_multi_send(gc_iknp_multi *, const uint8_t *u_in, size_t u_len, size_t per, gc_label *labels_out);
+int gc_iknp_multi_receive_dev(gc_iknp_multi *, const void *d_choice_packed, size_t per, void *d_u_out, void *d_labels_out);
+int gc_iknp_multi_send_dev(gc_iknp_multi *, const void *d_u_in, size_t per, void *d_labels_out);
+int gc_cot_multi_send_pads(gc_ctx *, const gc_label *seed, const gc_label *delta, const gc_label *data, const gc_wire *wires,
+                           size_t S, size_t per, gc_label *out);
+int gc_cot_multi_send_pads_dev(gc_ctx *, const void *d_seed, const void *d_delta, const void *d_data, const void *d_wires,
+                               size_t S, size_t per, void *d_out);
+int gc_cot_multi_receive_unpad(gc_ctx *, const gc_label *seed, const uint8_t *flags, const gc_label *sent, gc_label *result,
+                               size_t S, size_t per);
+int gc_cot_multi_receive_unpad_dev(gc_ctx *, const void *d_seed, const void *d_flags, const void *d_sent, void *d_result,
+                                   size_t S, size_t per);
+
 #ifdef __cplusplus
 }
 #endif

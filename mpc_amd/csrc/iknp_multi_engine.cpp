@@ -1,0 +1,312 @@
+// iknp_multi_engine.cpp — C ABI of the multi-session IKNP extension and COT pad loops (gc_iknp_multi_*, gc_cot_multi_*):
+// S sessions of `per` OTs each, session-major, one kernel per call (iknp_multi_kernels.hip; layouts: iknp_multi.h).
+#include <cstring>
+#include <new>
+
+#include "engine.h"
+#include "iknp_multi.h"
+
+using namespace gc;
+
+struct gc_iknp_multi {
+    gc_ctx *ctx = nullptr;
+    bool receiver = false;
+    size_t S = 0;
+    uint4 *d_keys = nullptr;   // sender: k0 [S][128]; receiver: the label pairs [S][128][2]
+    uint4 *d_delta = nullptr;  // sender: [S]
+    uint64_t pos = 0;          // bytes drawn so far from every column stream of every session
+};
+
+namespace {
+
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+};
+
+constexpr size_t kKeyBytesSend = 128 * sizeof(gc_label), kKeyBytesRecv = 128 * sizeof(gc_wire);
+
+// the byte counts of a call of S sessions of per OTs; false: one of them does not fit size_t
+struct MultiSizes {
+    size_t n, choice, u, labels;
+};
+bool multi_sizes(size_t S, size_t per, MultiSizes *z) {
+    if (per && S > SIZE_MAX / per) return false;
+    z->n = S * per;
+    if (z->n > SIZE_MAX / 64) return false;  // 16 bytes of label, 32 of wire and 32 of pad per OT, with room to spare
+    const uint64_t chunks = iknp_multi_chunks(per);
+    if (S > SIZE_MAX / (chunks ? chunks * 8192 : 1)) return false;
+    z->choice = S * (size_t)iknp_multi_choice_bytes(per);
+    z->u = S * (size_t)iknp_multi_u_bytes(per);
+    z->labels = z->n * sizeof(gc_label);
+    return true;
+}
+
+void multi_release(gc_iknp_multi *h) {
+    if (h->d_keys) (void)hipFree(h->d_keys);
+    if (h->d_delta) (void)hipFree(h->d_delta);
+    delete h;
+}
+
+int multi_alloc(void **p, size_t bytes) {
+    GC_HIP(hipMalloc(p, bytes));  // (out of memory: GC_E_NOMEM)
+    return GC_OK;
+}
+
+// copies of the base labels: from the host (synchronous) or from device memory, behind what is queued on the ctx stream
+int multi_fill(gc_iknp_multi *h, gc_ctx *ctx, const void *keys, const void *delta, bool dev) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    const size_t kb = h->S * (h->receiver ? kKeyBytesRecv : kKeyBytesSend);
+    int rc = multi_alloc((void **)&h->d_keys, kb);
+    if (rc == GC_OK && !h->receiver) rc = multi_alloc((void **)&h->d_delta, h->S * sizeof(gc_label));
+    if (rc != GC_OK) return rc;
+    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    GC_HIP(hipMemcpyAsync(h->d_keys, keys, kb, kind, ctx->stream));
+    if (!h->receiver) GC_HIP(hipMemcpyAsync(h->d_delta, delta, h->S * sizeof(gc_label), kind, ctx->stream));
+    if (!dev) GC_HIP(hipStreamSynchronize(ctx->stream));  // the caller's arrays are free again on return
+    return GC_OK;
+}
+
+gc_iknp_multi *multi_create(gc_ctx *ctx, bool receiver, const void *keys, const void *delta, size_t S, bool dev,
+                            int *status) try {
+    int rc = GC_OK;
+    gc_iknp_multi *h = nullptr;
+    if (!ctx || !keys || (!receiver && !delta) || S == 0 || S > SIZE_MAX / kKeyBytesRecv) {
+        rc = GC_E_ARG;
+    } else if (ctx->capturing) {
+        rc = GC_E_ARG;  // allocates: not between gc_ctx_capture_begin and _end
+    } else if (!(h = new (std::nothrow) gc_iknp_multi)) {
+        rc = GC_E_NOMEM;
+    } else {
+        h->ctx = ctx;
+        h->receiver = receiver;
+        h->S = S;
+        rc = multi_fill(h, ctx, keys, delta, dev);
+        if (rc != GC_OK) {
+            (void)hipStreamSynchronize(ctx->stream);  // a copy may be queued on what is freed next
+            multi_release(h);
+            h = nullptr;
+        }
+    }
+    if (status) *status = rc;
+    return h;
+} catch (...) {
+    const int rc__ = gc::on_exception();
+    if (status) *status = rc__;
+    return nullptr;
+}
+
+// the checks every receive / send shares; GC_OK with *z filled, or the code to return (per = 0: z->n = 0)
+int multi_call_args(const gc_iknp_multi *h, bool receiver, size_t per, MultiSizes *z) {
+    if (!h || h->receiver != receiver || !multi_sizes(h->S, per, z)) return GC_E_ARG;
+    // the stream position is a kernel argument and advances with every call: a replayed capture would reuse it
+    if (per && h->ctx->capturing) return GC_E_ARG;
+    return GC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+gc_iknp_multi *gc_iknp_multi_sender_create(gc_ctx *ctx, const gc_label *delta, const gc_label *k0, size_t S, int *status) {
+    return multi_create(ctx, false, k0, delta, S, false, status);
+}
+
+gc_iknp_multi *gc_iknp_multi_sender_create_dev(gc_ctx *ctx, const void *d_delta, const void *d_k0, size_t S, int *status) {
+    return multi_create(ctx, false, d_k0, d_delta, S, true, status);
+}
+
+gc_iknp_multi *gc_iknp_multi_receiver_create(gc_ctx *ctx, const gc_wire *base, size_t S, int *status) {
+    return multi_create(ctx, true, base, nullptr, S, false, status);
+}
+
+gc_iknp_multi *gc_iknp_multi_receiver_create_dev(gc_ctx *ctx, const void *d_base, size_t S, int *status) {
+    return multi_create(ctx, true, d_base, nullptr, S, true, status);
+}
+
+void gc_iknp_multi_free(gc_iknp_multi *h) {
+    if (!h) return;
+    if (h->ctx) {
+        (void)hipSetDevice(h->ctx->device);
+        (void)hipStreamSynchronize(h->ctx->stream);  // a _dev call may still read the labels
+    }
+    multi_release(h);
+}
+
+int gc_iknp_multi_info(const gc_iknp_multi *h, size_t *S, int *receiver, uint64_t *pos) {
+    if (!h) return GC_E_ARG;
+    if (S) *S = h->S;
+    if (receiver) *receiver = h->receiver ? 1 : 0;
+    if (pos) *pos = h->pos;
+    return GC_OK;
+}
+
+int gc_iknp_multi_receive_dev(gc_iknp_multi *h, const void *d_choice_packed, size_t per, void *d_u_out, void *d_labels_out) {
+    MultiSizes z;
+    int rc = multi_call_args(h, true, per, &z);
+    if (rc != GC_OK) return rc;
+    if (per == 0) return GC_OK;
+    if (!d_choice_packed || !d_u_out || !d_labels_out) return GC_E_ARG;
+    gc_ctx *ctx = h->ctx;
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_HIP(launch_iknp_multi(true, h->d_keys, nullptr, h->pos, h->S, per, (const uint8_t *)d_choice_packed, nullptr,
+                             (uint8_t *)d_u_out, (uint4 *)d_labels_out, ctx->d_te0, ctx->stream));
+    h->pos += iknp_multi_advance(per);
+    return GC_OK;
+}
+
+int gc_iknp_multi_send_dev(gc_iknp_multi *h, const void *d_u_in, size_t per, void *d_labels_out) {
+    MultiSizes z;
+    int rc = multi_call_args(h, false, per, &z);
+    if (rc != GC_OK) return rc;
+    if (per == 0) return GC_OK;
+    if (!d_u_in || !d_labels_out) return GC_E_ARG;
+    gc_ctx *ctx = h->ctx;
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_HIP(launch_iknp_multi(false, h->d_keys, h->d_delta, h->pos, h->S, per, nullptr, (const uint8_t *)d_u_in, nullptr,
+                             (uint4 *)d_labels_out, ctx->d_te0, ctx->stream));
+    h->pos += iknp_multi_advance(per);
+    return GC_OK;
+}
+
+int gc_iknp_multi_receive(gc_iknp_multi *h, const uint8_t *choice, size_t per, uint8_t *u_out, gc_label *labels_out) try {
+    MultiSizes z;
+    int rc = multi_call_args(h, true, per, &z);
+    if (rc != GC_OK) return rc;
+    if (per == 0) return GC_OK;
+    if (!choice || !u_out || !labels_out) return GC_E_ARG;
+    const size_t cb = (size_t)iknp_multi_choice_bytes(per);
+    std::vector<uint8_t> bbuf(z.choice, 0);  // iknp.go:472-477, per session
+    for (size_t s = 0; s < h->S; s++)
+        for (size_t j = 0; j < per; j++)
+            if (choice[s * per + j]) bbuf[s * cb + j / 8] |= (uint8_t)(1u << (j % 8));
+    gc_ctx *ctx = h->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    DevBuf d_bits, d_u, d_lab;
+    GC_HIP(d_bits.alloc(z.choice));
+    GC_HIP(d_u.alloc(z.u));
+    GC_HIP(d_lab.alloc(z.labels));
+    hipStream_t st = ctx->stream;
+    GC_HIP(hipMemcpyAsync(d_bits.p, bbuf.data(), z.choice, hipMemcpyHostToDevice, st));
+    GC_HIP(launch_iknp_multi(true, h->d_keys, nullptr, h->pos, h->S, per, (const uint8_t *)d_bits.p, nullptr,
+                             (uint8_t *)d_u.p, (uint4 *)d_lab.p, ctx->d_te0, st));
+    GC_HIP(hipMemcpyAsync(u_out, d_u.p, z.u, hipMemcpyDeviceToHost, st));
+    GC_HIP(hipMemcpyAsync(labels_out, d_lab.p, z.labels, hipMemcpyDeviceToHost, st));
+    GC_HIP(hipStreamSynchronize(st));
+    h->pos += iknp_multi_advance(per);
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_iknp_multi_send(gc_iknp_multi *h, const uint8_t *u_in, size_t u_len, size_t per, gc_label *labels_out) try {
+    MultiSizes z;
+    int rc = multi_call_args(h, false, per, &z);
+    if (rc != GC_OK) return rc;
+    if (per == 0) return GC_OK;
+    if (!u_in || !labels_out || u_len != z.u) return GC_E_ARG;  // "invalid chunk size" (iknp.go:207-209)
+    gc_ctx *ctx = h->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    DevBuf d_u, d_lab;
+    GC_HIP(d_u.alloc(z.u));
+    GC_HIP(d_lab.alloc(z.labels));
+    hipStream_t st = ctx->stream;
+    GC_HIP(hipMemcpyAsync(d_u.p, u_in, z.u, hipMemcpyHostToDevice, st));
+    GC_HIP(launch_iknp_multi(false, h->d_keys, h->d_delta, h->pos, h->S, per, nullptr, (const uint8_t *)d_u.p, nullptr,
+                             (uint4 *)d_lab.p, ctx->d_te0, st));
+    GC_HIP(hipMemcpyAsync(labels_out, d_lab.p, z.labels, hipMemcpyDeviceToHost, st));
+    GC_HIP(hipStreamSynchronize(st));
+    h->pos += iknp_multi_advance(per);
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+// ---- the COT pad loops (cot.go:136-235) per session: key index j of session s under seed_s, delta_s -----------------------
+
+int gc_cot_multi_send_pads_dev(gc_ctx *ctx, const void *d_seed, const void *d_delta, const void *d_data, const void *d_wires,
+                               size_t S, size_t per, void *d_out) {
+    MultiSizes z;
+    if (!ctx || S == 0 || !multi_sizes(S, per, &z)) return GC_E_ARG;
+    if (per == 0) return GC_OK;
+    if (!d_seed || !d_delta || !d_data || !d_wires || !d_out) return GC_E_ARG;
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_HIP(launch_cot_multi_send((const uint4 *)d_seed, (const uint4 *)d_delta, (const uint4 *)d_data, (const uint4 *)d_wires, S,
+                                 per, (uint4 *)d_out, ctx->d_te0, ctx->stream));
+    return GC_OK;
+}
+
+int gc_cot_multi_receive_unpad_dev(gc_ctx *ctx, const void *d_seed, const void *d_flags, const void *d_sent, void *d_result,
+                                   size_t S, size_t per) {
+    MultiSizes z;
+    if (!ctx || S == 0 || !multi_sizes(S, per, &z)) return GC_E_ARG;
+    if (per == 0) return GC_OK;
+    if (!d_seed || !d_flags || !d_sent || !d_result) return GC_E_ARG;
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_HIP(launch_cot_multi_recv((const uint4 *)d_seed, (const uint8_t *)d_flags, (const uint4 *)d_sent, (uint4 *)d_result, S,
+                                 per, ctx->d_te0, ctx->stream));
+    return GC_OK;
+}
+
+int gc_cot_multi_send_pads(gc_ctx *ctx, const gc_label *seed, const gc_label *delta, const gc_label *data,
+                           const gc_wire *wires, size_t S, size_t per, gc_label *out) try {
+    MultiSizes z;
+    if (!ctx || S == 0 || !multi_sizes(S, per, &z)) return GC_E_ARG;
+    if (per == 0) return GC_OK;
+    if (!seed || !delta || !data || !wires || !out) return GC_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    DevBuf d_seed, d_delta, d_data, d_w, d_out;
+    GC_HIP(d_seed.alloc(S * 16));
+    GC_HIP(d_delta.alloc(S * 16));
+    GC_HIP(d_data.alloc(z.n * 16));
+    GC_HIP(d_w.alloc(z.n * 32));
+    GC_HIP(d_out.alloc(z.n * 32));
+    hipStream_t st = ctx->stream;
+    GC_HIP(hipMemcpyAsync(d_seed.p, seed, S * 16, hipMemcpyHostToDevice, st));
+    GC_HIP(hipMemcpyAsync(d_delta.p, delta, S * 16, hipMemcpyHostToDevice, st));
+    GC_HIP(hipMemcpyAsync(d_data.p, data, z.n * 16, hipMemcpyHostToDevice, st));
+    GC_HIP(hipMemcpyAsync(d_w.p, wires, z.n * 32, hipMemcpyHostToDevice, st));
+    GC_HIP(launch_cot_multi_send((const uint4 *)d_seed.p, (const uint4 *)d_delta.p, (const uint4 *)d_data.p,
+                                 (const uint4 *)d_w.p, S, per, (uint4 *)d_out.p, ctx->d_te0, st));
+    GC_HIP(hipMemcpyAsync(out, d_out.p, z.n * 32, hipMemcpyDeviceToHost, st));
+    GC_HIP(hipStreamSynchronize(st));
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_cot_multi_receive_unpad(gc_ctx *ctx, const gc_label *seed, const uint8_t *flags, const gc_label *sent,
+                               gc_label *result, size_t S, size_t per) try {
+    MultiSizes z;
+    if (!ctx || S == 0 || !multi_sizes(S, per, &z)) return GC_E_ARG;
+    if (per == 0) return GC_OK;
+    if (!seed || !flags || !sent || !result) return GC_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    DevBuf d_seed, d_f, d_s, d_r;
+    GC_HIP(d_seed.alloc(S * 16));
+    GC_HIP(d_f.alloc(z.n));
+    GC_HIP(d_s.alloc(z.n * 32));
+    GC_HIP(d_r.alloc(z.n * 16));
+    hipStream_t st = ctx->stream;
+    GC_HIP(hipMemcpyAsync(d_seed.p, seed, S * 16, hipMemcpyHostToDevice, st));
+    GC_HIP(hipMemcpyAsync(d_f.p, flags, z.n, hipMemcpyHostToDevice, st));
+    GC_HIP(hipMemcpyAsync(d_s.p, sent, z.n * 32, hipMemcpyHostToDevice, st));
+    GC_HIP(hipMemcpyAsync(d_r.p, result, z.n * 16, hipMemcpyHostToDevice, st));
+    GC_HIP(launch_cot_multi_recv((const uint4 *)d_seed.p, (const uint8_t *)d_f.p, (const uint4 *)d_s.p, (uint4 *)d_r.p, S, per,
+                                 ctx->d_te0, st));
+    GC_HIP(hipMemcpyAsync(result, d_r.p, z.n * 16, hipMemcpyDeviceToHost, st));
+    GC_HIP(hipStreamSynchronize(st));
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+}  // extern "C"

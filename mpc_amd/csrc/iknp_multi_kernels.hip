@@ -1,0 +1,380 @@
+// iknp_multi_kernels.hip — the IKNP OT extension and the COT pad loops for S sessions of equal length in one launch each
+// (gc_iknp_multi_*, gc_cot_multi_*): byte for byte what k_iknp_fused / k_cot_dual give on each session alone.
+//
+// k_iknp_multi has the shape of k_iknp_fused (iknp_fused_kernels.hip): persistent workgroups of kIknpThreads lanes around
+// the perm-addressed dual table, lane = (slice, column), a slice of 128 lanes produces the column bytes of one chunk, the
+// chunk goes through a swizzled buffer in LDS, one wave transposes it (createLabels, iknp.go:647-683) and stores the labels
+// coalesced.  Where that kernel walks the chunks of one session, this one walks (session, chunk) ITEMS (iknp_multi.h), so:
+//   * the column key is per item: 16 bytes per lane from the handle's copy of the base labels, expanded in the lane by the
+//     on-the-fly schedule of aes_otf_dual.h (key = BE(label), words {y, x, w, z}).  No round keys in LDS: a session of 128
+//     OTs would load 22 KiB of them to encrypt 2 KiB;
+//   * a lane encrypts the blocks its item needs, ceil((pos % 16 + byte_rows) / 16): ONE for a session of 128 OTs at
+//     position 0, where a full chunk takes four (five off a block boundary).  The count is the same for every item but the
+//     last chunk of a session, and uniform over the two waves of a slice;
+//   * quarters of the chunk buffer and dword rows of the transpose that hold no OT are skipped.
+// LDS: 64 KiB table | 8 (sender) or 4 (receiver: 4 items x 2 streams) chunk buffers of 8 448 bytes.
+//
+// k_cot_multi is k_cot_dual's body (ot_kernels.hip) with the seed and delta of the lane's session read from arrays and the
+// MITCCRH key index restarting at 0 in every session; a wave may span sessions.
+#include <algorithm>
+#include <cstdlib>
+
+#include "aes_device.h"
+#include "aes_otf_dual.h"
+#include "iknp_multi.h"
+#include "kernels.h"
+
+namespace gc {
+
+namespace {
+
+constexpr int IKT = kIknpThreads;
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+using lds_u4 = __attribute__((address_space(3))) u32x4;
+using lds_w32 = __attribute__((address_space(3))) uint32_t;
+
+__device__ __forceinline__ uint4 lds_ld4(uint32_t addr) {
+    const u32x4 v = *(lds_u4 *)(uintptr_t)addr;
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void lds_st4(uint32_t addr, uint4 v) {
+    u32x4 w;
+    w.x = v.x, w.y = v.y, w.z = v.z, w.w = v.w;
+    *(lds_u4 *)(uintptr_t)addr = w;
+}
+__device__ __forceinline__ uint32_t lds_ld1(uint32_t addr) { return *(lds_w32 *)(uintptr_t)addr; }
+__device__ __forceinline__ void lds_st1(uint32_t addr, uint32_t v) { *(lds_w32 *)(uintptr_t)addr = v; }
+
+// The chunk buffer of k_iknp_fused (see there for the choice of the swizzle): position in dwords of dword rd of column col
+constexpr uint32_t kCgStride = 520;                 // dwords per column group: 32 columns x 16 + 8 (bank skew)
+constexpr uint32_t kChunkBuf = 512 * 16 + 16 * 16;  // 8 448 bytes
+__device__ __forceinline__ uint32_t chunk_pos(uint32_t col, uint32_t rd) {
+    const uint32_t cg = col >> 5, k = col & 31u;
+    return cg * kCgStride + k * 16u + (((rd >> 2) ^ ((k >> 1) & 3u)) << 2) + (rd & 3u);
+}
+
+// Keystream block j of the lane's column as four little-endian dwords.  The key schedule runs again for every block
+// (aes128_otf_dual consumes its key), and the blocks go one at a time: the case this kernel is for needs one, and two in
+// lock-step next to the finished stream words do not fit the 128 VGPRs of a 1024-lane workgroup.  HI0: every counter of the
+// launch is below 2^32 (launch-uniform), word 2 of the block is the literal zero.
+template <bool HI0>
+__device__ __forceinline__ void stream_block(const uint32_t (&key)[4], uint64_t j, uint32_t lo0, uint32_t (&out)[4]) {
+    uint32_t k[4] = {key[0], key[1], key[2], key[3]};
+    uint32_t s[1][4] = {{0u, 0u, HI0 ? 0u : (uint32_t)(j >> 32), (uint32_t)j}};
+    aes128_otf_dual<1>(s, k, lo0);
+#pragma unroll
+    for (int c = 0; c < 4; c++) out[c] = __builtin_bswap32(s[0][c]);
+}
+
+// The keystream bytes of one column from stream byte position p on (p mod 16 == sh, launch-uniform), as far as nb blocks
+// (1 .. 5, 5 only when MISALIGNED) give them: t[0..15] little-endian dwords, zero behind.  prg() of iknp.go:632-637 restated
+// for a lane.  Off a block boundary quarter q of the column is bytes [sh, sh + 16) of blocks q and q + 1: it is cut out as
+// soon as block q + 1 is there (zeros when it is not needed), so only one block waits next to the finished quarters.
+template <bool MISALIGNED, bool HI0>
+__device__ __forceinline__ void column_stream(uint64_t p, uint32_t sh, uint32_t nb, const uint32_t (&key)[4], uint32_t lo0,
+                                              uint32_t (&t)[16]) {
+    const uint64_t j0 = p >> 4;
+    if constexpr (!MISALIGNED) {
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            uint32_t cur[4] = {0u, 0u, 0u, 0u};
+            if ((uint32_t)b < nb) stream_block<HI0>(key, j0 + b, lo0, cur);
+#pragma unroll
+            for (int i = 0; i < 4; i++) t[4 * b + i] = cur[i];
+        }
+    } else {
+        const uint32_t ws = sh >> 2, bs = sh & 3u;  // dwords and bytes of the shift
+        uint32_t c[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // the block before | the block
+#pragma unroll
+        for (int b = 0; b < 5; b++) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) c[i] = c[4 + i], c[4 + i] = 0u;
+            if ((uint32_t)b < nb) {
+                uint32_t cur[4];
+                stream_block<HI0>(key, j0 + b, lo0, cur);
+#pragma unroll
+                for (int i = 0; i < 4; i++) c[4 + i] = cur[i];
+            }
+            if (b > 0) {
+                uint32_t d[5];  // dwords ws .. ws + 4 of the pair
+#pragma unroll
+                for (int i = 0; i < 5; i++) d[i] = ws == 0 ? c[i] : ws == 1 ? c[i + 1] : ws == 2 ? c[i + 2] : c[i + 3];
+#pragma unroll
+                for (int i = 0; i < 4; i++) t[4 * (b - 1) + i] = __builtin_amdgcn_alignbyte(d[i + 1], d[i], bs);
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ uint32_t load_u8s(const uint8_t *src, uint32_t nbytes) {  // up to 4 bytes, little-endian
+    uint32_t v = 0;
+    for (uint32_t b = 0; b < nbytes; b++) v |= (uint32_t)src[b] << (8 * b);
+    return v;
+}
+
+// bytes [16q, 16q + 16) of a column of byte_rows (<= 64) bytes, 16q < byte_rows; bytes past byte_rows read as zero and are
+// not written.  A column whose length is a multiple of 16 starts 16-byte aligned (col * byte_rows behind an offset that is a
+// multiple of 128) and goes as whole quarters; any other goes byte by byte.
+__device__ __forceinline__ uint4 load_quarter(const uint8_t *src, uint32_t byte_rows, uint32_t q) {
+    if ((byte_rows & 15u) == 0) return ((const uint4 *)src)[q];
+    uint32_t v[4];
+#pragma unroll
+    for (uint32_t i = 0; i < 4; i++) {
+        const uint32_t o = 16u * q + 4u * i;
+        v[i] = o < byte_rows ? load_u8s(src + o, byte_rows - o < 4 ? byte_rows - o : 4) : 0;
+    }
+    return make_uint4(v[0], v[1], v[2], v[3]);
+}
+__device__ __forceinline__ void store_quarter(uint8_t *dst, uint32_t byte_rows, uint32_t q, uint4 x) {
+    if ((byte_rows & 15u) == 0) {
+        ((uint4 *)dst)[q] = x;
+        return;
+    }
+    const uint32_t v[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (uint32_t i = 0; i < 4; i++)
+        for (uint32_t b = 0; b < 4; b++)
+            if (16u * q + 4u * i + b < byte_rows) dst[16 * q + 4 * i + b] = (uint8_t)(v[i] >> (8 * b));
+}
+
+// keys: the handle's base labels, [S][128] uint4 (sender: k0) or [S][128][2] (receiver: l0, l1 of every pair);
+// delta: [S] uint4 (sender).  choice / u_in / u_out / labels: the arrays of the call, laid out as iknp_multi.h says.
+template <bool RECV, bool MISALIGNED, bool HI0>
+__global__ __launch_bounds__(IKT) void k_iknp_multi(const uint4 *__restrict__ keys, const uint32_t *__restrict__ delta,
+                                                    uint64_t pos0, uint64_t S, uint64_t per,
+                                                    const uint8_t *__restrict__ choice, const uint8_t *__restrict__ u_in,
+                                                    uint8_t *__restrict__ u_out, uint4 *__restrict__ labels,
+                                                    const uint32_t *__restrict__ g_te0) {
+    extern __shared__ uint4 smem[];
+    constexpr uint32_t NCH = RECV ? kIknpRecvChunks : kIknpSendChunks;  // items per workgroup step
+    constexpr uint32_t kBuf = kTeDualBytes;                             // byte address of chunk buffer 0
+    load_te_dual((uint32_t *)smem, g_te0);
+    __syncthreads();
+    const uint32_t lo0 = te_lane_off();
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t slice = wave >> 1, col = threadIdx.x & 127u;
+    const uint32_t cig = RECV ? (slice & 3u) : slice;  // item inside the step
+    const uint32_t stream = RECV ? (slice >> 2) : 0u;  // receiver: 0 = g0 (t), 1 = g1
+    const uint32_t bufaddr = kBuf + cig * kChunkBuf;
+    const uint32_t sh = (uint32_t)(pos0 & 15u);
+    const uint64_t items = iknp_multi_items(S, per);
+    const uint64_t steps = iknp_multi_steps(items, NCH);
+
+    for (uint64_t step = blockIdx.x; step < steps; step += gridDim.x) {
+        const uint64_t it = step * NCH + cig;
+        const bool valid = it < items;
+        const IknpMultiItem m = iknp_multi_item(valid ? it : 0, per, pos0);
+        const uint32_t byte_rows = valid ? m.byte_rows : 0;
+        const uint32_t nq = (byte_rows + 15u) / 16u;  // quarters of the column that hold bytes
+        uint32_t t[16];
+        if (valid) {
+            const uint4 kl = keys[(m.session * 128 + col) * (RECV ? 2 : 1) + stream];
+            const uint32_t key[4] = {kl.y, kl.x, kl.w, kl.z};  // BE(label) (newPrg, iknp.go:622-630)
+            column_stream<MISALIGNED, HI0>(m.stream_pos, sh, m.blocks, key, lo0, t);
+        }
+        const uint64_t at = m.u_off + (uint64_t)col * byte_rows;  // column-major message layout (iknp.go:490-499)
+        if (RECV) {
+            if (valid && stream == 1) {
+#pragma unroll
+                for (uint32_t q = 0; q < 4; q++)
+                    if (q < nq)
+                        lds_st4(bufaddr + 4 * chunk_pos(col, 4 * q), make_uint4(t[4 * q], t[4 * q + 1], t[4 * q + 2], t[4 * q + 3]));
+            }
+            __syncthreads();
+            if (valid && stream == 0) {
+#pragma unroll
+                for (uint32_t q = 0; q < 4; q++)
+                    if (q < nq) {
+                        // the choice bytes, the same for every column.  Whole quarters: the contract of the call (gcengine.h)
+                        // is that an item's 64 bytes exist whatever its length is; padding bytes fall behind byte_rows and
+                        // are not stored
+                        const uint4 b = ((const uint4 *)(choice + m.choice_off))[q];
+                        const uint4 t1 = lds_ld4(bufaddr + 4 * chunk_pos(col, 4 * q));
+                        store_quarter(u_out + at, byte_rows, q,
+                                      make_uint4(t[4 * q] ^ t1.x ^ b.x, t[4 * q + 1] ^ t1.y ^ b.y, t[4 * q + 2] ^ t1.z ^ b.z,
+                                                 t[4 * q + 3] ^ t1.w ^ b.w));
+                    }
+            }
+        } else if (valid) {
+            // Delta.Bit(i): bit i of D0 for i < 64 (label.go:129-141) — D0 is the low limb
+            const uint32_t word = delta[m.session * 4 + (col >> 5)];
+            if ((word >> (col & 31u)) & 1u) {
+#pragma unroll
+                for (uint32_t q = 0; q < 4; q++)
+                    if (q < nq) {
+                        const uint4 u = load_quarter(u_in + at, byte_rows, q);
+                        t[4 * q] ^= u.x, t[4 * q + 1] ^= u.y, t[4 * q + 2] ^= u.z, t[4 * q + 3] ^= u.w;
+                    }
+            }
+        }
+        if (valid && stream == 0) {
+#pragma unroll
+            for (uint32_t q = 0; q < 4; q++)
+                if (q < nq)
+                    lds_st4(bufaddr + 4 * chunk_pos(col, 4 * q), make_uint4(t[4 * q], t[4 * q + 1], t[4 * q + 2], t[4 * q + 3]));
+        }
+        __syncthreads();
+        // createLabels: wave w transposes item w of the step; lane = (rd, cg): dword rd (OTs 32rd .. 32rd+31) of the 32
+        // columns of group cg.  A dword row without an OT was not written above and is not read here.
+        if (wave < NCH && step * NCH + wave < items) {
+            const IknpMultiItem wm = iknp_multi_item(step * NCH + wave, per, pos0);
+            const uint32_t wrows = wm.rows;
+            const uint32_t wbuf = kBuf + wave * kChunkBuf;
+            const uint32_t rd = lane >> 2, cg = lane & 3u;
+            if (32u * rd < wrows) {
+                uint32_t base[4];
+#pragma unroll
+                for (uint32_t h = 0; h < 4; h++)
+                    base[h] = wbuf + 4 * (cg * kCgStride + (((rd >> 2) ^ h) << 2) + (rd & 3u));  // chunk_pos without 16 k
+                uint32_t x[32];
+#pragma unroll
+                for (uint32_t k = 0; k < 32; k++) x[k] = lds_ld1(base[(k >> 1) & 3u] + 64u * k);
+                // 32 x 32 bit transpose (masked swaps): afterwards x[i] bit k = column (cg*32+k), OT 32rd+i
+                uint32_t msk = 0x0000ffffu;
+#pragma unroll
+                for (uint32_t j = 16; j != 0; j >>= 1, msk ^= msk << j) {
+#pragma unroll
+                    for (uint32_t k = 0; k < 32; k = ((k | j) + 1) & ~j) {
+                        const uint32_t tt = ((x[k] >> j) ^ x[k | j]) & msk;
+                        x[k] ^= tt << j;
+                        x[k | j] ^= tt;
+                    }
+                }
+                // labels back through the same buffer (a wave's DS operations execute in order and every write depends
+                // on the lane's 32 reads); label r sits at 16 * (r + r / 32)
+                const uint32_t wbase = wbuf + 16 * (33 * rd) + 4 * cg;
+#pragma unroll
+                for (uint32_t i = 0; i < 32; i++) lds_st1(wbase + 16 * i, x[i]);
+            }
+            const uint32_t rbase = wbuf + 16 * (lane + (lane >> 5));
+#pragma unroll
+            for (uint32_t mth = 0; mth < 8; mth++) {
+                const uint32_t r = lane + 64 * mth;  // label r was written by the lanes of dword row r / 32 < ceil(wrows / 32)
+                if (r < wrows) labels[wm.label_off + r] = lds_ld4(rbase + 16 * 66 * mth);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// MITCCRH key of OT index gid: BE(Label{D0:gid, D1:0} ^ seed)   (mitccrh.go:70-82)
+__device__ __forceinline__ void mitccrh_key(uint4 seed, uint64_t gid, uint32_t (&k)[4]) {
+    const uint64_t d0 = (((uint64_t)seed.y << 32) | seed.x) ^ gid;
+    k[0] = (uint32_t)(d0 >> 32);
+    k[1] = (uint32_t)d0;
+    k[2] = seed.w;
+    k[3] = seed.z;
+}
+
+// SEND: COT.Send pads   (cot.go:160-181): out[2i] = H_j(x_i) ^ L0_i, out[2i+1] = H_j(x_i ^ delta_s) ^ L1_i
+// else: COT.Receive     (cot.go:203-232): out[i] = data[2i + flag_i] ^ H_j(out[i])         (data = the 2n labels received)
+// for OT i = s * per + j of n = S * per, H_j under key BE(Label{j, 0} ^ seed_s)
+template <bool SEND>
+__global__ __launch_bounds__(kCotThreads) void k_cot_multi(const uint4 *__restrict__ seeds, const uint4 *__restrict__ deltas,
+                                                           const uint4 *__restrict__ data, const uint4 *__restrict__ wires,
+                                                           const uint8_t *__restrict__ flags, uint4 *__restrict__ out,
+                                                           uint64_t n, uint64_t per, const uint32_t *__restrict__ g_te0) {
+    extern __shared__ uint4 smem[];
+    constexpr int NB = SEND ? 2 : 1;
+    load_te_dual((uint32_t *)smem, g_te0);
+    __syncthreads();
+    const uint32_t lo0 = te_lane_off();
+    const bool small = n <= 0xffffffffull;  // launch-uniform: the session of an OT by a 32-bit division
+    for (uint64_t i = (uint64_t)blockIdx.x * kCotThreads + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kCotThreads) {
+        const uint64_t s = small ? (uint64_t)((uint32_t)i / (uint32_t)per) : i / per;
+        uint32_t k[4];
+        mitccrh_key(seeds[s], i - s * per, k);
+        uint4 x[NB], pad[NB];
+        if (SEND) {
+            x[0] = data[i];
+            x[NB - 1] = lxor(x[0], deltas[s]);
+            pad[0] = wires[2 * i];
+            pad[NB - 1] = wires[2 * i + 1];
+        } else {
+            x[0] = out[i];
+            pad[0] = data[2 * i + (flags[i] ? 1 : 0)];
+        }
+        uint32_t st[NB][4];
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            st[b][0] = x[b].y;
+            st[b][1] = x[b].x;
+            st[b][2] = x[b].w;
+            st[b][3] = x[b].z;
+        }
+        aes128_otf_dual<NB>(st, k, lo0);
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            const uint4 h = lxor(lxor(x[b], cols_to_label(st[b])), pad[b]);
+            if (SEND) out[2 * i + b] = h;
+            else out[i] = h;
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_iknp_multi(bool recv, const uint4 *keys, const uint4 *delta, uint64_t pos0, size_t S, size_t per,
+                             const uint8_t *choice, const uint8_t *u_in, uint8_t *u_out, uint4 *labels, const uint32_t *te0,
+                             hipStream_t s) {
+    if (S == 0 || per == 0) return hipSuccess;
+    const uint32_t nch = recv ? kIknpRecvChunks : kIknpSendChunks;
+    const uint64_t steps = iknp_multi_steps(iknp_multi_items(S, per), nch);
+    const unsigned grid = (unsigned)std::min<uint64_t>(steps, kIknpMultiGrid);
+    const size_t lds = kTeDualBytes + (size_t)nch * kChunkBuf;
+    const bool mis = (pos0 & 15u) != 0;
+    // every counter this launch encrypts below 2^32 blocks (64 GiB of keystream per column); GC_IKNP_GENERIC=1 forces the
+    // general form, as in launch_iknp_fused
+    const char *gen = getenv("GC_IKNP_GENERIC");
+    const bool hi0 = ((pos0 >> 4) + 4 * iknp_multi_chunks(per) + 8) < (1ull << 32) && !(gen && gen[0] == '1');
+    hipError_t e = hipSuccess;
+#define GC_IKM(R, M, H)                                                                                             \
+    do {                                                                                                            \
+        e = hipFuncSetAttribute((const void *)k_iknp_multi<R, M, H>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
+                                (int)lds);                                                                          \
+        if (e == hipSuccess)                                                                                        \
+            hipLaunchKernelGGL((k_iknp_multi<R, M, H>), dim3(grid), dim3(IKT), lds, s, keys, (const uint32_t *)delta, \
+                               pos0, (uint64_t)S, (uint64_t)per, choice, u_in, u_out, labels, te0);                 \
+    } while (0)
+#define GC_IKM2(R, M)                \
+    do {                             \
+        if (hi0) GC_IKM(R, M, true); \
+        else GC_IKM(R, M, false);    \
+    } while (0)
+    if (recv) {
+        if (mis) GC_IKM2(true, true);
+        else GC_IKM2(true, false);
+    } else {
+        if (mis) GC_IKM2(false, true);
+        else GC_IKM2(false, false);
+    }
+#undef GC_IKM2
+#undef GC_IKM
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
+template <typename K>
+static hipError_t launch_cot_multi(K kern, const uint4 *seeds, const uint4 *deltas, const uint4 *data, const uint4 *wires,
+                                   const uint8_t *flags, uint4 *out, size_t n, size_t per, const uint32_t *te0, hipStream_t s) {
+    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kTeDualBytes);
+    if (e != hipSuccess) return e;
+    const unsigned grid = (unsigned)std::min<size_t>(kCotGrid, (n + kCotThreads - 1) / kCotThreads);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kCotThreads), kTeDualBytes, s, seeds, deltas, data, wires, flags, out,
+                       (uint64_t)n, (uint64_t)per, te0);
+    return hipGetLastError();
+}
+
+hipError_t launch_cot_multi_send(const uint4 *seeds, const uint4 *deltas, const uint4 *data, const uint4 *wires, size_t S,
+                                 size_t per, uint4 *out, const uint32_t *te0, hipStream_t s) {
+    if (S == 0 || per == 0) return hipSuccess;
+    return launch_cot_multi(k_cot_multi<true>, seeds, deltas, data, wires, nullptr, out, S * per, per, te0, s);
+}
+
+hipError_t launch_cot_multi_recv(const uint4 *seeds, const uint8_t *flags, const uint4 *sent, uint4 *result, size_t S,
+                                 size_t per, const uint32_t *te0, hipStream_t s) {
+    if (S == 0 || per == 0) return hipSuccess;
+    return launch_cot_multi(k_cot_multi<false>, seeds, nullptr, sent, nullptr, flags, result, S * per, per, te0, s);
+}
+
+}  // namespace gc

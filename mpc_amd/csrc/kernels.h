@@ -324,6 +324,21 @@ void launch_cot_send(uint4 seed, uint4 delta, const uint4 *data, const uint4 *wi
 void launch_cot_recv(uint4 seed, const uint8_t *flags, const uint4 *sent, uint4 *result, size_t n,
                      const uint32_t *te0, hipStream_t s);
 
+// ---- S sessions of equal length per launch (iknp_multi_kernels.hip; the items and their offsets: iknp_multi.h) ----
+constexpr int kIknpMultiGrid = 256;   // k_iknp_multi: at most this many workgroups of kIknpThreads lanes, each walking steps of
+                                      // kIknpSendChunks / kIknpRecvChunks (session, chunk) items (step += gridDim.x)
+// keys: [S][128] base labels (sender) or [S][128][2] label pairs (receiver); delta: [S] (sender); every session at stream
+// position pos0; choice [S][chunks * 64], u [S][u_bytes(per)], labels [S][per].  recv / send as launch_iknp_fused.
+hipError_t launch_iknp_multi(bool recv, const uint4 *keys, const uint4 *delta, uint64_t pos0, size_t S, size_t per,
+                             const uint8_t *choice, const uint8_t *u_in, uint8_t *u_out, uint4 *labels, const uint32_t *te0,
+                             hipStream_t s);
+// the COT pad loops with seeds / deltas [S] and the key index restarting at 0 in every session (k_cot_multi: at most kCotGrid
+// workgroups of kCotThreads lanes)
+hipError_t launch_cot_multi_send(const uint4 *seeds, const uint4 *deltas, const uint4 *data, const uint4 *wires /*[S*per][2]*/,
+                                 size_t S, size_t per, uint4 *out, const uint32_t *te0, hipStream_t s);
+hipError_t launch_cot_multi_recv(const uint4 *seeds, const uint8_t *flags, const uint4 *sent, uint4 *result, size_t S,
+                                 size_t per, const uint32_t *te0, hipStream_t s);
+
 // ---- VOLE kernels (vole_kernels.hip) ---------------------------------------------------------
 // every value 32 bytes big-endian (2 uint4 per element); labels: gc_label [m].  sender: r = BE256(AES-CTR_label(0^32))
 // mod p, u = (r + x * y) mod p; receiver: u_out = u_msg mod p (u_out may be u_msg)

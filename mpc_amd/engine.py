@@ -261,6 +261,20 @@ def lib():
         "gc_co_multi_base_info": (i32, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
         "gc_co_multi_base_decrypt": (i32, [vp, vp, vp, vp, sz, C.c_uint64, vp, C.POINTER(C.c_size_t)]),
         "gc_co_multi_base_decrypt_dev": (i32, [vp, vp, vp, vp, sz, C.c_uint64, vp, vp]),
+        "gc_iknp_multi_sender_create": (vp, [vp, vp, vp, sz, ip]),
+        "gc_iknp_multi_sender_create_dev": (vp, [vp, vp, vp, sz, ip]),
+        "gc_iknp_multi_receiver_create": (vp, [vp, vp, sz, ip]),
+        "gc_iknp_multi_receiver_create_dev": (vp, [vp, vp, sz, ip]),
+        "gc_iknp_multi_free": (None, [vp]),
+        "gc_iknp_multi_info": (i32, [vp, C.POINTER(C.c_size_t), ip, C.POINTER(C.c_uint64)]),
+        "gc_iknp_multi_receive": (i32, [vp, vp, sz, vp, vp]),
+        "gc_iknp_multi_send": (i32, [vp, vp, sz, sz, vp]),
+        "gc_iknp_multi_receive_dev": (i32, [vp, vp, sz, vp, vp]),
+        "gc_iknp_multi_send_dev": (i32, [vp, vp, sz, vp]),
+        "gc_cot_multi_send_pads": (i32, [vp, vp, vp, vp, vp, sz, sz, vp]),
+        "gc_cot_multi_send_pads_dev": (i32, [vp, vp, vp, vp, vp, sz, sz, vp]),
+        "gc_cot_multi_receive_unpad": (i32, [vp, vp, vp, vp, vp, sz, sz]),
+        "gc_cot_multi_receive_unpad_dev": (i32, [vp, vp, vp, vp, vp, sz, sz]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -1743,3 +1757,144 @@ class CoMultiBase:
                 raise EngineError(GC_E_ARG, "CoMultiBase.close: close the handle before its Context")
             lib().gc_co_multi_base_free(self.h)
             self.h = None
+
+
+# ---- IKNP extension and COT pads for several sessions per call (gc_iknp_multi_*, gc_cot_multi_*) ----
+
+
+class _IKNPMulti:
+    """what the two roles of a gc_iknp_multi handle share"""
+
+    h = None
+
+    def _created(self, ctx, S, h, st, what):
+        self.ctx = ctx  # gc_iknp_multi_free waits for this ctx's stream: the handle has to go first
+        self.S = S
+        self.h = h
+        if not self.h:
+            raise EngineError(st.value, what)
+
+    def info(self):
+        """gc_iknp_multi_info -> (S, receiver, pos)"""
+        S, r, pos = C.c_size_t(0), C.c_int(0), C.c_uint64(0)
+        _check(lib().gc_iknp_multi_info(self.h, C.byref(S), C.byref(r), C.byref(pos)), "gc_iknp_multi_info")
+        return S.value, bool(r.value), pos.value
+
+    @property
+    def pos(self):
+        return self.info()[2]
+
+    def u_bytes(self, per):
+        """bytes of the u-matrices of one call: S * gc_iknp_u_bytes(per)"""
+        return self.S * lib().gc_iknp_u_bytes(per)
+
+    def close(self):
+        if self.h:
+            if self.ctx.h is None:  # the stream the free would wait for is gone with the ctx
+                raise EngineError(GC_E_ARG, "%s.close: close the handle before its Context" % type(self).__name__)
+            lib().gc_iknp_multi_free(self.h)
+            self.h = None
+
+
+class IKNPMultiReceiver(_IKNPMulti):
+    """gc_iknp_multi, receiver: S sessions of equal length per call, each byte for byte IKNPReceiver on that session alone.
+    base: WIRE [S, 128] (host), or a device buffer of S * 128 gc_wire with S given"""
+
+    def __init__(self, ctx, base, S=None):
+        st = C.c_int(0)
+        if S is None:
+            bw = np.ascontiguousarray(base, dtype=WIRE).reshape(-1, 128)
+            S = len(bw)
+            h = lib().gc_iknp_multi_receiver_create(ctx.h, _p(bw) if S else None, S, C.byref(st))
+            what = "gc_iknp_multi_receiver_create"
+        else:
+            S = int(S)
+            h = lib().gc_iknp_multi_receiver_create_dev(ctx.h, _dp(base), S, C.byref(st))
+            what = "gc_iknp_multi_receiver_create_dev"
+        self._created(ctx, S, h, st, what)
+
+    def receive(self, b, per):
+        """b: one byte per OT, [S * per] session-major -> (u bytes of all sessions, labels [S * per])"""
+        bb = np.ascontiguousarray(b, dtype=np.uint8).reshape(-1)
+        S, per, n = _multi(self.S, per, bb)
+        ub = self.u_bytes(per)
+        u = np.zeros(max(ub, 1), np.uint8)
+        res = np.zeros(max(n, 1), LABEL)
+        _check(lib().gc_iknp_multi_receive(self.h, _p(bb) if n else None, per, _p(u), _p(res)), "gc_iknp_multi_receive")
+        return u[:ub].tobytes(), res[:n]
+
+    def receive_dev(self, d_choice_packed, per, d_u_out, d_labels_out):
+        """device pointers; asynchronous on the ctx stream.  d_choice_packed: 64 * ceil(per / 512) bytes per session"""
+        _check(lib().gc_iknp_multi_receive_dev(self.h, _dp(d_choice_packed), per, _dp(d_u_out), _dp(d_labels_out)),
+               "gc_iknp_multi_receive_dev")
+
+
+class IKNPMultiSender(_IKNPMulti):
+    """gc_iknp_multi, sender: delta LABEL [S] and k0 LABEL [S, 128] (host), or device buffers of those with S given"""
+
+    def __init__(self, ctx, delta, k0, S=None):
+        st = C.c_int(0)
+        if S is None:
+            k = np.ascontiguousarray(k0, dtype=LABEL).reshape(-1, 128)
+            d = np.ascontiguousarray(delta, dtype=LABEL).reshape(-1)
+            S = len(k)
+            assert len(d) == S
+            h = lib().gc_iknp_multi_sender_create(ctx.h, _p(d) if S else None, _p(k) if S else None, S, C.byref(st))
+            what = "gc_iknp_multi_sender_create"
+        else:
+            S = int(S)
+            h = lib().gc_iknp_multi_sender_create_dev(ctx.h, _dp(delta), _dp(k0), S, C.byref(st))
+            what = "gc_iknp_multi_sender_create_dev"
+        self._created(ctx, S, h, st, what)
+
+    def send(self, u, per):
+        """u: the receiver's u bytes of all sessions -> labels [S * per]"""
+        ub = np.frombuffer(bytes(u), np.uint8) if len(u) else np.zeros(1, np.uint8)
+        n = self.S * int(per)
+        res = np.zeros(max(n, 1), LABEL)
+        _check(lib().gc_iknp_multi_send(self.h, _p(ub), len(u), per, _p(res)), "gc_iknp_multi_send")
+        return res[:n]
+
+    def send_dev(self, d_u_in, per, d_labels_out):
+        """device pointers; asynchronous on the ctx stream"""
+        _check(lib().gc_iknp_multi_send_dev(self.h, _dp(d_u_in), per, _dp(d_labels_out)), "gc_iknp_multi_send_dev")
+
+
+def cot_multi_send_pads(ctx, seeds, deltas, data, wires, S, per):
+    """gc_cot_multi_send_pads: seeds, deltas LABEL [S]; data LABEL [S * per], wires WIRE [S * per] -> LABEL [S * per * 2]"""
+    sd = np.ascontiguousarray(seeds, dtype=LABEL).reshape(-1)
+    dl = np.ascontiguousarray(deltas, dtype=LABEL).reshape(-1)
+    d = np.ascontiguousarray(data, dtype=LABEL).reshape(-1)
+    w = np.ascontiguousarray(wires, dtype=WIRE).reshape(-1)
+    S, per, n = _multi(S, per, d, w)
+    assert len(sd) == S and len(dl) == S
+    out = np.zeros(max(2 * n, 1), LABEL)
+    _check(lib().gc_cot_multi_send_pads(ctx.h, _p(sd) if S else None, _p(dl) if S else None, _p(d) if n else None,
+                                        _p(w) if n else None, S, per, _p(out)), "gc_cot_multi_send_pads")
+    return out[: 2 * n]
+
+
+def cot_multi_send_pads_dev(ctx, d_seeds, d_deltas, d_data, d_wires, S, per, d_out):
+    """device pointers for every array, the seeds and deltas included; asynchronous on the ctx stream"""
+    _check(lib().gc_cot_multi_send_pads_dev(ctx.h, _dp(d_seeds), _dp(d_deltas), _dp(d_data), _dp(d_wires), S, per, _dp(d_out)),
+           "gc_cot_multi_send_pads_dev")
+
+
+def cot_multi_receive_unpad(ctx, seeds, flags, sent, result, S, per):
+    """gc_cot_multi_receive_unpad: seeds LABEL [S]; flags u8 [S * per], sent LABEL [S * per * 2], result LABEL [S * per] (the
+    receiver's IKNP labels) -> the unpadded labels"""
+    sd = np.ascontiguousarray(seeds, dtype=LABEL).reshape(-1)
+    f = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+    s = np.ascontiguousarray(sent, dtype=LABEL).reshape(-1)
+    r = np.ascontiguousarray(result, dtype=LABEL).reshape(-1).copy()
+    S, per, n = _multi(S, per, f, r)
+    assert len(sd) == S and len(s) == 2 * n
+    _check(lib().gc_cot_multi_receive_unpad(ctx.h, _p(sd) if S else None, _p(f) if n else None, _p(s) if n else None,
+                                            _p(r) if n else None, S, per), "gc_cot_multi_receive_unpad")
+    return r
+
+
+def cot_multi_receive_unpad_dev(ctx, d_seeds, d_flags, d_sent, d_result, S, per):
+    """device pointers; asynchronous on the ctx stream; d_result holds the IKNP labels on entry"""
+    _check(lib().gc_cot_multi_receive_unpad_dev(ctx.h, _dp(d_seeds), _dp(d_flags), _dp(d_sent), _dp(d_result), S, per),
+           "gc_cot_multi_receive_unpad_dev")
