@@ -13,39 +13,12 @@
 // digit of the secret scalar, as the AES tables are indexed by secret bytes; the ladder calls remain for callers who mind.
 #include <algorithm>
 
-#include "co_sha256.h"
+#include "co_lane.h"
 #include "kernels.h"
 
 namespace gc {
 
 namespace {
-
-// 32 big-endian bytes as two 16-byte loads <-> limbs
-__device__ __forceinline__ Fe load_be_fe(const uint4 *p) {
-    const uint4 a = p[0], b = p[1];
-    const uint32_t w[kVoleLimbs] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    Fe f;
-    vole_from_be_words(w, f.v);
-    return f;
-}
-__device__ __forceinline__ void store_be_fe(uint4 *p, const Fe &f) {
-    uint32_t w[kVoleLimbs];
-    vole_to_be_words(f.v, w);
-    p[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    p[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
-__device__ __forceinline__ uint4 bswap4(const uint4 v) {
-    return make_uint4(__builtin_bswap32(v.x), __builtin_bswap32(v.y), __builtin_bswap32(v.z), __builtin_bswap32(v.w));
-}
-
-// one table entry as four 16-byte loads
-struct TabLoad {
-    __device__ __forceinline__ CoTabEntry operator()(const CoTabEntry *e) const {
-        const uint4 *p = reinterpret_cast<const uint4 *>(e);
-        const uint4 a = p[0], b = p[1], c = p[2], d = p[3];
-        return CoTabEntry{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}, {c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w}};
-    }
-};
 
 __global__ __launch_bounds__(kCoTabThreads) void k_co_choices_tab(const CoTabEntry *__restrict__ g_tab, Aff A,
                                                                   const uint4 *__restrict__ scalars,
@@ -69,14 +42,8 @@ __global__ __launch_bounds__(kCoTabThreads) void k_co_decrypt_tab(const CoTabEnt
                                                                   const uint4 *__restrict__ ct, size_t n, uint64_t id0,
                                                                   uint4 *__restrict__ labels_out) {
     for (size_t i = (size_t)blockIdx.x * kCoTabThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kCoTabThreads) {
-        const Jac s = pt_mul_tab<kCoTabWidthA>(load_be_fe(scalars + 2 * i), a_tab, TabLoad());
-        Fe x, y;
-        pt_to_affine(s, fe_inv(s.z), x, y);
-        uint32_t m[4];
-        co_derive_mask(x, y, id0 + i, m);
-        const uint4 c = bswap4(ct[2 * i + (choice[i] ? 1 : 0)]);
-        // SetData: D0 = BE64(bytes 0..7), D1 = BE64(bytes 8..15)
-        labels_out[i] = make_uint4(m[1] ^ c.y, m[0] ^ c.x, m[3] ^ c.w, m[2] ^ c.z);
+        co_decrypt_tail(pt_mul_tab<kCoTabWidthA>(load_be_fe(scalars + 2 * i), a_tab, TabLoad()), id0 + i, ct, choice, i,
+                        labels_out);
     }
 }
 

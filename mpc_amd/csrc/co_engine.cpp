@@ -14,6 +14,7 @@
 #define GC_CO_TABLE_BUILD 1  // co_table.h: the host-side table build as well
 
 #include <cstring>
+#include <iterator>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -25,16 +26,40 @@ using namespace gc;
 
 namespace {
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
-
 // n OTs of at most 64 bytes per array: refuse an n whose byte count does not fit size_t
 bool bytes_fit(size_t n) { return n <= SIZE_MAX / 64; }
+
+// bytes per OT (or per session) of the arrays at the boundary
+constexpr size_t kScalarBytes = 32, kPointBytes = sizeof(gc_p256_point), kWireBytes = sizeof(gc_wire), kCtBytes = 32,
+                 kLabelBytes = sizeof(gc_label);
+
+// the verdict on the launch just made
+int launched() {
+    GC_HIP(hipGetLastError());
+    return GC_OK;
+}
+
+// A host form is staging around the operation of its _dev form: one Staged per array, in the order of the operation's
+// arguments.  stage_in allocates EVERY device copy before it copies the first input; stage_out copies the outputs (a status
+// block is one of them) and waits, once.
+struct Staged {
+    const void *in;  // copied to the device before the operation, or NULL
+    void *out;       // copied back behind it, or NULL
+    size_t bytes;
+    DevBuf d;
+};
+int stage_in(Staged *io, size_t k, hipStream_t s) {
+    for (size_t j = 0; j < k; j++) GC_HIP(io[j].d.alloc(io[j].bytes));
+    for (size_t j = 0; j < k; j++)
+        if (io[j].in) GC_HIP(hipMemcpyAsync(io[j].d.p, io[j].in, io[j].bytes, hipMemcpyHostToDevice, s));
+    return GC_OK;
+}
+int stage_out(Staged *io, size_t k, hipStream_t s) {
+    for (size_t j = 0; j < k; j++)
+        if (io[j].out) GC_HIP(hipMemcpyAsync(io[j].out, io[j].d.p, io[j].bytes, hipMemcpyDeviceToHost, s));
+    GC_HIP(hipStreamSynchronize(s));
+    return GC_OK;
+}
 
 Fe load_fe(const uint8_t *b) {
     Fe f;
@@ -143,6 +168,19 @@ int co_base_init(gc_co_base *h, gc_ctx *ctx) {
 
 bool base_args(const gc_co_base *h, size_t n, bool pointers) { return h && (n == 0 || pointers) && bytes_fit(n); }
 
+// The operations of the handle on device pointers, the device set: what a _dev form does behind its argument checks
+int base_choices_run(gc_co_base *h, const void *d_scalars, const void *d_choice, size_t n, void *d_points_out) {
+    launch_co_choices_tab(h->ctx->d_co_g_tab, h->a, (const uint4 *)d_scalars, (const uint8_t *)d_choice, n, (uint4 *)d_points_out,
+                          h->ctx->stream);
+    return launched();
+}
+int base_decrypt_run(gc_co_base *h, const void *d_scalars, const void *d_choice, const void *d_ct, size_t n, uint64_t id0,
+                     void *d_labels_out) {
+    launch_co_decrypt_tab(h->d_tab, (const uint4 *)d_scalars, (const uint8_t *)d_choice, (const uint4 *)d_ct, n, id0,
+                          (uint4 *)d_labels_out, h->ctx->stream);
+    return launched();
+}
+
 }  // namespace
 
 extern "C" {
@@ -180,24 +218,16 @@ void gc_co_base_free(gc_co_base *h) {
 int gc_co_base_choices_dev(gc_co_base *h, const void *d_scalars, const void *d_choice, size_t n, void *d_points_out) {
     if (!base_args(h, n, d_scalars && d_choice && d_points_out)) return GC_E_ARG;
     if (n == 0) return GC_OK;
-    gc_ctx *ctx = h->ctx;
-    GC_HIP(hipSetDevice(ctx->device));
-    launch_co_choices_tab(ctx->d_co_g_tab, h->a, (const uint4 *)d_scalars, (const uint8_t *)d_choice, n, (uint4 *)d_points_out,
-                          ctx->stream);
-    GC_HIP(hipGetLastError());
-    return GC_OK;
+    GC_HIP(hipSetDevice(h->ctx->device));
+    return base_choices_run(h, d_scalars, d_choice, n, d_points_out);
 }
 
 int gc_co_base_decrypt_dev(gc_co_base *h, const void *d_scalars, const void *d_choice, const void *d_ct, size_t n,
                            uint64_t id0, void *d_labels_out) {
     if (!base_args(h, n, d_scalars && d_choice && d_ct && d_labels_out)) return GC_E_ARG;
     if (n == 0) return GC_OK;
-    gc_ctx *ctx = h->ctx;
-    GC_HIP(hipSetDevice(ctx->device));
-    launch_co_decrypt_tab(h->d_tab, (const uint4 *)d_scalars, (const uint8_t *)d_choice, (const uint4 *)d_ct, n, id0,
-                          (uint4 *)d_labels_out, ctx->stream);
-    GC_HIP(hipGetLastError());
-    return GC_OK;
+    GC_HIP(hipSetDevice(h->ctx->device));
+    return base_decrypt_run(h, d_scalars, d_choice, d_ct, n, id0, d_labels_out);
 }
 
 int gc_co_base_choices(gc_co_base *h, const uint8_t *scalars, const uint8_t *choice, size_t n, gc_p256_point *points_out) try {
@@ -206,18 +236,11 @@ int gc_co_base_choices(gc_co_base *h, const uint8_t *scalars, const uint8_t *cho
     gc_ctx *ctx = h->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_sc, d_ch, d_out;
-    GC_HIP(d_sc.alloc(n * 32));
-    GC_HIP(d_ch.alloc(n));
-    GC_HIP(d_out.alloc(n * 64));
-    hipStream_t s = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_sc.p, scalars, n * 32, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_ch.p, choice, n, hipMemcpyHostToDevice, s));
-    launch_co_choices_tab(ctx->d_co_g_tab, h->a, (const uint4 *)d_sc.p, (const uint8_t *)d_ch.p, n, (uint4 *)d_out.p, s);
-    GC_HIP(hipGetLastError());
-    GC_HIP(hipMemcpyAsync(points_out, d_out.p, n * 64, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipStreamSynchronize(s));
-    return GC_OK;
+    Staged io[] = {{scalars, nullptr, n * kScalarBytes}, {choice, nullptr, n}, {nullptr, points_out, n * kPointBytes}};
+    int rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = base_choices_run(h, io[0].d.p, io[1].d.p, n, io[2].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    return rc;
 } catch (...) {
     return gc::on_exception();
 }
@@ -229,21 +252,12 @@ int gc_co_base_decrypt(gc_co_base *h, const uint8_t *scalars, const uint8_t *cho
     gc_ctx *ctx = h->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_sc, d_ch, d_ct, d_out;
-    GC_HIP(d_sc.alloc(n * 32));
-    GC_HIP(d_ch.alloc(n));
-    GC_HIP(d_ct.alloc(n * 32));
-    GC_HIP(d_out.alloc(n * 16));
-    hipStream_t s = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_sc.p, scalars, n * 32, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_ch.p, choice, n, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_ct.p, ct, n * 32, hipMemcpyHostToDevice, s));
-    launch_co_decrypt_tab(h->d_tab, (const uint4 *)d_sc.p, (const uint8_t *)d_ch.p, (const uint4 *)d_ct.p, n, id0,
-                          (uint4 *)d_out.p, s);
-    GC_HIP(hipGetLastError());
-    GC_HIP(hipMemcpyAsync(labels_out, d_out.p, n * 16, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipStreamSynchronize(s));
-    return GC_OK;
+    Staged io[] = {{scalars, nullptr, n * kScalarBytes}, {choice, nullptr, n}, {ct, nullptr, n * kCtBytes},
+                   {nullptr, labels_out, n * kLabelBytes}};
+    int rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = base_decrypt_run(h, io[0].d.p, io[1].d.p, io[2].d.p, n, id0, io[3].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    return rc;
 } catch (...) {
     return gc::on_exception();
 }
@@ -263,6 +277,33 @@ int gc_co_sender_setup(const uint8_t *a, gc_p256_point *A_out, gc_p256_point *Aa
     return GC_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// The one-session operations on device pointers, the device set: what a _dev form does behind its checks
+int encrypt_run(gc_ctx *ctx, const CoSender &ses, const void *d_points, const void *d_wires, size_t n, uint64_t id0, void *d_ct,
+                void *d_status) {
+    GC_HIP(reset_status(d_status, ctx->stream));
+    launch_co_encrypt(ses, (const uint4 *)d_points, (const uint4 *)d_wires, n, id0, (uint4 *)d_ct,
+                      (unsigned long long *)d_status, ctx->stream);
+    return launched();
+}
+int choices_run(gc_ctx *ctx, const CoBase &base, const void *d_scalars, const void *d_choice, size_t n, void *d_points_out) {
+    launch_co_choices(base, (const uint4 *)d_scalars, (const uint8_t *)d_choice, n, (uint4 *)d_points_out, ctx->stream);
+    return launched();
+}
+int decrypt_run(gc_ctx *ctx, const CoBase &base, const void *d_scalars, const void *d_choice, const void *d_ct, size_t n,
+                uint64_t id0, void *d_labels_out) {
+    launch_co_decrypt(base, (const uint4 *)d_scalars, (const uint8_t *)d_choice, (const uint4 *)d_ct, n, id0,
+                      (uint4 *)d_labels_out, ctx->stream);
+    return launched();
+}
+
+}  // namespace
+
+extern "C" {
+
 int gc_co_sender_encrypt_dev(gc_ctx *ctx, const uint8_t *a, const gc_p256_point *AaInv, const void *d_points,
                              const void *d_wires, size_t n, uint64_t id0, void *d_ct, void *d_status) {
     if (!ctx || !a || !AaInv || (n && (!d_points || !d_wires || !d_ct || !d_status)) || !bytes_fit(n)) return GC_E_ARG;
@@ -271,11 +312,7 @@ int gc_co_sender_encrypt_dev(gc_ctx *ctx, const uint8_t *a, const gc_p256_point 
     if (rc != GC_OK) return rc;
     if (n == 0) return GC_OK;
     GC_HIP(hipSetDevice(ctx->device));
-    GC_HIP(reset_status(d_status, ctx->stream));
-    launch_co_encrypt(ses, (const uint4 *)d_points, (const uint4 *)d_wires, n, id0, (uint4 *)d_ct,
-                      (unsigned long long *)d_status, ctx->stream);
-    GC_HIP(hipGetLastError());
-    return GC_OK;
+    return encrypt_run(ctx, ses, d_points, d_wires, n, id0, d_ct, d_status);
 }
 
 int gc_co_receiver_choices_dev(gc_ctx *ctx, const gc_p256_point *A, const void *d_scalars, const void *d_choice, size_t n,
@@ -286,9 +323,7 @@ int gc_co_receiver_choices_dev(gc_ctx *ctx, const gc_p256_point *A, const void *
     if (rc != GC_OK) return rc;
     if (n == 0) return GC_OK;
     GC_HIP(hipSetDevice(ctx->device));
-    launch_co_choices(base, (const uint4 *)d_scalars, (const uint8_t *)d_choice, n, (uint4 *)d_points_out, ctx->stream);
-    GC_HIP(hipGetLastError());
-    return GC_OK;
+    return choices_run(ctx, base, d_scalars, d_choice, n, d_points_out);
 }
 
 int gc_co_receiver_decrypt_dev(gc_ctx *ctx, const gc_p256_point *A, const void *d_scalars, const void *d_choice,
@@ -299,42 +334,27 @@ int gc_co_receiver_decrypt_dev(gc_ctx *ctx, const gc_p256_point *A, const void *
     if (rc != GC_OK) return rc;
     if (n == 0) return GC_OK;
     GC_HIP(hipSetDevice(ctx->device));
-    launch_co_decrypt(base, (const uint4 *)d_scalars, (const uint8_t *)d_choice, (const uint4 *)d_ct, n, id0,
-                      (uint4 *)d_labels_out, ctx->stream);
-    GC_HIP(hipGetLastError());
-    return GC_OK;
+    return decrypt_run(ctx, base, d_scalars, d_choice, d_ct, n, id0, d_labels_out);
 }
 
 int gc_co_sender_encrypt(gc_ctx *ctx, const uint8_t *a, const gc_p256_point *AaInv, const gc_p256_point *points,
                          const gc_wire *wires, size_t n, uint64_t id0, uint8_t *ct, size_t *bad_index) try {
     if (!ctx || !a || !AaInv || (n && (!points || !wires || !ct)) || !bytes_fit(n)) return GC_E_ARG;
     CoSender ses;
-    const int rc = sender_session(a, AaInv, &ses);
+    int rc = sender_session(a, AaInv, &ses);
     if (rc != GC_OK) return rc;
     if (n == 0) return GC_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_pts, d_wires, d_ct, d_status;
-    GC_HIP(d_pts.alloc(n * 64));
-    GC_HIP(d_wires.alloc(n * 32));
-    GC_HIP(d_ct.alloc(n * 32));
-    GC_HIP(d_status.alloc(16));
-    hipStream_t s = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_pts.p, points, n * 64, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_wires.p, wires, n * 32, hipMemcpyHostToDevice, s));
-    GC_HIP(reset_status(d_status.p, s));
-    launch_co_encrypt(ses, (const uint4 *)d_pts.p, (const uint4 *)d_wires.p, n, id0, (uint4 *)d_ct.p,
-                      (unsigned long long *)d_status.p, s);
-    GC_HIP(hipGetLastError());
     uint64_t status[2] = {0, 0};
-    GC_HIP(hipMemcpyAsync(ct, d_ct.p, n * 32, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipMemcpyAsync(status, d_status.p, 16, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipStreamSynchronize(s));
-    if (status[0]) {  // ErrPointNotOnCurve (co_helpers.go:119-121)
-        if (bad_index) *bad_index = (size_t)status[1];
-        return GC_E_POINT;
-    }
-    return GC_OK;
+    Staged io[] = {{points, nullptr, n * kPointBytes}, {wires, nullptr, n * kWireBytes}, {nullptr, ct, n * kCtBytes},
+                   {nullptr, status, sizeof status}};
+    rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = encrypt_run(ctx, ses, io[0].d.p, io[1].d.p, n, id0, io[2].d.p, io[3].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    if (rc != GC_OK || !status[0]) return rc;
+    if (bad_index) *bad_index = (size_t)status[1];
+    return GC_E_POINT;  // ErrPointNotOnCurve (co_helpers.go:119-121)
 } catch (...) {
     return gc::on_exception();
 }
@@ -343,23 +363,16 @@ int gc_co_receiver_choices(gc_ctx *ctx, const gc_p256_point *A, const uint8_t *s
                            gc_p256_point *points_out) try {
     if (!ctx || !A || (n && (!scalars || !choice || !points_out)) || !bytes_fit(n)) return GC_E_ARG;
     CoBase base;
-    const int rc = receiver_session(A, &base);
+    int rc = receiver_session(A, &base);
     if (rc != GC_OK) return rc;
     if (n == 0) return GC_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_sc, d_ch, d_out;
-    GC_HIP(d_sc.alloc(n * 32));
-    GC_HIP(d_ch.alloc(n));
-    GC_HIP(d_out.alloc(n * 64));
-    hipStream_t s = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_sc.p, scalars, n * 32, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_ch.p, choice, n, hipMemcpyHostToDevice, s));
-    launch_co_choices(base, (const uint4 *)d_sc.p, (const uint8_t *)d_ch.p, n, (uint4 *)d_out.p, s);
-    GC_HIP(hipGetLastError());
-    GC_HIP(hipMemcpyAsync(points_out, d_out.p, n * 64, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipStreamSynchronize(s));
-    return GC_OK;
+    Staged io[] = {{scalars, nullptr, n * kScalarBytes}, {choice, nullptr, n}, {nullptr, points_out, n * kPointBytes}};
+    rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = choices_run(ctx, base, io[0].d.p, io[1].d.p, n, io[2].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    return rc;
 } catch (...) {
     return gc::on_exception();
 }
@@ -368,25 +381,17 @@ int gc_co_receiver_decrypt(gc_ctx *ctx, const gc_p256_point *A, const uint8_t *s
                            const uint8_t *ct, size_t n, uint64_t id0, gc_label *labels_out) try {
     if (!ctx || !A || (n && (!scalars || !choice || !ct || !labels_out)) || !bytes_fit(n)) return GC_E_ARG;
     CoBase base;
-    const int rc = receiver_session(A, &base);
+    int rc = receiver_session(A, &base);
     if (rc != GC_OK) return rc;
     if (n == 0) return GC_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_sc, d_ch, d_ct, d_out;
-    GC_HIP(d_sc.alloc(n * 32));
-    GC_HIP(d_ch.alloc(n));
-    GC_HIP(d_ct.alloc(n * 32));
-    GC_HIP(d_out.alloc(n * 16));
-    hipStream_t s = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_sc.p, scalars, n * 32, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_ch.p, choice, n, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_ct.p, ct, n * 32, hipMemcpyHostToDevice, s));
-    launch_co_decrypt(base, (const uint4 *)d_sc.p, (const uint8_t *)d_ch.p, (const uint4 *)d_ct.p, n, id0, (uint4 *)d_out.p, s);
-    GC_HIP(hipGetLastError());
-    GC_HIP(hipMemcpyAsync(labels_out, d_out.p, n * 16, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipStreamSynchronize(s));
-    return GC_OK;
+    Staged io[] = {{scalars, nullptr, n * kScalarBytes}, {choice, nullptr, n}, {ct, nullptr, n * kCtBytes},
+                   {nullptr, labels_out, n * kLabelBytes}};
+    rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = decrypt_run(ctx, base, io[0].d.p, io[1].d.p, io[2].d.p, n, id0, io[3].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    return rc;
 } catch (...) {
     return gc::on_exception();
 }
@@ -447,6 +452,36 @@ int multi_status(const uint64_t (&st)[4], int session_code, size_t *bad_index, s
     return st[0] ? GC_E_POINT : GC_OK;  // ErrPointNotOnCurve (co_helpers.go:119-121)
 }
 
+// The multi operations on device pointers, the device set and (setup, choices) G's table there: what a _dev form does behind
+// its checks
+int multi_setup_run(gc_ctx *ctx, const void *d_a, size_t S, void *d_A_out, void *d_AaInv_out, void *d_status) {
+    GC_HIP(reset_status4(d_status, ctx->stream));
+    launch_co_multi_setup(order_mod(), ctx->d_co_g_tab, (const uint4 *)d_a, S, (uint4 *)d_A_out, (uint4 *)d_AaInv_out,
+                          (unsigned long long *)d_status, ctx->stream);
+    return launched();
+}
+int multi_encrypt_run(gc_ctx *ctx, const void *d_a, const void *d_AaInv, const void *d_points, const void *d_wires, size_t S,
+                      size_t per, uint64_t id0, void *d_ct, void *d_status) {
+    GC_HIP(reset_status4(d_status, ctx->stream));
+    launch_co_multi_encrypt((const uint4 *)d_a, (const uint4 *)d_AaInv, (const uint4 *)d_points, (const uint4 *)d_wires, S, per,
+                            id0, (uint4 *)d_ct, (unsigned long long *)d_status, ctx->stream);
+    return launched();
+}
+int multi_choices_run(gc_ctx *ctx, const void *d_A, const void *d_scalars, const void *d_choice, size_t S, size_t per,
+                      void *d_points_out, void *d_status) {
+    GC_HIP(reset_status4(d_status, ctx->stream));
+    launch_co_multi_choices(ctx->d_co_g_tab, (const uint4 *)d_A, (const uint4 *)d_scalars, (const uint8_t *)d_choice, S, per,
+                            (uint4 *)d_points_out, (unsigned long long *)d_status, ctx->stream);
+    return launched();
+}
+int multi_decrypt_run(gc_ctx *ctx, const void *d_A, const void *d_scalars, const void *d_choice, const void *d_ct, size_t S,
+                      size_t per, uint64_t id0, void *d_labels_out, void *d_status) {
+    GC_HIP(reset_status4(d_status, ctx->stream));
+    launch_co_multi_decrypt((const uint4 *)d_A, (const uint4 *)d_scalars, (const uint8_t *)d_choice, (const uint4 *)d_ct, S, per,
+                            id0, (uint4 *)d_labels_out, (unsigned long long *)d_status, ctx->stream);
+    return launched();
+}
+
 }  // namespace
 
 extern "C" {
@@ -456,11 +491,7 @@ int gc_co_multi_sender_setup_dev(gc_ctx *ctx, const void *d_a, size_t S, void *d
     if (S == 0) return GC_OK;
     const int rc = multi_g_table(ctx);
     if (rc != GC_OK) return rc;
-    GC_HIP(reset_status4(d_status, ctx->stream));
-    launch_co_multi_setup(order_mod(), ctx->d_co_g_tab, (const uint4 *)d_a, S, (uint4 *)d_A_out, (uint4 *)d_AaInv_out,
-                          (unsigned long long *)d_status, ctx->stream);
-    GC_HIP(hipGetLastError());
-    return GC_OK;
+    return multi_setup_run(ctx, d_a, S, d_A_out, d_AaInv_out, d_status);
 } catch (...) {
     return gc::on_exception();
 }
@@ -472,11 +503,7 @@ int gc_co_multi_sender_encrypt_dev(gc_ctx *ctx, const void *d_a, const void *d_A
         return GC_E_ARG;
     if (n == 0) return GC_OK;
     GC_HIP(hipSetDevice(ctx->device));
-    GC_HIP(reset_status4(d_status, ctx->stream));
-    launch_co_multi_encrypt((const uint4 *)d_a, (const uint4 *)d_AaInv, (const uint4 *)d_points, (const uint4 *)d_wires, S, per,
-                            id0, (uint4 *)d_ct, (unsigned long long *)d_status, ctx->stream);
-    GC_HIP(hipGetLastError());
-    return GC_OK;
+    return multi_encrypt_run(ctx, d_a, d_AaInv, d_points, d_wires, S, per, id0, d_ct, d_status);
 }
 
 int gc_co_multi_receiver_choices_dev(gc_ctx *ctx, const void *d_A, const void *d_scalars, const void *d_choice, size_t S,
@@ -487,11 +514,7 @@ int gc_co_multi_receiver_choices_dev(gc_ctx *ctx, const void *d_A, const void *d
     if (n == 0) return GC_OK;
     const int rc = multi_g_table(ctx);
     if (rc != GC_OK) return rc;
-    GC_HIP(reset_status4(d_status, ctx->stream));
-    launch_co_multi_choices(ctx->d_co_g_tab, (const uint4 *)d_A, (const uint4 *)d_scalars, (const uint8_t *)d_choice, S, per,
-                            (uint4 *)d_points_out, (unsigned long long *)d_status, ctx->stream);
-    GC_HIP(hipGetLastError());
-    return GC_OK;
+    return multi_choices_run(ctx, d_A, d_scalars, d_choice, S, per, d_points_out, d_status);
 } catch (...) {
     return gc::on_exception();
 }
@@ -503,11 +526,7 @@ int gc_co_multi_receiver_decrypt_dev(gc_ctx *ctx, const void *d_A, const void *d
         return GC_E_ARG;
     if (n == 0) return GC_OK;
     GC_HIP(hipSetDevice(ctx->device));
-    GC_HIP(reset_status4(d_status, ctx->stream));
-    launch_co_multi_decrypt((const uint4 *)d_A, (const uint4 *)d_scalars, (const uint8_t *)d_choice, (const uint4 *)d_ct, S, per,
-                            id0, (uint4 *)d_labels_out, (unsigned long long *)d_status, ctx->stream);
-    GC_HIP(hipGetLastError());
-    return GC_OK;
+    return multi_decrypt_run(ctx, d_A, d_scalars, d_choice, d_ct, S, per, id0, d_labels_out, d_status);
 }
 
 int gc_co_multi_sender_setup(gc_ctx *ctx, const uint8_t *a, size_t S, gc_p256_point *A_out, gc_p256_point *AaInv_out,
@@ -517,25 +536,15 @@ int gc_co_multi_sender_setup(gc_ctx *ctx, const uint8_t *a, size_t S, gc_p256_po
     const std::vector<CoTabEntry> &g = g_table();
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    const int rc = multi_g_table_locked(ctx, g);
+    int rc = multi_g_table_locked(ctx, g);
     if (rc != GC_OK) return rc;
-    DevBuf d_a, d_A, d_ainv, d_status;
-    GC_HIP(d_a.alloc(S * 32));
-    GC_HIP(d_A.alloc(S * 64));
-    GC_HIP(d_ainv.alloc(S * 64));
-    GC_HIP(d_status.alloc(32));
-    hipStream_t s = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_a.p, a, S * 32, hipMemcpyHostToDevice, s));
-    GC_HIP(reset_status4(d_status.p, s));
-    launch_co_multi_setup(order_mod(), ctx->d_co_g_tab, (const uint4 *)d_a.p, S, (uint4 *)d_A.p, (uint4 *)d_ainv.p,
-                          (unsigned long long *)d_status.p, s);
-    GC_HIP(hipGetLastError());
     uint64_t status[4] = {0, 0, 0, 0};
-    GC_HIP(hipMemcpyAsync(A_out, d_A.p, S * 64, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipMemcpyAsync(AaInv_out, d_ainv.p, S * 64, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipMemcpyAsync(status, d_status.p, 32, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipStreamSynchronize(s));
-    return multi_status(status, GC_E_ARG, nullptr, bad_session);
+    Staged io[] = {{a, nullptr, S * kScalarBytes}, {nullptr, A_out, S * kPointBytes}, {nullptr, AaInv_out, S * kPointBytes},
+                   {nullptr, status, sizeof status}};
+    rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = multi_setup_run(ctx, io[0].d.p, S, io[1].d.p, io[2].d.p, io[3].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    return rc == GC_OK ? multi_status(status, GC_E_ARG, nullptr, bad_session) : rc;
 } catch (...) {
     return gc::on_exception();
 }
@@ -548,27 +557,13 @@ int gc_co_multi_sender_encrypt(gc_ctx *ctx, const uint8_t *a, const gc_p256_poin
     if (n == 0) return GC_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_a, d_ainv, d_pts, d_wires, d_ct, d_status;
-    GC_HIP(d_a.alloc(S * 32));
-    GC_HIP(d_ainv.alloc(S * 64));
-    GC_HIP(d_pts.alloc(n * 64));
-    GC_HIP(d_wires.alloc(n * 32));
-    GC_HIP(d_ct.alloc(n * 32));
-    GC_HIP(d_status.alloc(32));
-    hipStream_t s = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_a.p, a, S * 32, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_ainv.p, AaInv, S * 64, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_pts.p, points, n * 64, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_wires.p, wires, n * 32, hipMemcpyHostToDevice, s));
-    GC_HIP(reset_status4(d_status.p, s));
-    launch_co_multi_encrypt((const uint4 *)d_a.p, (const uint4 *)d_ainv.p, (const uint4 *)d_pts.p, (const uint4 *)d_wires.p, S,
-                            per, id0, (uint4 *)d_ct.p, (unsigned long long *)d_status.p, s);
-    GC_HIP(hipGetLastError());
     uint64_t status[4] = {0, 0, 0, 0};
-    GC_HIP(hipMemcpyAsync(ct, d_ct.p, n * 32, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipMemcpyAsync(status, d_status.p, 32, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipStreamSynchronize(s));
-    return multi_status(status, GC_E_ARG, bad_index, bad_session);
+    Staged io[] = {{a, nullptr, S * kScalarBytes}, {AaInv, nullptr, S * kPointBytes}, {points, nullptr, n * kPointBytes},
+                   {wires, nullptr, n * kWireBytes}, {nullptr, ct, n * kCtBytes}, {nullptr, status, sizeof status}};
+    int rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = multi_encrypt_run(ctx, io[0].d.p, io[1].d.p, io[2].d.p, io[3].d.p, S, per, id0, io[4].d.p, io[5].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    return rc == GC_OK ? multi_status(status, GC_E_ARG, bad_index, bad_session) : rc;
 } catch (...) {
     return gc::on_exception();
 }
@@ -581,27 +576,15 @@ int gc_co_multi_receiver_choices(gc_ctx *ctx, const gc_p256_point *A, const uint
     const std::vector<CoTabEntry> &g = g_table();
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    const int rc = multi_g_table_locked(ctx, g);
+    int rc = multi_g_table_locked(ctx, g);
     if (rc != GC_OK) return rc;
-    DevBuf d_A, d_sc, d_ch, d_out, d_status;
-    GC_HIP(d_A.alloc(S * 64));
-    GC_HIP(d_sc.alloc(n * 32));
-    GC_HIP(d_ch.alloc(n));
-    GC_HIP(d_out.alloc(n * 64));
-    GC_HIP(d_status.alloc(32));
-    hipStream_t s = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_A.p, A, S * 64, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_sc.p, scalars, n * 32, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_ch.p, choice, n, hipMemcpyHostToDevice, s));
-    GC_HIP(reset_status4(d_status.p, s));
-    launch_co_multi_choices(ctx->d_co_g_tab, (const uint4 *)d_A.p, (const uint4 *)d_sc.p, (const uint8_t *)d_ch.p, S, per,
-                            (uint4 *)d_out.p, (unsigned long long *)d_status.p, s);
-    GC_HIP(hipGetLastError());
     uint64_t status[4] = {0, 0, 0, 0};
-    GC_HIP(hipMemcpyAsync(points_out, d_out.p, n * 64, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipMemcpyAsync(status, d_status.p, 32, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipStreamSynchronize(s));
-    return multi_status(status, GC_E_POINT, nullptr, bad_session);
+    Staged io[] = {{A, nullptr, S * kPointBytes}, {scalars, nullptr, n * kScalarBytes}, {choice, nullptr, n},
+                   {nullptr, points_out, n * kPointBytes}, {nullptr, status, sizeof status}};
+    rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = multi_choices_run(ctx, io[0].d.p, io[1].d.p, io[2].d.p, S, per, io[3].d.p, io[4].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    return rc == GC_OK ? multi_status(status, GC_E_POINT, nullptr, bad_session) : rc;
 } catch (...) {
     return gc::on_exception();
 }
@@ -614,27 +597,13 @@ int gc_co_multi_receiver_decrypt(gc_ctx *ctx, const gc_p256_point *A, const uint
     if (n == 0) return GC_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_A, d_sc, d_ch, d_ct, d_out, d_status;
-    GC_HIP(d_A.alloc(S * 64));
-    GC_HIP(d_sc.alloc(n * 32));
-    GC_HIP(d_ch.alloc(n));
-    GC_HIP(d_ct.alloc(n * 32));
-    GC_HIP(d_out.alloc(n * 16));
-    GC_HIP(d_status.alloc(32));
-    hipStream_t s = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_A.p, A, S * 64, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_sc.p, scalars, n * 32, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_ch.p, choice, n, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_ct.p, ct, n * 32, hipMemcpyHostToDevice, s));
-    GC_HIP(reset_status4(d_status.p, s));
-    launch_co_multi_decrypt((const uint4 *)d_A.p, (const uint4 *)d_sc.p, (const uint8_t *)d_ch.p, (const uint4 *)d_ct.p, S, per,
-                            id0, (uint4 *)d_out.p, (unsigned long long *)d_status.p, s);
-    GC_HIP(hipGetLastError());
     uint64_t status[4] = {0, 0, 0, 0};
-    GC_HIP(hipMemcpyAsync(labels_out, d_out.p, n * 16, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipMemcpyAsync(status, d_status.p, 32, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipStreamSynchronize(s));
-    return multi_status(status, GC_E_POINT, nullptr, bad_session);
+    Staged io[] = {{A, nullptr, S * kPointBytes}, {scalars, nullptr, n * kScalarBytes}, {choice, nullptr, n},
+                   {ct, nullptr, n * kCtBytes}, {nullptr, labels_out, n * kLabelBytes}, {nullptr, status, sizeof status}};
+    int rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = multi_decrypt_run(ctx, io[0].d.p, io[1].d.p, io[2].d.p, io[3].d.p, S, per, id0, io[4].d.p, io[5].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    return rc == GC_OK ? multi_status(status, GC_E_POINT, nullptr, bad_session) : rc;
 } catch (...) {
     return gc::on_exception();
 }
@@ -743,6 +712,15 @@ bool multi_base_args(const gc_co_multi_base *h, size_t per, bool pointers, size_
     return h && multi_count(h->S, per, n) && (*n == 0 || pointers);
 }
 
+// the decrypt on device pointers, the device set: what the _dev form does behind its checks
+int multi_base_decrypt_run(gc_co_multi_base *h, const void *d_scalars, const void *d_choice, const void *d_ct, size_t per,
+                           uint64_t id0, void *d_labels_out, void *d_status) {
+    GC_HIP(reset_status4(d_status, h->ctx->stream));
+    launch_co_multi_decrypt_tab(h->d_tabs, h->d_good, (const uint4 *)d_scalars, (const uint8_t *)d_choice, (const uint4 *)d_ct,
+                                h->S, per, id0, (uint4 *)d_labels_out, (unsigned long long *)d_status, h->ctx->stream);
+    return launched();
+}
+
 }  // namespace
 
 extern "C" {
@@ -777,13 +755,8 @@ int gc_co_multi_base_decrypt_dev(gc_co_multi_base *h, const void *d_scalars, con
     size_t n = 0;
     if (!multi_base_args(h, per, d_scalars && d_choice && d_ct && d_labels_out && d_status, &n)) return GC_E_ARG;
     if (n == 0) return GC_OK;
-    gc_ctx *ctx = h->ctx;
-    GC_HIP(hipSetDevice(ctx->device));
-    GC_HIP(reset_status4(d_status, ctx->stream));
-    launch_co_multi_decrypt_tab(h->d_tabs, h->d_good, (const uint4 *)d_scalars, (const uint8_t *)d_choice, (const uint4 *)d_ct,
-                                h->S, per, id0, (uint4 *)d_labels_out, (unsigned long long *)d_status, ctx->stream);
-    GC_HIP(hipGetLastError());
-    return GC_OK;
+    GC_HIP(hipSetDevice(h->ctx->device));
+    return multi_base_decrypt_run(h, d_scalars, d_choice, d_ct, per, id0, d_labels_out, d_status);
 }
 
 int gc_co_multi_base_decrypt(gc_co_multi_base *h, const uint8_t *scalars, const uint8_t *choice, const uint8_t *ct, size_t per,
@@ -794,25 +767,13 @@ int gc_co_multi_base_decrypt(gc_co_multi_base *h, const uint8_t *scalars, const 
     gc_ctx *ctx = h->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_sc, d_ch, d_ct, d_out, d_status;
-    GC_HIP(d_sc.alloc(n * 32));
-    GC_HIP(d_ch.alloc(n));
-    GC_HIP(d_ct.alloc(n * 32));
-    GC_HIP(d_out.alloc(n * 16));
-    GC_HIP(d_status.alloc(32));
-    hipStream_t s = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_sc.p, scalars, n * 32, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_ch.p, choice, n, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_ct.p, ct, n * 32, hipMemcpyHostToDevice, s));
-    GC_HIP(reset_status4(d_status.p, s));
-    launch_co_multi_decrypt_tab(h->d_tabs, h->d_good, (const uint4 *)d_sc.p, (const uint8_t *)d_ch.p, (const uint4 *)d_ct.p, h->S,
-                                per, id0, (uint4 *)d_out.p, (unsigned long long *)d_status.p, s);
-    GC_HIP(hipGetLastError());
     uint64_t status[4] = {0, 0, 0, 0};
-    GC_HIP(hipMemcpyAsync(labels_out, d_out.p, n * 16, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipMemcpyAsync(status, d_status.p, 32, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipStreamSynchronize(s));
-    return multi_status(status, GC_E_POINT, nullptr, bad_session);
+    Staged io[] = {{scalars, nullptr, n * kScalarBytes}, {choice, nullptr, n}, {ct, nullptr, n * kCtBytes},
+                   {nullptr, labels_out, n * kLabelBytes}, {nullptr, status, sizeof status}};
+    int rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = multi_base_decrypt_run(h, io[0].d.p, io[1].d.p, io[2].d.p, per, id0, io[3].d.p, io[4].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    return rc == GC_OK ? multi_status(status, GC_E_POINT, nullptr, bad_session) : rc;
 } catch (...) {
     return gc::on_exception();
 }

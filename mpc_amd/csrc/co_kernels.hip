@@ -6,9 +6,10 @@
 //   k_co_decrypt   DecryptCOCiphertexts (:202-216): label_i = SetData(deriveMask(b_i * A, id)[:16] ^ (choice_i ? ct1 : ct0))
 //
 // One lane = one OT, grid-stride over 64-bit indices, 256-thread workgroups, a capped grid.  The curve arithmetic is p256.h,
-// the hash co_sha256.h; nothing is indexed by a register, so nothing lives in scratch.  Points cross the boundary as
-// gc_p256_point (x, y: 32 bytes big-endian each; 64 zero bytes = infinity), scalars as 32 bytes big-endian, any value below
-// 2^256, taken mod N.
+// the hash co_sha256.h, and what a lane does behind its multiplication (byte order, status, the encrypt and decrypt tails) is co_lane.h, shared with the table
+// and the multi-session kernels; nothing is indexed by a register, so nothing lives in scratch.  Points cross the boundary
+// as gc_p256_point (x, y: 32 bytes big-endian each; 64 zero bytes = infinity), scalars as 32 bytes big-endian, any value
+// below 2^256, taken mod N.
 //
 // In k_co_encrypt the scalar a is a kernel argument: the walk over its bits (pt_mul) is uniform control flow, every lane of
 // the grid doubles and adds in step.  In the receiver kernels the base is uniform (G, A) and the scalar is the lane's, so the
@@ -17,33 +18,12 @@
 // receiver's choice) stands in with Z = 1 and hashes as two empty coordinates, as crypto/elliptic's (0, 0) does in Go.
 #include <algorithm>
 
-#include "co_sha256.h"
+#include "co_lane.h"
 #include "kernels.h"
 
 namespace gc {
 
 namespace {
-
-// 32 big-endian bytes as two 16-byte loads <-> limbs
-__device__ __forceinline__ Fe load_be_fe(const uint4 *p) {
-    const uint4 a = p[0], b = p[1];
-    const uint32_t w[kVoleLimbs] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    Fe f;
-    vole_from_be_words(w, f.v);
-    return f;
-}
-__device__ __forceinline__ void store_be_fe(uint4 *p, const Fe &f) {
-    uint32_t w[kVoleLimbs];
-    vole_to_be_words(f.v, w);
-    p[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    p[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
-
-// GetData(label) = BE64(D0) || BE64(D1) (label.go:105-108) as four big-endian words, and back (SetData)
-__device__ __forceinline__ uint4 label_be_words(const uint4 l) { return make_uint4(l.y, l.x, l.w, l.z); }
-__device__ __forceinline__ uint4 bswap4(const uint4 v) {
-    return make_uint4(__builtin_bswap32(v.x), __builtin_bswap32(v.y), __builtin_bswap32(v.z), __builtin_bswap32(v.w));
-}
 
 // status[0] += bad points, status[1] = min(lowest bad index)
 __global__ __launch_bounds__(kCoThreads) void k_co_encrypt(CoSender ses, const uint4 *__restrict__ points,
@@ -52,37 +32,14 @@ __global__ __launch_bounds__(kCoThreads) void k_co_encrypt(CoSender ses, const u
     for (size_t i = (size_t)blockIdx.x * kCoThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kCoThreads) {
         Aff b;
         if (!pt_on_curve(load_be_fe(points + 4 * i), load_be_fe(points + 4 * i + 2), b)) {
-            atomicAdd(status, 1ull);
-            atomicMin(status + 1, (unsigned long long)i);
-            ct[2 * i] = make_uint4(0u, 0u, 0u, 0u);
-            ct[2 * i + 1] = make_uint4(0u, 0u, 0u, 0u);
+            co_bad_point(status, i);
+            store_zero(ct + 2 * i, 2);
             continue;
         }
         Fe a;
 #pragma unroll
         for (int j = 0; j < kVoleLimbs; j++) a.v[j] = ses.a[j];
-        const Jac s = pt_mul(a, b);
-        const Jac t = pt_madd<true>(s, ses.ainv);
-        // 1 / Zs and 1 / Zt from one inversion; a Z of zero (infinity) stands in as 1 and is selected away in pt_to_affine
-        const Fe zs = fe_select(pt_is_inf(s), fe_one(), s.z), zt = fe_select(pt_is_inf(t), fe_one(), t.z);
-        const Fe inv = fe_inv(fe_mul(zs, zt));
-        Fe sx, sy, tx, ty;
-        pt_to_affine(s, fe_mul(inv, zt), sx, sy);
-        pt_to_affine(t, fe_mul(inv, zs), tx, ty);
-        uint32_t m0[4] = {0u, 0u, 0u, 0u}, m1[4] = {0u, 0u, 0u, 0u};
-        GC_P256_NOUNROLL
-        for (int h = 0; h < 2; h++) {  // one copy of the hash in the code
-            uint32_t m[4];
-            co_derive_mask(fe_select(h != 0, tx, sx), fe_select(h != 0, ty, sy), id0 + i, m);
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                m0[j] = h ? m0[j] : m[j];
-                m1[j] = m[j];
-            }
-        }
-        const uint4 l0 = label_be_words(wires[2 * i]), l1 = label_be_words(wires[2 * i + 1]);
-        ct[2 * i] = bswap4(make_uint4(m0[0] ^ l0.x, m0[1] ^ l0.y, m0[2] ^ l0.z, m0[3] ^ l0.w));
-        ct[2 * i + 1] = bswap4(make_uint4(m1[0] ^ l1.x, m1[1] ^ l1.y, m1[2] ^ l1.z, m1[3] ^ l1.w));
+        co_encrypt_tail(pt_mul(a, b), ses.ainv, id0 + i, wires, i, ct);
     }
 }
 
@@ -109,14 +66,7 @@ __global__ __launch_bounds__(kCoThreads) void k_co_decrypt(Aff A, const uint4 *_
 #pragma unroll
     for (int j = 0; j < kVoleLimbs; j++) asm volatile("" : "+v"(A.x.v[j]), "+v"(A.y.v[j]));
     for (size_t i = (size_t)blockIdx.x * kCoThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kCoThreads) {
-        const Jac s = pt_mul(sc_reduce(load_be_fe(scalars + 2 * i)), A);
-        Fe x, y;
-        pt_to_affine(s, fe_inv(s.z), x, y);
-        uint32_t m[4];
-        co_derive_mask(x, y, id0 + i, m);
-        const uint4 c = bswap4(ct[2 * i + (choice[i] ? 1 : 0)]);
-        // SetData: D0 = BE64(bytes 0..7), D1 = BE64(bytes 8..15)
-        labels_out[i] = make_uint4(m[1] ^ c.y, m[0] ^ c.x, m[3] ^ c.w, m[2] ^ c.z);
+        co_decrypt_tail(pt_mul(sc_reduce(load_be_fe(scalars + 2 * i)), A), id0 + i, ct, choice, i, labels_out);
     }
 }
 

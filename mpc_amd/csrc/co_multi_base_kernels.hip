@@ -17,8 +17,8 @@
 // All index arithmetic is size_t.  No LDS, no scratch; nothing is indexed by a register.
 #include <algorithm>
 
+#include "co_lane.h"
 #include "co_multi_table.h"
-#include "co_sha256.h"
 #include "kernels.h"
 
 namespace gc {
@@ -27,41 +27,6 @@ namespace {
 
 constexpr size_t kWindows = co_tab_windows(kCoTabWidthA);
 constexpr size_t kEntries = co_tab_entries(kCoTabWidthA);
-
-// 32 big-endian bytes as two 16-byte loads -> limbs
-__device__ __forceinline__ Fe load_be_fe(const uint4 *p) {
-    const uint4 a = p[0], b = p[1];
-    const uint32_t w[kVoleLimbs] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    Fe f;
-    vole_from_be_words(w, f.v);
-    return f;
-}
-__device__ __forceinline__ uint4 bswap4(const uint4 v) {
-    return make_uint4(__builtin_bswap32(v.x), __builtin_bswap32(v.y), __builtin_bswap32(v.z), __builtin_bswap32(v.w));
-}
-
-// eight limbs as two 16-byte loads or stores
-struct LimbMem {
-    __device__ __forceinline__ Fe ld(const uint32_t *p) const {
-        const uint4 *q = reinterpret_cast<const uint4 *>(p);
-        const uint4 a = q[0], b = q[1];
-        return Fe{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
-    }
-    __device__ __forceinline__ void st(uint32_t *p, const Fe &f) const {
-        uint4 *q = reinterpret_cast<uint4 *>(p);
-        q[0] = make_uint4(f.v[0], f.v[1], f.v[2], f.v[3]);
-        q[1] = make_uint4(f.v[4], f.v[5], f.v[6], f.v[7]);
-    }
-};
-
-// one table entry as four 16-byte loads
-struct TabLoad {
-    __device__ __forceinline__ CoTabEntry operator()(const CoTabEntry *e) const {
-        const uint4 *p = reinterpret_cast<const uint4 *>(e);
-        const uint4 a = p[0], b = p[1], c = p[2], d = p[3];
-        return CoTabEntry{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}, {c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w}};
-    }
-};
 
 __global__ __launch_bounds__(kCoMultiTabBaseThreads) void k_co_multi_tab_bases(const uint4 *__restrict__ A_all, size_t S,
                                                                                uint32_t *__restrict__ good,
@@ -91,21 +56,12 @@ __global__ __launch_bounds__(kCoMultiTabThreads) void k_co_multi_decrypt_tab(con
     for (size_t i = (size_t)blockIdx.x * kCoMultiTabThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kCoMultiTabThreads) {
         const size_t s = i / per, j = i - s * per;
         if (!good[s]) {  // before any table access: a bad session has no table
-            if (j == 0) {
-                atomicAdd(status + 2, 1ull);
-                atomicMin(status + 3, (unsigned long long)s);
-            }
-            labels_out[i] = make_uint4(0u, 0u, 0u, 0u);
+            co_bad_session(status, s, j == 0);
+            store_zero(labels_out + i, 1);
             continue;
         }
-        const Jac sp = pt_mul_tab<kCoTabWidthA>(load_be_fe(scalars + 2 * i), tabs + s * kEntries, TabLoad());
-        Fe x, y;
-        pt_to_affine(sp, fe_inv(sp.z), x, y);
-        uint32_t m[4];
-        co_derive_mask(x, y, id0 + j, m);
-        const uint4 c = bswap4(ct[2 * i + (choice[i] ? 1 : 0)]);
-        // SetData: D0 = BE64(bytes 0..7), D1 = BE64(bytes 8..15)
-        labels_out[i] = make_uint4(m[1] ^ c.y, m[0] ^ c.x, m[3] ^ c.w, m[2] ^ c.z);
+        co_decrypt_tail(pt_mul_tab<kCoTabWidthA>(load_be_fe(scalars + 2 * i), tabs + s * kEntries, TabLoad()), id0 + j, ct,
+                        choice, i, labels_out);
     }
 }
 

@@ -20,55 +20,13 @@
 // behind the ladder, so that it does not sit in registers through it.
 #include <algorithm>
 
+#include "co_lane.h"
 #include "co_multi.h"
-#include "co_sha256.h"
 #include "kernels.h"
 
 namespace gc {
 
 namespace {
-
-// 32 big-endian bytes as two 16-byte loads <-> limbs
-__device__ __forceinline__ Fe load_be_fe(const uint4 *p) {
-    const uint4 a = p[0], b = p[1];
-    const uint32_t w[kVoleLimbs] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    Fe f;
-    vole_from_be_words(w, f.v);
-    return f;
-}
-__device__ __forceinline__ void store_be_fe(uint4 *p, const Fe &f) {
-    uint32_t w[kVoleLimbs];
-    vole_to_be_words(f.v, w);
-    p[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    p[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
-__device__ __forceinline__ void store_zero(uint4 *p, int n16) {
-#pragma unroll
-    for (int j = 0; j < n16; j++) p[j] = make_uint4(0u, 0u, 0u, 0u);
-}
-
-// GetData(label) = BE64(D0) || BE64(D1) (label.go:105-108) as four big-endian words, and back (SetData)
-__device__ __forceinline__ uint4 label_be_words(const uint4 l) { return make_uint4(l.y, l.x, l.w, l.z); }
-__device__ __forceinline__ uint4 bswap4(const uint4 v) {
-    return make_uint4(__builtin_bswap32(v.x), __builtin_bswap32(v.y), __builtin_bswap32(v.z), __builtin_bswap32(v.w));
-}
-
-// one table entry as four 16-byte loads
-struct TabLoad {
-    __device__ __forceinline__ CoTabEntry operator()(const CoTabEntry *e) const {
-        const uint4 *p = reinterpret_cast<const uint4 *>(e);
-        const uint4 a = p[0], b = p[1], c = p[2], d = p[3];
-        return CoTabEntry{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}, {c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w}};
-    }
-};
-
-// status[2] += 1 and status[3] = min(s), by the lane of the session's OT 0 alone
-__device__ __forceinline__ void bad_session(unsigned long long *status, size_t s, bool first) {
-    if (first) {
-        atomicAdd(status + 2, 1ull);
-        atomicMin(status + 3, (unsigned long long)s);
-    }
-}
 
 __global__ __launch_bounds__(kCoMultiThreads) void k_co_multi_setup(VoleMod modn, const CoTabEntry *__restrict__ g_tab,
                                                                     const uint4 *__restrict__ a, size_t S,
@@ -77,7 +35,7 @@ __global__ __launch_bounds__(kCoMultiThreads) void k_co_multi_setup(VoleMod modn
     for (size_t s = (size_t)blockIdx.x * kCoMultiThreads + threadIdx.x; s < S; s += (size_t)gridDim.x * kCoMultiThreads) {
         Fe ax, ay, tx, ty;
         if (!co_multi_setup_session<kCoTabWidthG>(load_be_fe(a + 2 * s), modn, g_tab, TabLoad(), ax, ay, tx, ty))
-            bad_session(status, s, true);  // (the outputs are zero)
+            co_bad_session(status, s, true);  // (the outputs are zero)
         store_be_fe(A_out + 4 * s, ax);
         store_be_fe(A_out + 4 * s + 2, ay);
         store_be_fe(AaInv_out + 4 * s, tx);
@@ -103,41 +61,20 @@ __global__ __launch_bounds__(kCoMultiThreads) void k_co_multi_encrypt(const uint
         if (!b_ok || fe_is_zero(a)) {
             // no ladder for this lane: whether the session or the point is to blame is decided here (a bad session wins)
             if (fe_is_zero(a) || !pt_on_curve(load_be_fe(ainv_all + 4 * s), load_be_fe(ainv_all + 4 * s + 2), ainv)) {
-                bad_session(status, s, j == 0);
+                co_bad_session(status, s, j == 0);
             } else {
-                atomicAdd(status, 1ull);
-                atomicMin(status + 1, (unsigned long long)i);
+                co_bad_point(status, i);
             }
             store_zero(ct + 2 * i, 2);
             continue;
         }
         const Jac sp = pt_mul(a, b);
         if (!pt_on_curve(load_be_fe(ainv_all + 4 * s), load_be_fe(ainv_all + 4 * s + 2), ainv)) {
-            bad_session(status, s, j == 0);
+            co_bad_session(status, s, j == 0);
             store_zero(ct + 2 * i, 2);
             continue;
         }
-        const Jac t = pt_madd<true>(sp, ainv);
-        // 1 / Zs and 1 / Zt from one inversion; a Z of zero (infinity) stands in as 1 and is selected away in pt_to_affine
-        const Fe zs = fe_select(pt_is_inf(sp), fe_one(), sp.z), zt = fe_select(pt_is_inf(t), fe_one(), t.z);
-        const Fe inv = fe_inv(fe_mul(zs, zt));
-        Fe sx, sy, tx, ty;
-        pt_to_affine(sp, fe_mul(inv, zt), sx, sy);
-        pt_to_affine(t, fe_mul(inv, zs), tx, ty);
-        uint32_t m0[4] = {0u, 0u, 0u, 0u}, m1[4] = {0u, 0u, 0u, 0u};
-        GC_P256_NOUNROLL
-        for (int h = 0; h < 2; h++) {  // one copy of the hash in the code
-            uint32_t m[4];
-            co_derive_mask(fe_select(h != 0, tx, sx), fe_select(h != 0, ty, sy), id0 + j, m);
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                m0[q] = h ? m0[q] : m[q];
-                m1[q] = m[q];
-            }
-        }
-        const uint4 l0 = label_be_words(wires[2 * i]), l1 = label_be_words(wires[2 * i + 1]);
-        ct[2 * i] = bswap4(make_uint4(m0[0] ^ l0.x, m0[1] ^ l0.y, m0[2] ^ l0.z, m0[3] ^ l0.w));
-        ct[2 * i + 1] = bswap4(make_uint4(m1[0] ^ l1.x, m1[1] ^ l1.y, m1[2] ^ l1.z, m1[3] ^ l1.w));
+        co_encrypt_tail(sp, ainv, id0 + j, wires, i, ct);
     }
 }
 
@@ -152,7 +89,7 @@ __global__ __launch_bounds__(kCoMultiThreads) void k_co_multi_choices(const CoTa
         Jac b = pt_mul_tab<kCoTabWidthG>(load_be_fe(scalars + 2 * i), g_tab, TabLoad());
         Aff add;
         if (!pt_on_curve(load_be_fe(A_all + 4 * s), load_be_fe(A_all + 4 * s + 2), add)) {  // ensureOnCurve(Ax, Ay)
-            bad_session(status, s, j == 0);
+            co_bad_session(status, s, j == 0);
             store_zero(points_out + 4 * i, 4);
             continue;
         }
@@ -175,18 +112,11 @@ __global__ __launch_bounds__(kCoMultiThreads) void k_co_multi_decrypt(const uint
         const size_t s = i / per, j = i - s * per;
         Aff A;
         if (!pt_on_curve(load_be_fe(A_all + 4 * s), load_be_fe(A_all + 4 * s + 2), A)) {  // ensureOnCurve(Ax, Ay)
-            bad_session(status, s, j == 0);
+            co_bad_session(status, s, j == 0);
             store_zero(labels_out + i, 1);
             continue;
         }
-        const Jac sp = pt_mul(sc_reduce(load_be_fe(scalars + 2 * i)), A);
-        Fe x, y;
-        pt_to_affine(sp, fe_inv(sp.z), x, y);
-        uint32_t m[4];
-        co_derive_mask(x, y, id0 + j, m);
-        const uint4 c = bswap4(ct[2 * i + (choice[i] ? 1 : 0)]);
-        // SetData: D0 = BE64(bytes 0..7), D1 = BE64(bytes 8..15)
-        labels_out[i] = make_uint4(m[1] ^ c.y, m[0] ^ c.x, m[3] ^ c.w, m[2] ^ c.z);
+        co_decrypt_tail(pt_mul(sc_reduce(load_be_fe(scalars + 2 * i)), A), id0 + j, ct, choice, i, labels_out);
     }
 }
 

@@ -1122,19 +1122,6 @@ int gc_batch_decode(const gc_batch *gb, const gc_batch *ev, void *d_bits_out, vo
 
 // ---- read-backs --------------------------------------------------------------------------------
 
-namespace {
-
-// temp device buffer freed on scope exit
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
-
-}  // namespace
-
 int gc_batch_read_r(gc_batch *b, gc_label *r_out) {
     if (!b || !r_out) return GC_E_ARG;
     gc_ctx *ctx = b->circ->ctx;

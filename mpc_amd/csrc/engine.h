@@ -17,6 +17,15 @@
 namespace gc {
 extern thread_local char tls_error[512];
 void set_error(const char *what, hipError_t e);
+
+// a temporary device buffer, freed on scope exit
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+};
 }  // namespace gc
 
 #define GC_HIP(expr)                                                   \

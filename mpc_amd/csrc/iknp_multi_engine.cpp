@@ -19,14 +19,6 @@ struct gc_iknp_multi {
 
 namespace {
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
-
 constexpr size_t kKeyBytesSend = 128 * sizeof(gc_label), kKeyBytesRecv = 128 * sizeof(gc_wire);
 
 // the byte counts of a call of S sessions of per OTs; false: one of them does not fit size_t

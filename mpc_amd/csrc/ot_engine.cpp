@@ -22,14 +22,6 @@ struct gc_iknp {
 
 namespace {
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
-
 inline uint4 to_u4(const gc_label &l) {
     return make_uint4((uint32_t)l.d0, (uint32_t)(l.d0 >> 32), (uint32_t)l.d1, (uint32_t)(l.d1 >> 32));
 }

@@ -9,14 +9,6 @@ using namespace gc;
 
 namespace {
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
-
 // m elements of 32 bytes: refuse an m whose byte count does not fit size_t
 bool bytes_fit(size_t m) { return m <= SIZE_MAX / 32; }
 

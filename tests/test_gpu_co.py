@@ -426,6 +426,8 @@ def test_misuse(ctx, pool):
         z = engine._b32(zero)
         assert L.gc_co_sender_encrypt(ctx.h, p(z), p(AaInv), p(pts), p(wires), n, 0, p(ct), C.byref(bad)) == E_ARG
         assert L.gc_co_sender_encrypt_dev(ctx.h, p(z), p(AaInv), vp(d.ptr), vp(d.ptr), n, 0, vp(d.ptr), vp(d.ptr)) == E_ARG
+        assert L.gc_co_sender_encrypt(ctx.h, p(z), p(AaInv), None, None, 0, 0, None, None) == E_ARG  # checked before n = 0 returns
+        assert L.gc_co_sender_encrypt_dev(ctx.h, p(z), p(AaInv), None, None, 0, 0, None, None) == E_ARG
     # a bad A: off the curve, an encoding >= p, infinity
     for badA in (HOSTILE["off_curve"], HOSTILE["x_equals_p"], co.INF):
         q = engine.co_point(badA)
@@ -434,6 +436,14 @@ def test_misuse(ctx, pool):
         assert L.gc_co_receiver_choices_dev(ctx.h, p(q), vp(d.ptr), vp(d.ptr), n, vp(d.ptr)) == E_POINT
         assert L.gc_co_receiver_decrypt_dev(ctx.h, p(q), vp(d.ptr), vp(d.ptr), vp(d.ptr), n, 0, vp(d.ptr)) == E_POINT
         assert L.gc_co_receiver_choices(ctx.h, p(q), None, None, 0, None) == E_POINT  # checked before n = 0 returns
+        assert L.gc_co_receiver_decrypt(ctx.h, p(q), None, None, None, 0, 0, None) == E_POINT
+        assert L.gc_co_receiver_choices_dev(ctx.h, p(q), None, None, 0, None) == E_POINT
+        assert L.gc_co_receiver_decrypt_dev(ctx.h, p(q), None, None, None, 0, 0, None) == E_POINT
+        # ... and behind the pointers and the count: a NULL or an n whose bytes do not fit is GC_E_ARG whatever A is
+        assert L.gc_co_receiver_choices(ctx.h, p(q), None, p(ch), n, p(out_pts)) == E_ARG
+        assert L.gc_co_receiver_decrypt_dev(ctx.h, p(q), vp(d.ptr), vp(d.ptr), None, n, 0, vp(d.ptr)) == E_ARG
+        assert L.gc_co_receiver_decrypt(ctx.h, p(q), p(sc), p(ch), p(ct), (1 << 58) + 1, 0, p(out_lab)) == E_ARG
+        assert L.gc_co_receiver_choices_dev(ctx.h, p(q), vp(d.ptr), vp(d.ptr), (1 << 58) + 1, vp(d.ptr)) == E_ARG
         assert L.gc_co_sender_encrypt(ctx.h, p(a), p(q), p(pts), p(wires), n, 0, p(ct), None) == E_ARG  # the caller's own constant
     # n = 0: GC_OK with no other pointer, nothing written
     out_pts[:], ct[:] = 0x77, 0x77
