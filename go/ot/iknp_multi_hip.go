@@ -6,6 +6,8 @@
 //
 // Every session keeps its own ot.IO and is framed on it exactly as iknp.go:499 / :203 frame one session, so each of the S
 // peers may be an unmodified Go party.  Arrays are session-major: OT j of session s is element s*per + j.
+// receiveMalicious / sendMalicious add the malicious branch of Receive / Send (iknp.go:373-465, :138-194) for all S
+// sessions: a second extension at 256 and the KOS tags / check of every session in one device call (gc_kos_multi_*).
 package ot
 
 /*
@@ -17,6 +19,7 @@ import "C"
 
 import (
 	"fmt"
+	"io"
 	"unsafe"
 )
 
@@ -221,6 +224,141 @@ func cotMultiSendPadsDev(ctx *C.gc_ctx, dSeeds, dDeltas, dData, dWires unsafe.Po
 
 func cotMultiReceiveUnpadDev(ctx *C.gc_ctx, dSeeds, dFlags, dSent, dResult unsafe.Pointer, sessions, per int) error {
 	if st := C.gc_cot_multi_receive_unpad_dev(ctx, dSeeds, dFlags, dSent, dResult, C.size_t(sessions), C.size_t(per)); st != C.GC_OK {
+		return multiErr(st)
+	}
+	return nil
+}
+
+// receiveMalicious runs (*IKNPReceiver).Receive(b, result, true) (iknp.go:364-465) for every session.  Session s draws
+// b0, b1 and seed2 from rands[s] in the reference's order (:374-381, :403), the 256 random choices of all sessions are
+// extended in one call, seed2 goes out on ios[s], and x, t0, t1 of all sessions come from one device call.
+func (m *hipIKNPMulti) receiveMalicious(ios []IO, rands []io.Reader, b []bool, per int, result []Label) error {
+	if len(rands) != m.s {
+		panic("len(rands) != sessions")
+	}
+	if err := m.receive(ios, b, per, result); err != nil {
+		return err
+	}
+	bcv := make([]bool, m.s*256)
+	for s := 0; s < m.s; s++ {
+		b0, err := NewLabel(rands[s])
+		if err != nil {
+			return err
+		}
+		b1, err := NewLabel(rands[s])
+		if err != nil {
+			return err
+		}
+		for i := 0; i < 256; i++ { // iknp.go:382-389
+			if i < 128 {
+				bcv[s*256+i] = b0.Bit(i) == 1
+			} else {
+				bcv[s*256+i] = b1.Bit(i-128) == 1
+			}
+		}
+	}
+	choiceVector := make([]Label, m.s*256)
+	if err := m.receive(ios, bcv, 256, choiceVector); err != nil {
+		return err
+	}
+	seed2 := make([]Label, m.s)
+	var ld LabelData
+	for s, io := range ios {
+		var err error
+		if seed2[s], err = NewLabel(rands[s]); err != nil {
+			return err
+		}
+		if err := io.SendLabel(seed2[s], &ld); err != nil {
+			return err
+		}
+		if err := io.Flush(); err != nil {
+			return err
+		}
+	}
+	tags := make([]Label, 3*m.s) // x, t0, t1 of every session
+	var resPtr *C.gc_label
+	var bPtr *C.uint8_t
+	if per > 0 {
+		resPtr = (*C.gc_label)(unsafe.Pointer(&result[0]))
+		bPtr = (*C.uint8_t)(unsafe.Pointer(&b[0]))
+	}
+	st := C.gc_kos_multi_receiver_tags(m.ctx, (*C.gc_label)(unsafe.Pointer(&seed2[0])), resPtr, bPtr,
+		(*C.gc_label)(unsafe.Pointer(&choiceVector[0])), (*C.uint8_t)(unsafe.Pointer(&bcv[0])), C.size_t(m.s),
+		C.size_t(per), (*C.gc_label)(unsafe.Pointer(&tags[0])))
+	if st != C.GC_OK {
+		return multiErr(st)
+	}
+	for s, io := range ios {
+		for k := 0; k < 3; k++ { // iknp.go:456-464
+			if err := io.SendLabel(tags[3*s+k], &ld); err != nil {
+				return err
+			}
+		}
+		if err := io.Flush(); err != nil {
+			return err
+		}
+	}
+	return nil
+}
+
+// sendMalicious runs (*IKNPSender).Send(per, true) (iknp.go:129-194) for every session: deltas are the S deltas the
+// handle was created with.  A failing check is the reference's error, naming the lowest failing session.
+func (m *hipIKNPMulti) sendMalicious(ios []IO, deltas []Label, per int) ([]Label, error) {
+	if len(deltas) != m.s {
+		panic("len(deltas) != sessions")
+	}
+	result, err := m.send(ios, per)
+	if err != nil {
+		return nil, err
+	}
+	choiceVector, err := m.send(ios, 256)
+	if err != nil {
+		return nil, err
+	}
+	seed2 := make([]Label, m.s)
+	tags := make([]Label, 3*m.s)
+	var ld LabelData
+	for s, io := range ios { // a session's peer sends seed2 before it computes, and the tags behind (iknp.go:408, 456-464)
+		if err := io.ReceiveLabel(&seed2[s], &ld); err != nil {
+			return nil, err
+		}
+	}
+	for s, io := range ios {
+		for k := 0; k < 3; k++ {
+			if err := io.ReceiveLabel(&tags[3*s+k], &ld); err != nil {
+				return nil, err
+			}
+		}
+	}
+	var resPtr *C.gc_label
+	if per > 0 {
+		resPtr = (*C.gc_label)(unsafe.Pointer(&result[0]))
+	}
+	var bad C.size_t
+	st := C.gc_kos_multi_sender_check(m.ctx, (*C.gc_label)(unsafe.Pointer(&seed2[0])), resPtr,
+		(*C.gc_label)(unsafe.Pointer(&choiceVector[0])), (*C.gc_label)(unsafe.Pointer(&deltas[0])),
+		(*C.gc_label)(unsafe.Pointer(&tags[0])), C.size_t(m.s), C.size_t(per), nil, &bad)
+	if st != C.GC_OK {
+		return nil, multiErr(st)
+	}
+	if bad != ^C.size_t(0) {
+		return nil, fmt.Errorf("OT extension check failed (session %d)", uint64(bad))
+	}
+	return result, nil
+}
+
+// device-resident forms of the two KOS calls: every array in HBM, asynchronous on the ctx stream, no stream position (they
+// may be captured).  dChoicePacked / dBcvPacked are the buffers receiveDev consumed at per and at 256, dResult /
+// dChoiceVec the labels it (or sendDev) left; dTags holds x, t0, t1 of every session.
+func kosMultiReceiverTagsDev(ctx *C.gc_ctx, dSeed2, dResult, dChoicePacked, dChoiceVec, dBcvPacked unsafe.Pointer, sessions, per int, dTags unsafe.Pointer) error {
+	if st := C.gc_kos_multi_receiver_tags_dev(ctx, dSeed2, dResult, dChoicePacked, dChoiceVec, dBcvPacked, C.size_t(sessions), C.size_t(per), dTags); st != C.GC_OK {
+		return multiErr(st)
+	}
+	return nil
+}
+
+func kosMultiSenderCheckDev(ctx *C.gc_ctx, dSeed2, dResult, dChoiceVec, dDelta, dTags unsafe.Pointer, sessions, per int, dOk, dStatus unsafe.Pointer) error {
+	if st := C.gc_kos_multi_sender_check_dev(ctx, dSeed2, dResult, dChoiceVec, dDelta, dTags, C.size_t(sessions), C.size_t(per), dOk, dStatus); st != C.GC_OK {
 		return multiErr(st)
 	}
 	return nil

@@ -854,8 +854,8 @@ int gc_co_multi_base_decrypt_dev(gc_co_multi_base *, const void *d_scalars, cons
  * gc_cot_receive_unpad on that session alone.  Conventions are those of gc_co_multi_*: session-major (OT j of session s is
  * element s * per + j of every per-OT array), the session constants are arrays, a _dev form takes device pointers for EVERY
  * array (16-byte aligned) and is asynchronous on the ctx stream with one kernel per call, a host form takes host pointers
- * and is synchronous and staged.  Sessions of unequal length, bit-COT, ROT and a KOS check over the handle are not offered:
- * gc_kos_*_dev runs per session on slices of the session-major label arrays.
+ * and is synchronous and staged.  Sessions of unequal length, bit-COT and ROT are not offered.  The KOS check of the
+ * malicious variant over these arrays is gc_kos_multi_* below.
  *   The handle holds copies of the base labels in device memory (sender: delta [S] and k0 [S][128], 2 KiB + 16 bytes per
  *   session; receiver: base [S][128] gc_wire, 4 KiB per session) and no round keys: the kernel expands a column's key in the
  *   lane.  It holds ONE stream position: sessions of equal length advance in lock step, every call advances it by what
@@ -894,6 +894,41 @@ int gc_cot_multi_receive_unpad(gc_ctx *, const gc_label *seed, const uint8_t *fl
                                size_t S, size_t per);
 int gc_cot_multi_receive_unpad_dev(gc_ctx *, const void *d_seed, const void *d_flags, const void *d_sent, void *d_result,
                                    size_t S, size_t per);
+
+/* ------------------------------------------------------------------------------------------
+ * KOS consistency check for several sessions per call (ot/iknp.go:129-194, ot/iknp.go:364-466, ot/gf128.go:14-27; additive)
+ * The tags and the check of the
+ * malicious variant for the S sessions of a gc_iknp_multi handle, one kernel per call.  Byte for byte, session s of a multi
+ * call is gc_kos_receiver_tags / gc_kos_sender_check on that session alone: chi_i is label i of the AES-128-CTR stream keyed
+ * by seed2[s], indices 0 .. per-1 go with result[s][.] and per .. per+255 with choice_vec[s][.]; the index restarts in every
+ * session and goes on at per, not at a padded length.
+ *   Layouts, session-major: seed2 and delta [S]; result [S][per]; choice_vec [S][256]; tags [S][3] gc_label in the order
+ *   x, t0, t1.  Host forms take one byte per choice, b [S][per] and bcv [S][256].  _dev forms take the packed buffers the
+ *   extension consumed: d_choice_packed is the buffer of gc_iknp_multi_receive_dev at this `per` (session s at byte
+ *   s * 64 * ceil(per / 512), LSB first), d_bcv_packed that of the call at per = 256 (64 bytes per session), d_result and
+ *   d_choice_vec the d_labels_out of those two calls.  Only the bytes that hold choice bits are read: what the padding holds
+ *   reaches no output.  d_ok is [S] bytes, 1 = the check passed; d_status is two uint64 {failed sessions, lowest failing
+ *   session (all ones: none)}, reset on the stream by the call as the gc_co_*_dev status blocks are.
+ *   The host form of the check returns GC_OK whether or not sessions fail (as gc_kos_sender_check does with *ok = 0) and
+ *   writes ok_out [S] and *bad_session (the lowest failing session, (size_t)-1 for none); either may be NULL, not both.
+ *   Sizes: per = 0 is valid and sums over the choice vector alone (the per-OT arrays may then be NULL); S = 0 returns GC_OK
+ *   and writes nothing.  GC_E_ARG: a NULL ctx, a NULL array that is needed, a device pointer to labels (d_seed2, d_result,
+ *   d_choice_vec, d_delta, d_tags, d_tags_out) that is not 16-byte aligned or a d_status that is not 8-byte aligned, a size
+ *   that does not fit size_t, a host form between gc_ctx_capture_begin and _end.
+ *   The _dev forms are asynchronous on the ctx stream, allocate nothing, wait for nothing, copy nothing to the host and
+ *   carry no stream position: they may be captured.  Host forms are synchronous and staged.
+ *   A team of lanes owns a session: one wave up to per + 256 = 1 024 labels, a workgroup above.  Sessions so long and so few
+ *   that S workgroups cannot fill the device are the ground of the one-session gc_kos_*_dev, which spreads ONE session over
+ *   the whole grid; there is no split-session form here. */
+int gc_kos_multi_receiver_tags(gc_ctx *, const gc_label *seed2, const gc_label *result, const uint8_t *b,
+                               const gc_label *choice_vec, const uint8_t *bcv, size_t S, size_t per, gc_label *tags_out);
+int gc_kos_multi_receiver_tags_dev(gc_ctx *, const void *d_seed2, const void *d_result, const void *d_choice_packed,
+                                   const void *d_choice_vec, const void *d_bcv_packed, size_t S, size_t per, void *d_tags_out);
+int gc_kos_multi_sender_check(gc_ctx *, const gc_label *seed2, const gc_label *result, const gc_label *choice_vec,
+                              const gc_label *delta, const gc_label *tags, size_t S, size_t per, uint8_t *ok_out,
+                              size_t *bad_session);
+int gc_kos_multi_sender_check_dev(gc_ctx *, const void *d_seed2, const void *d_result, const void *d_choice_vec,
+                                  const void *d_delta, const void *d_tags, size_t S, size_t per, void *d_ok, void *d_status);
 
 #ifdef __cplusplus
 }

@@ -339,6 +339,20 @@ hipError_t launch_cot_multi_send(const uint4 *seeds, const uint4 *deltas, const 
 hipError_t launch_cot_multi_recv(const uint4 *seeds, const uint8_t *flags, const uint4 *sent, uint4 *result, size_t S,
                                  size_t per, const uint32_t *te0, hipStream_t s);
 
+// ---- the KOS check for S sessions per launch (kos_multi_kernels.hip; teams, labels and choice bits: kos_multi.h) ----
+constexpr int kKosMultiThreads = 1024;  // k_kos_multi: lanes per workgroup
+constexpr int kKosMultiGrid = 256;      // ... at most this many workgroups; a team takes a session per trip
+constexpr int kKosMultiWaveMax = 1024;  // ... one wave per session while per + 256 <= this (16 labels a lane), the whole
+                                        // workgroup per session above
+// seed2, delta [S]; result [S][per]; cv [S][256]; choice [S][64 * ceil(per / 512)] and bcv [S][64] packed LSB first;
+// tags [S][3] {x, t0, t1}; ok [S] bytes; status {failed sessions (added to), lowest failing session (min-ed into)}.  Label
+// arrays 16-byte aligned, status 8; result and choice may be null when per = 0.
+hipError_t launch_kos_multi_tags(const uint4 *seed2, const uint4 *result, const uint8_t *choice, const uint4 *cv,
+                                 const uint8_t *bcv, size_t S, size_t per, uint4 *tags_out, const uint32_t *te0, hipStream_t s);
+hipError_t launch_kos_multi_check(const uint4 *seed2, const uint4 *result, const uint4 *cv, const uint4 *delta,
+                                  const uint4 *tags, size_t S, size_t per, uint8_t *ok, unsigned long long *status,
+                                  const uint32_t *te0, hipStream_t s);
+
 // ---- VOLE kernels (vole_kernels.hip) ---------------------------------------------------------
 // every value 32 bytes big-endian (2 uint4 per element); labels: gc_label [m].  sender: r = BE256(AES-CTR_label(0^32))
 // mod p, u = (r + x * y) mod p; receiver: u_out = u_msg mod p (u_out may be u_msg)

@@ -1,0 +1,154 @@
+// kos_multi_engine.cpp — C ABI of the multi-session KOS check (gc_kos_multi_*): the tags and the check of the malicious IKNP
+// variant for S sessions of `per` OTs each, session-major, one kernel per call (kos_multi_kernels.hip; layouts: kos_multi.h).
+// The _dev forms only reset the status block and launch: no allocation, no wait, nothing copied to the host, so they may be
+// captured.  The host forms stage their arrays the way the host forms of iknp_multi_engine.cpp do.
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "engine.h"
+#include "kos_multi.h"
+
+using namespace gc;
+
+namespace {
+
+constexpr size_t kLabel = sizeof(gc_label);
+
+// the byte counts of a call; false: one of them does not fit size_t
+struct KosSizes {
+    size_t n, choice_row;  // S * per; bytes of one session's packed choice bits
+};
+bool kos_sizes(size_t S, size_t per, KosSizes *z) {
+    if (per && S > SIZE_MAX / per) return false;
+    z->n = S * per;
+    if (z->n > SIZE_MAX / 64 || S > SIZE_MAX / (64 * kKosCvLabels)) return false;  // labels, tags and the choice vectors
+    z->choice_row = (size_t)kos_multi_choice_row(per);
+    if (z->choice_row && S > SIZE_MAX / z->choice_row) return false;
+    return true;
+}
+
+bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+int tags_run(gc_ctx *ctx, const void *d_seed2, const void *d_result, const void *d_choice, const void *d_cv, const void *d_bcv,
+             size_t S, size_t per, void *d_tags) {
+    GC_HIP(launch_kos_multi_tags((const uint4 *)d_seed2, (const uint4 *)d_result, (const uint8_t *)d_choice, (const uint4 *)d_cv,
+                                 (const uint8_t *)d_bcv, S, per, (uint4 *)d_tags, ctx->d_te0, ctx->stream));
+    return GC_OK;
+}
+
+int check_run(gc_ctx *ctx, const void *d_seed2, const void *d_result, const void *d_cv, const void *d_delta, const void *d_tags,
+              size_t S, size_t per, void *d_ok, void *d_status) {
+    // the status block before the kernel: {0, ~0}
+    GC_HIP(hipMemsetAsync(d_status, 0, 8, ctx->stream));
+    GC_HIP(hipMemsetAsync((uint8_t *)d_status + 8, 0xff, 8, ctx->stream));
+    GC_HIP(launch_kos_multi_check((const uint4 *)d_seed2, (const uint4 *)d_result, (const uint4 *)d_cv, (const uint4 *)d_delta,
+                                  (const uint4 *)d_tags, S, per, (uint8_t *)d_ok, (unsigned long long *)d_status, ctx->d_te0,
+                                  ctx->stream));
+    return GC_OK;
+}
+
+// one byte per choice -> rows of `row` bytes, packed LSB first (iknp.go:472-477), zero-padded
+std::vector<uint8_t> pack_rows(const uint8_t *b, size_t S, size_t per, size_t row) {
+    std::vector<uint8_t> out(S * row, 0);
+    for (size_t s = 0; s < S; s++)
+        for (size_t j = 0; j < per; j++)
+            if (b[s * per + j]) out[s * row + j / 8] |= (uint8_t)(1u << (j % 8));
+    return out;
+}
+
+int to_dev(DevBuf &d, const void *src, size_t bytes, hipStream_t st) {
+    GC_HIP(d.alloc(bytes));
+    if (src && bytes) GC_HIP(hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, st));
+    return GC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gc_kos_multi_receiver_tags_dev(gc_ctx *ctx, const void *d_seed2, const void *d_result, const void *d_choice_packed,
+                                   const void *d_choice_vec, const void *d_bcv_packed, size_t S, size_t per, void *d_tags_out) {
+    KosSizes z;
+    if (!ctx || !kos_sizes(S, per, &z)) return GC_E_ARG;
+    if (S == 0) return GC_OK;
+    if (!d_seed2 || !d_choice_vec || !d_bcv_packed || !d_tags_out || (per && (!d_result || !d_choice_packed))) return GC_E_ARG;
+    if (!aligned(d_seed2, 16) || !aligned(d_result, 16) || !aligned(d_choice_vec, 16) || !aligned(d_tags_out, 16))
+        return GC_E_ARG;
+    GC_HIP(hipSetDevice(ctx->device));
+    return tags_run(ctx, d_seed2, d_result, d_choice_packed, d_choice_vec, d_bcv_packed, S, per, d_tags_out);
+}
+
+int gc_kos_multi_sender_check_dev(gc_ctx *ctx, const void *d_seed2, const void *d_result, const void *d_choice_vec,
+                                  const void *d_delta, const void *d_tags, size_t S, size_t per, void *d_ok, void *d_status) {
+    KosSizes z;
+    if (!ctx || !kos_sizes(S, per, &z)) return GC_E_ARG;
+    if (S == 0) return GC_OK;
+    if (!d_seed2 || !d_choice_vec || !d_delta || !d_tags || !d_ok || !d_status || (per && !d_result)) return GC_E_ARG;
+    if (!aligned(d_seed2, 16) || !aligned(d_result, 16) || !aligned(d_choice_vec, 16) || !aligned(d_delta, 16) ||
+        !aligned(d_tags, 16) || !aligned(d_status, 8))
+        return GC_E_ARG;
+    GC_HIP(hipSetDevice(ctx->device));
+    return check_run(ctx, d_seed2, d_result, d_choice_vec, d_delta, d_tags, S, per, d_ok, d_status);
+}
+
+int gc_kos_multi_receiver_tags(gc_ctx *ctx, const gc_label *seed2, const gc_label *result, const uint8_t *b,
+                               const gc_label *choice_vec, const uint8_t *bcv, size_t S, size_t per, gc_label *tags_out) try {
+    KosSizes z;
+    if (!ctx || !kos_sizes(S, per, &z)) return GC_E_ARG;
+    if (S == 0) return GC_OK;
+    if (!seed2 || !choice_vec || !bcv || !tags_out || (per && (!result || !b))) return GC_E_ARG;
+    if (ctx->capturing) return GC_E_ARG;  // allocates and waits
+    const std::vector<uint8_t> bits = pack_rows(b, S, per, z.choice_row), cbits = pack_rows(bcv, S, kKosCvLabels, kKosBcvRow);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DevBuf d_seed, d_res, d_bits, d_cv, d_cb, d_tags;
+    int rc = to_dev(d_seed, seed2, S * kLabel, st);
+    if (rc == GC_OK) rc = to_dev(d_res, result, z.n * kLabel, st);
+    if (rc == GC_OK) rc = to_dev(d_bits, bits.data(), bits.size(), st);
+    if (rc == GC_OK) rc = to_dev(d_cv, choice_vec, S * kKosCvLabels * kLabel, st);
+    if (rc == GC_OK) rc = to_dev(d_cb, cbits.data(), cbits.size(), st);
+    if (rc == GC_OK) rc = to_dev(d_tags, nullptr, S * 3 * kLabel, st);
+    if (rc == GC_OK) rc = tags_run(ctx, d_seed.p, d_res.p, d_bits.p, d_cv.p, d_cb.p, S, per, d_tags.p);
+    if (rc == GC_OK) GC_HIP(hipMemcpyAsync(tags_out, d_tags.p, S * 3 * kLabel, hipMemcpyDeviceToHost, st));
+    GC_HIP(hipStreamSynchronize(st));  // also on an error: a copy may be queued on what is freed next
+    return rc;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_kos_multi_sender_check(gc_ctx *ctx, const gc_label *seed2, const gc_label *result, const gc_label *choice_vec,
+                              const gc_label *delta, const gc_label *tags, size_t S, size_t per, uint8_t *ok_out,
+                              size_t *bad_session) try {
+    KosSizes z;
+    if (!ctx || !kos_sizes(S, per, &z)) return GC_E_ARG;
+    if (S == 0) return GC_OK;
+    if (!seed2 || !choice_vec || !delta || !tags || (!ok_out && !bad_session) || (per && !result)) return GC_E_ARG;
+    if (ctx->capturing) return GC_E_ARG;  // allocates and waits
+    std::vector<uint8_t> ok(S, 0);
+    uint64_t status[2] = {0, 0};
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DevBuf d_seed, d_res, d_cv, d_delta, d_tags, d_ok, d_status;
+    int rc = to_dev(d_seed, seed2, S * kLabel, st);
+    if (rc == GC_OK) rc = to_dev(d_res, result, z.n * kLabel, st);
+    if (rc == GC_OK) rc = to_dev(d_cv, choice_vec, S * kKosCvLabels * kLabel, st);
+    if (rc == GC_OK) rc = to_dev(d_delta, delta, S * kLabel, st);
+    if (rc == GC_OK) rc = to_dev(d_tags, tags, S * 3 * kLabel, st);
+    if (rc == GC_OK) rc = to_dev(d_ok, nullptr, S, st);
+    if (rc == GC_OK) rc = to_dev(d_status, nullptr, sizeof status, st);
+    if (rc == GC_OK) rc = check_run(ctx, d_seed.p, d_res.p, d_cv.p, d_delta.p, d_tags.p, S, per, d_ok.p, d_status.p);
+    if (rc == GC_OK) GC_HIP(hipMemcpyAsync(ok.data(), d_ok.p, S, hipMemcpyDeviceToHost, st));
+    if (rc == GC_OK) GC_HIP(hipMemcpyAsync(status, d_status.p, sizeof status, hipMemcpyDeviceToHost, st));
+    GC_HIP(hipStreamSynchronize(st));
+    if (rc != GC_OK) return rc;
+    if (ok_out) std::copy(ok.begin(), ok.end(), ok_out);
+    if (bad_session) *bad_session = status[0] ? (size_t)status[1] : (size_t)-1;
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+}  // extern "C"

@@ -13,6 +13,7 @@
 #include "aes_device.h"
 #include "aes_otf_dual.h"
 #include "kernels.h"
+#include "kos_clmul.h"
 
 namespace gc {
 
@@ -298,23 +299,7 @@ __global__ __launch_bounds__(kCotThreads) void k_kos_accumulate(const uint32_t *
         const uint32_t chi[4] = {st[0][1], st[0][0], st[0][3], st[0][2]};  // little-endian word vector: D0 low, D0 high, D1 low, D1 high
         const uint4 b = v[i];
         const uint32_t bw[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-        for (int w = 0; w < 4; w++) {  // q = chi * bw[w] (128 x 32 -> 160 bits), added at word offset w
-            uint32_t cur[5] = {chi[0], chi[1], chi[2], chi[3], 0u}, q[5] = {0u, 0u, 0u, 0u, 0u};
-            uint32_t word = bw[w];
-#pragma unroll 8
-            for (int k = 0; k < 32; k++) {
-                const uint32_t m = 0u - (word & 1u);
-                word >>= 1;
-#pragma unroll
-                for (int t = 0; t < 5; t++) q[t] = __builtin_amdgcn_bitop3_b32(q[t], cur[t], m, 0x78);  // q ^ (cur & m)
-#pragma unroll
-                for (int t = 4; t > 0; t--) cur[t] = __builtin_amdgcn_alignbit(cur[t], cur[t - 1], 31);
-                cur[0] <<= 1;
-            }
-#pragma unroll
-            for (int t = 0; t < 5; t++) p[w + t] ^= q[t];
-        }
+        kos_clmul_acc(p, chi, bw);  // p ^= chi * b, four 128 x 32 -> 160-bit partial products (kos_clmul.h)
         if (bits && bits[i]) {
 #pragma unroll
             for (int t = 0; t < 4; t++) xs[t] ^= chi[t];

@@ -275,6 +275,10 @@ def lib():
         "gc_cot_multi_send_pads_dev": (i32, [vp, vp, vp, vp, vp, sz, sz, vp]),
         "gc_cot_multi_receive_unpad": (i32, [vp, vp, vp, vp, vp, sz, sz]),
         "gc_cot_multi_receive_unpad_dev": (i32, [vp, vp, vp, vp, vp, sz, sz]),
+        "gc_kos_multi_receiver_tags": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, vp]),
+        "gc_kos_multi_receiver_tags_dev": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, vp]),
+        "gc_kos_multi_sender_check": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp]),
+        "gc_kos_multi_sender_check_dev": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -1898,3 +1902,55 @@ def cot_multi_receive_unpad_dev(ctx, d_seeds, d_flags, d_sent, d_result, S, per)
     """device pointers; asynchronous on the ctx stream; d_result holds the IKNP labels on entry"""
     _check(lib().gc_cot_multi_receive_unpad_dev(ctx.h, _dp(d_seeds), _dp(d_flags), _dp(d_sent), _dp(d_result), S, per),
            "gc_cot_multi_receive_unpad_dev")
+
+
+# ---- KOS check for several sessions per call (gc_kos_multi_*) ----
+
+
+def kos_multi_receiver_tags(ctx, seed2, result, b, choice_vec, bcv, S, per):
+    """gc_kos_multi_receiver_tags: seed2 LABEL [S]; result LABEL [S * per], b u8 [S * per]; choice_vec LABEL [S * 256], bcv u8
+    [S * 256] -> tags LABEL [S, 3] (x, t0, t1 of every session)"""
+    sd = np.ascontiguousarray(seed2, dtype=LABEL).reshape(-1)
+    r = np.ascontiguousarray(result, dtype=LABEL).reshape(-1)
+    bb = np.ascontiguousarray(b, dtype=np.uint8).reshape(-1)
+    cv = np.ascontiguousarray(choice_vec, dtype=LABEL).reshape(-1)
+    bc = np.ascontiguousarray(bcv, dtype=np.uint8).reshape(-1)
+    S, per, n = _multi(S, per, r, bb)
+    assert len(sd) == S and len(cv) == 256 * S and len(bc) == 256 * S
+    tags = np.zeros((max(S, 1), 3), LABEL)
+    _check(lib().gc_kos_multi_receiver_tags(ctx.h, _p(sd) if S else None, _p(r) if n else None, _p(bb) if n else None,
+                                            _p(cv) if S else None, _p(bc) if S else None, S, per, _p(tags)),
+           "gc_kos_multi_receiver_tags")
+    return tags[:S]
+
+
+def kos_multi_receiver_tags_dev(ctx, d_seed2, d_result, d_choice_packed, d_choice_vec, d_bcv_packed, S, per, d_tags_out):
+    """device pointers for every array; asynchronous on the ctx stream.  d_choice_packed / d_bcv_packed: the packed choice
+    buffers of the gc_iknp_multi_receive_dev calls at `per` and at 256"""
+    _check(lib().gc_kos_multi_receiver_tags_dev(ctx.h, _dp(d_seed2), _dp(d_result), _dp(d_choice_packed), _dp(d_choice_vec),
+                                                _dp(d_bcv_packed), S, per, _dp(d_tags_out)), "gc_kos_multi_receiver_tags_dev")
+
+
+def kos_multi_sender_check(ctx, seed2, result, choice_vec, delta, tags, S, per):
+    """gc_kos_multi_sender_check: seed2, delta LABEL [S]; result LABEL [S * per]; choice_vec LABEL [S * 256]; tags LABEL [S, 3]
+    -> (ok u8 [S], lowest failing session or None)"""
+    sd = np.ascontiguousarray(seed2, dtype=LABEL).reshape(-1)
+    r = np.ascontiguousarray(result, dtype=LABEL).reshape(-1)
+    cv = np.ascontiguousarray(choice_vec, dtype=LABEL).reshape(-1)
+    dl = np.ascontiguousarray(delta, dtype=LABEL).reshape(-1)
+    tg = np.ascontiguousarray(tags, dtype=LABEL).reshape(-1)
+    S, per, n = _multi(S, per, r)
+    assert len(sd) == S and len(dl) == S and len(cv) == 256 * S and len(tg) == 3 * S
+    ok = np.zeros(max(S, 1), np.uint8)
+    bad = C.c_size_t(0)
+    _check(lib().gc_kos_multi_sender_check(ctx.h, _p(sd) if S else None, _p(r) if n else None, _p(cv) if S else None,
+                                           _p(dl) if S else None, _p(tg) if S else None, S, per, _p(ok), C.byref(bad)),
+           "gc_kos_multi_sender_check")
+    return ok[:S], (None if not S or bad.value == C.c_size_t(-1).value else bad.value)
+
+
+def kos_multi_sender_check_dev(ctx, d_seed2, d_result, d_choice_vec, d_delta, d_tags, S, per, d_ok, d_status):
+    """device pointers; asynchronous on the ctx stream.  d_ok: [S] bytes; d_status: two uint64 {failed sessions, lowest
+    failing session (all ones: none)}"""
+    _check(lib().gc_kos_multi_sender_check_dev(ctx.h, _dp(d_seed2), _dp(d_result), _dp(d_choice_vec), _dp(d_delta), _dp(d_tags),
+                                               S, per, _dp(d_ok), _dp(d_status)), "gc_kos_multi_sender_check_dev")
