@@ -6,6 +6,8 @@
 //
 // Every session keeps its own ot.IO and is framed on it exactly as iknp.go:499 / :203 frame one session, so each of the S
 // peers may be an unmodified Go party.  Arrays are session-major: OT j of session s is element s*per + j.
+// ReceiveBits / SendBits are bit-COT (iknp.go:554-620, :259-310) for all S sessions in one device call each; a GMW party
+// holds its P - 1 peer sessions in one handle per role (go/gmw/triples_hip.go).
 // receiveMalicious / sendMalicious add the malicious branch of Receive / Send (iknp.go:373-465, :138-194) for all S
 // sessions: a second extension at 256 and the KOS tags / check of every session in one device call (gc_kos_multi_*).
 package ot
@@ -179,6 +181,108 @@ func (m *hipIKNPMulti) receiveDev(dChoicePacked unsafe.Pointer, per int, dU, dLa
 
 func (m *hipIKNPMulti) sendDev(dU unsafe.Pointer, per int, dLabels unsafe.Pointer) error {
 	if st := C.gc_iknp_multi_send_dev(m.h, dU, C.size_t(per), dLabels); st != C.GC_OK {
+		return multiErr(st)
+	}
+	return nil
+}
+
+// IKNPMulti is the handle as other packages of the shim see it (go/gmw holds one per role over a party's peers).
+type IKNPMulti = hipIKNPMulti
+
+// Sessions reports S.
+func (m *hipIKNPMulti) Sessions() int { return m.s }
+
+// Handle is the gc_iknp_multi pointer for calls from another cgo package (C types are per package).
+func (m *hipIKNPMulti) Handle() unsafe.Pointer { return unsafe.Pointer(m.h) }
+
+// UBytes is the length of one session's u-matrix at per OTs.
+func UBytes(per int) int { return int(C.gc_iknp_u_bytes(C.size_t(per))) }
+
+// ReceiveBits runs (*IKNPReceiver).ReceiveBits (iknp.go:554-620) for every session in one device call.  choices holds the
+// words of session s from word s*stride on; stride 0 is one vector of (per+63)/64 words for every session.  result holds
+// S * ((per+63)/64) words.  The u-matrices come back session after session, UBytes(per) bytes each, for the caller to
+// frame on each session's IO with SendU: the order of the messages on a connection is the caller's.
+func (m *hipIKNPMulti) ReceiveBits(choices []uint64, stride, per int, result []uint64) ([]byte, error) {
+	words := (per + 63) / 64
+	if len(result) < m.s*words {
+		return nil, fmt.Errorf("result buffer len=%v too short for n=%v", len(result), per)
+	}
+	need := words
+	if stride != 0 {
+		need = (m.s-1)*stride + words
+	}
+	if len(choices) < need {
+		return nil, fmt.Errorf("choices buffer len=%v too short for n=%v", len(choices), per)
+	}
+	if per == 0 {
+		return nil, nil
+	}
+	u := make([]byte, m.s*UBytes(per))
+	st := C.gc_iknp_multi_receive_bits(m.h, (*C.uint64_t)(unsafe.Pointer(&choices[0])), C.size_t(stride), C.size_t(per),
+		(*C.uint8_t)(unsafe.Pointer(&u[0])), (*C.uint64_t)(unsafe.Pointer(&result[0])))
+	if st != C.GC_OK {
+		return nil, multiErr(st)
+	}
+	return u, nil
+}
+
+// SendBits runs (*IKNPSender).SendBits (iknp.go:259-310) for every session in one device call: u holds the u-matrices the
+// sessions' peers sent (ReceiveU), session after session.
+func (m *hipIKNPMulti) SendBits(u []byte, per int, result []uint64) error {
+	if len(result) < m.s*((per+63)/64) {
+		return fmt.Errorf("result buffer len=%v too short for n=%v", len(result), per)
+	}
+	if per == 0 {
+		return nil
+	}
+	st := C.gc_iknp_multi_send_bits(m.h, (*C.uint8_t)(unsafe.Pointer(&u[0])), C.size_t(len(u)), C.size_t(per),
+		(*C.uint64_t)(unsafe.Pointer(&result[0])))
+	if st != C.GC_OK {
+		return multiErr(st)
+	}
+	return nil
+}
+
+// SendU frames one session's u-matrix as ReceiveBits does (iknp.go:597, :615): a message per chunk, then Flush.
+func SendU(io IO, u []byte) error {
+	for ofs := 0; ofs < len(u); ofs += chunkSize {
+		end := ofs + chunkSize
+		if end > len(u) {
+			end = len(u)
+		}
+		if err := io.SendData(u[ofs:end]); err != nil {
+			return err
+		}
+	}
+	return io.Flush()
+}
+
+// ReceiveU reads the chunk messages of one session's u-matrix at per OTs into dst (UBytes(per) bytes) as SendBits reads
+// them (iknp.go:266-272).
+func ReceiveU(io IO, dst []byte) error {
+	for at := 0; at < len(dst); {
+		chunk, err := io.ReceiveData()
+		if err != nil {
+			return err
+		}
+		if len(chunk)%K != 0 || at+len(chunk) > len(dst) {
+			return fmt.Errorf("invalid chunk size: %v", len(chunk))
+		}
+		at += copy(dst[at:], chunk)
+	}
+	return nil
+}
+
+// device-resident forms of bit-COT: one kernel each, nothing allocated, asynchronous on the ctx stream
+func (m *hipIKNPMulti) ReceiveBitsDev(dChoices unsafe.Pointer, stride, per int, dU, dResult unsafe.Pointer) error {
+	if st := C.gc_iknp_multi_receive_bits_dev(m.h, dChoices, C.size_t(stride), C.size_t(per), dU, dResult); st != C.GC_OK {
+		return multiErr(st)
+	}
+	return nil
+}
+
+func (m *hipIKNPMulti) SendBitsDev(dU unsafe.Pointer, per int, dResult unsafe.Pointer) error {
+	if st := C.gc_iknp_multi_send_bits_dev(m.h, dU, C.size_t(per), dResult); st != C.GC_OK {
 		return multiErr(st)
 	}
 	return nil

@@ -854,8 +854,8 @@ int gc_co_multi_base_decrypt_dev(gc_co_multi_base *, const void *d_scalars, cons
  * gc_cot_receive_unpad on that session alone.  Conventions are those of gc_co_multi_*: session-major (OT j of session s is
  * element s * per + j of every per-OT array), the session constants are arrays, a _dev form takes device pointers for EVERY
  * array (16-byte aligned) and is asynchronous on the ctx stream with one kernel per call, a host form takes host pointers
- * and is synchronous and staged.  Sessions of unequal length, bit-COT and ROT are not offered.  The KOS check of the
- * malicious variant over these arrays is gc_kos_multi_* below.
+ * and is synchronous and staged.  Sessions of unequal length and ROT are not offered.  The KOS check of the
+ * malicious variant over these arrays is gc_kos_multi_* below, bit-COT on the same handle gc_iknp_multi_*_bits* behind it.
  *   The handle holds copies of the base labels in device memory (sender: delta [S] and k0 [S][128], 2 KiB + 16 bytes per
  *   session; receiver: base [S][128] gc_wire, 4 KiB per session) and no round keys: the kernel expands a column's key in the
  *   lane.  It holds ONE stream position: sessions of equal length advance in lock step, every call advances it by what
@@ -929,6 +929,46 @@ int gc_kos_multi_sender_check(gc_ctx *, const gc_label *seed2, const gc_label *r
                               size_t *bad_session);
 int gc_kos_multi_sender_check_dev(gc_ctx *, const void *d_seed2, const void *d_result, const void *d_choice_vec,
                                   const void *d_delta, const void *d_tags, size_t S, size_t per, void *d_ok, void *d_status);
+
+/* ------------------------------------------------------------------------------------------
+ * Bit-COT for several sessions per call, and a GMW triple batch over all peers (ot/iknp.go:259-310, ot/iknp.go:554-620,
+ * gmw/triples.go:287-466; additive)
+ * ReceiveBits / SendBits on the S sessions of a gc_iknp_multi handle, one kernel per call.  Byte for byte, session s is
+ * gc_iknp_receive_bits / gc_iknp_send_bits on that session alone from the same stream position; the handle's position
+ * advances as it does for the label calls at `per`, and bit calls and label calls on one handle may be mixed.  With
+ * W = ceil(per / 64):
+ *   result  u64 [S][W]: bit i of session s is bit i % 64 of word s * W + i / 64.  Every one of the S * W words is written,
+ *           with zero in the bits at and behind `per`.
+ *   u       as for gc_iknp_multi_receive_dev / _send_dev: S * gc_iknp_u_bytes(per) bytes.  The sender reads column 0 of a
+ *           chunk only (its first ceil(rows / 8) bytes), and only for sessions whose delta has bit 0 set; the host form
+ *           uploads nothing else.
+ *   choices u64 words; session s reads W words from word s * choice_stride.  choice_stride = 0: ONE vector of W words for
+ *           every session (a party's b in a triple batch).  Otherwise choice_stride >= W.  No byte outside those words is
+ *           read, and there is no padding contract.  As in gc_iknp_receive_bits the choice words enter u whole or not at
+ *           all: a chunk of r rows folds in floor(ceil(r / 8) / 8) words, so the choice bits of a trailing partial word do
+ *           not reach u (iknp.go:577-592).
+ *   Errors: per = 0 returns GC_OK and does nothing.  GC_E_ARG with the position unchanged: the wrong role, a NULL handle,
+ *   NULL arrays with per > 0, a choice_stride in (0, W), a u_len other than S * gc_iknp_u_bytes(per), a size that does not
+ *   fit size_t, a call between gc_ctx_capture_begin and _end.
+ *   The _dev forms take device pointers (d_u_*: 16-byte aligned, d_choices / d_result: 8), allocate nothing, wait for
+ *   nothing, use no workspace and run one kernel on the ctx stream.  The host forms are synchronous and staged.
+ *   GC_IKNP_GENERIC=1 has the meaning it has for gc_iknp_*.
+ * gc_gmw_triples_multi_*: the local words of tripleBatch for the S peer sessions at once, one kernel each, asynchronous on
+ * the ctx stream (sender_u: the stream of the handle's ctx); all arrays are device u64, [S][words] unless noted.
+ *   sender_u       u_s = a ^ (Delta_s.Bit(0) ? ~0 : 0); a is [words]; Delta is read from the sender handle's device copy
+ *   sender_fold    c ^= XOR over s of (s_s ^ (u_s & v_s)); c is [words]
+ *   receiver_fold  c ^= XOR over s of r_s; c is [words]
+ *   words = 0 returns GC_OK; S = 0, a NULL ctx / handle / array, a receiver handle, S * words * 8 past size_t: GC_E_ARG. */
+int gc_iknp_multi_receive_bits_dev(gc_iknp_multi *, const void *d_choices, size_t choice_stride, size_t per,
+                                   void *d_u_out, void *d_result);
+int gc_iknp_multi_send_bits_dev(gc_iknp_multi *, const void *d_u_in, size_t per, void *d_result);
+int gc_iknp_multi_receive_bits(gc_iknp_multi *, const uint64_t *choices, size_t choice_stride, size_t per,
+                               uint8_t *u_out, uint64_t *result);
+int gc_iknp_multi_send_bits(gc_iknp_multi *, const uint8_t *u_in, size_t u_len, size_t per, uint64_t *result);
+int gc_gmw_triples_multi_sender_u_dev(gc_iknp_multi *sender, const void *d_a, void *d_u, size_t words);
+int gc_gmw_triples_multi_sender_fold_dev(gc_ctx *, const void *d_s, const void *d_u, const void *d_v, void *d_c,
+                                         size_t S, size_t words);
+int gc_gmw_triples_multi_receiver_fold_dev(gc_ctx *, const void *d_r, void *d_c, size_t S, size_t words);
 
 #ifdef __cplusplus
 }

@@ -1,10 +1,13 @@
 // iknp_multi_engine.cpp — C ABI of the multi-session IKNP extension and COT pad loops (gc_iknp_multi_*, gc_cot_multi_*):
-// S sessions of `per` OTs each, session-major, one kernel per call (iknp_multi_kernels.hip; layouts: iknp_multi.h).
+// S sessions of `per` OTs each, session-major, one kernel per call (iknp_multi_kernels.hip; layouts: iknp_multi.h), of
+// bit-COT on the same handle (gc_iknp_multi_*_bits*) and of the triple folds over S peers (gc_gmw_triples_multi_*;
+// iknp_multi_bits_kernels.hip, iknp_multi_bits.h).
+#include <algorithm>
 #include <cstring>
 #include <new>
 
 #include "engine.h"
-#include "iknp_multi.h"
+#include "iknp_multi_bits.h"
 
 using namespace gc;
 
@@ -299,6 +302,152 @@ int gc_cot_multi_receive_unpad(gc_ctx *ctx, const gc_label *seed, const uint8_t 
     return GC_OK;
 } catch (...) {
     return gc::on_exception();
+}
+
+// ---- bit-COT (ReceiveBits / SendBits, iknp.go:259-310, 554-620) per session: column 0 of the same matrix ------------------
+
+namespace {
+
+// the checks of a bits call on top of multi_call_args; *words = S * ceil(per / 64)
+int bits_call_args(const gc_iknp_multi *h, bool receiver, size_t per, MultiSizes *z, size_t *words) {
+    int rc = multi_call_args(h, receiver, per, z);
+    if (rc != GC_OK) return rc;
+    *words = h->S * (size_t)iknp_bits_words(per);  // below S * per + S, which multi_sizes has bounded
+    return GC_OK;
+}
+
+// stride 0 or >= W, and the span of words the call reads fits size_t in bytes
+bool bits_choice_span(size_t S, size_t per, size_t stride, size_t *span) {
+    if (!iknp_bits_stride_ok(stride, per)) return false;
+    if (stride && S - 1 > (SIZE_MAX / 16) / stride) return false;
+    *span = (size_t)iknp_bits_choice_span(S, per, stride);
+    return true;
+}
+
+}  // namespace
+
+int gc_iknp_multi_receive_bits_dev(gc_iknp_multi *h, const void *d_choices, size_t choice_stride, size_t per, void *d_u_out,
+                                   void *d_result) {
+    MultiSizes z;
+    size_t words, span;
+    int rc = bits_call_args(h, true, per, &z, &words);
+    if (rc != GC_OK) return rc;
+    if (per == 0) return GC_OK;
+    if (!d_choices || !d_u_out || !d_result || !bits_choice_span(h->S, per, choice_stride, &span)) return GC_E_ARG;
+    gc_ctx *ctx = h->ctx;
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_HIP(launch_iknp_multi_recv_bits(h->d_keys, h->pos, h->S, per, (const uint64_t *)d_choices, choice_stride,
+                                       (uint8_t *)d_u_out, (uint64_t *)d_result, ctx->d_te0, ctx->stream));
+    h->pos += iknp_multi_advance(per);
+    return GC_OK;
+}
+
+int gc_iknp_multi_send_bits_dev(gc_iknp_multi *h, const void *d_u_in, size_t per, void *d_result) {
+    MultiSizes z;
+    size_t words;
+    int rc = bits_call_args(h, false, per, &z, &words);
+    if (rc != GC_OK) return rc;
+    if (per == 0) return GC_OK;
+    if (!d_u_in || !d_result) return GC_E_ARG;
+    gc_ctx *ctx = h->ctx;
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_HIP(launch_iknp_multi_send_bits(h->d_keys, h->d_delta, h->pos, h->S, per, (const uint8_t *)d_u_in,
+                                       (size_t)iknp_multi_u_bytes(per), 8192, (uint64_t *)d_result, ctx->d_te0, ctx->stream));
+    h->pos += iknp_multi_advance(per);
+    return GC_OK;
+}
+
+int gc_iknp_multi_receive_bits(gc_iknp_multi *h, const uint64_t *choices, size_t choice_stride, size_t per, uint8_t *u_out,
+                               uint64_t *result) try {
+    MultiSizes z;
+    size_t words, span;
+    int rc = bits_call_args(h, true, per, &z, &words);
+    if (rc != GC_OK) return rc;
+    if (per == 0) return GC_OK;
+    if (!choices || !u_out || !result || !bits_choice_span(h->S, per, choice_stride, &span)) return GC_E_ARG;
+    gc_ctx *ctx = h->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    DevBuf d_ch, d_u, d_res;
+    GC_HIP(d_ch.alloc(span * 8));
+    GC_HIP(d_u.alloc(z.u));
+    GC_HIP(d_res.alloc(words * 8));
+    hipStream_t st = ctx->stream;
+    GC_HIP(hipMemcpyAsync(d_ch.p, choices, span * 8, hipMemcpyHostToDevice, st));
+    GC_HIP(launch_iknp_multi_recv_bits(h->d_keys, h->pos, h->S, per, (const uint64_t *)d_ch.p, choice_stride,
+                                       (uint8_t *)d_u.p, (uint64_t *)d_res.p, ctx->d_te0, st));
+    GC_HIP(hipMemcpyAsync(u_out, d_u.p, z.u, hipMemcpyDeviceToHost, st));
+    GC_HIP(hipMemcpyAsync(result, d_res.p, words * 8, hipMemcpyDeviceToHost, st));
+    GC_HIP(hipStreamSynchronize(st));
+    h->pos += iknp_multi_advance(per);
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_iknp_multi_send_bits(gc_iknp_multi *h, const uint8_t *u_in, size_t u_len, size_t per, uint64_t *result) try {
+    MultiSizes z;
+    size_t words;
+    int rc = bits_call_args(h, false, per, &z, &words);
+    if (rc != GC_OK) return rc;
+    if (per == 0) return GC_OK;
+    if (!u_in || !result || u_len != z.u) return GC_E_ARG;  // "invalid chunk size" (iknp.go:270-272)
+    // column 0 is all the kernel reads: a session's ceil(per / 8) bytes in a row, 1 / 128 of the message
+    const size_t row = (size_t)iknp_bits_col0_row(per), ub = (size_t)iknp_multi_u_bytes(per), bytes = (per + 7) / 8;
+    std::vector<uint8_t> col0(h->S * row, 0);
+    for (size_t s = 0; s < h->S; s++)
+        for (size_t at = 0; at < bytes; at += 64)
+            memcpy(&col0[s * row + at], u_in + s * ub + (at / 64) * 8192, std::min<size_t>(64, bytes - at));
+    gc_ctx *ctx = h->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    DevBuf d_u, d_res;
+    GC_HIP(d_u.alloc(col0.size()));
+    GC_HIP(d_res.alloc(words * 8));
+    hipStream_t st = ctx->stream;
+    GC_HIP(hipMemcpyAsync(d_u.p, col0.data(), col0.size(), hipMemcpyHostToDevice, st));
+    GC_HIP(launch_iknp_multi_send_bits(h->d_keys, h->d_delta, h->pos, h->S, per, (const uint8_t *)d_u.p, row, 64,
+                                       (uint64_t *)d_res.p, ctx->d_te0, st));
+    GC_HIP(hipMemcpyAsync(result, d_res.p, words * 8, hipMemcpyDeviceToHost, st));
+    GC_HIP(hipStreamSynchronize(st));
+    h->pos += iknp_multi_advance(per);
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+// ---- tripleBatch's local words for S peers in one launch each (triples.go:340-349, 362-364, 387-389) ----------------------
+
+static bool fold_sizes(size_t S, size_t words) { return S != 0 && (!words || S <= (SIZE_MAX / 8) / words); }
+
+int gc_gmw_triples_multi_sender_u_dev(gc_iknp_multi *sender, const void *d_a, void *d_u, size_t words) {
+    if (!sender || sender->receiver || !fold_sizes(sender->S, words)) return GC_E_ARG;
+    if (!words) return GC_OK;
+    if (!d_a || !d_u) return GC_E_ARG;
+    gc_ctx *ctx = sender->ctx;
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_HIP(launch_gmw_multi_sender_u(sender->d_delta, (const uint64_t *)d_a, (uint64_t *)d_u, sender->S, words, ctx->stream));
+    return GC_OK;
+}
+
+int gc_gmw_triples_multi_sender_fold_dev(gc_ctx *ctx, const void *d_s, const void *d_u, const void *d_v, void *d_c, size_t S,
+                                         size_t words) {
+    if (!ctx || !fold_sizes(S, words)) return GC_E_ARG;
+    if (!words) return GC_OK;
+    if (!d_s || !d_u || !d_v || !d_c) return GC_E_ARG;
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_HIP(launch_gmw_multi_sender_fold((const uint64_t *)d_s, (const uint64_t *)d_u, (const uint64_t *)d_v, (uint64_t *)d_c, S,
+                                        words, ctx->stream));
+    return GC_OK;
+}
+
+int gc_gmw_triples_multi_receiver_fold_dev(gc_ctx *ctx, const void *d_r, void *d_c, size_t S, size_t words) {
+    if (!ctx || !fold_sizes(S, words)) return GC_E_ARG;
+    if (!words) return GC_OK;
+    if (!d_r || !d_c) return GC_E_ARG;
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_HIP(launch_gmw_multi_receiver_fold((const uint64_t *)d_r, (uint64_t *)d_c, S, words, ctx->stream));
+    return GC_OK;
 }
 
 }  // extern "C"

@@ -339,6 +339,27 @@ hipError_t launch_cot_multi_send(const uint4 *seeds, const uint4 *deltas, const 
 hipError_t launch_cot_multi_recv(const uint4 *seeds, const uint8_t *flags, const uint4 *sent, uint4 *result, size_t S,
                                  size_t per, const uint32_t *te0, hipStream_t s);
 
+// ---- bit-COT for S sessions per launch and the triple folds over S peers (iknp_multi_bits_kernels.hip; iknp_multi_bits.h) ----
+// k_iknp_multi_recv_bits has the launch shape of k_iknp_multi's receiver (kIknpThreads, kIknpMultiGrid, kIknpRecvChunks).
+constexpr int kIknpBitsSendThreads = 256;  // k_iknp_multi_send_bits: one lane = 16 result bytes of one session per trip
+constexpr int kIknpBitsSendGrid = 256;     // ... at most this many workgroups (lane += gridDim.x * kIknpBitsSendThreads)
+constexpr int kGmwMultiFoldThreads = 256;  // k_gmw_multi_*: one lane = one word per trip
+constexpr int kGmwMultiFoldGrid = 2048;    // ... at most this many workgroups
+// choices: u64 words, session s from word s * stride (0: one vector for all); result [S][ceil(per / 64)] u64, every word
+// written; u_out as launch_iknp_multi.  The sender reads u_in at s * u_session + chunk * u_chunk + byte (column 0 only) and
+// only for sessions whose delta has bit 0 set; a full 16-byte group is read as one uint4, so u_in, u_session and u_chunk are
+// multiples of 16.
+hipError_t launch_iknp_multi_recv_bits(const uint4 *keys, uint64_t pos0, size_t S, size_t per, const uint64_t *choices,
+                                       size_t stride, uint8_t *u_out, uint64_t *result, const uint32_t *te0, hipStream_t s);
+hipError_t launch_iknp_multi_send_bits(const uint4 *keys, const uint4 *delta, uint64_t pos0, size_t S, size_t per,
+                                       const uint8_t *u_in, size_t u_session, size_t u_chunk, uint64_t *result,
+                                       const uint32_t *te0, hipStream_t s);
+// u [S][words] = a ^ (delta_s.Bit(0) ? ~0 : 0);  c ^= XOR_s (sv_s ^ (u_s & v_s));  c ^= XOR_s r_s
+hipError_t launch_gmw_multi_sender_u(const uint4 *delta, const uint64_t *a, uint64_t *u, size_t S, size_t words, hipStream_t s);
+hipError_t launch_gmw_multi_sender_fold(const uint64_t *sv, const uint64_t *u, const uint64_t *v, uint64_t *c, size_t S,
+                                        size_t words, hipStream_t s);
+hipError_t launch_gmw_multi_receiver_fold(const uint64_t *r, uint64_t *c, size_t S, size_t words, hipStream_t s);
+
 // ---- the KOS check for S sessions per launch (kos_multi_kernels.hip; teams, labels and choice bits: kos_multi.h) ----
 constexpr int kKosMultiThreads = 1024;  // k_kos_multi: lanes per workgroup
 constexpr int kKosMultiGrid = 256;      // ... at most this many workgroups; a team takes a session per trip

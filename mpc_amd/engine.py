@@ -271,6 +271,13 @@ def lib():
         "gc_iknp_multi_send": (i32, [vp, vp, sz, sz, vp]),
         "gc_iknp_multi_receive_dev": (i32, [vp, vp, sz, vp, vp]),
         "gc_iknp_multi_send_dev": (i32, [vp, vp, sz, vp]),
+        "gc_iknp_multi_receive_bits_dev": (i32, [vp, vp, sz, sz, vp, vp]),
+        "gc_iknp_multi_send_bits_dev": (i32, [vp, vp, sz, vp]),
+        "gc_iknp_multi_receive_bits": (i32, [vp, vp, sz, sz, vp, vp]),
+        "gc_iknp_multi_send_bits": (i32, [vp, vp, sz, sz, vp]),
+        "gc_gmw_triples_multi_sender_u_dev": (i32, [vp, vp, vp, sz]),
+        "gc_gmw_triples_multi_sender_fold_dev": (i32, [vp, vp, vp, vp, vp, sz, sz]),
+        "gc_gmw_triples_multi_receiver_fold_dev": (i32, [vp, vp, vp, sz, sz]),
         "gc_cot_multi_send_pads": (i32, [vp, vp, vp, vp, vp, sz, sz, vp]),
         "gc_cot_multi_send_pads_dev": (i32, [vp, vp, vp, vp, vp, sz, sz, vp]),
         "gc_cot_multi_receive_unpad": (i32, [vp, vp, vp, vp, vp, sz, sz]),
@@ -1832,6 +1839,29 @@ class IKNPMultiReceiver(_IKNPMulti):
         _check(lib().gc_iknp_multi_receive_dev(self.h, _dp(d_choice_packed), per, _dp(d_u_out), _dp(d_labels_out)),
                "gc_iknp_multi_receive_dev")
 
+    def receive_bits(self, choices, per, stride=None):
+        """bit-COT.  choices: u64 words, [S, W] (W = ceil(per / 64)) or, shared by all sessions, [W]; with `stride` given the
+        flat words as they are, session s from word s * stride -> (u bytes of all sessions, result u64 [S, W])"""
+        ch = np.ascontiguousarray(choices, dtype=np.uint64)
+        per = int(per)
+        W = (per + 63) // 64
+        if stride is None:
+            stride = 0 if ch.ndim == 1 else W
+            assert ch.size == (W if ch.ndim == 1 else self.S * W)
+        ch = ch.reshape(-1)
+        ub = self.u_bytes(per)
+        u = np.zeros(max(ub, 1), np.uint8)
+        res = np.zeros(max(self.S * W, 1), np.uint64)
+        _check(lib().gc_iknp_multi_receive_bits(self.h, _p(ch) if ch.size else None, stride, per, _p(u), _p(res)),
+               "gc_iknp_multi_receive_bits")
+        return u[:ub].tobytes(), res[:self.S * W].reshape(self.S, W)
+
+    def receive_bits_dev(self, d_choices, stride, per, d_u_out, d_result):
+        """device pointers; asynchronous on the ctx stream, one kernel.  d_choices: u64 words, session s from word
+        s * stride (0: one vector for every session); d_result: u64 [S, ceil(per / 64)]"""
+        _check(lib().gc_iknp_multi_receive_bits_dev(self.h, _dp(d_choices), stride, per, _dp(d_u_out), _dp(d_result)),
+               "gc_iknp_multi_receive_bits_dev")
+
 
 class IKNPMultiSender(_IKNPMulti):
     """gc_iknp_multi, sender: delta LABEL [S] and k0 LABEL [S, 128] (host), or device buffers of those with S given"""
@@ -1862,6 +1892,35 @@ class IKNPMultiSender(_IKNPMulti):
     def send_dev(self, d_u_in, per, d_labels_out):
         """device pointers; asynchronous on the ctx stream"""
         _check(lib().gc_iknp_multi_send_dev(self.h, _dp(d_u_in), per, _dp(d_labels_out)), "gc_iknp_multi_send_dev")
+
+    def send_bits(self, u, per):
+        """bit-COT.  u: the receiver's u bytes of all sessions -> result u64 [S, ceil(per / 64)]"""
+        ub = np.frombuffer(bytes(u), np.uint8) if len(u) else np.zeros(1, np.uint8)
+        W = (int(per) + 63) // 64
+        res = np.zeros(max(self.S * W, 1), np.uint64)
+        _check(lib().gc_iknp_multi_send_bits(self.h, _p(ub), len(u), per, _p(res)), "gc_iknp_multi_send_bits")
+        return res[:self.S * W].reshape(self.S, W)
+
+    def send_bits_dev(self, d_u_in, per, d_result):
+        """device pointers; asynchronous on the ctx stream, one kernel that reads column 0 of d_u_in only"""
+        _check(lib().gc_iknp_multi_send_bits_dev(self.h, _dp(d_u_in), per, _dp(d_result)), "gc_iknp_multi_send_bits_dev")
+
+
+def gmw_triples_multi_sender_u_dev(sender, d_a, d_u, words):
+    """d_u [S, words] = d_a [words] ^ (Delta_s.Bit(0) ? ~0 : 0) for the S sessions of an IKNPMultiSender (triples.go:340-349)"""
+    _check(lib().gc_gmw_triples_multi_sender_u_dev(sender.h, _dp(d_a), _dp(d_u), words), "gc_gmw_triples_multi_sender_u_dev")
+
+
+def gmw_triples_multi_sender_fold_dev(ctx, d_s, d_u, d_v, d_c, S, words):
+    """d_c [words] ^= XOR over s of (d_s[s] ^ (d_u[s] & d_v[s])), all [S, words] (triples.go:362-364)"""
+    _check(lib().gc_gmw_triples_multi_sender_fold_dev(ctx.h, _dp(d_s), _dp(d_u), _dp(d_v), _dp(d_c), S, words),
+           "gc_gmw_triples_multi_sender_fold_dev")
+
+
+def gmw_triples_multi_receiver_fold_dev(ctx, d_r, d_c, S, words):
+    """d_c [words] ^= XOR over s of d_r[s], [S, words] (triples.go:387-389)"""
+    _check(lib().gc_gmw_triples_multi_receiver_fold_dev(ctx.h, _dp(d_r), _dp(d_c), S, words),
+           "gc_gmw_triples_multi_receiver_fold_dev")
 
 
 def cot_multi_send_pads(ctx, seeds, deltas, data, wires, S, per):
