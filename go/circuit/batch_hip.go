@@ -115,6 +115,7 @@ type BatchPipeline struct {
 	mis    *DevBuf // u32: output labels that matched neither L0 nor L1
 	graph  *C.gc_graph
 	key    []byte
+	keys   *DevBuf // [batch][keylen] u8: one AES key per instance (GarbleBatchKeys / EvalBatchKeys), allocated at first use
 }
 
 // NewBatchPipeline loads the circuit on `device` and allocates the state of `batch` instances.
@@ -225,6 +226,58 @@ func (p *BatchPipeline) Step(key []byte) error {
 	return nil
 }
 
+// KeysSupported reports whether this pipeline can run GarbleBatchKeys / EvalBatchKeys (gc_batch_keyed_supported: the
+// flattened kernels with the wires in LDS, and the tile's key table fits behind them).
+func (p *BatchPipeline) KeysSupported() bool {
+	return C.gc_batch_keyed_supported(p.gb) != 0 && C.gc_batch_keyed_supported(p.ev) != 0
+}
+
+func (p *BatchPipeline) uploadKeys(keys []byte, keylen int) error {
+	if keylen != 16 && keylen != 24 && keylen != 32 {
+		return aes.KeySizeError(keylen) // same error as Garble / Eval (garble.go:260, eval.go:20)
+	}
+	if len(keys) != p.batch*keylen {
+		return fmt.Errorf("BatchPipeline: %d key bytes for batch %d of %d-byte keys", len(keys), p.batch, keylen)
+	}
+	if p.keys == nil {
+		var err error
+		if p.keys, err = NewDevBuf(unsafe.Pointer(p.ctx), p.batch*32); err != nil {
+			return err
+		}
+	}
+	return p.keys.Upload(keys)
+}
+
+// GarbleBatchKeys garbles all instances, instance i under keys[i*keylen:(i+1)*keylen]: what `batch` concurrent Garbler
+// sessions hold, each having drawn its own key (garbler.go:47-53) and sent it to its peer (:64).  Enqueues and returns.
+func (p *BatchPipeline) GarbleBatchKeys(keys []byte, keylen int) error {
+	if err := p.uploadKeys(keys, keylen); err != nil {
+		return err
+	}
+	if st := C.gc_batch_garble_keyed(p.gb, p.keys.ptr, C.size_t(keylen), p.rnd.ptr); st != C.GC_OK {
+		return statusError(st)
+	}
+	return nil
+}
+
+// EvalBatchKeys hands the evaluator its input labels, evaluates instance i under keys[i*keylen:(i+1)*keylen] (the key the
+// peer received, evaluator.go) and decodes the outputs (Outputs / OutputLabels read them).  Enqueues and returns.
+func (p *BatchPipeline) EvalBatchKeys(keys []byte, keylen int) error {
+	if err := p.uploadKeys(keys, keylen); err != nil {
+		return err
+	}
+	if st := C.gc_batch_select_inputs(p.ev, p.gb, p.bits.ptr); st != C.GC_OK {
+		return statusError(st)
+	}
+	if st := C.gc_batch_eval_keyed(p.ev, p.keys.ptr, C.size_t(keylen), p.gb); st != C.GC_OK {
+		return statusError(st)
+	}
+	if st := C.gc_batch_decode(p.gb, p.ev, p.out.ptr, p.mis.ptr); st != C.GC_OK {
+		return statusError(st)
+	}
+	return nil
+}
+
 // Outputs waits for the GPU and returns the decoded output bits of the last Step (batch x Outputs.Size(), one byte
 // per output wire) and the number of output labels that were neither L0 nor L1 of their wire (0 unless a table or
 // label was corrupted).
@@ -289,7 +342,7 @@ func (p *BatchPipeline) Close() {
 		C.gc_graph_free(p.graph)
 		p.graph = nil
 	}
-	for _, d := range []*DevBuf{p.rnd, p.bits, p.out, p.mis} {
+	for _, d := range []*DevBuf{p.rnd, p.bits, p.out, p.mis, p.keys} {
 		d.Free()
 	}
 	if p.gb != nil {

@@ -445,6 +445,20 @@ int gc_batch_set_inputs(gc_batch *evaluator, const void *d_labels);
 /* evaluate with the tables of `tables` (device layout [slab_rows][bstride]); may be the
  * garbler's batch itself */
 int gc_batch_eval(gc_batch *evaluator, const uint8_t *key, size_t keylen, const gc_batch *tables);
+/* The same two passes with ONE AES KEY PER INSTANCE: circuit.Garbler draws a fresh key on every call and sends it to the
+ * peer (circuit/garbler.go:47-53, 64), so a batch that gathers S concurrent sessions holds S keys.
+ * d_keys = u8 [batch][keylen], one AES key per instance (garbler.go:47-53); keylen 16, 24 or 32 for all.  Device-resident
+ * like their one-key twins: enqueued on the ctx stream, nothing is waited for; the round keys are expanded ON THE DEVICE
+ * as part of the pass, so a captured graph replays with whatever keys the buffer holds at replay time.  Instance i's
+ * bytes are those of gc_batch_garble / gc_batch_eval with key i.
+ * Scope (gc_batch_keyed_supported: 1 / 0): schedule 1, wires in LDS (gc_batch_wires_in_lds) on the flattened kernels,
+ * and the tile's key table fits into LDS behind the wire slots.  Not built: schedules 0 and 2, the HBM-wire kernels,
+ * the streaming jobs, the host-buffer calls gc_garble / gc_eval.
+ * GC_E_KEYSIZE for any other keylen, GC_E_ARG for a NULL pointer, GC_E_ARG with a gc_last_error() text for a batch
+ * outside the scope. */
+int gc_batch_garble_keyed(gc_batch *, const void *d_keys, size_t keylen, const void *d_rnd);
+int gc_batch_eval_keyed(gc_batch *evaluator, const void *d_keys, size_t keylen, const gc_batch *tables);
+int gc_batch_keyed_supported(const gc_batch *);
 /* BitFromLabel (circuit/helpers.go:18-28) for every output wire: d_bits_out = u8 [batch][noutputs];
  * *d_mismatch (u32, device) counts labels that match neither L0 nor L1 */
 int gc_batch_decode(const gc_batch *garbler, const gc_batch *evaluator, void *d_bits_out, void *d_mismatch);
@@ -497,6 +511,11 @@ uint32_t gc_batch_last_launches(gc_batch *);
  * XOR run, chunk-end barrier, -, -} followed by the same 8 for wave 3, from the most recent
  * instrumented pass. */
 int gc_batch_debug_profile(gc_batch *, int enable, uint64_t *out8);
+/* developer aid (synchronous): the round-key words the keyed passes hash with, as the device expands them from d_keys:
+ * words_out = u32 [batch][4 * (rounds + 1)], big-endian words of the AES key schedule with the last round key XORed with
+ * round key 0; host_words_out (may be NULL) receives the same from the host's schedule.  Any batch. */
+int gc_batch_debug_keyed_schedule(gc_batch *, const void *d_keys, size_t keylen, uint32_t *words_out,
+                                  uint32_t *host_words_out);
 
 /* ------------------------------------------------------------------------------------------
  * IKNP OT extension + MITCCRH (ot/iknp.go, ot/mitccrh.go, ot/cot.go)

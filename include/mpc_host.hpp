@@ -483,6 +483,20 @@ private:
     std::mutex mu_;
 };
 
+// Many Garbler / Evaluator sessions gathered into one device-resident batch (gc_batch_*): every session drew its own key
+// (garbler.go:47-53) and sent it to its peer (:64), so instance i is garbled and evaluated under key i.  d_keys = u8
+// [batch][keylen] and d_rnd are device buffers (gc_dev_alloc); the calls enqueue on the ctx stream and do not wait.
+// BatchKeysSupported: gc_batch_keyed_supported (schedule 1, wires in LDS, the key table fits).
+inline bool BatchKeysSupported(const gc_batch *b) { return gc_batch_keyed_supported(b) != 0; }
+inline void GarbleBatchKeys(gc_batch *b, const void *d_keys, size_t keylen, const void *d_rnd) {
+    if (keylen != 16 && keylen != 24 && keylen != 32) throw Error("crypto/aes: invalid key size " + std::to_string(keylen));
+    check(gc_batch_garble_keyed(b, d_keys, keylen, d_rnd), "gc_batch_garble_keyed");
+}
+inline void EvalBatchKeys(gc_batch *evaluator, const void *d_keys, size_t keylen, const gc_batch *tables) {
+    if (keylen != 16 && keylen != 24 && keylen != 32) throw Error("crypto/aes: invalid key size " + std::to_string(keylen));
+    check(gc_batch_eval_keyed(evaluator, d_keys, keylen, tables), "gc_batch_eval_keyed");
+}
+
 // ParseBristol (parser.go:265-494), same validation messages
 inline Circuit ParseBristol(std::istream &in) {
     auto fail = [](const std::string &m) -> void { throw Error(m); };

@@ -773,6 +773,7 @@ void gc_batch_free(gc_batch *b) {
     drop_graphs(b);
     free_buffers(b);
     if (b->d_rk) (void)hipFree(b->d_rk);
+    if (b->d_keyed_rk) (void)hipFree(b->d_keyed_rk);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
     delete b;
@@ -1108,6 +1109,114 @@ int gc_batch_eval(gc_batch *ev, const uint8_t *key, size_t keylen, const gc_batc
     if (!ctx->capturing) GC_HIP(hipEventRecord(ev->ev1, ctx->stream));
     ev->timed = !ctx->capturing;
     return GC_OK;
+}
+
+// ---- one AES key per instance (fused_flat_keyed_kernels.hip) ----------------------------------------------------
+// Scope: schedule 1 on the flattened kernels with the wires in LDS, and the tile's key table (sized for AES-256, so that the
+// answer does not depend on the key length) fits behind the wire slots.  nullptr, or what keeps the batch out.
+static const char *keyed_out_of_scope(const gc_batch *b) {
+    if (b->schedule != 1 || b->single_phase) return "schedule 1 only";
+    if (!uses_flat(b)) return "the batch does not run the flattened kernels with its wires in LDS";
+    const Plan &p = b->circ->plan.p;
+    if (fused_flat_keyed_bytes(p.n_flat_slots, b->g.ti_log2, p.fl_unit_stride, 14) > kFlatLdsBytes)
+        return "the tile's key table does not fit into LDS behind the wire slots";
+    return nullptr;
+}
+
+int gc_batch_keyed_supported(const gc_batch *b) try {
+    return b && !keyed_out_of_scope(b);
+} catch (...) {
+    (void)gc::on_exception();
+    return 0;
+}
+
+static int keyed_rounds(size_t keylen) { return keylen == 16 ? 10 : keylen == 24 ? 12 : keylen == 32 ? 14 : 0; }
+
+// d_keys u8 [batch][keylen] -> b->d_keyed_rk, on the ctx stream: part of the pass (and of a captured graph), so a replay
+// expands whatever the caller's buffer holds then
+static int expand_keys(gc_batch *b, const void *d_keys, int rounds) {
+    if (!b->d_keyed_rk) GC_HIP(hipMalloc((void **)&b->d_keyed_rk, (size_t)b->g.batch * 60 * sizeof(uint32_t)));
+    GC_HIP(launch_expand_keys((const uint8_t *)d_keys, rounds, b->g.batch, b->circ->ctx->d_te0, b->d_keyed_rk, b->circ->ctx->stream));
+    return GC_OK;
+}
+
+static int run_keyed(gc_batch *b, bool eval, const void *d_keys, size_t keylen, const uint4 *T, const uint4 *rnd, const char *what) {
+    const int rounds = keyed_rounds(keylen);
+    if (!rounds) return GC_E_KEYSIZE;
+    gc_ctx *ctx = b->circ->ctx;
+    GC_HIP(hipSetDevice(ctx->device));
+    if (const char *why = keyed_out_of_scope(b)) {
+        std::snprintf(gc::tls_error, sizeof gc::tls_error, "%s: %s", what, why);
+        return GC_E_ARG;
+    }
+    int rc = expand_keys(b, d_keys, rounds);
+    if (rc != GC_OK) return rc;
+    const Plan &p = b->circ->plan.p;
+    FusedFlatArgs f{};
+    f.prog = b->circ->d_fl_prog;
+    f.units = b->circ->d_fl_units;
+    f.hgslot = b->circ->d_fl_hgslot;
+    f.ogslot = b->circ->d_fl_ogslot;
+    f.in_lds = b->circ->d_fl_in_lds;
+    f.nunits = (uint32_t)p.fl_units.size();
+    f.ninputs = p.info.ninputs;
+    f.nls = p.n_flat_slots;
+    f.ustride = p.fl_unit_stride;
+    f.W = b->d_W;
+    f.R = b->d_R;
+    f.T = const_cast<uint4 *>(T);
+    f.rk = b->d_keyed_rk;
+    f.te0 = ctx->d_te0;
+    f.rounds = rounds;
+    f.rnd = rnd;
+    f.has_or = p.info.n_or != 0;
+    if (!ctx->capturing) GC_HIP(hipEventRecord(b->ev0, ctx->stream));
+    GC_HIP(launch_fused_flat_keyed(eval, f, b->g, ctx->stream));
+    if (!ctx->capturing) GC_HIP(hipEventRecord(b->ev1, ctx->stream));
+    b->timed = !ctx->capturing;
+    b->last_launches = f.nunits ? 1 : 0;
+    b->have_all_wires = false;
+    return GC_OK;
+}
+
+int gc_batch_garble_keyed(gc_batch *b, const void *d_keys, size_t keylen, const void *d_rnd) try {
+    if (!b || !d_keys || !d_rnd) return GC_E_ARG;
+    b->r_known = false;  // (drawn on the device)
+    return run_keyed(b, false, d_keys, keylen, b->d_T, (const uint4 *)d_rnd, "gc_batch_garble_keyed");
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_batch_eval_keyed(gc_batch *ev, const void *d_keys, size_t keylen, const gc_batch *tables) try {
+    if (!ev || !d_keys || !tables || !same_layout(ev, tables)) return GC_E_ARG;
+    return run_keyed(ev, true, d_keys, keylen, tables->d_T, nullptr, "gc_batch_eval_keyed");
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_batch_debug_keyed_schedule(gc_batch *b, const void *d_keys, size_t keylen, uint32_t *words_out, uint32_t *host_words_out) try {
+    if (!b || !d_keys || !words_out) return GC_E_ARG;
+    const int rounds = keyed_rounds(keylen);
+    if (!rounds) return GC_E_KEYSIZE;
+    gc_ctx *ctx = b->circ->ctx;
+    if (ctx->capturing) return GC_E_ARG;
+    GC_HIP(hipSetDevice(ctx->device));
+    int rc = expand_keys(b, d_keys, rounds);
+    if (rc != GC_OK) return rc;
+    const size_t nw = 4 * (size_t)(rounds + 1);
+    GC_HIP(hipMemcpyAsync(words_out, b->d_keyed_rk, b->g.batch * nw * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<uint8_t> keys(host_words_out ? b->g.batch * keylen : 0);
+    if (host_words_out) GC_HIP(hipMemcpyAsync(keys.data(), d_keys, keys.size(), hipMemcpyDeviceToHost, ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));
+    for (uint32_t i = 0; host_words_out && i < b->g.batch; i++) {  // aes_host.h's schedule, folded as the kernels use it
+        AesKey k;
+        aes_expand_key(keys.data() + i * keylen, keylen, &k);
+        for (int c = 0; c < 4; c++) k.w[4 * rounds + c] ^= k.w[c];
+        std::memcpy(host_words_out + i * nw, k.w, nw * sizeof(uint32_t));
+    }
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
 }
 
 int gc_batch_decode(const gc_batch *gb, const gc_batch *ev, void *d_bits_out, void *d_mismatch) {

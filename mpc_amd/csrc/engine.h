@@ -142,6 +142,7 @@ struct gc_batch {
     uint4 *d_T = nullptr;  // garbled tables [slab_rows][bstride]
     uint4 *d_R = nullptr;  // [bstride]
     uint32_t *d_rk = nullptr;
+    uint32_t *d_keyed_rk = nullptr;  // gc_batch_*_keyed: the expanded keys of every instance [batch][60], allocated at first use
     uint64_t *d_prof = nullptr;  // debug cycle breakdown of the fused kernels (gc_batch_debug_profile)
     uint32_t rk_host[60] = {0};
     const gc::StoreXchg *xchg = nullptr;  // gc_pass_dev: (device address) the cooperative pass exchanges labels with the wire store itself

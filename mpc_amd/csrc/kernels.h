@@ -167,6 +167,16 @@ struct FusedFlatArgs {
 size_t fused_flat_bytes(uint32_t nls, uint32_t ti_log2, uint32_t ustride);
 hipError_t launch_fused_flat(bool eval, const FusedFlatArgs &a, const BatchGeom &g, hipStream_t s);
 
+// The same pass with one AES key per instance (fused_flat_keyed_kernels.hip).  launch_expand_keys: d_keys u8 [batch][4 (rounds -
+// 6)] -> d_out round-key words [batch][4 (rounds + 1)] in the word order of FlatJob::rk, the last round key folded with
+// round key 0.  launch_fused_flat_keyed: a.rk = that array; the tile's schedules go into an LDS key table behind the wire
+// slots, so the launch needs fused_flat_keyed_bytes <= kFlatLdsBytes (hipErrorInvalidConfiguration otherwise); the garbler
+// needs a.rnd; a.prof is ignored.
+size_t fused_flat_keyed_bytes(uint32_t nls, uint32_t ti_log2, uint32_t ustride, int rounds);
+hipError_t launch_expand_keys(const uint8_t *d_keys, int rounds, uint32_t batch, const uint32_t *te0, uint32_t *d_out,
+                              hipStream_t s);
+hipError_t launch_fused_flat_keyed(bool eval, const FusedFlatArgs &a, const BatchGeom &g, hipStream_t s);
+
 // What one workgroup of the flattened kernels needs.  The batch launches pass ONE of these as the kernel argument (every
 // workgroup = one tile of the same circuit); the streaming engine's step groups pass an ARRAY in device memory, one
 // record per workgroup (launch_fused_flat_jobs): workgroup j runs ONE instance of job j's circuit — its own plan, wire

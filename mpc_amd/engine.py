@@ -141,6 +141,10 @@ def lib():
         "gc_batch_set_inputs": (i32, [vp, vp]),
         "gc_batch_eval": (i32, [vp, vp, sz, vp]),
         "gc_batch_decode": (i32, [vp, vp, vp, vp]),
+        "gc_batch_garble_keyed": (i32, [vp, vp, sz, vp]),
+        "gc_batch_eval_keyed": (i32, [vp, vp, sz, vp]),
+        "gc_batch_keyed_supported": (i32, [vp]),
+        "gc_batch_debug_keyed_schedule": (i32, [vp, vp, sz, vp, vp]),
         "gc_batch_read_r": (i32, [vp, vp]),
         "gc_batch_read_slab": (i32, [vp, vp]),
         "gc_batch_read_wires": (i32, [vp, vp]),
@@ -698,6 +702,24 @@ class Batch:
     def eval(self, key, tables):
         k = _u8(key)
         _check(lib().gc_batch_eval(self.h, _p(k), len(k), tables.h), "gc_batch_eval")
+
+    def keyed_supported(self):
+        """can this batch run garble_keyed / eval_keyed (gc_batch_keyed_supported)?"""
+        return bool(lib().gc_batch_keyed_supported(self.h))
+
+    def garble_keyed(self, d_keys, keylen, d_rnd):
+        """gc_batch_garble_keyed: d_keys = device u8 [batch][keylen], one AES key per instance"""
+        _check(lib().gc_batch_garble_keyed(self.h, _dp(d_keys), keylen, _dp(d_rnd)), "gc_batch_garble_keyed")
+
+    def eval_keyed(self, d_keys, keylen, tables):
+        _check(lib().gc_batch_eval_keyed(self.h, _dp(d_keys), keylen, tables.h), "gc_batch_eval_keyed")
+
+    def debug_keyed_schedule(self, d_keys, keylen):
+        """(device, host) round-key words [batch][4 * (rounds + 1)] of the keyed passes (gc_batch_debug_keyed_schedule)"""
+        nw = 4 * (keylen // 4 + 7)
+        dev, host = np.zeros((self.batch, nw), np.uint32), np.zeros((self.batch, nw), np.uint32)
+        _check(lib().gc_batch_debug_keyed_schedule(self.h, _dp(d_keys), keylen, _p(dev), _p(host)), "gc_batch_debug_keyed_schedule")
+        return dev, host
 
     def decode(self, evaluator, d_bits_out, d_mismatch):
         _check(lib().gc_batch_decode(self.h, evaluator.h, _dp(d_bits_out), _dp(d_mismatch)),

@@ -1,0 +1,156 @@
+"""One AES key per instance (gc_batch_garble_keyed / gc_batch_eval_keyed) beside the one-key batch calls: aes_128 x 1 024 and
+sha256xor x 256 under 32-byte keys, everything in HBM, one JSON line per circuit.
+
+Method: the one-key form and the keyed form alternate in one process.  Each of the four passes (garble and eval of either
+form) is recorded once in a hipGraph; PREWARM untimed launches of the step bring the card to its sustained clocks, as bench.py
+warms its headline; then --reps rounds, each timing the four passes one after the other: a host clock around k launches that end
+in gc_ctx_sync, k sized once so that a window lasts at least --window seconds.  ms per pass = window / k; the median of the
+rounds is reported with every round beside it.
+
+  garble_ms / eval_ms            the one-key passes (gc_batch_garble / gc_batch_eval)
+  keyed_garble_ms / ..eval_ms    the keyed passes; the garbler's includes k_expand_keys (it is part of the call)
+  keyed_over_one_key             their ratios, garble, eval and the sum
+  expand_ms                      what the key expansion adds to a pass: keyed minus one-key garble of a ONE-GATE circuit at the
+                                 same batch (expansion kernel + the load of the LDS key table; the hashing is nothing there)
+  one_instance_batches_ms        what a caller with per-session keys had to do before: one batch of ONE instance per session,
+                                 garble + eval under its own key, timed on at most --sample sessions and scaled to the batch
+  keyed_over_one_instance        keyed garble + eval against that"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from mpc_amd import circuit, engine, parse_file  # noqa: E402
+
+PREWARM = 100  # untimed launches ahead of the windows (bench.py: PREWARM_STEPS)
+CASES = [("aes_128", 1024), ("sha256xor", 256)]
+
+
+def window(ctx, launch, k):
+    ctx.sync()
+    t0 = time.perf_counter()
+    for _ in range(k):
+        launch()
+    ctx.sync()
+    return (time.perf_counter() - t0) / k * 1e3
+
+
+def alternate(ctx, passes, reps, seconds):
+    """{name: [ms per launch, one per round]} of graphs / callables timed round-robin"""
+    for launch in passes.values():
+        for _ in range(PREWARM):
+            launch()
+    ks = {}
+    for name, launch in passes.items():
+        ms = window(ctx, launch, 20)
+        ks[name] = max(20, int(seconds * 1e3 / max(ms, 1e-3)))
+    out = {name: [] for name in passes}
+    for _ in range(reps):
+        for name, launch in passes.items():
+            out[name].append(window(ctx, launch, ks[name]))
+    return out
+
+
+def graphs_of(ctx, gb, ev, d_bits, garble, evaluate):
+    """the two passes run once directly (key upload, allocations), then as one hipGraph each"""
+    garble()
+    ev.select_inputs(gb, d_bits)
+    evaluate()
+    ctx.sync()
+    return ctx.capture(garble), ctx.capture(evaluate)
+
+
+def measure(ctx, c, batch, reps, seconds, sample):
+    rng = np.random.default_rng(7)
+    dc = engine.DeviceCircuit(ctx, c)
+    gb, ev = engine.Batch(dc, batch), engine.Batch(dc, batch)
+    assert gb.keyed_supported() and ev.keyed_supported()
+    d_rnd = ctx.random_u8((batch, c.num_inputs + 1, 16), 256, seed=1234)
+    d_bits = ctx.random_u8((batch, c.num_inputs), 2, seed=4321)
+    keys = rng.integers(0, 256, (batch, 32), dtype=np.uint8)
+    d_keys = ctx.to_device(keys)
+    key = keys[0].tobytes()
+    g1, e1 = graphs_of(ctx, gb, ev, d_bits, lambda: gb.garble(key, d_rnd), lambda: ev.eval(key, gb))
+    gk, ek = graphs_of(ctx, gb, ev, d_bits, lambda: gb.garble_keyed(d_keys, 32, d_rnd), lambda: ev.eval_keyed(d_keys, 32, gb))
+    t = alternate(ctx, {"garble": g1.launch, "keyed_garble": gk.launch, "eval": e1.launch, "keyed_eval": ek.launch}, reps, seconds)
+    # the expansion alone: a one-gate circuit at the same batch
+    tiny = circuit.and_chain(1)
+    dct = engine.DeviceCircuit(ctx, tiny)
+    tb = engine.Batch(dct, batch)
+    d_trnd = ctx.random_u8((batch, tiny.num_inputs + 1, 16), 256, seed=99)
+    tb.garble(key, d_trnd)
+    tb.garble_keyed(d_keys, 32, d_trnd)
+    ctx.sync()
+    t1, tk = ctx.capture(lambda: tb.garble(key, d_trnd)), ctx.capture(lambda: tb.garble_keyed(d_keys, 32, d_trnd))
+    tt = alternate(ctx, {"tiny": t1.launch, "tiny_keyed": tk.launch}, reps, seconds / 4)
+    # one batch of one instance per session: what per-session keys cost a caller without the keyed calls
+    n1 = min(sample, batch)
+    singles = []
+    for i in range(n1):
+        a, b = engine.Batch(dc, 1), engine.Batch(dc, 1)
+        singles.append((a, b, keys[i].tobytes(), ctx.random_u8((1, c.num_inputs + 1, 16), 256, seed=i)))
+
+    def sessions():
+        for a, b, k, r in singles:
+            a.garble(k, r)
+            b.select_inputs(a, d_bits)
+            b.eval(k, a)
+
+    sessions()
+    ts = [window(ctx, sessions, 3) * batch / n1 for _ in range(reps)]
+    med = {k: statistics.median(v) for k, v in list(t.items()) + list(tt.items())}
+    one, keyed = med["garble"] + med["eval"], med["keyed_garble"] + med["keyed_eval"]
+    row = {
+        "bench": "batch_keyed", "circuit": c.name, "batch": batch, "key_bytes": 32, "tile_instances": gb.tile_instances,
+        "and_gates": dc.info.n_and, "reps": reps, "window_s": seconds,
+        "garble_ms": med["garble"], "eval_ms": med["eval"], "keyed_garble_ms": med["keyed_garble"],
+        "keyed_eval_ms": med["keyed_eval"],
+        "keyed_over_one_key": {"garble": med["keyed_garble"] / med["garble"], "eval": med["keyed_eval"] / med["eval"],
+                               "garble_plus_eval": keyed / one},
+        "expand_ms": med["tiny_keyed"] - med["tiny"], "one_gate_garble_ms": med["tiny"], "one_gate_keyed_garble_ms": med["tiny_keyed"],
+        "one_instance_batches_ms": statistics.median(ts), "one_instance_batches_timed": n1,
+        "keyed_over_one_instance": keyed / statistics.median(ts),
+        "keyed_and_gates_per_s": dc.info.n_and * batch / (keyed * 1e-3),
+        "one_key_and_gates_per_s": dc.info.n_and * batch / (one * 1e-3),
+        "ms_all": {k: v for k, v in list(t.items()) + list(tt.items())}, "one_instance_batches_ms_all": ts,
+    }
+    for g in (g1, e1, gk, ek, t1, tk):
+        g.close()
+    for a, b, _, _ in singles:
+        a.close()
+        b.close()
+    for b in (gb, ev, tb):
+        b.close()
+    dct.close()
+    dc.close()
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--window", type=float, default=0.2)
+    ap.add_argument("--sample", type=int, default=64, help="one-instance batches the sequential row is timed on")
+    ap.add_argument("--out", default=None, help="also append the lines to this file")
+    a = ap.parse_args()
+    ctx = engine.Context(0)
+    for name, batch in CASES:
+        c = parse_file(os.path.join(ROOT, "tests", "golden", name + ".gcf"))
+        c.name = name
+        line = json.dumps(measure(ctx, c, batch, a.reps, a.window, a.sample))
+        print(line, flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
