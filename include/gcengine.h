@@ -116,6 +116,10 @@ int gc_plan_describe(const gc_plan *, uint32_t *level_of_gate, uint32_t *tweak_o
 /* 64-bit fingerprint of the device program of the plan (level steps, hash-phase schedule, flattened unit program and LDS
  * slots): equal fingerprints = the same work launched for this circuit.  bench.py ties PMC counters to it (round 6). */
 int gc_plan_fingerprint(const gc_plan *, uint64_t *fp);
+/* The two figures of the flattened schedule that fix a batch's tile and LDS image beside n_flat_slots (host only, for tests
+ * that predict them): unit_stride16 = uint4 per LDS stage buffer (the largest unit), max_parts = the largest number of
+ * lanes one XOR list is spread over (1, 2 or 4).  Either pointer may be NULL.  GC_E_ARG: no flattened schedule. */
+int gc_plan_flat_geometry(const gc_plan *, uint32_t *unit_stride16, uint32_t *max_parts);
 
 /* ------------------------------------------------------------------------------------------
  * Device context + circuit

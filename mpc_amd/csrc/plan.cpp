@@ -926,6 +926,13 @@ int gc_plan_fingerprint(const gc_plan *pl, uint64_t *fp) try {
     return gc::on_exception();
 }
 
+int gc_plan_flat_geometry(const gc_plan *pl, uint32_t *unit_stride16, uint32_t *max_parts) {
+    if (!pl || pl->p.n_flat_slots == 0xffffffffu) return GC_E_ARG;
+    if (unit_stride16) *unit_stride16 = pl->p.fl_unit_stride;
+    if (max_parts) *max_parts = pl->p.fl_max_parts;
+    return GC_OK;
+}
+
 int gc_plan_describe(const gc_plan *pl, uint32_t *level_of_gate, uint32_t *tweak_of_gate, uint32_t *row_of_gate,
                      uint32_t *slot_of_gate) try {
     if (!pl) return GC_E_ARG;

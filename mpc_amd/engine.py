@@ -82,6 +82,7 @@ def lib():
         "gc_plan_simulate": (i32, [vp, vp, vp]),
         "gc_plan_describe": (i32, [vp, vp, vp, vp, vp]),
         "gc_plan_fingerprint": (i32, [vp, vp]),
+        "gc_plan_flat_geometry": (i32, [vp, vp, vp]),
         "gc_device_count": (i32, []),
         "gc_ctx_create": (vp, [i32, ip]),
         "gc_ctx_destroy": (None, [vp]),
@@ -354,6 +355,12 @@ class PinnedArray:
 # ---- plan (host only) ---------------------------------------------------------------------
 
 
+def _flat_geometry(plan_h):
+    us, mp = C.c_uint32(0), C.c_uint32(0)
+    _check(lib().gc_plan_flat_geometry(plan_h, C.byref(us), C.byref(mp)), "gc_plan_flat_geometry")
+    return us.value, mp.value
+
+
 class Plan:
     """Levelised plan of a circuit; needs no GPU (gc_plan_*)."""
 
@@ -407,6 +414,10 @@ class Plan:
         fp = C.c_uint64(0)
         _check(lib().gc_plan_fingerprint(self.h, C.byref(fp)), "gc_plan_fingerprint")
         return "%016x" % fp.value
+
+    def flat_geometry(self):
+        """(uint4 per LDS stage buffer, largest part count of an XOR list) of the flattened schedule"""
+        return _flat_geometry(self.h)
 
     def simulate(self, in_bits):
         """plaintext walk of the flattened unit program (gc_plan_simulate): output bits"""
@@ -589,6 +600,10 @@ class DeviceCircuit:
 
     def set_schedule(self, schedule):
         _check(lib().gc_circ_set_schedule(self.h, schedule), "gc_circ_set_schedule")
+
+    def flat_geometry(self):
+        """Plan.flat_geometry of the uploaded circuit's plan"""
+        return _flat_geometry(lib().gc_circ_plan(self.h))
 
     @property
     def tables_wire_bytes(self):

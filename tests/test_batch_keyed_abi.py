@@ -27,6 +27,8 @@ def test_the_three_prototypes_are_in_the_header():
     assert "#define GC_ABI_VERSION 2" in open(os.path.join(ROOT, "include", "gcengine.h")).read()
     assert "int gc_batch_garble(gc_batch *, const uint8_t *key, size_t keylen, const void *d_rnd);" in h
     assert "int gc_batch_eval(gc_batch *evaluator, const uint8_t *key, size_t keylen, const gc_batch *tables);" in h
+    # the host-only view of the flattened geometry that the keyed tests predict tiles from: additive as well
+    assert "int gc_plan_flat_geometry(const gc_plan *, uint32_t *unit_stride16, uint32_t *max_parts);" in h
 
 
 def test_header_compiles_as_c99_and_the_calls_can_be_named_from_c(tmp_path):
@@ -36,6 +38,10 @@ def test_header_compiles_as_c99_and_the_calls_can_be_named_from_c(tmp_path):
                    "    if (!gc_batch_keyed_supported(g)) return GC_E_ARG;\n"
                    "    if (gc_batch_garble_keyed(g, k, 32, r) != GC_OK) return GC_E_KEYSIZE;\n"
                    "    return gc_batch_eval_keyed(e, k, 32, g);\n"
+                   "}\n"
+                   "int geometry(const gc_plan *p) {\n"
+                   "    uint32_t stride16, parts;\n"
+                   "    return gc_plan_flat_geometry(p, &stride16, &parts) == GC_OK ? (int)(stride16 + parts) : -1;\n"
                    "}\n")
     r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), "-c",
                         str(src), "-o", str(tmp_path / "keyed.o")], capture_output=True, text=True)
@@ -49,11 +55,14 @@ def test_library_exports_the_calls_and_null_handles_are_argument_errors():
     assert L.gc_batch_keyed_supported(None) == 0
     assert L.gc_batch_garble_keyed(None, None, 32, None) == engine.GC_E_ARG
     assert L.gc_batch_eval_keyed(None, None, 32, None) == engine.GC_E_ARG
+    assert hasattr(L, "gc_plan_flat_geometry")
+    assert L.gc_plan_flat_geometry(None, None, None) == engine.GC_E_ARG
 
 
 def test_python_binding_has_the_methods():
     for m in ("garble_keyed", "eval_keyed", "keyed_supported"):
         assert callable(getattr(engine.Batch, m)), m
+    assert callable(engine.Plan.flat_geometry) and callable(engine.DeviceCircuit.flat_geometry)
 
 
 @pytest.mark.parametrize("path,names", [

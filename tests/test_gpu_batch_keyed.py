@@ -10,9 +10,17 @@ import pytest
 
 import oracle
 from mpc_amd import LABEL, circuit, engine
+from tests import keyed_geometry as kg
 from tests.util import bits_lsb, drbg, int_from_bits
 
 pytestmark = pytest.mark.gpu
+
+
+def stream(tag, n):
+    """n seeded bytes: the SHA-256 counter stream, past 1 MiB numpy's generator (a hash call per 32 bytes takes seconds there)"""
+    if n <= 1 << 20:
+        return drbg(tag, n)
+    return np.random.default_rng(int.from_bytes(drbg(tag, 8), "big")).bytes(n)
 
 
 def distinct_keys(tag, batch, keylen):
@@ -31,13 +39,18 @@ def ctx():
 class Pair:
     """a garbler and an evaluator batch of one circuit with their device buffers"""
 
-    def __init__(self, ctx, c, batch, tag):
+    def __init__(self, ctx, c, batch, tag, shape=None):
+        """shape: the kg.Shape predicted for (c, batch); both batches must have got it"""
         self.ctx, self.c, self.batch = ctx, c, batch
         self.dc = engine.DeviceCircuit(ctx, c)
         self.gb, self.ev = engine.Batch(self.dc, batch), engine.Batch(self.dc, batch)
+        if shape is not None:
+            assert (int(self.dc.info.n_flat_slots),) + self.dc.flat_geometry() == (shape.nls, shape.ustride, shape.parts)
+            kg.check_batch(self.gb, shape)
+            kg.check_batch(self.ev, shape)
         self.stride = 16 * (c.num_inputs + 1)
-        self.rnd = drbg("keyed/rnd/" + tag, self.stride * batch)
-        self.bits = (np.frombuffer(drbg("keyed/bits/" + tag, batch * c.num_inputs), np.uint8) & 1).reshape(batch, -1)
+        self.rnd = stream("keyed/rnd/" + tag, self.stride * batch)
+        self.bits = (np.frombuffer(stream("keyed/bits/" + tag, batch * c.num_inputs), np.uint8) & 1).reshape(batch, -1)
         self.d_rnd, self.d_bits = ctx.to_device(self.rnd), ctx.to_device(self.bits)
         self.d_out, self.d_mis = ctx.zeros((batch, c.num_outputs)), ctx.zeros(1, np.int32)
 
@@ -79,6 +92,14 @@ class Pair:
         for f in ("slab", "l0", "active", "bits"):
             assert (got[f][i] == ref[f]).all(), "%s %s of instance %d" % (what, f, i)
 
+    def check_same(self, got, one, idx, what=""):
+        """instances idx of `got` equal those of `one` (the results of another pass) in all five fields"""
+        idx = np.asarray(idx)
+        for f in ("R", "slab", "l0", "active", "bits"):
+            eq = got[f][idx] == one[f][idx]
+            bad = idx[~eq.reshape(len(idx), -1).all(axis=1)]
+            assert not len(bad), "%s %s of instances %s ..." % (what, f, bad[:8].tolist())
+
     def close(self):
         self.gb.close()
         self.ev.close()
@@ -91,32 +112,31 @@ class Pair:
 @pytest.mark.parametrize("keylen", [16, 24, 32])
 def test_key_schedule_on_the_device_equals_the_hosts(ctx, keylen):
     """k_expand_keys against aes_host.h's schedule (and the oracle's, an implementation of its own), word for word, in the
-    form the kernels hash with: big-endian words, the last round key XORed with round key 0"""
-    batch, nr = 5, keylen // 4 + 6
-    p = Pair(ctx, circuit.adder(8), batch, "sched")
-    keys = distinct_keys("sched%d" % keylen, batch, keylen)
-    dev, host = p.gb.debug_keyed_schedule(ctx.to_device(keys), keylen)
-    assert dev.shape == (batch, 4 * (nr + 1))
-    assert (dev == host).all()
-    for i in range(batch):
-        rk, rounds = oracle.aes_round_keys(keys[i].tobytes())
-        w = np.frombuffer(rk, ">u4").astype(np.uint32)
-        assert rounds == nr and len(w) == 4 * (nr + 1)
-        w[4 * nr:] ^= w[:4]
-        assert (dev[i] == w).all(), "instance %d" % i
-    p.close()
+    form the kernels hash with: big-endian words, the last round key XORed with round key 0.  One lane is one instance and a
+    block 256 lanes: 5 is a partly filled block, 256 a full one, 257 and 1 027 go past it (the `gi >= batch` guard in a
+    second and a fifth block).  Keys with the edge patterns of kg.edge_keys."""
+    nr = keylen // 4 + 6
+    for batch in (5, 256, 257, 1027):
+        p = Pair(ctx, circuit.adder(8), batch, "sched")
+        keys = distinct_keys("sched%d" % keylen, batch, keylen) if batch == 5 else kg.edge_keys("sched%d" % keylen, batch, keylen)
+        dev, host = p.gb.debug_keyed_schedule(ctx.to_device(keys), keylen)
+        assert dev.shape == (batch, 4 * (nr + 1))
+        assert (dev == host).all()
+        for i in range(batch):
+            rk, rounds = oracle.aes_round_keys(keys[i].tobytes())
+            w = np.frombuffer(rk, ">u4").astype(np.uint32)
+            assert rounds == nr and len(w) == 4 * (nr + 1)
+            w[4 * nr:] ^= w[:4]
+            assert (dev[i] == w).all(), "%d instances: instance %d" % (batch, i)
+        p.close()
 
 
 # ---- 2. parity with the oracle -------------------------------------------------------------------------------------------
 
-CIRCUITS = {
-    "adder8": lambda: circuit.adder(8),  # narrow units only
-    # 320 ANDs per level: 1 280 garbler blocks per instance, several passes of 1 024 column lanes per unit
-    "wide": lambda: circuit.synthetic_levelised(levels=3, width=320, and_frac=1.0, seed=11),
-    # every gate kind: the HAS_OR build; odd gate counts leave the last pass of a unit partial
-    "mixed": lambda: circuit.synthetic_levelised(levels=3, width=320, and_frac=0.45, seed=12, or_frac=0.2, inv_frac=0.15,
-                                                 xnor_frac=0.1),
-}
+# adder8: narrow units only; wide: 320 ANDs per level, several passes of 1 024 column lanes per unit; mixed: every gate kind,
+# the HAS_OR build, odd gate counts leave the last pass of a unit partial (tests/keyed_geometry.py, whose host test pins the
+# tile width each batch gets)
+CIRCUITS = {name: kg.CIRCUITS[name] for name in ("adder8", "wide", "mixed")}
 
 
 @pytest.mark.parametrize("batch", [1, 3, 5, 8, 1027])
@@ -126,7 +146,7 @@ def test_every_instance_equals_the_oracle_under_its_own_key(ctx, name, batch):
     if name == "mixed":
         s = c.stats()
         assert s["OR"] and s["INV"] and s["XNOR"] and s["AND"]
-    p = Pair(ctx, c, batch, "%s/%d" % (name, batch))
+    p = Pair(ctx, c, batch, "%s/%d" % (name, batch), kg.predict(name, batch))
     assert p.gb.keyed_supported() and p.ev.keyed_supported()
     ti = p.gb.tile_instances
     print("%s x %d: TI = %d" % (name, batch, ti))
