@@ -1,0 +1,180 @@
+//go:build gchip
+
+package circuit
+
+/*
+#include "gcengine.h"
+*/
+import "C"
+
+import (
+	"fmt"
+	"unsafe"
+
+	"github.com/markkurossi/mpc/ot"
+)
+
+// SOURCE ONLY (no Go toolchain in the build image).  S sessions of ONE streamed program per call (additive to the reference:
+// a host that gathers S concurrent two-party sessions onto one GPU).  Every session runs the same SSA step
+// (compiler/ssa/streamer.go:412-524) on the same circuit with the same in[] / out[]; they differ in key, R and labels.  A
+// step is one keyed batch pass over S instances; session s's bytes and wires are those of Streaming.Garble
+// (circuit/stream_garble.go:161-192) for that session alone.  Keys, random streams, byte streams and OT labels stay in device
+// buffers (DevBuf); the host moves the bytes to its S connections.
+
+// StreamingBatch is the garbler's side: NewStreaming + Garble + GetInput for S sessions.
+type StreamingBatch struct {
+	ctx      *C.gc_ctx
+	h        *C.gc_stream_batch
+	sessions int
+}
+
+// wireIDs is ws as the uint32 array the C calls take (never empty, so that its first element has an address).
+func wireIDs(ws []Wire) *C.uint32_t {
+	ids := make([]uint32, len(ws)+1)
+	for i, w := range ws {
+		ids[i] = uint32(w)
+	}
+	return (*C.uint32_t)(unsafe.Pointer(&ids[0]))
+}
+
+// NewStreamingBatch replaces NewStreaming (stream_garble.go:41-75) for `sessions` sessions.  keys: [sessions][keylen] u8,
+// rnd: [sessions][1+len(inputs)][16] — per session R, then one L0 per input, as cfg.GetRandom() would deliver them.  ctx is
+// a gc_ctx* as an unsafe.Pointer (see NewDevBuf).
+func NewStreamingBatch(ctx unsafe.Pointer, sessions int, keys *DevBuf, keylen int, rnd *DevBuf, inputs []Wire) (*StreamingBatch, error) {
+	if keys.Size() < sessions*keylen || rnd.Size() < sessions*(1+len(inputs))*16 {
+		return nil, fmt.Errorf("NewStreamingBatch: keys or random streams shorter than %d sessions need", sessions)
+	}
+	var st C.int
+	p := wireIDs(inputs)
+	h := C.gc_stream_batch_create((*C.gc_ctx)(ctx), C.uint32_t(sessions), keys.Ptr(), C.size_t(keylen), rnd.Ptr(), p,
+		C.uint32_t(len(inputs)), &st)
+	if h == nil {
+		return nil, statusError(st)
+	}
+	return &StreamingBatch{ctx: (*C.gc_ctx)(ctx), h: h, sessions: sessions}, nil
+}
+
+// Close releases the wire store and the cached circuits.
+func (s *StreamingBatch) Close() {
+	if s.h != nil {
+		C.gc_stream_batch_free(s.h)
+		s.h = nil
+	}
+}
+
+// StepBytes is the number of bytes Garble writes for this step — the same for every session (host only).
+func StepBytes(c *Circuit, in, out []Wire) int {
+	pi := wireIDs(in)
+	po := wireIDs(out)
+	n := C.gc_stream_batch_step_bytes((*C.gc_gate)(unsafe.Pointer(&c.Gates[0])), C.uint32_t(len(c.Gates)),
+		C.uint32_t(c.NumWires), pi, C.uint32_t(len(in)), po, C.uint32_t(len(out)))
+	return int(n)
+}
+
+// Garble is (*Streaming).Garble(c, in, out) (stream_garble.go:161-192) for every session: session k's bytes land at
+// dst.At(off + k*stride), exactly as :391-446 writes them into conn.WriteBuf.  Queued on the ctx stream; the returned byte
+// count is known at once.  stride: a multiple of 4 that holds the steps the caller appends.
+func (s *StreamingBatch) Garble(c *Circuit, in, out []Wire, dst *DevBuf, off, stride int) (int, error) {
+	if len(c.Gates) == 0 {
+		return 0, nil
+	}
+	pi := wireIDs(in)
+	po := wireIDs(out)
+	var n C.size_t
+	st := C.gc_stream_batch_garble(s.h, (*C.gc_gate)(unsafe.Pointer(&c.Gates[0])), C.uint32_t(len(c.Gates)),
+		C.uint32_t(c.NumWires), pi, C.uint32_t(len(in)), po, C.uint32_t(len(out)), dst.At(off), C.size_t(stride), &n)
+	if st != C.GC_OK {
+		return int(n), statusError(st)
+	}
+	return int(n), nil
+}
+
+// GetInput is (*Streaming).GetInput(w) (stream_garble.go:117-119) of every session.
+func (s *StreamingBatch) GetInput(w Wire) ([]ot.Wire, error) {
+	out := make([]ot.Wire, s.sessions)
+	if st := C.gc_stream_batch_get_wire(s.h, C.uint32_t(w), (*C.gc_wire)(unsafe.Pointer(&out[0]))); st != C.GC_OK {
+		return nil, statusError(st)
+	}
+	return out, nil
+}
+
+// GatherWires writes both labels of the named wires as ot.Wire [sessions][len(ws)] into dst: what the multi-session COT
+// sender (ot.COTMultiSendPads) consumes for the peers' inputs (garbler.go:102-132 per session).
+func (s *StreamingBatch) GatherWires(ws []Wire, dst *DevBuf) error {
+	if dst.Size() < s.sessions*len(ws)*32 {
+		return fmt.Errorf("GatherWires: %d bytes for %d x %d wires", dst.Size(), s.sessions, len(ws))
+	}
+	p := wireIDs(ws)
+	st := C.gc_stream_batch_gather_wires(s.h, p, C.uint32_t(len(ws)), dst.Ptr())
+	if st != C.GC_OK {
+		return statusError(st)
+	}
+	return nil
+}
+
+// StreamEvalBatch is the evaluator's side: the store of circuit.StreamEval (stream_evaluator.go:29-96) for S sessions.
+type StreamEvalBatch struct {
+	ctx      *C.gc_ctx
+	h        *C.gc_stream_eval_batch
+	sessions int
+}
+
+// NewStreamEvalBatch replaces NewStreamEval (stream_evaluator.go:37-50) for `sessions` sessions; keys as NewStreamingBatch.
+func NewStreamEvalBatch(ctx unsafe.Pointer, sessions int, keys *DevBuf, keylen int) (*StreamEvalBatch, error) {
+	if keys.Size() < sessions*keylen {
+		return nil, fmt.Errorf("NewStreamEvalBatch: keys shorter than %d sessions need", sessions)
+	}
+	var st C.int
+	h := C.gc_stream_eval_batch_create((*C.gc_ctx)(ctx), C.uint32_t(sessions), keys.Ptr(), C.size_t(keylen), &st)
+	if h == nil {
+		return nil, statusError(st)
+	}
+	return &StreamEvalBatch{ctx: (*C.gc_ctx)(ctx), h: h, sessions: sessions}, nil
+}
+
+// Close releases the wire store and the cached circuits.
+func (e *StreamEvalBatch) Close() {
+	if e.h != nil {
+		C.gc_stream_eval_batch_free(e.h)
+		e.h = nil
+	}
+}
+
+// SetWires sets the wires ws of every session from labels: ot.Label [sessions][len(ws)] in device memory (the OT results).
+func (e *StreamEvalBatch) SetWires(ws []Wire, labels *DevBuf) error {
+	if labels.Size() < e.sessions*len(ws)*16 {
+		return fmt.Errorf("SetWires: %d bytes for %d x %d labels", labels.Size(), e.sessions, len(ws))
+	}
+	p := wireIDs(ws)
+	st := C.gc_stream_eval_batch_set_wires(e.h, p, C.uint32_t(len(ws)), labels.Ptr())
+	if st != C.GC_OK {
+		return statusError(st)
+	}
+	return nil
+}
+
+// Get is StreamEval.Get(false, w) (stream_evaluator.go:61-66) of every session.
+func (e *StreamEvalBatch) Get(w Wire) ([]ot.Label, error) {
+	out := make([]ot.Label, e.sessions)
+	if st := C.gc_stream_eval_batch_get_wire(e.h, C.uint32_t(w), (*C.gc_label)(unsafe.Pointer(&out[0]))); st != C.GC_OK {
+		return nil, statusError(st)
+	}
+	return out, nil
+}
+
+// EvalBlock is InitCircuit + the gate loop of the OpCircuit case (stream_evaluator.go:269-432) for every session.  ref holds
+// one session's block bytes on the host; blocks holds all of them, stride bytes apart from offset off.  bad receives one
+// u32 per session: the structure bytes in which its block differs from ref — such a session is run again through
+// StreamEval.evalBlock by the caller.  Returns the bytes one block takes.
+func (e *StreamEvalBatch) EvalBlock(numGates, numTmpWires, numWires int, ref []byte, blocks *DevBuf, off, stride int, bad *DevBuf) (int, error) {
+	if bad.Size() < 4*e.sessions || len(ref) == 0 {
+		return 0, fmt.Errorf("EvalBlock: no reference block, or %d bytes for %d counters", bad.Size(), e.sessions)
+	}
+	var used C.size_t
+	st := C.gc_stream_eval_batch_circuit(e.h, C.uint32_t(numGates), C.uint32_t(numTmpWires), C.uint32_t(numWires),
+		(*C.uint8_t)(unsafe.Pointer(&ref[0])), C.size_t(len(ref)), blocks.At(off), C.size_t(stride), bad.Ptr(), &used)
+	if st != C.GC_OK {
+		return 0, statusError(st)
+	}
+	return int(used), nil
+}

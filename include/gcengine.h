@@ -522,6 +522,72 @@ int gc_batch_debug_keyed_schedule(gc_batch *, const void *d_keys, size_t keylen,
                                   uint32_t *host_words_out);
 
 /* ------------------------------------------------------------------------------------------
+ * Streaming for S sessions of ONE program per call (additive) — a host that gathers S concurrent
+ * two-party sessions running the same streamed program (compiler/ssa/streamer.go -> circuit.Streaming.Garble).  Every
+ * session runs the same SSA step on the same circuit with the same in[] / out[]; they differ in key, R and labels.  A step
+ * is ONE keyed batch pass over S instances (gc_batch_garble_keyed / gc_batch_eval_keyed) between a gather from and a scatter
+ * into a device-resident wire store [wire id][bstride] (bstride = sessions rounded up to 64; garbler: R per session plus
+ * L0, evaluator: the active label), which grows on demand with the largest id of in[] / out[].  Session s's results are byte
+ * for byte those of gc_stream_* / gc_stream_eval_* for that session alone, with its own key and random stream.  All d_*
+ * arguments are DEVICE pointers.  Steps of a handle are serial on the ctx stream; only the sessions are parallel.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct gc_stream_batch gc_stream_batch;
+typedef struct gc_stream_eval_batch gc_stream_eval_batch;
+/* NewStreaming (stream_garble.go:41-75) for `sessions` (1 .. 65 535) sessions:
+ *  d_keys  u8 [sessions][keylen], keylen 16, 24 or 32 for all (GC_E_KEYSIZE otherwise); copied
+ *  d_rnd   u8 [sessions][1 + ninputs][16]: per session what gc_stream_create's rnd holds — R (its S bit is forced on), then one
+ *          L0 per entry of inputs[]; read before the call returns
+ * A wire never set reads as (L0, L1) = (0, R), as in gc_stream.  GC_E_ARG for a wire id >= GC_STREAM_MAX_WIRES (here and
+ * in every call below), GC_E_NOMEM when the store cannot grow. */
+gc_stream_batch *gc_stream_batch_create(gc_ctx *, uint32_t sessions, const void *d_keys, size_t keylen, const void *d_rnd,
+                                        const uint32_t *inputs, uint32_t ninputs, int *status);
+void gc_stream_batch_free(gc_stream_batch *);
+/* host only, no GPU: the bytes (*Streaming).Garble(c, in, out) writes for this step (stream_garble.go:385-449) — the same for
+ * every session; 0 for a step that gc_stream_batch_garble refuses by its shape (see there; gc_last_error() says why) */
+size_t gc_stream_batch_step_bytes(const gc_gate *gates, uint32_t ngates, uint32_t nwires, const uint32_t *in, uint32_t nin,
+                                  const uint32_t *out, uint32_t nout);
+/* (*Streaming).Garble(c, in, out) for all sessions (stream_garble.go:161-192; the tweak restarts at 0 per circuit): enqueued
+ * on the ctx stream — gather of in[] from the store, the keyed pass, scatter through out[], serialiser — and not waited for.
+ * *written = the step's bytes (= gc_stream_batch_step_bytes), known when the call returns; session s's bytes land at
+ * (u8 *)d_out + s * stride exactly as :391-446 writes them; stride: any multiple of 4 >= *written; d_out: any byte alignment
+ * (a caller appends step after step at a running offset).  in[] and out[] may name the same GLOBAL wire (in-place update):
+ * a gate that reads such an input after the gate that set the output sees the new label, as in gc_stream_garble.  The
+ * circuit + batch are recognised by gate-list content and cached per handle, bounded in device bytes
+ * (GC_STREAM_BATCH_CACHE_BYTES, default 1 GiB; least recently used first).  ngates == 0 writes nothing and is GC_OK.  Not inside a pipeline capture (GC_E_ARG).
+ * Refused with GC_E_ARG and a gc_last_error() text, the store unchanged: a step whose circuit is outside
+ * gc_batch_keyed_supported at this number of sessions (no LDS plan, or the key table does not fit); a circuit whose output
+ * range overlaps its input range (nwires - nout < nin); a gate that writes an input-mapped wire.  GC_E_GATE / GC_E_WIRE for
+ * an invalid op / a wire id >= nwires. */
+int gc_stream_batch_garble(gc_stream_batch *, const gc_gate *gates, uint32_t ngates, uint32_t nwires, const uint32_t *in,
+                           uint32_t nin, const uint32_t *out, uint32_t nout, void *d_out, size_t stride, size_t *written);
+/* (*Streaming).GetInput(w) of every session: out[sessions]; waits for the ctx stream */
+int gc_stream_batch_get_wire(gc_stream_batch *, uint32_t w, gc_wire *out);
+/* {L0, L0 ^ R} of the named global wires as gc_wire [sessions][n] in device memory — what gc_cot_multi_send_pads_dev consumes
+ * for the peer's inputs; asynchronous (ids[] may be reused on return) */
+int gc_stream_batch_gather_wires(gc_stream_batch *, const uint32_t *ids, uint32_t n, void *d_wires_out);
+
+/* the evaluator's side: the store of circuit.StreamEval for `sessions` sessions; d_keys as above */
+gc_stream_eval_batch *gc_stream_eval_batch_create(gc_ctx *, uint32_t sessions, const void *d_keys, size_t keylen, int *status);
+void gc_stream_eval_batch_free(gc_stream_eval_batch *);
+/* input labels (OT results): d_labels = gc_label [sessions][n] for the wires ids[0 .. n); asynchronous */
+int gc_stream_eval_batch_set_wires(gc_stream_eval_batch *, const uint32_t *ids, uint32_t n, const void *d_labels);
+/* out[sessions]: the active label of wire w in every session; waits for the ctx stream */
+int gc_stream_eval_batch_get_wire(gc_stream_eval_batch *, uint32_t w, gc_label *out);
+/* ONE OpCircuit block of every session (the per-gate loop of StreamEvaluator, stream_evaluator.go:270-432).  ref_block: a
+ * HOST copy of any one session's block bytes; it is parsed and checked as gc_stream_eval_circuit parses a block, with the same
+ * refusals (GC_E_GATE, GC_E_ROWS, GC_E_ARG) and the same size checks before anything is sized by the peer's data.  d_blocks:
+ * all blocks in device memory, `stride` bytes apart (a multiple of 4, >= len).  On the device: every session's bytes
+ * outside the table rows are compared with ref_block's — d_bad[s] (u32 [sessions], zeroed by the call) = the number of
+ * differing bytes —, its rows are taken at ref_block's offsets, inputs gathered, the keyed pass, outputs scattered.  A
+ * session with d_bad[s] != 0 is the caller's to run again through gc_stream_eval_*: its output wires are unspecified, and
+ * nothing was read outside [0, len) of its block or written outside its own column of the store (every offset comes from
+ * ref_block); every other session is exact.  A changed ROW byte is data, not structure: d_bad stays 0 and the labels are what
+ * StreamEvaluator computes from those bytes.  *consumed = bytes of a block.  GC_E_ARG with a gc_last_error() text for a
+ * block whose circuit is outside gc_batch_keyed_supported. */
+int gc_stream_eval_batch_circuit(gc_stream_eval_batch *, uint32_t ngates, uint32_t ntmp, uint32_t nwires, const uint8_t *ref_block,
+                                 size_t len, const void *d_blocks, size_t stride, void *d_bad, size_t *consumed);
+
+/* ------------------------------------------------------------------------------------------
  * IKNP OT extension + MITCCRH (ot/iknp.go, ot/mitccrh.go, ot/cot.go)
  * ------------------------------------------------------------------------------------------ */
 typedef struct gc_iknp gc_iknp;

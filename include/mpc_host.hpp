@@ -497,6 +497,81 @@ inline void EvalBatchKeys(gc_batch *evaluator, const void *d_keys, size_t keylen
     check(gc_batch_eval_keyed(evaluator, d_keys, keylen, tables), "gc_batch_eval_keyed");
 }
 
+// S sessions of ONE streamed program per call (gc_stream_batch_*, gc_stream_eval_batch_*): a step is one keyed batch pass over S
+// instances between a device-resident wire store per handle; session s's bytes are those of Streaming.Garble
+// (stream_garble.go:161-192) with its own key and random stream.  d_* are device buffers (gc_dev_alloc).
+class StreamingBatch {
+public:
+    StreamingBatch(gc_ctx *ctx, uint32_t sessions, const void *d_keys, size_t keylen, const void *d_rnd,
+                   const std::vector<uint32_t> &inputs)
+        : sessions_(sessions) {
+        int st = GC_OK;
+        h_ = gc_stream_batch_create(ctx, sessions, d_keys, keylen, d_rnd, inputs.data(), (uint32_t)inputs.size(), &st);
+        if (!h_) check(st, "gc_stream_batch_create");
+    }
+    ~StreamingBatch() { gc_stream_batch_free(h_); }
+    StreamingBatch(const StreamingBatch &) = delete;
+    StreamingBatch &operator=(const StreamingBatch &) = delete;
+    static size_t StepBytes(const std::vector<gc_gate> &gates, uint32_t nwires, const std::vector<uint32_t> &in,
+                            const std::vector<uint32_t> &out) {
+        return gc_stream_batch_step_bytes(gates.data(), (uint32_t)gates.size(), nwires, in.data(), (uint32_t)in.size(), out.data(),
+                                          (uint32_t)out.size());
+    }
+    // queues the step; session s's bytes land at d_out + s * stride; returns the step's byte count
+    size_t Garble(const std::vector<gc_gate> &gates, uint32_t nwires, const std::vector<uint32_t> &in,
+                  const std::vector<uint32_t> &out, void *d_out, size_t stride) {
+        size_t n = 0;
+        check(gc_stream_batch_garble(h_, gates.data(), (uint32_t)gates.size(), nwires, in.data(), (uint32_t)in.size(), out.data(),
+                                     (uint32_t)out.size(), d_out, stride, &n),
+              "gc_stream_batch_garble");
+        return n;
+    }
+    std::vector<gc_wire> GetInput(uint32_t w) {
+        std::vector<gc_wire> out(sessions_);
+        check(gc_stream_batch_get_wire(h_, w, out.data()), "gc_stream_batch_get_wire");
+        return out;
+    }
+    void GatherWires(const std::vector<uint32_t> &ids, void *d_wires_out) {
+        check(gc_stream_batch_gather_wires(h_, ids.data(), (uint32_t)ids.size(), d_wires_out), "gc_stream_batch_gather_wires");
+    }
+
+private:
+    gc_stream_batch *h_ = nullptr;
+    uint32_t sessions_;
+};
+
+class StreamEvalBatch {
+public:
+    StreamEvalBatch(gc_ctx *ctx, uint32_t sessions, const void *d_keys, size_t keylen) : sessions_(sessions) {
+        int st = GC_OK;
+        h_ = gc_stream_eval_batch_create(ctx, sessions, d_keys, keylen, &st);
+        if (!h_) check(st, "gc_stream_eval_batch_create");
+    }
+    ~StreamEvalBatch() { gc_stream_eval_batch_free(h_); }
+    StreamEvalBatch(const StreamEvalBatch &) = delete;
+    StreamEvalBatch &operator=(const StreamEvalBatch &) = delete;
+    void SetWires(const std::vector<uint32_t> &ids, const void *d_labels) {
+        check(gc_stream_eval_batch_set_wires(h_, ids.data(), (uint32_t)ids.size(), d_labels), "gc_stream_eval_batch_set_wires");
+    }
+    std::vector<gc_label> Get(uint32_t w) {
+        std::vector<gc_label> out(sessions_);
+        check(gc_stream_eval_batch_get_wire(h_, w, out.data()), "gc_stream_eval_batch_get_wire");
+        return out;
+    }
+    // one OpCircuit block of every session; d_bad: u32 [sessions], the structure bytes in which a block differs from ref
+    size_t EvalBlock(uint32_t ngates, uint32_t ntmp, uint32_t nwires, const std::vector<uint8_t> &ref, const void *d_blocks,
+                     size_t stride, void *d_bad) {
+        size_t used = 0;
+        check(gc_stream_eval_batch_circuit(h_, ngates, ntmp, nwires, ref.data(), ref.size(), d_blocks, stride, d_bad, &used),
+              "gc_stream_eval_batch_circuit");
+        return used;
+    }
+
+private:
+    gc_stream_eval_batch *h_ = nullptr;
+    uint32_t sessions_;
+};
+
 // ParseBristol (parser.go:265-494), same validation messages
 inline Circuit ParseBristol(std::istream &in) {
     auto fail = [](const std::string &m) -> void { throw Error(m); };

@@ -1,0 +1,767 @@
+// stream_batch.cpp — S sessions of ONE streamed program per call (gc_stream_batch_*, gc_stream_eval_batch_*).
+// Every session runs the same SSA step on the same circuit with the same in[] / out[]; they differ in key, R and labels.  A
+// step is therefore one keyed batch pass over S instances (gc_batch_garble_keyed / gc_batch_eval_keyed) between a gather from
+// and a scatter into a device-resident wire store [wire id][bstride], and its bytes are one skeleton for all sessions — the
+// op | flag bytes and wire ids of circuit/stream_garble.go:391-441 — plus per-session table rows.  Steps are serial on the ctx
+// stream (program order there IS the reference's loop, stream_garble.go:161-192); only the sessions are parallel.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <unordered_map>
+#include <vector>
+
+#include "engine.h"
+#include "stream_batch.h"
+
+namespace gcs {
+uint32_t stream_max_wires();  // stream_eval.cpp (GC_STREAM_MAX_WIRES)
+}
+
+using namespace gc;
+
+namespace {
+
+constexpr uint32_t kNone = 0xffffffffu;
+constexpr int kRing = 4;  // steps whose constants may be on their way to the device at once
+
+size_t cache_budget() {
+    static const size_t v = [] {
+        const char *e = std::getenv("GC_STREAM_BATCH_CACHE_BYTES");
+        const unsigned long long n = e ? std::strtoull(e, nullptr, 0) : 0;
+        return n ? (size_t)n : (size_t)1 << 30;
+    }();
+    return v;
+}
+
+int refuse(const char *what, const char *why) {
+    std::snprintf(gc::tls_error, sizeof gc::tls_error, "%s: %s", what, why);
+    return GC_E_ARG;
+}
+
+inline size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+// ---- the bytes of a step that are the same for every session ---------------------------------------------------------
+// (*Streaming).Garble's gate loop (stream_garble.go:385-449) without the labels: op | flags, the wire ids through in[] / out[]
+// in their 16- or 32-bit form, and 16 zero bytes per table row.  bytes / row_off may be null (the size alone).
+size_t step_skeleton(const gc_gate *gates, uint32_t ngates, uint32_t nwires, const uint32_t *in, uint32_t nin, const uint32_t *out,
+                     uint32_t nout, std::vector<uint8_t> *bytes, std::vector<uint32_t> *row_off) {
+    const uint32_t first_tmp = nin, first_out = nwires - nout;
+    size_t pos = 0;
+    for (uint32_t g = 0; g < ngates; g++) {
+        const gc_gate &q = gates[g];
+        uint32_t flags = q.op;
+        auto get = [&](uint32_t w, uint32_t bit) -> uint32_t {  // Get / Set through in[] first (:131-157), else a tmp wire
+            if (w < first_tmp) return in[w];
+            if (w >= first_out) return out[w - first_out];
+            flags |= bit;
+            return w;
+        };
+        const uint32_t bi = q.op != GC_INV ? get(q.in1, 0x40) : 0;
+        const uint32_t ai = get(q.in0, 0x80), ci = get(q.out, 0x20);
+        const bool shortf = ai <= 0xffff && bi <= 0xffff && ci <= 0xffff;
+        const uint32_t wc = q.op == GC_INV ? 2 : 3;
+        const uint32_t rows = q.op == GC_AND ? 2 : q.op == GC_OR ? 3 : q.op == GC_INV ? 1 : 0;
+        const size_t size = 1 + (shortf ? 2u : 4u) * wc + 16u * rows;
+        if (bytes) {
+            bytes->resize(pos + size, 0);
+            uint8_t *p = bytes->data() + pos;
+            *p++ = (uint8_t)(flags | (shortf ? 0x10 : 0));
+            auto put = [&](uint32_t v) {
+                if (!shortf) *p++ = (uint8_t)(v >> 24), *p++ = (uint8_t)(v >> 16);
+                *p++ = (uint8_t)(v >> 8), *p++ = (uint8_t)v;
+            };
+            put(ai);
+            if (wc == 3) put(bi);
+            put(ci);
+            for (uint32_t r = 0; r < rows; r++) row_off->push_back((uint32_t)(pos + size - 16u * (rows - r)));
+        }
+        pos += size;
+    }
+    return pos;
+}
+
+// what every garbler step is checked for before anything is touched; nullptr, or the reason
+const char *step_refused(const gc_gate *gates, uint32_t ngates, uint32_t nwires, uint32_t nin, uint32_t nout, int *rc) {
+    *rc = GC_E_ARG;
+    if (nin > nwires || nout > nwires) return "more inputs or outputs than wires";
+    if (nwires - nout < nin) return "the circuit's output range overlaps its input range (nwires - nout < nin)";
+    for (uint32_t g = 0; g < ngates; g++) {
+        const gc_gate &q = gates[g];
+        if (q.op > GC_INV) {
+            *rc = GC_E_GATE;
+            return "invalid gate type";
+        }
+        if (q.in0 >= nwires || q.out >= nwires || (q.op != GC_INV && q.in1 >= nwires)) {
+            *rc = GC_E_WIRE;
+            return "wire id >= nwires";
+        }
+        if (q.out < nin) return "a gate writes an input-mapped wire";
+    }
+    return nullptr;
+}
+
+// ---- circuits of a handle, recognised by gate-list content -----------------------------------------------------------
+struct SbCirc {
+    std::vector<gc_gate> gates;  // {in0, in1, out, op}, the rest zero
+    uint32_t nwires = 0, nin = 0, nout = 0;
+    uint64_t hash = 0, last_use = 0;
+    gc_circ *circ = nullptr;
+    gc_batch *batch = nullptr;
+    size_t dev_bytes = 0;
+};
+
+uint64_t content_hash(const gc_gate *g, uint32_t n, uint32_t nwires, uint32_t nin, uint32_t nout) {
+    uint64_t h = 1469598103934665603ull;
+    auto mix = [&](uint64_t v) { h = (h ^ v) * 1099511628211ull; };
+    mix(n), mix(nwires), mix(nin), mix(nout);
+    for (uint32_t i = 0; i < n; i++) mix(((uint64_t)g[i].in0 << 32) | g[i].in1), mix(((uint64_t)g[i].out << 8) | g[i].op);
+    return h ^ (h >> 29);
+}
+
+struct SbStage {  // the constants of one step: pinned host copy, device copy, and when the device is done with them
+    uint8_t *pin = nullptr, *dev = nullptr;
+    size_t cap = 0;
+    hipEvent_t done = nullptr;
+    bool used = false;
+};
+
+struct SbCore {
+    gc_ctx *ctx = nullptr;
+    uint32_t S = 0, bstride = 0;
+    size_t keylen = 0;
+    uint8_t *d_keys = nullptr;
+    uint4 *d_store = nullptr;  // [rows][bstride]: L0 (garbler) / the active label (evaluator); zero = never set
+    uint32_t rows = 0;
+    std::vector<std::unique_ptr<SbCirc>> cache;
+    size_t cache_bytes = 0;
+    uint64_t tick = 0;
+    SbStage ring[kRing];
+    uint32_t next = 0;
+
+    Layout store_layout() const { return Layout{31, 0x7fffffffu, bstride, 0}; }
+
+    ~SbCore() {
+        if (ctx) {
+            (void)hipSetDevice(ctx->device);
+            (void)hipStreamSynchronize(ctx->stream);
+        }
+        for (auto &e : cache) {
+            gc_batch_free(e->batch);
+            gc_circ_free(e->circ);
+        }
+        for (auto &r : ring) {
+            if (r.pin) (void)hipHostFree(r.pin);
+            if (r.dev) (void)hipFree(r.dev);
+            if (r.done) (void)hipEventDestroy(r.done);
+        }
+        if (d_keys) (void)hipFree(d_keys);
+        if (d_store) (void)hipFree(d_store);
+    }
+
+    int init(gc_ctx *c, uint32_t sessions, const void *keys, size_t kl) {
+        if (!c || sessions == 0 || sessions > 65535u || !keys) return GC_E_ARG;  // (a session is a grid row of the serialiser)
+        if (kl != 16 && kl != 24 && kl != 32) return GC_E_KEYSIZE;
+        ctx = c, S = sessions, bstride = (sessions + 63u) & ~63u, keylen = kl;
+        GC_HIP(hipSetDevice(ctx->device));
+        GC_HIP(hipMalloc((void **)&d_keys, (size_t)S * keylen));
+        GC_HIP(hipMemcpyAsync(d_keys, keys, (size_t)S * keylen, hipMemcpyDeviceToDevice, ctx->stream));
+        return GC_OK;
+    }
+
+    // the store holds wire ids [0, max_id]; new rows are zero
+    int ensure(uint32_t max_id) {
+        if (max_id < rows) return GC_OK;
+        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>({(uint64_t)max_id + 1, 2ull * rows, 1024}), gcs::stream_max_wires());
+        uint4 *nw = nullptr;
+        GC_HIP(hipMalloc((void **)&nw, (size_t)want * bstride * sizeof(uint4)));
+        hipError_t e = hipMemsetAsync(nw + (size_t)rows * bstride, 0, (size_t)(want - rows) * bstride * sizeof(uint4), ctx->stream);
+        if (e == hipSuccess && rows)
+            e = hipMemcpyAsync(nw, d_store, (size_t)rows * bstride * sizeof(uint4), hipMemcpyDeviceToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(nw);
+            GC_HIP(e);
+        }
+        if (d_store) (void)hipFree(d_store);
+        d_store = nw, rows = (uint32_t)want;
+        return GC_OK;
+    }
+
+    // the circuit + batch of S instances for this gate list; a batch outside the keyed scope is refused (and not kept)
+    int find_or_load(const gc_gate *gates, uint32_t ngates, uint32_t nwires, uint32_t nin, uint32_t nout, const char *what,
+                     SbCirc **out) {
+        const uint64_t h = content_hash(gates, ngates, nwires, nin, nout);
+        for (auto &e : cache) {
+            if (e->hash != h || e->gates.size() != ngates || e->nwires != nwires || e->nin != nin || e->nout != nout) continue;
+            bool same = true;
+            for (uint32_t i = 0; i < ngates && same; i++)
+                same = e->gates[i].in0 == gates[i].in0 && e->gates[i].in1 == gates[i].in1 && e->gates[i].out == gates[i].out &&
+                       e->gates[i].op == gates[i].op;
+            if (!same) continue;
+            e->last_use = ++tick;
+            *out = e.get();
+            return GC_OK;
+        }
+        std::unique_ptr<SbCirc> e(new SbCirc);
+        e->gates.assign(ngates, gc_gate{});
+        for (uint32_t i = 0; i < ngates; i++)
+            e->gates[i].in0 = gates[i].in0, e->gates[i].in1 = gates[i].in1, e->gates[i].out = gates[i].out, e->gates[i].op = gates[i].op;
+        e->nwires = nwires, e->nin = nin, e->nout = nout, e->hash = h;
+        int st = GC_OK;
+        e->circ = gc_circ_load(ctx, e->gates.data(), ngates, nwires, nin, nout, &st);
+        if (!e->circ) return st;
+        e->batch = gc_batch_create(e->circ, S, &st);
+        if (e->batch && !gc_batch_keyed_supported(e->batch)) {
+            st = refuse(what, "the step's circuit is outside gc_batch_keyed_supported at this number of sessions (no LDS plan, or the "
+                              "tile's key table does not fit)");
+        }
+        if (!e->batch || st != GC_OK) {
+            if (e->batch) gc_batch_free(e->batch);
+            gc_circ_free(e->circ);
+            return st;
+        }
+        const gc_plan_info &pi = e->circ->plan.p.info;
+        const size_t bs = gc_batch_stride(e->batch);
+        e->dev_bytes = ((size_t)pi.nslots + std::max<uint32_t>(pi.slab_rows, 1) + 1) * bs * sizeof(uint4) + (size_t)S * 240;
+        // bounded in device bytes, least recently used first (gc_batch_free waits for the ctx stream: nothing uses them then)
+        while (!cache.empty() && cache_bytes + e->dev_bytes > cache_budget()) {
+            size_t lru = 0;
+            for (size_t i = 1; i < cache.size(); i++)
+                if (cache[i]->last_use < cache[lru]->last_use) lru = i;
+            gc_batch_free(cache[lru]->batch);
+            gc_circ_free(cache[lru]->circ);
+            cache_bytes -= cache[lru]->dev_bytes;
+            cache.erase(cache.begin() + (long)lru);
+        }
+        cache_bytes += e->dev_bytes;
+        e->last_use = ++tick;
+        *out = e.get();
+        cache.push_back(std::move(e));
+        return GC_OK;
+    }
+
+    int stage(size_t need, SbStage **out) {
+        SbStage &r = ring[next++ % kRing];
+        if (!r.done) GC_HIP(hipEventCreateWithFlags(&r.done, hipEventDisableTiming));
+        if (r.used) GC_HIP(hipEventSynchronize(r.done));
+        r.used = false;
+        if (r.cap < need) {
+            if (r.pin) (void)hipHostFree(r.pin);
+            if (r.dev) (void)hipFree(r.dev);
+            r.pin = r.dev = nullptr, r.cap = 0;
+            const size_t cap = std::max<size_t>(need + need / 2, (size_t)1 << 16);
+            GC_HIP(hipHostMalloc((void **)&r.pin, cap, hipHostMallocDefault));
+            GC_HIP(hipMalloc((void **)&r.dev, cap));
+            r.cap = cap;
+        }
+        *out = &r;
+        return GC_OK;
+    }
+};
+
+// One step's constants as one blob: in ids | out ids | row offsets | first row per piece | skeleton (zero-padded)
+struct StepBlob {
+    size_t o_in = 0, o_out = 0, o_row = 0, o_piece = 0, o_skel = 0, total = 0;
+    uint32_t npieces = 0;
+    void plan(uint32_t nin, uint32_t nout, size_t nrows, size_t nbytes) {
+        npieces = (uint32_t)((nbytes + gcsb::kPieceBytes - 1) / gcsb::kPieceBytes);
+        o_in = 0;
+        o_out = up16(o_in + 4 * (size_t)nin);
+        o_row = up16(o_out + 4 * (size_t)nout);
+        o_piece = up16(o_row + 4 * nrows);
+        o_skel = up16(o_piece + 4 * (size_t)npieces);
+        total = o_skel + up16(nbytes) + 16;
+    }
+};
+
+// fills the stage, sends it, and describes it to the kernels
+int send_step(SbCore &c, const StepBlob &b, const uint32_t *in, uint32_t nin, const uint32_t *out, uint32_t nout,
+              const std::vector<uint32_t> &row_off, const uint8_t *skel, size_t nbytes, SbStage **stp, gcsb::StepDev *dev) {
+    SbStage *st = nullptr;
+    int rc = c.stage(b.total, &st);
+    if (rc != GC_OK) return rc;
+    std::memset(st->pin, 0, b.total);
+    if (nin) std::memcpy(st->pin + b.o_in, in, 4 * (size_t)nin);
+    if (nout) std::memcpy(st->pin + b.o_out, out, 4 * (size_t)nout);
+    if (!row_off.empty()) std::memcpy(st->pin + b.o_row, row_off.data(), 4 * row_off.size());
+    uint32_t *piece = (uint32_t *)(st->pin + b.o_piece);
+    size_t r = 0;
+    for (uint32_t p = 0; p < b.npieces; p++) {
+        while (r < row_off.size() && (size_t)row_off[r] + 16 <= (size_t)p * gcsb::kPieceBytes) r++;
+        piece[p] = (uint32_t)r;
+    }
+    if (nbytes) std::memcpy(st->pin + b.o_skel, skel, nbytes);
+    GC_HIP(hipMemcpyAsync(st->dev, st->pin, b.total, hipMemcpyHostToDevice, c.ctx->stream));
+    st->used = true;  // (from here on the event must be recorded before the stage is reused: step_sent)
+    dev->skel = st->dev + b.o_skel;
+    dev->row_off = (const uint32_t *)(st->dev + b.o_row);
+    dev->piece_row = (const uint32_t *)(st->dev + b.o_piece);
+    dev->nbytes = (uint32_t)nbytes, dev->nrows = (uint32_t)row_off.size(), dev->npieces = b.npieces, dev->pad_ = 0;
+    *stp = st;
+    return GC_OK;
+}
+int step_sent(SbCore &c, SbStage *st) {
+    GC_HIP(hipEventRecord(st->done, c.ctx->stream));
+    return GC_OK;
+}
+
+// out[] with all but the LAST of equal ids marked "not stored" (Set in order: the last one wins)
+void last_wins(const uint32_t *ids, uint32_t n, std::vector<uint32_t> *marked) {
+    marked->assign(ids, ids + n);
+    std::unordered_map<uint32_t, uint32_t> seen;
+    for (uint32_t j = n; j-- > 0;)
+        if (!seen.emplace(ids[j], j).second) (*marked)[j] = kNone;
+}
+
+}  // namespace
+
+struct gc_stream_batch : SbCore {
+    uint4 *d_R = nullptr;    // [bstride]
+    uint4 *d_rnd = nullptr;  // a step's inputs in the d_rnd form of gc_batch_garble_keyed, [S][1 + nin]
+    size_t rnd_cap = 0;
+    std::vector<gc_gate> rewritten;
+    std::vector<uint8_t> skel;
+    std::vector<uint32_t> row_off, out_marked;
+    ~gc_stream_batch() {
+        if (ctx) {
+            (void)hipSetDevice(ctx->device);
+            (void)hipStreamSynchronize(ctx->stream);
+        }
+        if (d_R) (void)hipFree(d_R);
+        if (d_rnd) (void)hipFree(d_rnd);
+    }
+};
+
+struct gc_stream_eval_batch : SbCore {
+    std::vector<gc_gate> gates;
+    std::vector<uint8_t> skel;
+    std::vector<uint32_t> row_off, in_ids, out_ids;
+    std::vector<uint64_t> last_t, last_w;  // who wrote (tmp / global) wire last: generation << 32 | id
+    uint32_t gen = 0;
+};
+
+namespace {
+
+// in[] / out[] naming the same GLOBAL wire (an in-place update): the reference resolves stream.wire(index) per gate
+// (stream_garble.go:131-157), so a gate that reads the input-mapped wire after the gate that Set the output-mapped one sees
+// the NEW label.  The pass garbles from a snapshot of the inputs: such reads are redirected to the producing circuit wire —
+// the same global id and flags on the wire, so the bytes do not change (stream_garble.cpp: rewrite_aliased, restated for a
+// handle without that stream's state).  Returns whether anything was rewritten (*gates then points at s->rewritten).
+bool rewrite_aliased(gc_stream_batch *s, const gc_gate **gates, uint32_t ngates, uint32_t nwires, const uint32_t *in, uint32_t nin,
+                     const uint32_t *out, uint32_t nout) {
+    const uint32_t first_out = nwires - nout;
+    std::unordered_map<uint32_t, uint32_t> out_j;
+    for (uint32_t j = 0; j < nout; j++) out_j[out[j]] = j;
+    bool aliased = false;
+    for (uint32_t i = 0; i < nin && !aliased; i++) aliased = out_j.count(in[i]) != 0;
+    if (!aliased) return false;
+    std::vector<uint8_t> set(nout, 0);
+    s->rewritten.assign(*gates, *gates + ngates);
+    for (uint32_t g = 0; g < ngates; g++) {
+        gc_gate &q = s->rewritten[g];
+        auto redirect = [&](uint32_t w) {
+            if (w >= nin) return w;
+            auto it = out_j.find(in[w]);
+            return it != out_j.end() && set[it->second] ? first_out + it->second : w;
+        };
+        q.in0 = redirect(q.in0);
+        if (q.op != GC_INV) q.in1 = redirect(q.in1);
+        if (q.out >= first_out) set[q.out - first_out] = 1;
+    }
+    *gates = s->rewritten.data();
+    return true;
+}
+
+int garble_step(gc_stream_batch *s, const gc_gate *gates, uint32_t ngates, uint32_t nwires, const uint32_t *in, uint32_t nin,
+                const uint32_t *out, uint32_t nout, void *d_out, size_t stride, size_t *written) {
+    static const char *const what = "gc_stream_batch_garble";
+    if (!s || !written || (ngates && !gates) || (nin && !in) || (nout && !out)) return GC_E_ARG;
+    *written = 0;
+    if (ngates == 0) return GC_OK;
+    if (s->ctx->capturing) return GC_E_ARG;  // (the step's constants are a host copy)
+    int rc = GC_OK;
+    if (const char *why = step_refused(gates, ngates, nwires, nin, nout, &rc)) {
+        std::snprintf(gc::tls_error, sizeof gc::tls_error, "%s: %s", what, why);
+        return rc;
+    }
+    uint32_t mx = 0;
+    for (uint32_t i = 0; i < nin; i++) mx = std::max(mx, in[i]);
+    for (uint32_t i = 0; i < nout; i++) mx = std::max(mx, out[i]);
+    if (mx >= gcs::stream_max_wires()) return refuse(what, "a global wire id >= GC_STREAM_MAX_WIRES");
+    GC_HIP(hipSetDevice(s->ctx->device));
+    // the bytes are those of the caller's gate list; the pass runs the list with in-place reads redirected
+    s->skel.clear(), s->row_off.clear();
+    const size_t nbytes = step_skeleton(gates, ngates, nwires, in, nin, out, nout, &s->skel, &s->row_off);
+    *written = nbytes;
+    if (nbytes >= 0x7fffffffu) return refuse(what, "a step of 2 GiB or more");
+    if (!d_out || stride % 4 != 0 || stride < nbytes) return refuse(what, "stride must be a multiple of 4 and >= the step's bytes");
+    const gc_gate *run = gates;
+    rewrite_aliased(s, &run, ngates, nwires, in, nin, out, nout);
+    SbCirc *ent = nullptr;
+    rc = s->find_or_load(run, ngates, nwires, nin, nout, what, &ent);
+    if (rc != GC_OK) return rc;
+    // ---- nothing below refuses the step: the store may change now
+    rc = s->ensure(mx);
+    if (rc != GC_OK) return rc;
+    const size_t rnd_need = (size_t)s->S * (1 + (size_t)nin) * sizeof(uint4);
+    if (s->rnd_cap < rnd_need) {
+        GC_HIP(hipStreamSynchronize(s->ctx->stream));
+        if (s->d_rnd) (void)hipFree(s->d_rnd);
+        s->d_rnd = nullptr, s->rnd_cap = 0;
+        GC_HIP(hipMalloc((void **)&s->d_rnd, rnd_need + rnd_need / 2));
+        s->rnd_cap = rnd_need + rnd_need / 2;
+    }
+    last_wins(out, nout, &s->out_marked);
+    StepBlob b;
+    b.plan(nin, nout, s->row_off.size(), nbytes);
+    SbStage *st = nullptr;
+    gcsb::StepDev dev{};
+    rc = send_step(*s, b, in, nin, s->out_marked.data(), nout, s->row_off, s->skel.data(), nbytes, &st, &dev);
+    if (rc != GC_OK) return rc;
+    hipStream_t q = s->ctx->stream;
+    const uint32_t *d_in = (const uint32_t *)(st->dev + b.o_in), *d_outi = (const uint32_t *)(st->dev + b.o_out);
+    gc_batch *bt = ent->batch;
+    // 1. the step's inputs out of the store, in the d_rnd form of the keyed pass: [S][1 + nin] big-endian labels, R first
+    launch_gather(s->d_store, s->store_layout(), 0, d_in, 0, nin, nullptr, 0, s->d_rnd + 1, 1 + (size_t)nin, s->S, q);
+    gcsb::launch_rnd_form(s->d_rnd, s->d_R, s->S, 1 + nin, q);
+    hipError_t e = hipGetLastError();
+    // 2. one keyed batch pass of S instances
+    if (e == hipSuccess) rc = gc_batch_garble_keyed(bt, s->d_keys, s->keylen, s->d_rnd);
+    if (e == hipSuccess && rc == GC_OK) {
+        // 3. the output L0s into the store through out[]; 4. every session's bytes
+        gcsb::launch_rows(bt->d_W, bt->g.lw, ent->circ->d_out_slots, s->d_store, s->store_layout(), d_outi, nout, s->S, q);
+        gcsb::launch_serialise(dev, bt->d_T, bt->g.lt, (uint8_t *)d_out, stride, s->S, q);
+        e = hipGetLastError();
+    }
+    const int rce = step_sent(*s, st);
+    GC_HIP(e);
+    return rc != GC_OK ? rc : rce;
+}
+
+// One OpCircuit block as the peer sent it, parsed into a single-assignment gate list — the gate loop of stream_eval.cpp's
+// eval_block (stream_evaluator.go:272-345) with the same refusals, restated for a handle without that stream's skeleton
+// and queue state.  Wire ids of the device circuit: [0, nin) the global wires read before the block writes them, in order
+// of first use; then one id per gate, first the gates that write a tmp wire, last the gates that write a global wire: those
+// are the outputs.  skel = the block's bytes with its rows zeroed.
+int parse_block(gc_stream_eval_batch *e, uint32_t ngates, uint32_t ntmp, uint32_t nwires, const uint8_t *buf, size_t len, size_t *used) {
+    if (e->last_t.size() < ntmp) e->last_t.resize(ntmp, 0);
+    if (++e->gen == 0) {
+        std::fill(e->last_t.begin(), e->last_t.end(), 0);
+        std::fill(e->last_w.begin(), e->last_w.end(), 0);
+        e->gen = 1;
+    }
+    const uint64_t gen = e->gen;
+    struct Parsed {
+        uint32_t in0, in1, op;
+        bool tmp;
+    };
+    std::vector<Parsed> ps(ngates);
+    std::vector<std::pair<uint32_t, uint32_t>> glob;  // (gate, global wire) of the gates that write a global wire
+    e->in_ids.clear(), e->row_off.clear();
+    static const uint8_t kRowsOf[5] = {0, 0, 2, 3, 1}, kWiresOf[5] = {3, 3, 3, 3, 2};
+    auto touch_w = [&](uint32_t idx) {
+        if (idx >= e->last_w.size()) e->last_w.resize((size_t)idx + 1 + e->last_w.size() / 2, 0);
+    };
+    size_t pos = 0;
+    for (uint32_t g = 0; g < ngates; g++) {
+        if (pos + 1 > len) return GC_E_ROWS;
+        uint8_t gop = buf[pos++];
+        const bool at = gop & 0x80, bt = gop & 0x40, ct = gop & 0x20, shortf = gop & 0x10;
+        gop &= 0x0f;
+        if (gop > GC_INV) return GC_E_GATE;  // "invalid operation"
+        const int nw = kWiresOf[gop];
+        const uint32_t rows = kRowsOf[gop], idsz = shortf ? 2u : 4u;
+        if (pos + (size_t)idsz * nw + 16 * (size_t)rows > len) return GC_E_ROWS;
+        uint32_t w[3] = {0, 0, 0};
+        for (int i = 0; i < nw; i++, pos += idsz)
+            w[i] = shortf ? ((uint32_t)buf[pos] << 8) | buf[pos + 1]
+                          : ((uint32_t)buf[pos] << 24) | ((uint32_t)buf[pos + 1] << 16) | ((uint32_t)buf[pos + 2] << 8) | buf[pos + 3];
+        int err = GC_OK;
+        auto use = [&](bool t, uint32_t idx) -> uint32_t {  // current id of a wire; bit 31: a circuit input
+            if (t) {
+                if (idx >= ntmp || (e->last_t[idx] >> 32) != gen) {  // tmp wires are private to their block
+                    err = GC_E_ARG;
+                    return 0;
+                }
+                return (uint32_t)e->last_t[idx];
+            }
+            if (idx >= nwires) {
+                err = GC_E_ARG;
+                return 0;
+            }
+            touch_w(idx);
+            if ((e->last_w[idx] >> 32) == gen) return (uint32_t)e->last_w[idx];
+            const uint32_t id = 0x80000000u | (uint32_t)e->in_ids.size();
+            e->in_ids.push_back(idx);
+            e->last_w[idx] = (gen << 32) | id;
+            return id;
+        };
+        Parsed &k = ps[g];
+        k.in0 = use(at, w[0]);
+        k.in1 = nw == 3 ? use(bt, w[1]) : k.in0;
+        if (err != GC_OK) return err;
+        k.op = gop, k.tmp = ct;
+        const uint32_t ci = w[nw - 1];
+        if (ct) {
+            if (ci >= ntmp) return GC_E_ARG;
+            e->last_t[ci] = (gen << 32) | g;
+        } else {
+            if (ci >= nwires) return GC_E_ARG;
+            touch_w(ci);
+            e->last_w[ci] = (gen << 32) | g;
+            glob.emplace_back(g, ci);
+        }
+        for (uint32_t r = 0; r < rows; r++, pos += 16) e->row_off.push_back((uint32_t)pos);
+    }
+    const uint32_t nin = (uint32_t)e->in_ids.size(), nout = (uint32_t)glob.size(), n_tmp = ngates - nout;
+    std::vector<uint32_t> id_of(ngates);
+    uint32_t kt = 0, kg = 0;
+    for (uint32_t g = 0; g < ngates; g++) id_of[g] = ps[g].tmp ? nin + kt++ : nin + n_tmp + kg++;
+    auto fix = [&](uint32_t v) { return (v & 0x80000000u) ? (v & 0x7fffffffu) : id_of[v]; };
+    e->gates.assign(ngates, gc_gate{});
+    for (uint32_t g = 0; g < ngates; g++) {
+        e->gates[g].in0 = fix(ps[g].in0);
+        e->gates[g].in1 = ps[g].op == GC_INV ? 0 : fix(ps[g].in1);
+        e->gates[g].out = id_of[g];
+        e->gates[g].op = (uint8_t)ps[g].op;
+    }
+    // only the LAST gate of the block that writes a global wire stores it (streaming.Set in gate order)
+    e->out_ids.resize(nout);
+    for (uint32_t k = 0; k < nout; k++) e->out_ids[k] = (uint32_t)e->last_w[glob[k].second] == glob[k].first ? glob[k].second : kNone;
+    e->skel.assign(buf, buf + pos);
+    for (uint32_t off : e->row_off) std::memset(e->skel.data() + off, 0, 16);
+    *used = pos;
+    return GC_OK;
+}
+
+int eval_step(gc_stream_eval_batch *e, uint32_t ngates, uint32_t ntmp, uint32_t nwires, const uint8_t *ref, size_t len,
+              const void *d_blocks, size_t stride, void *d_bad, size_t *consumed) {
+    static const char *const what = "gc_stream_eval_batch_circuit";
+    if (!e || !consumed || (!ref && len) || !d_bad) return GC_E_ARG;
+    *consumed = 0;
+    // the block is the peer's data: the same bounds as gc_stream_eval_circuit, before anything is sized by it
+    if ((uint64_t)ntmp > 64ull * ngates + (1u << 20) || nwires > gcs::stream_max_wires()) return GC_E_ARG;
+    if ((size_t)ngates > len / 5) return GC_E_ROWS;
+    if (e->ctx->capturing) return GC_E_ARG;
+    GC_HIP(hipSetDevice(e->ctx->device));
+    hipStream_t q = e->ctx->stream;
+    GC_HIP(hipMemsetAsync(d_bad, 0, (size_t)e->S * sizeof(uint32_t), q));
+    if (ngates == 0) return GC_OK;
+    size_t pos = 0;
+    int rc = parse_block(e, ngates, ntmp, nwires, ref, len, &pos);
+    if (rc != GC_OK) return rc;
+    if (pos >= 0x7fffffffu) return refuse(what, "a block of 2 GiB or more");
+    if (!d_blocks || stride % 4 != 0 || stride < len) return refuse(what, "stride must be a multiple of 4 and >= len");
+    const uint32_t nin = (uint32_t)e->in_ids.size(), nout = (uint32_t)e->out_ids.size();
+    SbCirc *ent = nullptr;
+    rc = e->find_or_load(e->gates.data(), ngates, nin + ngates, nin, nout, what, &ent);
+    if (rc != GC_OK) return rc;
+    uint32_t mx = 0;
+    for (uint32_t id : e->in_ids) mx = std::max(mx, id);
+    for (uint32_t id : e->out_ids) mx = std::max(mx, id == kNone ? 0u : id);
+    rc = e->ensure(mx);
+    if (rc != GC_OK) return rc;
+    StepBlob b;
+    b.plan(nin, nout, e->row_off.size(), pos);
+    SbStage *st = nullptr;
+    gcsb::StepDev dev{};
+    rc = send_step(*e, b, e->in_ids.data(), nin, e->out_ids.data(), nout, e->row_off, e->skel.data(), pos, &st, &dev);
+    if (rc != GC_OK) return rc;
+    const uint32_t *d_in = (const uint32_t *)(st->dev + b.o_in), *d_outi = (const uint32_t *)(st->dev + b.o_out);
+    gc_batch *bt = ent->batch;
+    // 1. + 2. skeleton compare and the rows into the batch's table array; 3. the inputs out of the store
+    gcsb::launch_ingest(dev, bt->d_T, bt->g.lt, (const uint8_t *)d_blocks, stride, e->S, (uint32_t *)d_bad, q);
+    gcsb::launch_rows(e->d_store, e->store_layout(), d_in, bt->d_W, bt->g.lw, nullptr, nin, e->S, q);
+    hipError_t err = hipGetLastError();
+    // 4. one keyed batch pass; 5. the outputs into the store
+    if (err == hipSuccess) rc = gc_batch_eval_keyed(bt, e->d_keys, e->keylen, bt);
+    if (err == hipSuccess && rc == GC_OK) {
+        gcsb::launch_rows(bt->d_W, bt->g.lw, ent->circ->d_out_slots, e->d_store, e->store_layout(), d_outi, nout, e->S, q);
+        err = hipGetLastError();
+    }
+    const int rce = step_sent(*e, st);
+    GC_HIP(err);
+    if (rc == GC_OK && rce == GC_OK) *consumed = pos;
+    return rc != GC_OK ? rc : rce;
+}
+
+// ids[] on the device for the length of one call (a host copy: the call waits for it)
+int ids_to_device(SbCore &c, const uint32_t *ids, uint32_t n, DevBuf *d) {
+    GC_HIP(d->alloc(4 * (size_t)n));
+    GC_HIP(hipMemcpyAsync(d->p, ids, 4 * (size_t)n, hipMemcpyHostToDevice, c.ctx->stream));
+    return GC_OK;
+}
+
+// one column of the store: wire w of every session (zero if the store never grew that far)
+int read_column(SbCore &c, uint32_t w, std::vector<gc_label> *col) {
+    col->assign(c.S, gc_label{0, 0});
+    GC_HIP(hipSetDevice(c.ctx->device));
+    if (w < c.rows)
+        GC_HIP(hipMemcpyAsync(col->data(), c.d_store + (size_t)w * c.bstride, (size_t)c.S * sizeof(gc_label), hipMemcpyDeviceToHost,
+                              c.ctx->stream));
+    GC_HIP(hipStreamSynchronize(c.ctx->stream));
+    return GC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+gc_stream_batch *gc_stream_batch_create(gc_ctx *ctx, uint32_t sessions, const void *d_keys, size_t keylen, const void *d_rnd,
+                                        const uint32_t *inputs, uint32_t ninputs, int *status) try {
+    int rc = GC_OK;
+    std::unique_ptr<gc_stream_batch> s(new (std::nothrow) gc_stream_batch);
+    if (!s) rc = GC_E_NOMEM;
+    if (rc == GC_OK && (!d_rnd || (ninputs && !inputs))) rc = GC_E_ARG;
+    if (rc == GC_OK) rc = s->init(ctx, sessions, d_keys, keylen);
+    uint32_t mx = 0;
+    for (uint32_t i = 0; rc == GC_OK && i < ninputs; i++) mx = std::max(mx, inputs[i]);
+    if (rc == GC_OK && mx >= gcs::stream_max_wires()) rc = refuse("gc_stream_batch_create", "an input wire id >= GC_STREAM_MAX_WIRES");
+    auto setup = [&]() -> int {
+        GC_HIP(hipMalloc((void **)&s->d_R, (size_t)s->bstride * sizeof(uint4)));
+        GC_HIP(hipMemsetAsync(s->d_R, 0, (size_t)s->bstride * sizeof(uint4), ctx->stream));
+        int r = s->ensure(mx);
+        if (r != GC_OK) return r;
+        std::vector<uint32_t> ids;
+        last_wins(inputs, ninputs, &ids);  // (NewStreaming Sets the inputs in order, stream_garble.go:62-72)
+        DevBuf d;
+        r = ids_to_device(*s, ids.data(), ninputs, &d);
+        if (r != GC_OK) return r;
+        gcsb::launch_init_store((const uint4 *)d_rnd, (const uint32_t *)d.p, ninputs, s->d_store, s->bstride, s->d_R, s->S, ctx->stream);
+        GC_HIP(hipGetLastError());
+        GC_HIP(hipStreamSynchronize(ctx->stream));
+        return GC_OK;
+    };
+    if (rc == GC_OK) rc = setup();
+    if (status) *status = rc;
+    return rc == GC_OK ? s.release() : nullptr;
+} catch (...) {
+    const int rc__ = gc::on_exception();
+    if (status) *status = rc__;
+    return nullptr;
+}
+
+void gc_stream_batch_free(gc_stream_batch *s) { delete s; }
+
+size_t gc_stream_batch_step_bytes(const gc_gate *gates, uint32_t ngates, uint32_t nwires, const uint32_t *in, uint32_t nin,
+                                  const uint32_t *out, uint32_t nout) try {
+    if ((ngates && !gates) || (nin && !in) || (nout && !out)) return 0;
+    int rc = GC_OK;
+    if (const char *why = step_refused(gates, ngates, nwires, nin, nout, &rc)) {
+        std::snprintf(gc::tls_error, sizeof gc::tls_error, "gc_stream_batch_step_bytes: %s", why);
+        return 0;
+    }
+    return step_skeleton(gates, ngates, nwires, in, nin, out, nout, nullptr, nullptr);
+} catch (...) {
+    (void)gc::on_exception();
+    return 0;
+}
+
+int gc_stream_batch_garble(gc_stream_batch *s, const gc_gate *gates, uint32_t ngates, uint32_t nwires, const uint32_t *in,
+                           uint32_t nin, const uint32_t *out, uint32_t nout, void *d_out, size_t stride, size_t *written) try {
+    return garble_step(s, gates, ngates, nwires, in, nin, out, nout, d_out, stride, written);
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_stream_batch_get_wire(gc_stream_batch *s, uint32_t w, gc_wire *out) try {
+    if (!s || !out) return GC_E_ARG;
+    std::vector<gc_label> l0, r(s->S);
+    int rc = read_column(*s, w, &l0);
+    if (rc != GC_OK) return rc;
+    GC_HIP(hipMemcpy(r.data(), s->d_R, (size_t)s->S * sizeof(gc_label), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < s->S; i++) out[i] = gc_wire{l0[i], gc_label{l0[i].d0 ^ r[i].d0, l0[i].d1 ^ r[i].d1}};
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_stream_batch_gather_wires(gc_stream_batch *s, const uint32_t *ids, uint32_t n, void *d_wires_out) try {
+    if (!s || (n && (!ids || !d_wires_out))) return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    uint32_t mx = 0;
+    for (uint32_t i = 0; i < n; i++) mx = std::max(mx, ids[i]);
+    if (mx >= gcs::stream_max_wires()) return refuse("gc_stream_batch_gather_wires", "a wire id >= GC_STREAM_MAX_WIRES");
+    GC_HIP(hipSetDevice(s->ctx->device));
+    int rc = s->ensure(mx);  // (a wire never set reads as (0, R))
+    if (rc != GC_OK) return rc;
+    StepBlob b;
+    b.plan(n, 0, 0, 0);
+    SbStage *st = nullptr;
+    gcsb::StepDev dev{};
+    rc = send_step(*s, b, ids, n, nullptr, 0, {}, nullptr, 0, &st, &dev);
+    if (rc != GC_OK) return rc;
+    launch_gather(s->d_store, s->store_layout(), 0, (const uint32_t *)(st->dev + b.o_in), 0, n, s->d_R, 1, (uint4 *)d_wires_out,
+                  2 * (size_t)n, s->S, s->ctx->stream);
+    const hipError_t e = hipGetLastError();
+    rc = step_sent(*s, st);
+    GC_HIP(e);
+    return rc;
+} catch (...) {
+    return gc::on_exception();
+}
+
+gc_stream_eval_batch *gc_stream_eval_batch_create(gc_ctx *ctx, uint32_t sessions, const void *d_keys, size_t keylen, int *status) try {
+    int rc = GC_OK;
+    std::unique_ptr<gc_stream_eval_batch> e(new (std::nothrow) gc_stream_eval_batch);
+    if (!e) rc = GC_E_NOMEM;
+    if (rc == GC_OK) rc = e->init(ctx, sessions, d_keys, keylen);
+    if (rc == GC_OK) rc = e->ensure(0);
+    if (status) *status = rc;
+    return rc == GC_OK ? e.release() : nullptr;
+} catch (...) {
+    const int rc__ = gc::on_exception();
+    if (status) *status = rc__;
+    return nullptr;
+}
+
+void gc_stream_eval_batch_free(gc_stream_eval_batch *e) { delete e; }
+
+int gc_stream_eval_batch_set_wires(gc_stream_eval_batch *e, const uint32_t *ids, uint32_t n, const void *d_labels) try {
+    if (!e || (n && (!ids || !d_labels))) return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    uint32_t mx = 0;
+    for (uint32_t i = 0; i < n; i++) mx = std::max(mx, ids[i]);
+    if (mx >= gcs::stream_max_wires()) return refuse("gc_stream_eval_batch_set_wires", "a wire id >= GC_STREAM_MAX_WIRES");
+    GC_HIP(hipSetDevice(e->ctx->device));
+    int rc = e->ensure(mx);
+    if (rc != GC_OK) return rc;
+    std::vector<uint32_t> marked;
+    last_wins(ids, n, &marked);
+    StepBlob b;
+    b.plan(n, 0, 0, 0);
+    SbStage *st = nullptr;
+    gcsb::StepDev dev{};
+    rc = send_step(*e, b, marked.data(), n, nullptr, 0, {}, nullptr, 0, &st, &dev);
+    if (rc != GC_OK) return rc;
+    launch_scatter((const uint4 *)d_labels, n, n, (const uint32_t *)(st->dev + b.o_in), 0, e->d_store, e->store_layout(), 0, e->S,
+                   e->ctx->stream);
+    const hipError_t err = hipGetLastError();
+    rc = step_sent(*e, st);
+    GC_HIP(err);
+    return rc;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_stream_eval_batch_get_wire(gc_stream_eval_batch *e, uint32_t w, gc_label *out) try {
+    if (!e || !out) return GC_E_ARG;
+    std::vector<gc_label> col;
+    int rc = read_column(*e, w, &col);
+    if (rc == GC_OK) std::memcpy(out, col.data(), (size_t)e->S * sizeof(gc_label));
+    return rc;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_stream_eval_batch_circuit(gc_stream_eval_batch *e, uint32_t ngates, uint32_t ntmp, uint32_t nwires, const uint8_t *ref_block,
+                                 size_t len, const void *d_blocks, size_t stride, void *d_bad, size_t *consumed) try {
+    return eval_step(e, ngates, ntmp, nwires, ref_block, len, d_blocks, stride, d_bad, consumed);
+} catch (...) {
+    return gc::on_exception();
+}
+
+}  // extern "C"

@@ -1,0 +1,187 @@
+// stream_batch_kernels.hip — the kernels around the keyed batch pass of a session-batched streaming step (stream_batch.h):
+// the movers between the per-handle wire store [wire id][bstride] and a step's batch, and the serialiser / ingester of the
+// stream wire format (circuit/stream_garble.go:391-446) for S byte streams at once.
+#include "stream_batch.h"
+
+namespace gcsb {
+
+using gc::Layout;
+
+namespace {
+
+__device__ __forceinline__ uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
+// ot.Label <-> its 16 big-endian bytes loaded as a uint4 of little-endian words (its own inverse)
+__device__ __forceinline__ uint4 label_be(uint4 v) { return make_uint4(bswap32(v.y), bswap32(v.x), bswap32(v.w), bswap32(v.z)); }
+
+__global__ __launch_bounds__(kThreads) void k_sb_rnd_form(uint4 *__restrict__ rnd, const uint4 *__restrict__ R, uint32_t S,
+                                                          uint32_t n1) {
+    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= (size_t)S * n1) return;
+    const uint32_t s = (uint32_t)(i / n1), j = (uint32_t)(i % n1);
+    rnd[i] = label_be(j == 0 ? R[s] : rnd[i]);
+}
+
+__global__ __launch_bounds__(kThreads) void k_sb_init_store(const uint4 *__restrict__ rnd, const uint32_t *__restrict__ ids,
+                                                            uint32_t n, uint4 *__restrict__ store, uint32_t bstride,
+                                                            uint4 *__restrict__ R, uint32_t S) {
+    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= (size_t)S * (n + 1)) return;
+    const uint32_t s = (uint32_t)(i / (n + 1)), j = (uint32_t)(i % (n + 1));
+    uint4 v = label_be(rnd[i]);
+    if (j == 0) {
+        v.y |= 0x80000000u;  // R.SetS(true) (stream_garble.go:60)
+        R[s] = v;
+    } else if (ids[j - 1] != 0xffffffffu) {
+        store[(size_t)ids[j - 1] * bstride + s] = v;
+    }
+}
+
+// lanes along the sessions: one row of the level-layout store is one coalesced run
+__global__ __launch_bounds__(kThreads) void k_sb_rows(const uint4 *__restrict__ src, Layout sl, const uint32_t *__restrict__ srow,
+                                                      uint4 *__restrict__ dst, Layout dl, const uint32_t *__restrict__ drow,
+                                                      uint32_t n, uint32_t S) {
+    const uint32_t s = blockIdx.x * kThreads + threadIdx.x;
+    if (s >= S) return;
+    for (uint32_t j = blockIdx.y; j < n; j += gridDim.y) {
+        const uint32_t sr = srow ? srow[j] : j, dr = drow ? drow[j] : j;
+        if (sr != 0xffffffffu && dr != 0xffffffffu) dst[dl.at(dr, s)] = src[sl.at(sr, s)];
+    }
+}
+
+// The piece [lo, lo + nb) of one session's bytes lives in LDS at stage + sh, sh = the low four bits of its global address, so
+// that everything but the two ragged ends moves as whole, aligned 16-byte lines.  (Byte accesses to global memory with every
+// lane in another cache line cost the one-session serialiser 30 us per 4 000 gates: stream_serialise.cpp.)
+__device__ __forceinline__ void piece_out(const uint8_t *stage, uint8_t *dst, uint32_t sh, uint32_t nb) {
+    const uint32_t head = min(nb, (16u - sh) & 15u);
+    const uint32_t body = (nb - head) >> 4, tail = (nb - head) & 15u;
+    if (threadIdx.x < head) dst[threadIdx.x] = stage[sh + threadIdx.x];
+    const uint4 *src16 = (const uint4 *)(stage + sh + head);
+    uint4 *dst16 = (uint4 *)(dst + head);
+    for (uint32_t k = threadIdx.x; k < body; k += kThreads) dst16[k] = src16[k];
+    if (threadIdx.x < tail) dst[head + 16u * body + threadIdx.x] = stage[sh + head + 16u * body + threadIdx.x];
+}
+__device__ __forceinline__ void piece_in(uint8_t *stage, const uint8_t *src, uint32_t sh, uint32_t nb) {
+    const uint32_t head = min(nb, (16u - sh) & 15u);
+    const uint32_t body = (nb - head) >> 4, tail = (nb - head) & 15u;
+    if (threadIdx.x < head) stage[sh + threadIdx.x] = src[threadIdx.x];
+    uint4 *dst16 = (uint4 *)(stage + sh + head);
+    const uint4 *src16 = (const uint4 *)(src + head);
+    for (uint32_t k = threadIdx.x; k < body; k += kThreads) dst16[k] = src16[k];
+    if (threadIdx.x < tail) stage[sh + head + 16u * body + threadIdx.x] = src[head + 16u * body + threadIdx.x];
+}
+
+// room for the piece, its shift, and the 15 bytes by which a row that starts in the piece may reach beyond it
+constexpr uint32_t kStageBytes = kPieceBytes + 48;
+
+__global__ __launch_bounds__(kThreads) void k_sb_serialise(StepDev d, const uint4 *__restrict__ T, Layout lt,
+                                                           uint8_t *__restrict__ out, size_t stride) {
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
+    const uint32_t p = blockIdx.x, s = blockIdx.y;
+    const uint32_t lo = p * kPieceBytes, hi = min(lo + kPieceBytes, d.nbytes), nb = hi - lo;
+    uint8_t *dst = out + (size_t)s * stride + lo;
+    const uint32_t sh = (uint32_t)((uintptr_t)dst & 15u);
+    // the skeleton of the piece (the same for every session), a word per lane
+    const uint32_t *sk = (const uint32_t *)(d.skel + lo);
+    for (uint32_t k = threadIdx.x; 4 * k < nb; k += kThreads) {
+        const uint32_t w = sk[k];
+        uint8_t *q = stage + sh + 4 * k;
+        q[0] = (uint8_t)w, q[1] = (uint8_t)(w >> 8), q[2] = (uint8_t)(w >> 16), q[3] = (uint8_t)(w >> 24);
+    }
+    __syncthreads();
+    // this session's rows: every row that has a byte in [lo, hi) — a row across a piece boundary is written by both pieces
+    for (uint32_t r = d.piece_row[p] + threadIdx.x; r < d.nrows; r += kThreads) {
+        const uint32_t off = d.row_off[r];
+        if (off >= hi) break;
+        const uint4 v = label_be(T[lt.at(r, s)]);
+        const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (uint32_t k = 0; k < 16; k++) {
+            const uint32_t at = off + k;
+            if (at >= lo && at < hi) stage[sh + at - lo] = (uint8_t)(w4[k >> 2] >> (8 * (k & 3)));
+        }
+    }
+    __syncthreads();
+    piece_out(stage, dst, sh, nb);
+}
+
+__global__ __launch_bounds__(kThreads) void k_sb_ingest(StepDev d, uint4 *__restrict__ T, Layout lt, const uint8_t *__restrict__ in,
+                                                        size_t stride, uint32_t *__restrict__ bad) {
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
+    const uint32_t p = blockIdx.x, s = blockIdx.y;
+    const uint32_t lo = p * kPieceBytes, hi = min(lo + kPieceBytes, d.nbytes), nb = hi - lo;
+    const uint32_t ext = min(hi + 15u, d.nbytes) - lo;  // with the tail of a row that starts before hi (all inside the block)
+    const uint8_t *src = in + (size_t)s * stride + lo;
+    const uint32_t sh = (uint32_t)((uintptr_t)src & 15u);
+    piece_in(stage, src, sh, ext);
+    __syncthreads();
+    // rows that START in the piece go to the table array (every offset is the skeleton's: nothing here depends on the bytes)
+    const uint32_t r0 = d.piece_row[p];
+    for (uint32_t r = r0 + threadIdx.x; r < d.nrows; r += kThreads) {
+        const uint32_t off = d.row_off[r];
+        if (off >= hi) break;
+        if (off < lo) continue;
+        const uint8_t *q = stage + sh + (off - lo);
+        uint32_t w4[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++)
+            w4[k] = (uint32_t)q[4 * k] | ((uint32_t)q[4 * k + 1] << 8) | ((uint32_t)q[4 * k + 2] << 16) | ((uint32_t)q[4 * k + 3] << 24);
+        T[lt.at(r, s)] = label_be(make_uint4(w4[0], w4[1], w4[2], w4[3]));
+    }
+    __syncthreads();
+    // ... and every row byte of the piece becomes zero, as in the skeleton: what is left to compare is structure
+    for (uint32_t r = r0 + threadIdx.x; r < d.nrows; r += kThreads) {
+        const uint32_t off = d.row_off[r];
+        if (off >= hi) break;
+#pragma unroll
+        for (uint32_t k = 0; k < 16; k++) {
+            const uint32_t at = off + k;
+            if (at >= lo && at < hi) stage[sh + at - lo] = 0;
+        }
+    }
+    __syncthreads();
+    const uint32_t *sk = (const uint32_t *)(d.skel + lo);
+    uint32_t diff = 0;
+    for (uint32_t k = threadIdx.x; 4 * k < nb; k += kThreads) {
+        const uint8_t *q = stage + sh + 4 * k;
+        const uint32_t have = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+        uint32_t x = have ^ sk[k];
+        if (nb - 4 * k < 4) x &= (1u << (8 * (nb - 4 * k))) - 1u;  // (the last word of the step may reach past its bytes)
+        diff += ((x & 0xffu) != 0) + ((x & 0xff00u) != 0) + ((x & 0xff0000u) != 0) + ((x & 0xff000000u) != 0);
+    }
+    for (int o = 32; o > 0; o >>= 1) diff += __shfl_down(diff, o, 64);
+    if ((threadIdx.x & 63) == 0 && diff) atomicAdd(bad + s, diff);
+}
+
+}  // namespace
+
+void launch_rnd_form(uint4 *rnd, const uint4 *R, uint32_t S, uint32_t n1, hipStream_t s) {
+    const size_t n = (size_t)S * n1;
+    hipLaunchKernelGGL(k_sb_rnd_form, dim3((uint32_t)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, rnd, R, S, n1);
+}
+
+void launch_init_store(const uint4 *rnd, const uint32_t *ids, uint32_t n, uint4 *store, uint32_t bstride, uint4 *R, uint32_t S,
+                       hipStream_t s) {
+    const size_t tot = (size_t)S * (n + 1);
+    hipLaunchKernelGGL(k_sb_init_store, dim3((uint32_t)((tot + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, rnd, ids, n, store,
+                       bstride, R, S);
+}
+
+void launch_rows(const uint4 *src, const Layout &sl, const uint32_t *srow, uint4 *dst, const Layout &dl, const uint32_t *drow,
+                 uint32_t n, uint32_t S, hipStream_t s) {
+    if (n == 0 || S == 0) return;
+    hipLaunchKernelGGL(k_sb_rows, dim3((S + kThreads - 1) / kThreads, n < 65535u ? n : 65535u), dim3(kThreads), 0, s, src, sl, srow, dst, dl,
+                       drow, n, S);
+}
+
+void launch_serialise(const StepDev &d, const uint4 *T, const Layout &lt, uint8_t *out, size_t stride, uint32_t S, hipStream_t s) {
+    if (d.npieces == 0 || S == 0) return;
+    hipLaunchKernelGGL(k_sb_serialise, dim3(d.npieces, S), dim3(kThreads), 0, s, d, T, lt, out, stride);
+}
+
+void launch_ingest(const StepDev &d, uint4 *T, const Layout &lt, const uint8_t *in, size_t stride, uint32_t S, uint32_t *bad,
+                   hipStream_t s) {
+    if (d.npieces == 0 || S == 0) return;
+    hipLaunchKernelGGL(k_sb_ingest, dim3(d.npieces, S), dim3(kThreads), 0, s, d, T, lt, in, stride, bad);
+}
+
+}  // namespace gcsb

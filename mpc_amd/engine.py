@@ -125,6 +125,17 @@ def lib():
         "gc_stream_eval_circuit": (i32, [vp, u32, u32, u32, vp, sz, C.POINTER(C.c_size_t)]),
         "gc_stream_eval_blocks": (i32, [vp, vp, sz, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
         "gc_stream_eval_stats": (i32, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "gc_stream_batch_create": (vp, [vp, u32, vp, sz, vp, vp, u32, ip]),
+        "gc_stream_batch_free": (None, [vp]),
+        "gc_stream_batch_step_bytes": (sz, [vp, u32, u32, vp, u32, vp, u32]),
+        "gc_stream_batch_garble": (i32, [vp, vp, u32, u32, vp, u32, vp, u32, vp, sz, C.POINTER(C.c_size_t)]),
+        "gc_stream_batch_get_wire": (i32, [vp, u32, vp]),
+        "gc_stream_batch_gather_wires": (i32, [vp, vp, u32, vp]),
+        "gc_stream_eval_batch_create": (vp, [vp, u32, vp, sz, ip]),
+        "gc_stream_eval_batch_free": (None, [vp]),
+        "gc_stream_eval_batch_set_wires": (i32, [vp, vp, u32, vp]),
+        "gc_stream_eval_batch_get_wire": (i32, [vp, u32, vp]),
+        "gc_stream_eval_batch_circuit": (i32, [vp, u32, u32, u32, vp, sz, vp, sz, vp, C.POINTER(C.c_size_t)]),
         "gc_batch_create": (vp, [vp, u32, ip]),
         "gc_batch_free": (None, [vp]),
         "gc_ctx_capture_begin": (i32, [vp]),
@@ -1008,6 +1019,90 @@ class StreamEval:
     def close(self):
         if self.h:
             lib().gc_stream_eval_free(self.h)
+            self.h = None
+
+
+def stream_batch_step_bytes(gates, nwires, in_, out_):
+    """gc_stream_batch_step_bytes (host only): the bytes Streaming.Garble writes for this step, the same for every session; 0
+    for a step gc_stream_batch_garble refuses by its shape (lib().gc_last_error() says why)"""
+    g = np.ascontiguousarray(gates, dtype=GATE)
+    i = np.ascontiguousarray(in_, dtype=np.uint32)
+    o = np.ascontiguousarray(out_, dtype=np.uint32)
+    return lib().gc_stream_batch_step_bytes(_p(g), len(g), nwires, _p(i), len(i), _p(o), len(o))
+
+
+class StreamBatch:
+    """gc_stream_batch: NewStreaming / Streaming.Garble / GetInput for S sessions of one program per call.  d_keys: device
+    u8 [S][keylen]; d_rnd: device u8 [S][1 + len(inputs)][16]."""
+
+    def __init__(self, ctx, sessions, d_keys, keylen, d_rnd, inputs):
+        self.sessions = sessions
+        inp = np.ascontiguousarray(inputs, dtype=np.uint32)
+        st = C.c_int(0)
+        self.h = lib().gc_stream_batch_create(ctx.h, sessions, _dp(d_keys), keylen, _dp(d_rnd), _p(inp), len(inp), C.byref(st))
+        if not self.h:
+            raise EngineError(st.value, "gc_stream_batch_create")
+
+    def garble(self, gates, nwires, in_, out_, d_out, stride):
+        """queues one step for every session; returns its byte count (session s's bytes: d_out + s * stride)"""
+        g = np.ascontiguousarray(gates, dtype=GATE)
+        i = np.ascontiguousarray(in_, dtype=np.uint32)
+        o = np.ascontiguousarray(out_, dtype=np.uint32)
+        n = C.c_size_t(0)
+        _check(lib().gc_stream_batch_garble(self.h, _p(g), len(g), nwires, _p(i), len(i), _p(o), len(o), _dp(d_out), stride,
+                                            C.byref(n)), "gc_stream_batch_garble")
+        return n.value
+
+    def get(self, w):
+        """WIRE [S]: both labels of global wire w in every session (waits for the ctx stream)"""
+        out = np.zeros(self.sessions, WIRE)
+        _check(lib().gc_stream_batch_get_wire(self.h, w, _p(out)), "gc_stream_batch_get_wire")
+        return out
+
+    def gather_wires(self, ids, d_wires_out):
+        """{L0, L0 ^ R} of the named wires as gc_wire [S][len(ids)] in device memory; asynchronous"""
+        i = np.ascontiguousarray(ids, dtype=np.uint32)
+        _check(lib().gc_stream_batch_gather_wires(self.h, _p(i), len(i), _dp(d_wires_out)), "gc_stream_batch_gather_wires")
+
+    def close(self):
+        if self.h:
+            lib().gc_stream_batch_free(self.h)
+            self.h = None
+
+
+class StreamEvalBatch:
+    """gc_stream_eval_batch: the store of StreamEval and one OpCircuit block per call for S sessions of one program"""
+
+    def __init__(self, ctx, sessions, d_keys, keylen):
+        self.sessions = sessions
+        st = C.c_int(0)
+        self.h = lib().gc_stream_eval_batch_create(ctx.h, sessions, _dp(d_keys), keylen, C.byref(st))
+        if not self.h:
+            raise EngineError(st.value, "gc_stream_eval_batch_create")
+
+    def set_wires(self, ids, d_labels):
+        """d_labels: device gc_label [S][len(ids)]; asynchronous"""
+        i = np.ascontiguousarray(ids, dtype=np.uint32)
+        _check(lib().gc_stream_eval_batch_set_wires(self.h, _p(i), len(i), _dp(d_labels)), "gc_stream_eval_batch_set_wires")
+
+    def get(self, w):
+        """LABEL [S]: the active label of global wire w in every session (waits for the ctx stream)"""
+        out = np.zeros(self.sessions, LABEL)
+        _check(lib().gc_stream_eval_batch_get_wire(self.h, w, _p(out)), "gc_stream_eval_batch_get_wire")
+        return out
+
+    def circuit(self, ngates, ntmp, nwires, ref_block, d_blocks, stride, d_bad):
+        """one OpCircuit block of every session: ref_block = host bytes of any one session's block, d_blocks = all of them in
+        device memory `stride` apart, d_bad = device u32 [S] (differing skeleton bytes per session); returns the bytes used"""
+        b = np.frombuffer(bytes(ref_block), np.uint8) if len(ref_block) else np.zeros(1, np.uint8)
+        n = C.c_size_t(0)
+        _check(lib().gc_stream_eval_batch_circuit(self.h, ngates, ntmp, nwires, _p(b), len(ref_block), _dp(d_blocks), stride,
+                                                  _dp(d_bad), C.byref(n)), "gc_stream_eval_batch_circuit")
+        return n.value
+
+    def close(self):
+        if self.h:
+            lib().gc_stream_eval_batch_free(self.h)
             self.h = None
 
 

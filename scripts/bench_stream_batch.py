@@ -1,0 +1,220 @@
+"""S sessions of one streamed program per call (gc_stream_batch_* / gc_stream_eval_batch_*) beside what the same caller had
+before: S one-session gc_streams on one ctx, one after the other.  Program: ed25519like1 of scripts/bench_stream.py (2 605
+steps, 10.4 M gates per session), 32-byte keys, S = 64, 256 and 1 024; one JSON line per S.
+
+Method (scripts/bench_batch_keyed.py, bench.py): all forms alternate in one process.  One untimed pass of each first — it loads
+and plans the circuits and brings the card to its sustained clocks — then --reps rounds; a window is one whole pass of the
+program between two gc_ctx_sync, timed by the host clock; the median of the rounds is reported with every round beside it.
+
+  batch garble        every step through gc_stream_batch_garble.  Every step's bytes go to the SAME device buffer (S x the
+                      largest step): the whole streams of 1 024 sessions are 234 GB, and a host drains them as they come.
+  batch garble+eval   step k garbled, then evaluated out of that buffer by gc_stream_eval_batch_circuit on the same ctx stream
+                      (the reference block of a step is any session's bytes: the one-session run's); eval = this minus garble
+  baseline            --sample one-session gc_streams (gc_stream_garble_begin_h / _finish_async at bench_stream.py's window,
+                      then gc_stream_eval_circuit over the bytes), run one after the other and scaled to S sessions
+
+--kernel-stats CSV adds the split of the device time of a pass from a `rocprofv3 --kernel-trace --stats` run of `--once S` (a
+run of its own: one garble+eval pass and nothing else): keyed pass (k_garble_flat_keyed / k_eval_flat_keyed + k_expand_keys),
+movers (k_gather, k_sb_rnd_form, k_sb_rows), serialiser (k_sb_serialise) and ingester (k_sb_ingest), and the serialiser's and
+ingester's bytes per second against 8 TB/s."""
+import argparse
+import csv
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from mpc_amd import engine  # noqa: E402
+from scripts import bench_stream as bs  # noqa: E402
+
+PROGRAM = "ed25519like1"
+HBM_BYTES_PER_S = 8e12
+
+
+class Program:
+    """the steps with their ctypes arguments converted once, their byte counts and (from a one-session run) a reference block
+    per step"""
+
+    def __init__(self, max_steps=None):
+        self.steps, self.prim = bs.PROGRAMS[PROGRAM]()
+        if max_steps:
+            self.steps = self.steps[:max_steps]
+        self.args = bs._Args(self.steps)
+        self.gates = sum(c.NumGates for c, _, _ in self.steps)
+        self.sizes = [engine.stream_batch_step_bytes(c.Gates, c.NumWires, i, o) for c, i, o in self.steps]
+        assert all(self.sizes)
+        self.bytes = sum(self.sizes)
+        self.stride = (max(self.sizes) + 15) & ~15
+        self.window = bs.WINDOWS.get(PROGRAM, 64)
+        self.eval_args = [(c.NumGates, c.NumWires, max(max(i), max(o)) + 1) for c, i, o in self.steps]
+
+
+def one_session(ctx, prog, key, rnd, evaluate=True):
+    """(garble seconds, eval seconds, stream bytes, sizes) of one gc_stream / gc_stream_eval over the program"""
+    stream, sizes, dt, _, g = bs.garble_program(ctx, key, prog.steps, prog.prim, rnd, prog.window)
+    de = bs.eval_program(ctx, key, prog.steps, prog.prim, g, stream, sizes)[0] if evaluate else 0.0
+    g.close()
+    return dt, de, stream, sizes
+
+
+class Batch:
+    def __init__(self, ctx, prog, S, ref_stream):
+        self.ctx, self.prog, self.S = ctx, prog, S
+        rng = np.random.default_rng(S)
+        self.keys = rng.integers(0, 256, (S, 32), dtype=np.uint8)
+        self.d_keys = engine.DeviceBuffer(ctx, data=self.keys)
+        rnd = rng.integers(0, 256, (S, 1 + len(prog.prim), 16), dtype=np.uint8)
+        self.d_rnd = engine.DeviceBuffer(ctx, data=rnd)
+        self.d_buf = engine.DeviceBuffer(ctx, shape=S * prog.stride)
+        self.d_bad = engine.DeviceBuffer(ctx, shape=S, dtype=np.uint32)
+        self.sb = engine.StreamBatch(ctx, S, self.d_keys, 32, self.d_rnd, prog.prim)
+        self.se = engine.StreamEvalBatch(ctx, S, self.d_keys, 32)
+        # all-zero inputs: the evaluator's active labels are the garbler's L0s
+        d_w = engine.DeviceBuffer(ctx, shape=(S, len(prog.prim)), dtype=engine.WIRE)
+        self.sb.gather_wires(prog.prim, d_w)
+        self.se.set_wires(prog.prim, engine.DeviceBuffer(ctx, data=np.ascontiguousarray(d_w.numpy()["l0"])))
+        offs = np.concatenate([[0], np.cumsum(prog.sizes)]).astype(np.int64)
+        self.refs = [np.ascontiguousarray(ref_stream[offs[k]: offs[k + 1]]) for k in range(len(prog.steps))]
+        self.n = C.c_size_t(0)
+
+    def run(self, evaluate):
+        L, pn, h, e = engine.lib(), C.byref(self.n), self.sb.h, self.se.h
+        buf, bad, stride = C.c_void_p(self.d_buf.ptr), C.c_void_p(self.d_bad.ptr), self.prog.stride
+        garble, circuit = L.gc_stream_batch_garble, L.gc_stream_eval_batch_circuit
+        for k, b in enumerate(self.prog.args.begin):
+            rc = garble(h, *b, buf, stride, pn)
+            if rc:
+                raise engine.EngineError(rc, "gc_stream_batch_garble(step %d)" % k)
+            if evaluate:
+                a, r = self.prog.eval_args[k], self.refs[k]
+                rc = circuit(e, a[0], a[1], a[2], r.ctypes.data_as(C.c_void_p), len(r), buf, stride, bad, pn)
+                if rc:
+                    raise engine.EngineError(rc, "gc_stream_eval_batch_circuit(step %d)" % k)
+
+    def window(self, evaluate):
+        self.ctx.sync()
+        t0 = time.perf_counter()
+        self.run(evaluate)
+        self.ctx.sync()
+        return time.perf_counter() - t0
+
+    def check(self):
+        """the evaluator's labels of the last outputs are the garbler's L0 or L1 in every session, no block differed"""
+        assert (self.d_bad.numpy() == 0).all()
+        for o in self.prog.steps[-1][2][:4]:
+            got, wire = self.se.get(o), self.sb.get(o)
+            assert ((got == wire["l0"]) | (got == wire["l1"])).all(), o
+
+    def close(self):
+        self.sb.close()
+        self.se.close()
+
+
+def measure(ctx, prog, S, reps, sample):
+    key0 = bytes(range(32))
+    rnd0 = bs.stream_rnd(PROGRAM, len(prog.prim))
+    _, _, ref_stream, _ = one_session(ctx, prog, key0, rnd0)  # (untimed: circuits loaded and planned, clocks up)
+    b = Batch(ctx, prog, S, ref_stream)
+    b.window(True)
+    b.check()
+    rng = np.random.default_rng(1)
+    singles = [(rng.integers(0, 256, 32, dtype=np.uint8).tobytes(), rng.integers(0, 256, 16 * (len(prog.prim) + 1), dtype=np.uint8).tobytes())
+               for _ in range(sample)]
+    t = {"garble": [], "garble_eval": [], "base_garble": [], "base_eval": []}
+    for _ in range(reps):
+        dg = de = 0.0
+        for key, rnd in singles:
+            a, e, _, _ = one_session(ctx, prog, key, rnd)
+            dg, de = dg + a, de + e
+        t["base_garble"].append(dg / sample * S)
+        t["base_eval"].append(de / sample * S)
+        t["garble"].append(b.window(False))
+        t["garble_eval"].append(b.window(True))
+    b.check()
+    med = {k: statistics.median(v) for k, v in t.items()}
+    ev = med["garble_eval"] - med["garble"]
+    n, total = len(prog.steps), prog.gates * S
+    row = {
+        "bench": "stream_batch", "program": PROGRAM, "sessions": S, "key_bytes": 32, "steps": n, "gates_per_session": prog.gates,
+        "bytes_per_session": prog.bytes, "reps": reps, "baseline_sessions_timed": sample, "baseline_window": prog.window,
+        "garble_s": med["garble"], "garble_plus_eval_s": med["garble_eval"], "eval_s": ev,
+        "garble_gates_per_s": total / med["garble"], "eval_gates_per_s": total / ev,
+        "garble_us_per_step": med["garble"] / n * 1e6, "eval_us_per_step": ev / n * 1e6,
+        "baseline_garble_s": med["base_garble"], "baseline_eval_s": med["base_eval"],
+        "baseline_garble_gates_per_s": total / med["base_garble"], "baseline_eval_gates_per_s": total / med["base_eval"],
+        "garble_speedup": med["base_garble"] / med["garble"], "eval_speedup": med["base_eval"] / ev,
+        "seconds_all": t,
+    }
+    b.close()
+    return row
+
+
+def once(ctx, prog, S):
+    """one garble+eval pass and nothing else timed: the run a kernel trace is taken of"""
+    _, _, ref_stream, _ = one_session(ctx, prog, bytes(range(32)), bs.stream_rnd(PROGRAM, len(prog.prim)), evaluate=False)
+    b = Batch(ctx, prog, S, ref_stream)
+    b.window(True)
+    b.check()
+    b.close()
+
+
+def split(path, prog, S):
+    """device seconds per group of kernels from a rocprofv3 kernel-stats csv of `--once S`"""
+    groups = {"keyed_garble": ("k_garble_flat_keyed",), "keyed_eval": ("k_eval_flat_keyed",), "expand_keys": ("k_expand_keys",),
+              "movers": ("k_gather", "k_sb_rnd_form", "k_sb_rows"), "serialiser": ("k_sb_serialise",), "ingester": ("k_sb_ingest",)}
+    sec = {g: 0.0 for g in groups}
+    calls = {g: 0 for g in groups}
+    for r in csv.DictReader(open(path)):
+        for g, names in groups.items():
+            if any(n + "<" in r["Name"] or n + "(" in r["Name"] for n in names):
+                sec[g] += float(r["TotalDurationNs"]) * 1e-9
+                calls[g] += int(r["Calls"])
+    moved = prog.bytes * S
+    return {"bench": "stream_batch_split", "program": PROGRAM, "sessions": S, "steps": len(prog.steps), "device_seconds": sec,
+            "launches": calls, "us_per_step": {g: v / len(prog.steps) * 1e6 for g, v in sec.items()},
+            "serialiser_bytes_per_s": moved / sec["serialiser"] if sec["serialiser"] else None,
+            "serialiser_fraction_of_8TBps": moved / sec["serialiser"] / HBM_BYTES_PER_S if sec["serialiser"] else None,
+            "ingester_bytes_per_s": moved / sec["ingester"] if sec["ingester"] else None,
+            "ingester_fraction_of_8TBps": moved / sec["ingester"] / HBM_BYTES_PER_S if sec["ingester"] else None}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sessions", type=int, nargs="*", default=[64, 256, 1024])
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sample", type=int, default=2, help="one-session streams the baseline is timed on")
+    ap.add_argument("--max-steps", type=int, default=None, help="only the first steps of the program (a quick look)")
+    ap.add_argument("--once", type=int, default=None, help="one garble+eval pass at this many sessions (for a kernel trace)")
+    ap.add_argument("--kernel-stats", default=None, help="kernel-stats csv of a traced --once run: print its split (with --sessions S)")
+    ap.add_argument("--out", default=None, help="also append the lines to this file")
+    a = ap.parse_args()
+    prog = Program(a.max_steps)
+
+    def emit(row):
+        line = json.dumps(row)
+        print(line, flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
+
+    if a.kernel_stats:
+        emit(split(a.kernel_stats, prog, a.sessions[0]))
+        return
+    ctx = engine.Context(0)
+    if a.once:
+        once(ctx, prog, a.once)
+    else:
+        for S in a.sessions:
+            emit(measure(ctx, prog, S, a.reps, a.sample))
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
