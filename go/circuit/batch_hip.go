@@ -226,10 +226,34 @@ func (p *BatchPipeline) Step(key []byte) error {
 	return nil
 }
 
-// KeysSupported reports whether this pipeline can run GarbleBatchKeys / EvalBatchKeys (gc_batch_keyed_supported: the
-// flattened kernels with the wires in LDS, and the tile's key table fits behind them).
+// KeysSupported reports whether this pipeline can run GarbleBatchKeys / EvalBatchKeys (gc_batch_keyed_supported: schedule 1,
+// and either the flattened kernels with the wires in LDS and the tile's key table fitting behind them, or the wires in HBM;
+// KeysPath says which).
 func (p *BatchPipeline) KeysSupported() bool {
 	return C.gc_batch_keyed_supported(p.gb) != 0 && C.gc_batch_keyed_supported(p.ev) != 0
+}
+
+// KeysPath reports which kernels GarbleBatchKeys / EvalBatchKeys run on this pipeline now (gc_batch_keyed_path): 0 none, 1 the
+// flattened kernels with the wires in LDS, 2 the level-walking kernels with the wires in HBM.  Both batches share a circuit and
+// a size, so they agree unless SetKeysPath failed half way.
+func (p *BatchPipeline) KeysPath() int {
+	g, e := int(C.gc_batch_keyed_path(p.gb)), int(C.gc_batch_keyed_path(p.ev))
+	if g != e {
+		return 0
+	}
+	return g
+}
+
+// SetKeysPath sends the keyed calls of both batches to the HBM-wire kernels (2) whatever their geometry — the way to serve a
+// pipeline whose key table does not fit into LDS — or back to the rule (0).
+func (p *BatchPipeline) SetKeysPath(path int) error {
+	if st := C.gc_batch_set_keyed_path(p.gb, C.int(path)); st != C.GC_OK {
+		return statusError(st)
+	}
+	if st := C.gc_batch_set_keyed_path(p.ev, C.int(path)); st != C.GC_OK {
+		return statusError(st)
+	}
+	return nil
 }
 
 func (p *BatchPipeline) uploadKeys(keys []byte, keylen int) error {

@@ -455,14 +455,25 @@ int gc_batch_eval(gc_batch *evaluator, const uint8_t *key, size_t keylen, const 
  * like their one-key twins: enqueued on the ctx stream, nothing is waited for; the round keys are expanded ON THE DEVICE
  * as part of the pass, so a captured graph replays with whatever keys the buffer holds at replay time.  Instance i's
  * bytes are those of gc_batch_garble / gc_batch_eval with key i.
- * Scope (gc_batch_keyed_supported: 1 / 0): schedule 1, wires in LDS (gc_batch_wires_in_lds) on the flattened kernels,
- * and the tile's key table fits into LDS behind the wire slots.  Not built: schedules 0 and 2, the HBM-wire kernels,
- * the streaming jobs, the host-buffer calls gc_garble / gc_eval.
+ * Scope (gc_batch_keyed_supported: 1 / 0; gc_batch_keyed_path: which kernels): schedule 1, and either the wires in LDS
+ * (gc_batch_wires_in_lds) on the flattened kernels with the tile's key table fitting into LDS behind the wire slots (path 1),
+ * or the wires in HBM — no LDS plan, one that does not fit, one still pending — on the level-walking keyed kernels (path
+ * 2), which leave every wire (gc_batch_read_wires).  A batch whose wires are in LDS but whose key table does not fit is
+ * refused unless gc_batch_set_keyed_path(b, 2) sends it to path 2.  Not built: schedules 0 and 2, the cooperative and
+ * level-launch one-instance forms, the streaming jobs, the host-buffer calls gc_garble / gc_eval.
  * GC_E_KEYSIZE for any other keylen, GC_E_ARG for a NULL pointer, GC_E_ARG with a gc_last_error() text for a batch
  * outside the scope. */
 int gc_batch_garble_keyed(gc_batch *, const void *d_keys, size_t keylen, const void *d_rnd);
 int gc_batch_eval_keyed(gc_batch *evaluator, const void *d_keys, size_t keylen, const gc_batch *tables);
 int gc_batch_keyed_supported(const gc_batch *);
+/* which kernels the keyed calls run on this batch now: 0 none (they return GC_E_ARG), 1 flattened with the wires in LDS,
+ * 2 level-walking with the wires in HBM */
+int gc_batch_keyed_path(const gc_batch *);
+/* 0 (default): the rule above.  2: path 2 for every schedule-1 batch, also one whose wires are in LDS under the one-key
+ * kernels (its arrays hold every wire slot whatever the kernel) — the way to serve a batch whose key table does not fit,
+ * at the HBM-wire kernels' cost.  Other values, schedule 0 / 2: GC_E_ARG.  Graphs captured before stay valid for what
+ * they captured. */
+int gc_batch_set_keyed_path(gc_batch *, int path);
 /* BitFromLabel (circuit/helpers.go:18-28) for every output wire: d_bits_out = u8 [batch][noutputs];
  * *d_mismatch (u32, device) counts labels that match neither L0 nor L1 */
 int gc_batch_decode(const gc_batch *garbler, const gc_batch *evaluator, void *d_bits_out, void *d_mismatch);
@@ -555,7 +566,7 @@ size_t gc_stream_batch_step_bytes(const gc_gate *gates, uint32_t ngates, uint32_
  * circuit + batch are recognised by gate-list content and cached per handle, bounded in device bytes
  * (GC_STREAM_BATCH_CACHE_BYTES, default 1 GiB; least recently used first).  ngates == 0 writes nothing and is GC_OK.  Not inside a pipeline capture (GC_E_ARG).
  * Refused with GC_E_ARG and a gc_last_error() text, the store unchanged: a step whose circuit is outside
- * gc_batch_keyed_supported at this number of sessions (no LDS plan, or the key table does not fit); a circuit whose output
+ * gc_batch_keyed_supported at this number of sessions (wires in LDS and the key table does not fit); a circuit whose output
  * range overlaps its input range (nwires - nout < nin); a gate that writes an input-mapped wire.  GC_E_GATE / GC_E_WIRE for
  * an invalid op / a wire id >= nwires. */
 int gc_stream_batch_garble(gc_stream_batch *, const gc_gate *gates, uint32_t ngates, uint32_t nwires, const uint32_t *in,

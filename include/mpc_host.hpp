@@ -486,8 +486,12 @@ private:
 // Many Garbler / Evaluator sessions gathered into one device-resident batch (gc_batch_*): every session drew its own key
 // (garbler.go:47-53) and sent it to its peer (:64), so instance i is garbled and evaluated under key i.  d_keys = u8
 // [batch][keylen] and d_rnd are device buffers (gc_dev_alloc); the calls enqueue on the ctx stream and do not wait.
-// BatchKeysSupported: gc_batch_keyed_supported (schedule 1, wires in LDS, the key table fits).
+// BatchKeysSupported: gc_batch_keyed_supported (schedule 1; wires in LDS and the key table fits, or wires in HBM).
+// BatchKeysPath: gc_batch_keyed_path (0 none, 1 the flattened kernels with the wires in LDS, 2 the level-walking kernels with
+// the wires in HBM); SetBatchKeysPath(b, 2) sends any schedule-1 batch to path 2, 0 restores the rule.
 inline bool BatchKeysSupported(const gc_batch *b) { return gc_batch_keyed_supported(b) != 0; }
+inline int BatchKeysPath(const gc_batch *b) { return gc_batch_keyed_path(b); }
+inline void SetBatchKeysPath(gc_batch *b, int path) { check(gc_batch_set_keyed_path(b, path), "gc_batch_set_keyed_path"); }
 inline void GarbleBatchKeys(gc_batch *b, const void *d_keys, size_t keylen, const void *d_rnd) {
     if (keylen != 16 && keylen != 24 && keylen != 32) throw Error("crypto/aes: invalid key size " + std::to_string(keylen));
     check(gc_batch_garble_keyed(b, d_keys, keylen, d_rnd), "gc_batch_garble_keyed");

@@ -1111,23 +1111,44 @@ int gc_batch_eval(gc_batch *ev, const uint8_t *key, size_t keylen, const gc_batc
     return GC_OK;
 }
 
-// ---- one AES key per instance (fused_flat_keyed_kernels.hip) ----------------------------------------------------
-// Scope: schedule 1 on the flattened kernels with the wires in LDS, and the tile's key table (sized for AES-256, so that the
-// answer does not depend on the key length) fits behind the wire slots.  nullptr, or what keeps the batch out.
-static const char *keyed_out_of_scope(const gc_batch *b) {
-    if (b->schedule != 1 || b->single_phase) return "schedule 1 only";
-    if (!uses_flat(b)) return "the batch does not run the flattened kernels with its wires in LDS";
+// ---- one AES key per instance (fused_flat_keyed_kernels.hip, fused_hbm_keyed_kernels.hip) -----------------------
+// Which kernels the keyed calls run on this batch: 1 = the flattened kernels with the wires in LDS, when the tile's key table
+// (sized for AES-256, so that the answer does not depend on the key length) fits behind the wire slots; 2 = the level-walking
+// kernels with the wires in HBM, for a batch without a usable LDS plan (none, one that does not fit, one still pending) and
+// for any schedule-1 batch that gc_batch_set_keyed_path sent there; 0 = none, *why says what keeps the batch out.
+static int keyed_path(const gc_batch *b, const char **why) {
+    *why = nullptr;
+    if (b->schedule != 1 || b->single_phase) {
+        *why = "schedule 1 only";
+        return 0;
+    }
+    if (b->keyed_force == 2 || !b->g.lds_wires) return 2;
+    if (!uses_flat(b)) {
+        *why = "the batch keeps its wires in LDS without the flattened kernels";
+        return 0;
+    }
     const Plan &p = b->circ->plan.p;
-    if (fused_flat_keyed_bytes(p.n_flat_slots, b->g.ti_log2, p.fl_unit_stride, 14) > kFlatLdsBytes)
-        return "the tile's key table does not fit into LDS behind the wire slots";
-    return nullptr;
+    if (fused_flat_keyed_bytes(p.n_flat_slots, b->g.ti_log2, p.fl_unit_stride, 14) > kFlatLdsBytes) {
+        *why = "the tile's key table does not fit into LDS behind the wire slots (gc_batch_set_keyed_path)";
+        return 0;
+    }
+    return 1;
 }
 
-int gc_batch_keyed_supported(const gc_batch *b) try {
-    return b && !keyed_out_of_scope(b);
+int gc_batch_keyed_path(const gc_batch *b) try {
+    const char *why;
+    return b ? keyed_path(b, &why) : 0;
 } catch (...) {
     (void)gc::on_exception();
     return 0;
+}
+
+int gc_batch_keyed_supported(const gc_batch *b) { return gc_batch_keyed_path(b) != 0; }
+
+int gc_batch_set_keyed_path(gc_batch *b, int path) {
+    if (!b || (path != 0 && path != 2) || b->schedule != 1 || b->single_phase) return GC_E_ARG;
+    b->keyed_force = path;
+    return GC_OK;
 }
 
 static int keyed_rounds(size_t keylen) { return keylen == 16 ? 10 : keylen == 24 ? 12 : keylen == 32 ? 14 : 0; }
@@ -1145,13 +1166,35 @@ static int run_keyed(gc_batch *b, bool eval, const void *d_keys, size_t keylen, 
     if (!rounds) return GC_E_KEYSIZE;
     gc_ctx *ctx = b->circ->ctx;
     GC_HIP(hipSetDevice(ctx->device));
-    if (const char *why = keyed_out_of_scope(b)) {
+    const char *why;
+    const int path = keyed_path(b, &why);
+    if (!path) {
         std::snprintf(gc::tls_error, sizeof gc::tls_error, "%s: %s", what, why);
         return GC_E_ARG;
     }
     int rc = expand_keys(b, d_keys, rounds);
     if (rc != GC_OK) return rc;
     const Plan &p = b->circ->plan.p;
+    if (path == 2) {  // wires in HBM: R and the input labels from a kernel of their own, as in gc_batch_garble
+        if (!eval) launch_init_garble(rnd, p.info.ninputs, b->d_W, b->d_R, b->g, ctx->stream);
+        FusedArgs a{};
+        a.descs = b->circ->d_descs;
+        a.steps = b->circ->d_steps;
+        a.nsteps = (uint32_t)p.levels.size();
+        a.ninputs = p.info.ninputs;
+        a.W = b->d_W;
+        a.R = b->d_R;
+        a.T = const_cast<uint4 *>(T);
+        a.te0 = ctx->d_te0;
+        a.rounds = rounds;
+        if (!ctx->capturing) GC_HIP(hipEventRecord(b->ev0, ctx->stream));
+        GC_HIP(launch_fused_hbm_keyed(eval, a, b->d_keyed_rk, p.info.n_or != 0, b->g, ctx->stream));
+        if (!ctx->capturing) GC_HIP(hipEventRecord(b->ev1, ctx->stream));
+        b->timed = !ctx->capturing;
+        b->last_launches = 1;
+        b->have_all_wires = true;
+        return GC_OK;
+    }
     FusedFlatArgs f{};
     f.prog = b->circ->d_fl_prog;
     f.units = b->circ->d_fl_units;

@@ -154,6 +154,7 @@ struct gc_batch {
     bool store_all = false;      // fused-LDS passes also write every wire to the global array
     bool single_phase = false;   // fused-LDS passes walk the XOR levels (fused_lds_kernels.hip) instead of the flat plan
     bool have_all_wires = false; // the global wire array holds every wire of the last pass
+    int keyed_force = 0;         // gc_batch_set_keyed_path: 2 = the keyed calls take the HBM-wire kernels whatever the geometry
     std::vector<gc_graph_entry> graphs;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;

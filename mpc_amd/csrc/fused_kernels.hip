@@ -17,6 +17,7 @@
 // gate-instance then exchange their results with DPP quad permutes (register-to-register, no LDS).
 // All hash lanes of all gate types share one AES code path, so mixed waves never run it twice.
 #include "aes_device.h"
+#include "col_lanes.h"
 #include "kernels.h"
 #include "level_gate.h"
 #include <cstdlib>
@@ -89,8 +90,6 @@ __device__ __forceinline__ uint32_t level_lanes(const Step &st, uint32_t ti_log2
     return ((st.n_and << ti_log2) << LQA) + ((st.n_or << ti_log2) << LQO) + ((st.n_inv << ti_log2) << LQI) +
            ((st.count - st.nonfree) << ti_log2);
 }
-
-enum LaneKind { K_NONE = 0, K_AND = 1, K_OR = 2, K_INV = 3, K_FREE = 4 };
 
 // PROF: per-workgroup s_memtime breakdown (debug builds of the launch only, gc_batch_debug_profile):
 //   prof[wg*8 + {0,1,2,3}] = cycles wave 0 spent in {descriptor fetch, label loads, hash+combine+stores,
@@ -317,43 +316,7 @@ __device__ __forceinline__ void load_col_keys(uint32_t *te, const uint32_t *__re
         te[kColKeyTab / 4 + threadIdx.x] = kv;
     }
 }
-__device__ __forceinline__ uint32_t col_pair4(uint32_t v) {  // value of the lane 4 further on (q even) / 4 back (q odd)
-    uint32_t r = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x104, 0xf, 0x5, false);
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)r, (int)v, 0x114, 0xf, 0xa, false);
-}
-__device__ __forceinline__ uint32_t col_whiten(uint32_t xc, uint32_t xc1, uint32_t c, uint32_t tweak, uint32_t k0) {
-    const uint32_t kcol = __builtin_amdgcn_alignbit(xc, c == 3 ? 0u : xc1, 31);
-    return xor3(kcol, c == 3 ? tweak : 0u, k0);
-}
-__device__ __forceinline__ uint32_t label_word(const uint4 *label, uint32_t byte_off) {
-    return *(const uint32_t *)((const char *)label + byte_off);
-}
-// lanes of a level in column form (LQA / LQI: log2 of the wide lanes per AND / INV gate-instance); 0xffffffff: has OR gates
-template <int LQA, int LQI>
-__device__ __forceinline__ uint32_t col_lanes(const Step &st, uint32_t ti_log2) {
-    if (st.n_or) return 0xffffffffu;
-    return ((((st.n_and << ti_log2) << LQA) + ((st.n_inv << ti_log2) << LQI)) << 2) + ((st.count - st.nonfree) << ti_log2);
-}
-// this lane's place in the column form and its gate's descriptor (fetched before the previous level's barrier)
-struct ColPos {
-    uint32_t kind, g, inst, q, c;  // kind: K_AND / K_INV / K_FREE / K_NONE
-};
-template <int LQA, int LQI>
-__device__ __forceinline__ ColPos col_classify(const Step &st, uint32_t J, uint32_t ti_log2, uint32_t tim) {
-    ColPos p{K_NONE, 0, 0, 0, 0};
-    const uint32_t e_and = ((st.n_and << ti_log2) << LQA) << 2, ncol = e_and + (((st.n_inv << ti_log2) << LQI) << 2);
-    if (J < e_and) {
-        const uint32_t w = J >> 2;
-        p.kind = K_AND, p.c = J & 3u, p.q = w & ((1u << LQA) - 1), p.inst = (w >> LQA) & tim, p.g = w >> (ti_log2 + LQA);
-    } else if (J < ncol) {
-        const uint32_t w = (J - e_and) >> 2;
-        p.kind = K_INV, p.c = J & 3u, p.q = w & ((1u << LQI) - 1), p.inst = (w >> LQI) & tim, p.g = st.n_and + (w >> (ti_log2 + LQI));
-    } else if (J - ncol < ((st.count - st.nonfree) << ti_log2)) {
-        const uint32_t u = J - ncol;
-        p.kind = K_FREE, p.inst = u & tim, p.g = st.nonfree + (u >> ti_log2);
-    }
-    return p;
-}
+// (the lane map and the label helpers of this form: col_lanes.h)
 
 template <int NR>
 __device__ __forceinline__ void garble_col_pass(const Step &st, const ColPos &p, const GateDesc &d, uint32_t ninputs,

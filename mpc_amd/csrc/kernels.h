@@ -177,6 +177,15 @@ hipError_t launch_expand_keys(const uint8_t *d_keys, int rounds, uint32_t batch,
                               hipStream_t s);
 hipError_t launch_fused_flat_keyed(bool eval, const FusedFlatArgs &a, const BatchGeom &g, hipStream_t s);
 
+// The level-walking pass with the wires in HBM and one AES key per instance (fused_hbm_keyed_kernels.hip): what the keyed calls
+// run on a batch without a usable LDS plan.  a.rk and a.prof are ignored, a.rounds selects the build; rk_per_instance = the
+// array launch_expand_keys wrote; R and the input labels are in place (launch_init_garble).  The tile's schedules go into LDS
+// behind the AES table and R: fused_hbm_keyed_bytes, checked against the LDS of a CU before the launch
+// (hipErrorInvalidConfiguration).  ONE launch; nothing in it reaches the host.
+size_t fused_hbm_keyed_bytes(uint32_t ti_log2, int rounds);
+hipError_t launch_fused_hbm_keyed(bool eval, const FusedArgs &a, const uint32_t *rk_per_instance, bool has_or, const BatchGeom &g,
+                                  hipStream_t s);
+
 // What one workgroup of the flattened kernels needs.  The batch launches pass ONE of these as the kernel argument (every
 // workgroup = one tile of the same circuit); the streaming engine's step groups pass an ARRAY in device memory, one
 // record per workgroup (launch_fused_flat_jobs): workgroup j runs ONE instance of job j's circuit — its own plan, wire

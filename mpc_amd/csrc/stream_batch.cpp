@@ -214,9 +214,11 @@ struct SbCore {
         e->circ = gc_circ_load(ctx, e->gates.data(), ngates, nwires, nin, nout, &st);
         if (!e->circ) return st;
         e->batch = gc_batch_create(e->circ, S, &st);
-        if (e->batch && !gc_batch_keyed_supported(e->batch)) {
-            st = refuse(what, "the step's circuit is outside gc_batch_keyed_supported at this number of sessions (no LDS plan, or the "
-                              "tile's key table does not fit)");
+        // (path 1 with the wires in LDS, path 2 with the wires in HBM; the handle does not force path 2 on a batch whose wires are
+        // in LDS and whose key table does not fit)
+        if (e->batch && gc_batch_keyed_path(e->batch) == 0) {
+            st = refuse(what, "the step's circuit is outside gc_batch_keyed_supported at this number of sessions (its wires are in "
+                              "LDS and the tile's key table does not fit)");
         }
         if (!e->batch || st != GC_OK) {
             if (e->batch) gc_batch_free(e->batch);

@@ -156,6 +156,8 @@ def lib():
         "gc_batch_garble_keyed": (i32, [vp, vp, sz, vp]),
         "gc_batch_eval_keyed": (i32, [vp, vp, sz, vp]),
         "gc_batch_keyed_supported": (i32, [vp]),
+        "gc_batch_keyed_path": (i32, [vp]),
+        "gc_batch_set_keyed_path": (i32, [vp, i32]),
         "gc_batch_debug_keyed_schedule": (i32, [vp, vp, sz, vp, vp]),
         "gc_batch_read_r": (i32, [vp, vp]),
         "gc_batch_read_slab": (i32, [vp, vp]),
@@ -732,6 +734,16 @@ class Batch:
     def keyed_supported(self):
         """can this batch run garble_keyed / eval_keyed (gc_batch_keyed_supported)?"""
         return bool(lib().gc_batch_keyed_supported(self.h))
+
+    @property
+    def keyed_path(self):
+        """which kernels garble_keyed / eval_keyed run on this batch now (gc_batch_keyed_path): 0 none, 1 the flattened kernels
+        with the wires in LDS, 2 the level-walking kernels with the wires in HBM"""
+        return int(lib().gc_batch_keyed_path(self.h))
+
+    def set_keyed_path(self, path):
+        """gc_batch_set_keyed_path: 2 sends the keyed calls to the HBM-wire kernels whatever the batch's geometry, 0 is the rule"""
+        _check(lib().gc_batch_set_keyed_path(self.h, int(path)), "gc_batch_set_keyed_path")
 
     def garble_keyed(self, d_keys, keylen, d_rnd):
         """gc_batch_garble_keyed: d_keys = device u8 [batch][keylen], one AES key per instance"""

@@ -14,7 +14,13 @@ rounds is reported with every round beside it.
                                  same batch (expansion kernel + the load of the LDS key table; the hashing is nothing there)
   one_instance_batches_ms        what a caller with per-session keys had to do before: one batch of ONE instance per session,
                                  garble + eval under its own key, timed on at most --sample sessions and scaled to the batch
-  keyed_over_one_instance        keyed garble + eval against that"""
+  keyed_over_one_instance        keyed garble + eval against that
+
+--hbm: the keyed kernels with the wires in HBM (path 2 of gc_batch_keyed_path) instead, same protocol, two lines:
+  (a) the synthetic levelised circuit of bench.py's `synthetic` row (131 072 gates, W = 1 024, f = 0.17) x 1 024, whose wires
+      are in HBM: the one-key HBM-wire pass against keyed path 2;
+  (b) aes_128 x 1 024: keyed path 1 (wires in LDS) against path 2 forced with gc_batch_set_keyed_path — what the fall-back
+      costs a batch that could run in LDS; the one-key pass beside them."""
 import argparse
 import json
 import os
@@ -133,14 +139,84 @@ def measure(ctx, c, batch, reps, seconds, sample):
     return row
 
 
+def measure_hbm(ctx, c, batch, reps, seconds, forced):
+    """forced = False: one key against keyed path 2 on a batch whose wires are in HBM; True: one key, keyed path 1 and keyed
+    path 2 (a second pair of batches sent there) on a batch whose wires are in LDS"""
+    rng = np.random.default_rng(7)
+    dc = engine.DeviceCircuit(ctx, c)
+    gb, ev = engine.Batch(dc, batch), engine.Batch(dc, batch)
+    assert gb.keyed_path == ev.keyed_path == (1 if forced else 2) and gb.lds_wires == forced
+    d_rnd = ctx.random_u8((batch, c.num_inputs + 1, 16), 256, seed=1234)
+    d_bits = ctx.random_u8((batch, c.num_inputs), 2, seed=4321)
+    keys = rng.integers(0, 256, (batch, 32), dtype=np.uint8)
+    d_keys = ctx.to_device(keys)
+    key = keys[0].tobytes()
+    g1, e1 = graphs_of(ctx, gb, ev, d_bits, lambda: gb.garble(key, d_rnd), lambda: ev.eval(key, gb))
+    gk, ek = graphs_of(ctx, gb, ev, d_bits, lambda: gb.garble_keyed(d_keys, 32, d_rnd), lambda: ev.eval_keyed(d_keys, 32, gb))
+    passes = {"garble": g1.launch, "eval": e1.launch}
+    graphs, batches = [g1, e1, gk, ek], [gb, ev]
+    if forced:
+        gb2, ev2 = engine.Batch(dc, batch), engine.Batch(dc, batch)
+        for b in (gb2, ev2):
+            b.set_keyed_path(2)
+        g2, e2 = graphs_of(ctx, gb2, ev2, d_bits, lambda: gb2.garble_keyed(d_keys, 32, d_rnd), lambda: ev2.eval_keyed(d_keys, 32, gb2))
+        passes.update({"path1_garble": gk.launch, "path1_eval": ek.launch, "path2_garble": g2.launch, "path2_eval": e2.launch})
+        graphs += [g2, e2]
+        batches += [gb2, ev2]
+    else:
+        passes.update({"path2_garble": gk.launch, "path2_eval": ek.launch})
+    t = alternate(ctx, passes, reps, seconds)
+    med = {k: statistics.median(v) for k, v in t.items()}
+    base = "path1" if forced else ""
+    bg, be = (med["path1_garble"], med["path1_eval"]) if forced else (med["garble"], med["eval"])
+    row = {
+        "bench": "batch_keyed_hbm", "circuit": c.name, "batch": batch, "key_bytes": 32, "tile_instances": gb.tile_instances,
+        "gates": int(dc.info.ngates), "and_gates": int(dc.info.n_and), "levels": int(dc.info.nlevels), "reps": reps,
+        "window_s": seconds, "wires_in_lds_under_one_key": bool(forced),
+        "one_key_garble_ms": med["garble"], "one_key_eval_ms": med["eval"],
+        "path2_garble_ms": med["path2_garble"], "path2_eval_ms": med["path2_eval"],
+        "path2_over": "keyed path 1" if forced else "the one-key HBM-wire pass",
+        "path2_over_base": {"garble": med["path2_garble"] / bg, "eval": med["path2_eval"] / be,
+                            "garble_plus_eval": (med["path2_garble"] + med["path2_eval"]) / (bg + be)},
+        "path2_and_gates_per_s": dc.info.n_and * batch / ((med["path2_garble"] + med["path2_eval"]) * 1e-3),
+        "ms_all": t,
+    }
+    if forced:
+        row["path1_garble_ms"], row["path1_eval_ms"] = med["path1_garble"], med["path1_eval"]
+    for g in graphs:
+        g.close()
+    for b in batches:
+        b.close()
+    dc.close()
+    return row
+
+
+def main_hbm(ctx, a):
+    syn = circuit.synthetic_levelised(128, 1024, 0.17, seed=101, ninputs=256)  # scripts/sweep_synthetic.py: the (1 024, 0.17) row
+    syn.name = "synthetic_w1024_f0.17"
+    aes = parse_file(os.path.join(ROOT, "tests", "golden", "aes_128.gcf"))
+    aes.name = "aes_128"
+    for c, forced in ((syn, False), (aes, True)):
+        line = json.dumps(measure_hbm(ctx, c, 1024, a.reps, a.window, forced))
+        print(line, flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--hbm", action="store_true", help="the keyed HBM-wire kernels (path 2) instead: see the module docstring")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.2)
     ap.add_argument("--sample", type=int, default=64, help="one-instance batches the sequential row is timed on")
     ap.add_argument("--out", default=None, help="also append the lines to this file")
     a = ap.parse_args()
     ctx = engine.Context(0)
+    if a.hbm:
+        main_hbm(ctx, a)
+        ctx.close()
+        return
     for name, batch in CASES:
         c = parse_file(os.path.join(ROOT, "tests", "golden", name + ".gcf"))
         c.name = name

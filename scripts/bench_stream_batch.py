@@ -16,7 +16,12 @@ program between two gc_ctx_sync, timed by the host clock; the median of the roun
 --kernel-stats CSV adds the split of the device time of a pass from a `rocprofv3 --kernel-trace --stats` run of `--once S` (a
 run of its own: one garble+eval pass and nothing else): keyed pass (k_garble_flat_keyed / k_eval_flat_keyed + k_expand_keys),
 movers (k_gather, k_sb_rnd_form, k_sb_rows), serialiser (k_sb_serialise) and ingester (k_sb_ingest), and the serialiser's and
-ingester's bytes per second against 8 TB/s."""
+ingester's bytes per second against 8 TB/s.
+
+--program big130_16: a program of WIDE steps instead — the first 16 steps of bench_stream.py's big130 (131 072 gates per step,
+64 levels of 2 048, four circuits in turn), whose circuits keep their wires in HBM and take the keyed HBM-wire kernels
+(k_garble_hbm_keyed / k_eval_hbm_keyed); the parent refused them.  Its four batches are larger than the default cache of a
+handle together, so the run raises GC_STREAM_BATCH_CACHE_BYTES to 16 GiB unless the caller set it."""
 import argparse
 import csv
 import ctypes as C
@@ -35,6 +40,7 @@ from mpc_amd import engine  # noqa: E402
 from scripts import bench_stream as bs  # noqa: E402
 
 PROGRAM = "ed25519like1"
+PROGRAMS = dict(bs.PROGRAMS, big130_16=lambda: bs.program_big(16 * 131072))
 HBM_BYTES_PER_S = 8e12
 
 
@@ -43,7 +49,7 @@ class Program:
     per step"""
 
     def __init__(self, max_steps=None):
-        self.steps, self.prim = bs.PROGRAMS[PROGRAM]()
+        self.steps, self.prim = PROGRAMS[PROGRAM]()
         if max_steps:
             self.steps = self.steps[:max_steps]
         self.args = bs._Args(self.steps)
@@ -167,7 +173,8 @@ def once(ctx, prog, S):
 
 def split(path, prog, S):
     """device seconds per group of kernels from a rocprofv3 kernel-stats csv of `--once S`"""
-    groups = {"keyed_garble": ("k_garble_flat_keyed",), "keyed_eval": ("k_eval_flat_keyed",), "expand_keys": ("k_expand_keys",),
+    groups = {"keyed_garble": ("k_garble_flat_keyed", "k_garble_hbm_keyed"), "keyed_eval": ("k_eval_flat_keyed", "k_eval_hbm_keyed"),
+              "expand_keys": ("k_expand_keys",),
               "movers": ("k_gather", "k_sb_rnd_form", "k_sb_rows"), "serialiser": ("k_sb_serialise",), "ingester": ("k_sb_ingest",)}
     sec = {g: 0.0 for g in groups}
     calls = {g: 0 for g in groups}
@@ -186,6 +193,7 @@ def split(path, prog, S):
 
 
 def main():
+    global PROGRAM
     ap = argparse.ArgumentParser()
     ap.add_argument("--sessions", type=int, nargs="*", default=[64, 256, 1024])
     ap.add_argument("--reps", type=int, default=5)
@@ -194,7 +202,11 @@ def main():
     ap.add_argument("--once", type=int, default=None, help="one garble+eval pass at this many sessions (for a kernel trace)")
     ap.add_argument("--kernel-stats", default=None, help="kernel-stats csv of a traced --once run: print its split (with --sessions S)")
     ap.add_argument("--out", default=None, help="also append the lines to this file")
+    ap.add_argument("--program", default=PROGRAM, choices=sorted(PROGRAMS), help="big130_16: wide steps, wires in HBM")
     a = ap.parse_args()
+    PROGRAM = a.program
+    if PROGRAM.startswith("big"):
+        os.environ.setdefault("GC_STREAM_BATCH_CACHE_BYTES", str(16 << 30))
     prog = Program(a.max_steps)
 
     def emit(row):
