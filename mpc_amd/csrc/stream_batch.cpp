@@ -347,31 +347,41 @@ struct gc_stream_eval_batch : SbCore {
 
 namespace {
 
-// in[] / out[] naming the same GLOBAL wire (an in-place update): the reference resolves stream.wire(index) per gate
-// (stream_garble.go:131-157), so a gate that reads the input-mapped wire after the gate that Set the output-mapped one sees
-// the NEW label.  The pass garbles from a snapshot of the inputs: such reads are redirected to the producing circuit wire —
-// the same global id and flags on the wire, so the bytes do not change (stream_garble.cpp: rewrite_aliased, restated for a
-// handle without that stream's state).  Returns whether anything was rewritten (*gates then points at s->rewritten).
+// in[] / out[] naming the same GLOBAL wire (an in-place update), or out[] naming one twice: the reference resolves
+// stream.wire(index) per gate (stream_garble.go:131-157), so a gate that reads such a wire — through its input-mapped or
+// through any of its output-mapped circuit wires — after a gate Set it sees the label of the LATEST Set, and the store keeps
+// what the last GATE Set, whatever its index in out[].  The pass garbles from a snapshot of the inputs: such reads are
+// redirected to the circuit wire of the latest Set (an output-mapped wire read before any Set: to the input-mapped wire of
+// the same id, if there is one) — the same global id and flags on the wire, so the bytes do not change (stream_garble.cpp:
+// rewrite_aliased, restated for a handle without that stream's state).  Returns whether anything may have been rewritten
+// (*gates then points at s->rewritten); *latest: global id -> the circuit wire a gate Set it through last.
 bool rewrite_aliased(gc_stream_batch *s, const gc_gate **gates, uint32_t ngates, uint32_t nwires, const uint32_t *in, uint32_t nin,
-                     const uint32_t *out, uint32_t nout) {
+                     const uint32_t *out, uint32_t nout, std::unordered_map<uint32_t, uint32_t> *latest) {
     const uint32_t first_out = nwires - nout;
-    std::unordered_map<uint32_t, uint32_t> out_j;
-    for (uint32_t j = 0; j < nout; j++) out_j[out[j]] = j;
+    latest->clear();
+    std::unordered_map<uint32_t, uint32_t> out_ids, in_i;
     bool aliased = false;
-    for (uint32_t i = 0; i < nin && !aliased; i++) aliased = out_j.count(in[i]) != 0;
+    for (uint32_t j = 0; j < nout; j++) aliased |= !out_ids.emplace(out[j], j).second;  // twice in out[]
+    for (uint32_t i = 0; i < nin && !aliased; i++) aliased = out_ids.count(in[i]) != 0;
     if (!aliased) return false;
-    std::vector<uint8_t> set(nout, 0);
+    for (uint32_t i = 0; i < nin; i++) in_i.emplace(in[i], i);
     s->rewritten.assign(*gates, *gates + ngates);
     for (uint32_t g = 0; g < ngates; g++) {
         gc_gate &q = s->rewritten[g];
         auto redirect = [&](uint32_t w) {
-            if (w >= nin) return w;
-            auto it = out_j.find(in[w]);
-            return it != out_j.end() && set[it->second] ? first_out + it->second : w;
+            if (w >= nin && w < first_out) return w;
+            const uint32_t id = w < nin ? in[w] : out[w - first_out];
+            auto it = latest->find(id);
+            if (it != latest->end()) return it->second;
+            if (w >= first_out) {
+                auto ii = in_i.find(id);
+                if (ii != in_i.end()) return ii->second;
+            }
+            return w;
         };
         q.in0 = redirect(q.in0);
         if (q.op != GC_INV) q.in1 = redirect(q.in1);
-        if (q.out >= first_out) set[q.out - first_out] = 1;
+        if (q.out >= first_out) (*latest)[out[q.out - first_out]] = q.out;
     }
     *gates = s->rewritten.data();
     return true;
@@ -401,7 +411,8 @@ int garble_step(gc_stream_batch *s, const gc_gate *gates, uint32_t ngates, uint3
     if (nbytes >= 0x7fffffffu) return refuse(what, "a step of 2 GiB or more");
     if (!d_out || stride % 4 != 0 || stride < nbytes) return refuse(what, "stride must be a multiple of 4 and >= the step's bytes");
     const gc_gate *run = gates;
-    rewrite_aliased(s, &run, ngates, nwires, in, nin, out, nout);
+    std::unordered_map<uint32_t, uint32_t> latest;
+    rewrite_aliased(s, &run, ngates, nwires, in, nin, out, nout, &latest);
     SbCirc *ent = nullptr;
     rc = s->find_or_load(run, ngates, nwires, nin, nout, what, &ent);
     if (rc != GC_OK) return rc;
@@ -416,7 +427,12 @@ int garble_step(gc_stream_batch *s, const gc_gate *gates, uint32_t ngates, uint3
         GC_HIP(hipMalloc((void **)&s->d_rnd, rnd_need + rnd_need / 2));
         s->rnd_cap = rnd_need + rnd_need / 2;
     }
+    // equal ids in out[]: the output of the gate that Set the id last is stored (one no gate Sets: the last index)
     last_wins(out, nout, &s->out_marked);
+    for (uint32_t j = 0; j < nout; j++) {
+        auto it = latest.find(out[j]);
+        if (it != latest.end()) s->out_marked[j] = it->second == nwires - nout + j ? out[j] : kNone;
+    }
     StepBlob b;
     b.plan(nin, nout, s->row_off.size(), nbytes);
     SbStage *st = nullptr;
