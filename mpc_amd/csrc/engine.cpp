@@ -678,37 +678,71 @@ static void free_buffers(gc_batch *b) {
     b->d_prof = nullptr;
 }
 
-// (re)allocate the label / table / R arrays for the batch's schedule (= memory layout)
-// live labels the kernel of this batch keeps in LDS: the flattened plan normally, the level-walking plan when
-// every wire has to be materialised (store_all) or schedule 2 was asked for
-// The flattened kernels are the choice unless every wire has to be materialised (store_all), schedule 2 was asked
-// for, or the circuit has no flattened plan.  They address a tile's table rows with 32-bit BYTE offsets:
-// slab_rows * 64 instances * 16 B < 2^32 (a circuit with >= 4 Mi table rows does not fit an LDS plan anyway).
-// ONE instance of a wide circuit: one launch per level with the gates on the lanes (run_levels); needs no LDS plan
-static bool one_wide(const gc_batch *b) {
-    return b->schedule == 1 && b->g.batch == 1 && !b->d_prof && wide_for_one_instance(b->circ->plan.p, false);
+// ---- which kernels a pass of a batch runs ----------------------------------------------------------------------------------
+// ONE decision, path_for(): everything that sizes a batch (geom_for), runs it (run_levels and its callers) or describes it
+// (keyed_path) asks it.  Per path: what selects it | the HBM layout it implies | who draws R and the input labels of a garble.
+//   Levels     schedule 0 | level layout, rows of bstride instances | the init kernel
+//   FusedHbm   schedule 1 / 2 with the wires in HBM: no LDS plan that fits, one still being built by the circuit's thread, or a
+//              batch sized for one wide instance | tiles of up to 64 instances | the init kernel
+//   WideLevels as FusedHbm, and: ONE instance, no debug profile, >= 2 levels that average >= 2.5 passes of 1024 lanes IN THIS
+//              PASS (a streamed SSA-step circuit: a single workgroup on one CU would walk it alone) — one launch per level,
+//              its passes spread over workgroups | a tile of one | the init kernel, or the caller (gc_pass_dev: the wire store)
+//   WideCoop   WideLevels when the ctx can run it as ONE cooperative launch (pass_path: coop_ready) | the same | the same, or
+//              the kernel itself from the wire store (gc_batch::xchg)
+//   FusedLds   wires in LDS, hash-phase order: every wire is to be kept (store_all), schedule 2, or no flattened plan (none, or
+//              >= 4 Mi table rows: the flattened kernels address a tile's rows with 32-bit byte offsets) | tiles sized by the
+//              level-walking plan's live labels (n_lds_slots) | the init kernel
+//   Flat       wires in LDS otherwise (the production path) | tiles sized by n_flat_slots, capped by fl_max_parts | the kernel
+//              itself, unless the plan has no unit (kernel_draws_labels)
+enum class Path { Levels, FusedHbm, WideLevels, WideCoop, FusedLds, Flat };
+
+// THE ONE ASYMMETRY.  Is the batch sized with its wires in HBM by choice?  Garbler and evaluator share a layout, so whether
+// ONE instance counts as wide is decided here with the garbler's pass count, wide_for_one_instance(plan, false), whatever
+// pass will run; whether a given pass then takes the wide form is decided per pass in path_for (level1_passes(st, eval)): the
+// evaluation of a batch sized as wide may still run FusedHbm.  (Pending: the circuit's own thread is building the LDS plans.)
+static bool sized_for_hbm(const gc_batch *b) {
+    return flat_pending(b->circ) ||
+           (b->schedule == 1 && b->g.batch == 1 && !b->d_prof && wide_for_one_instance(b->circ->plan.p, false));
 }
 
-static bool want_flat(const gc_batch *b) {
-    if (one_wide(b) || flat_pending(b->circ)) return false;
-    circ_ensure_flat(b->circ);
+// lds: the wires are in LDS (b->g.lds_wires) — or, while the batch is being sized, are wanted there.  Builds nothing; reads
+// none of the plan's LDS / flattened fields unless lds (whoever sized the batch with lds has built them: geom_for).
+static Path path_for(const gc_batch *b, bool eval, bool lds) {
     const Plan &p = b->circ->plan.p;
-    return !b->store_all && !b->single_phase && p.n_flat_slots != 0xffffffffu && p.info.slab_rows < (1u << 22);
+    if (b->schedule == 0) return Path::Levels;
+    if (lds)
+        return !b->store_all && !b->single_phase && p.n_flat_slots != 0xffffffffu && p.info.slab_rows < (1u << 22) ? Path::Flat
+                                                                                                                     : Path::FusedLds;
+    if (b->g.batch != 1 || b->d_prof || p.levels.size() < 2) return Path::FusedHbm;
+    uint64_t passes = 0;
+    for (const Step &st : p.levels) passes += level1_passes(st, eval);
+    return passes * 2 >= (uint64_t)p.levels.size() * 5 ? Path::WideLevels : Path::FusedHbm;
+}
+static Path batch_path(const gc_batch *b, bool eval) { return path_for(b, eval, b->g.lds_wires); }
+
+// the path of the pass that is about to be enqueued (first use of a ctx runs the cooperative self-test: not for queries)
+static Path pass_path(gc_batch *b, bool eval) {
+    const Path path = batch_path(b, eval);
+    return path == Path::WideLevels && coop_ready(b->circ->ctx) ? Path::WideCoop : path;
 }
 
+// a garble on this path draws R and the input labels inside the kernel (a launch of zero units is a no-op and draws nothing)
+static bool kernel_draws_labels(const gc_batch *b, Path path) { return path == Path::Flat && !b->circ->plan.p.fl_units.empty(); }
+
+// the layout of the batch's label / table / R arrays.  Sizing a batch is where the circuit's LDS plans are asked for: built
+// here on first demand, never by a query.
 static BatchGeom geom_for(const gc_batch *b) {
     const Plan &p = b->circ->plan.p;
-    // (no plan with the wires in LDS yet — the circuit's own thread is building it: the HBM-wire kernels; none of the plan's
-    // flattened / LDS fields is read while that thread writes them: constants instead)
-    const bool pend = flat_pending(b->circ);
-    if (pend) return make_geom(b->g.batch, b->schedule, p.info.nslots, p.info.slab_rows, 0xffffffffu, 6u, false, 0);
-    const bool flat = want_flat(b);
-    const uint32_t nls = one_wide(b) ? 0xffffffffu : flat ? p.n_flat_slots : p.n_lds_slots;
+    const bool lds = !sized_for_hbm(b);
+    if (lds) circ_ensure_flat(b->circ);
+    const bool flat = path_for(b, false, lds) == Path::Flat;
+    const uint32_t nls = !lds ? 0xffffffffu : flat ? p.n_flat_slots : p.n_lds_slots;
     // an XOR list spread over 2 / 4 lanes (TI apart) is joined with DPP row shifts: parts * TI <= 16
     const uint32_t max_t = flat ? (p.fl_max_parts >= 4 ? 2u : p.fl_max_parts == 2 ? 3u : 6u) : 6u;
-    return make_geom(b->g.batch, b->schedule, p.info.nslots, p.info.slab_rows, nls, max_t, flat, p.fl_unit_stride);
+    return make_geom(b->g.batch, b->schedule, p.info.nslots, p.info.slab_rows, nls, max_t, flat, flat ? p.fl_unit_stride : 0);
 }
 
+// (re)allocate the label / table / R arrays for the batch's schedule (= memory layout)
 static hipError_t alloc_buffers(gc_batch *b) {
     const Plan &p = b->circ->plan.p;
     b->g = geom_for(b);
@@ -861,52 +895,120 @@ static hipError_t enqueue_levels(gc_batch *b, bool eval, const uint4 *T, hipStre
     return hipGetLastError();
 }
 
-// does this batch run the flattened fused kernels?
-static bool uses_flat(const gc_batch *b) {
-    return b->schedule == 1 && b->g.lds_wires && want_flat(b) && !b->circ->plan.p.fl_units.empty();
-}
-
-// ONE instance of a wide circuit with its wires in HBM (a streamed SSA-step circuit): levels averaging >= 2.5 passes of
-// 1024 lanes are spread over workgroups (run_levels)
-static bool wide_one_instance(const gc_batch *b, bool eval) {
+// the kernel arguments of the level-walking passes with the wires in HBM / of the flattened passes: rk = the round keys of
+// the batch (one key) or of every instance (keyed)
+static FusedArgs fused_args(const gc_batch *b, const uint4 *T, const uint32_t *rk, int rounds) {
     const Plan &p = b->circ->plan.p;
-    if (b->schedule != 1 || b->g.lds_wires || b->g.batch != 1 || b->d_prof || p.levels.size() < 2) return false;
-    uint64_t passes = 0;
-    for (const Step &st : p.levels) passes += level1_passes(st, eval);
-    return passes * 2 >= (uint64_t)p.levels.size() * 5;
+    FusedArgs a{};
+    a.descs = b->circ->d_descs;
+    a.steps = b->circ->d_steps;
+    a.nsteps = (uint32_t)p.levels.size();
+    a.ninputs = p.info.ninputs;
+    a.W = b->d_W;
+    a.R = b->d_R;
+    a.T = const_cast<uint4 *>(T);
+    a.rk = rk;
+    a.te0 = b->circ->ctx->d_te0;
+    a.rounds = rounds;
+    a.prof = b->d_prof;
+    a.narrow_col = !std::getenv("GC_NO_COL") && fused_col_form_fits(p.levels.data(), (uint32_t)p.levels.size(), b->g.ti_log2);
+    return a;
 }
 
-static int run_levels(gc_batch *b, bool eval, const uint4 *T, const uint4 *rnd = nullptr) {
+static FusedFlatArgs flat_args(const gc_batch *b, const uint4 *T, const uint32_t *rk, int rounds, const uint4 *rnd) {
+    const Plan &p = b->circ->plan.p;
+    FusedFlatArgs f{};
+    f.prog = b->circ->d_fl_prog;
+    f.units = b->circ->d_fl_units;
+    f.hgslot = b->circ->d_fl_hgslot;
+    f.ogslot = b->circ->d_fl_ogslot;
+    f.in_lds = b->circ->d_fl_in_lds;
+    f.nunits = (uint32_t)p.fl_units.size();
+    f.ninputs = p.info.ninputs;
+    f.nls = p.n_flat_slots;
+    f.ustride = p.fl_unit_stride;
+    f.W = b->d_W;
+    f.R = b->d_R;
+    f.T = const_cast<uint4 *>(T);
+    f.rk = rk;
+    f.te0 = b->circ->ctx->d_te0;
+    f.rounds = rounds;
+    f.prof = b->d_prof;
+    f.rnd = rnd;
+    f.has_or = p.info.n_or != 0;
+    return f;
+}
+
+// The launches of `enqueue` (which returns the first launch error) as ONE graph launch: recorded once per (pass, key size,
+// table pointer, kind) of the batch and replayed.  A capture with a refused launch would miss it: such a capture is never
+// kept.  Capture unavailable, or a launch refused: direct launches of the same kernels (which report a refused launch), and no
+// further captures for this batch.
+enum { kGraphLevels = 0, kGraphWide = 3 };  // kind
+extern "C++" {  // (two templates)
+template <class F>
+static int launch_graphed(gc_batch *b, bool eval, const uint4 *T, int kind, F enqueue) {
     hipStream_t s = b->circ->ctx->stream;
-    const Plan &p = b->circ->plan.p;
-    // fused, LDS-resident wires, flattened XOR (the production path).  The level-walking kernel below keeps
-    // every intermediate wire (store_all / Garbled.Wires).
-    if (b->schedule == 1 && b->g.lds_wires && want_flat(b)) {
-        FusedFlatArgs f{};
-        f.prog = b->circ->d_fl_prog;
-        f.units = b->circ->d_fl_units;
-        f.hgslot = b->circ->d_fl_hgslot;
-        f.ogslot = b->circ->d_fl_ogslot;
-        f.in_lds = b->circ->d_fl_in_lds;
-        f.nunits = (uint32_t)p.fl_units.size();
-        f.ninputs = p.info.ninputs;
-        f.nls = p.n_flat_slots;
-        f.ustride = p.fl_unit_stride;
-        f.W = b->d_W;
-        f.R = b->d_R;
-        f.T = const_cast<uint4 *>(T);
-        f.rk = b->d_rk;
-        f.te0 = b->circ->ctx->d_te0;
-        f.rounds = b->rounds;
-        f.prof = b->d_prof;
-        f.rnd = rnd;
-        f.has_or = p.info.n_or != 0;
-        GC_HIP(launch_fused_flat(eval, f, b->g, s));
-        b->last_launches = f.nunits ? 1 : 0;
-        b->have_all_wires = false;
+    for (auto &ge : b->graphs)
+        if (ge.eval == eval && ge.rounds == b->rounds && ge.T == T && ge.kind == kind) {
+            GC_HIP(hipGraphLaunch(ge.exec, s));
+            return GC_OK;
+        }
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    hipError_t e;
+    {
+        std::lock_guard<std::mutex> cap(capture_mu());  // (one capture at a time in the process, see capture_mu)
+        const hipError_t e_begin = e = hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed);
+        hipError_t e_launch = hipSuccess, e_end = hipSuccess;
+        if (e == hipSuccess) {
+            e_launch = enqueue();
+            e = e_end = hipStreamEndCapture(s, &graph);
+            if (e == hipSuccess) e = e_launch;
+        }
+        if (e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        if (e != hipSuccess && kind == kGraphWide && std::getenv("GC_TRACE"))
+            std::fprintf(stderr, "[gc trace] level-launch capture failed: begin %d launch %d end %d instantiate %d\n", (int)e_begin,
+                         (int)e_launch, (int)e_end, (int)e);
+    }
+    if (graph) (void)hipGraphDestroy(graph);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        b->use_graph = false;
+        GC_HIP(enqueue());
         return GC_OK;
     }
-    if (b->schedule == 1 && b->g.lds_wires) {  // fused, LDS-resident wires, hash-phase order
+    b->graphs.push_back({eval, b->rounds, kind, T, exec});
+    GC_HIP(hipGraphLaunch(exec, s));
+    return GC_OK;
+}
+
+// the timing bracket of a pass (gc_batch_last_ms): events around what `pass` enqueues, none while the ctx records a pipeline
+template <class F>
+static int timed_pass(gc_batch *b, F pass) {
+    gc_ctx *ctx = b->circ->ctx;
+    if (!ctx->capturing) GC_HIP(hipEventRecord(b->ev0, ctx->stream));
+    const int rc = pass();
+    if (rc != GC_OK) return rc;
+    if (!ctx->capturing) GC_HIP(hipEventRecord(b->ev1, ctx->stream));
+    b->timed = !ctx->capturing;
+    return GC_OK;
+}
+}  // extern "C++"
+
+// enqueue one garble (eval == false) or eval pass on `path` (pass_path(b, eval): the caller may have acted on it already)
+static int run_levels(gc_batch *b, Path path, bool eval, const uint4 *T, const uint4 *rnd = nullptr) {
+    gc_ctx *ctx = b->circ->ctx;
+    hipStream_t s = ctx->stream;
+    const Plan &p = b->circ->plan.p;
+    b->have_all_wires = path == Path::FusedLds ? b->store_all : path != Path::Flat;  // (wires in HBM: every one of them)
+    switch (path) {
+    case Path::Flat: {
+        const FusedFlatArgs f = flat_args(b, T, b->d_rk, b->rounds, rnd);
+        GC_HIP(launch_fused_flat(eval, f, b->g, s));
+        b->last_launches = f.nunits ? 1 : 0;
+        return GC_OK;
+    }
+    case Path::FusedLds: {  // (also keeps every intermediate wire: store_all / Garbled.Wires)
         FusedLdsArgs f{};
         f.descs = b->circ->d_fdescs;
         f.gslot = b->circ->d_fgslot;
@@ -921,134 +1023,53 @@ static int run_levels(gc_batch *b, bool eval, const uint4 *T, const uint4 *rnd =
         f.R = b->d_R;
         f.T = const_cast<uint4 *>(T);
         f.rk = b->d_rk;
-        f.te0 = b->circ->ctx->d_te0;
+        f.te0 = ctx->d_te0;
         f.rounds = b->rounds;
         f.store_all = b->store_all;
         f.prof = b->d_prof;
         GC_HIP(launch_fused_lds(eval, f, b->g, s));
         b->last_launches = f.nsteps ? 1 : 0;
-        b->have_all_wires = b->store_all;
         return GC_OK;
     }
-    b->have_all_wires = true;
-    if (b->schedule == 1) {  // fused with global-memory wires (circuits whose live set exceeds LDS)
-        FusedArgs a{};
-        a.descs = b->circ->d_descs;
-        a.steps = b->circ->d_steps;
-        a.nsteps = (uint32_t)p.levels.size();
-        a.ninputs = p.info.ninputs;
-        a.W = b->d_W;
-        a.R = b->d_R;
-        a.T = const_cast<uint4 *>(T);
-        a.rk = b->d_rk;
-        a.te0 = b->circ->ctx->d_te0;
-        a.rounds = b->rounds;
-        a.prof = b->d_prof;
-        a.narrow_col = !std::getenv("GC_NO_COL") && fused_col_form_fits(p.levels.data(), (uint32_t)p.levels.size(), b->g.ti_log2);
-        // ONE instance of a wide circuit (a streamed SSA-step circuit): a single workgroup on one CU would walk it alone.
-        // When the levels average >= 2.5 passes of 1024 lanes, spread every level's passes over workgroups, one launch
-        // per level, recorded once in a hipGraph per (pass, key size, table pointer) and replayed.
-        if (wide_one_instance(b, eval)) {
-            {
-                if (coop_ready(b->circ->ctx)) {  // ONE launch: 32 workgroups of one XCD behind a barrier in its L2
-                    gc_ctx *cx = b->circ->ctx;
-                    // a workgroup that gives up raises the pinned word *h_coop_err itself (no copy per pass); it stays up
-                    // until gc_ctx_coop_check (gc_ctx_sync, gc_pass_dev, the streaming calls that hand results out) notes it
-                    // (with its stand-by workgroup: a pass that loses a workgroup is done again inside the same launch)
-                    launch_coop(eval, a, cx->d_coop, b->xchg, cx->coop_launched, s);
-                    GC_HIP(hipGetLastError());
-                    if (a.nsteps) cx->coop_launched++;  // (a launch that really went out) = the device's count of passes once this one has run
-                    b->last_launches = 1;
-                    return GC_OK;
-                }
-                b->last_launches = a.nsteps;
-                const int kGraphKey = 3;  // distinct from the schedule-0 graphs of this batch
-                if (!b->use_graph || b->circ->ctx->capturing || live_contexts() > 1) {
-                    launch_levels1(eval, a, p.levels.data(), s);
-                    GC_HIP(hipGetLastError());
-                    return GC_OK;
-                }
-                for (auto &ge : b->graphs)
-                    if (ge.eval == eval && ge.rounds == b->rounds && ge.T == T && ge.schedule == kGraphKey) {
-                        GC_HIP(hipGraphLaunch(ge.exec, s));
-                        return GC_OK;
-                    }
-                hipGraph_t graph = nullptr;
-                hipGraphExec_t exec = nullptr;
-                hipError_t e;
-                {
-                    std::lock_guard<std::mutex> cap(capture_mu());  // (one capture at a time in the process, see capture_mu)
-                    e = hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed);
-                    const hipError_t e_begin = e;
-                    hipError_t e_launch = hipSuccess, e_end = hipSuccess;
-                    if (e == hipSuccess) {
-                        launch_levels1(eval, a, p.levels.data(), s);
-                        e_launch = hipGetLastError();
-                        e = e_end = hipStreamEndCapture(s, &graph);
-                        if (e == hipSuccess) e = e_launch;
-                    }
-                    if (e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-                    if (e != hipSuccess && std::getenv("GC_TRACE"))
-                        std::fprintf(stderr, "[gc trace] level-launch capture failed: begin %d launch %d end %d instantiate %d\n", (int)e_begin,
-                                     (int)e_launch, (int)e_end, (int)e);
-                }
-                if (graph) (void)hipGraphDestroy(graph);
-                if (e != hipSuccess) {  // capture unavailable: direct launches of the same kernels
-                    (void)hipGetLastError();
-                    b->use_graph = false;
-                    launch_levels1(eval, a, p.levels.data(), s);
-                    GC_HIP(hipGetLastError());
-                    return GC_OK;
-                }
-                b->graphs.push_back({eval, b->rounds, kGraphKey, T, exec});
-                GC_HIP(hipGraphLaunch(exec, s));
-                return GC_OK;
-            }
-        }
+    case Path::FusedHbm: {
+        const FusedArgs a = fused_args(b, T, b->d_rk, b->rounds);
         if (eval) launch_eval_fused(a, b->g, s);
         else launch_garble_fused(a, b->g, s);
         GC_HIP(hipGetLastError());
         b->last_launches = a.nsteps ? 1 : 0;
         return GC_OK;
     }
-    b->last_launches = (uint32_t)p.levels.size();
-    if (!b->use_graph || p.levels.size() < 2 || live_contexts() > 1) {
-        GC_HIP(enqueue_levels(b, eval, T, s));
+    case Path::WideCoop: {  // ONE launch: 32 workgroups of one XCD behind a barrier in its L2
+        const FusedArgs a = fused_args(b, T, b->d_rk, b->rounds);
+        // a workgroup that gives up raises the pinned word *h_coop_err itself (no copy per pass); it stays up until
+        // gc_ctx_coop_check (gc_ctx_sync, gc_pass_dev, the streaming calls that hand results out) notes it (with its stand-by
+        // workgroup: a pass that loses a workgroup is done again inside the same launch)
+        launch_coop(eval, a, ctx->d_coop, b->xchg, ctx->coop_launched, s);
+        GC_HIP(hipGetLastError());
+        if (a.nsteps) ctx->coop_launched++;  // (a launch that really went out) = the device's count of passes once this one has run
+        b->last_launches = 1;
         return GC_OK;
     }
-    // one captured graph per (pass, rounds, table pointer, schedule)
-    for (auto &ge : b->graphs) {
-        if (ge.eval == eval && ge.rounds == b->rounds && ge.T == T && ge.schedule == b->schedule) {
-            GC_HIP(hipGraphLaunch(ge.exec, s));
-            return GC_OK;
-        }
-    }
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    hipError_t e;
-    {
-        std::lock_guard<std::mutex> cap(capture_mu());
-        e = hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed);
-        if (e == hipSuccess) {
-            // a level whose launch was refused would be missing from the graph: such a capture is never kept
-            const hipError_t e_launch = enqueue_levels(b, eval, T, s);
-            e = hipStreamEndCapture(s, &graph);
-            if (e == hipSuccess) e = e_launch;
-        }
-        if (e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    }
-    if (graph) (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) {
-        // capture unsupported in this environment, or a launch refused: direct launches of the same kernels (which report
-        // a refused launch)
-        (void)hipGetLastError();
-        b->use_graph = false;
-        GC_HIP(enqueue_levels(b, eval, T, s));
+    case Path::WideLevels: {
+        const FusedArgs a = fused_args(b, T, b->d_rk, b->rounds);
+        b->last_launches = a.nsteps;
+        auto levels = [&] {
+            launch_levels1(eval, a, p.levels.data(), s);
+            return hipGetLastError();
+        };
+        if (b->use_graph && !ctx->capturing && live_contexts() <= 1) return launch_graphed(b, eval, T, kGraphWide, levels);
+        GC_HIP(levels());
         return GC_OK;
     }
-    b->graphs.push_back({eval, b->rounds, b->schedule, T, exec});
-    GC_HIP(hipGraphLaunch(exec, s));
-    return GC_OK;
+    case Path::Levels: {
+        b->last_launches = (uint32_t)p.levels.size();
+        auto levels = [&] { return enqueue_levels(b, eval, T, s); };
+        if (b->use_graph && p.levels.size() >= 2 && live_contexts() <= 1) return launch_graphed(b, eval, T, kGraphLevels, levels);
+        GC_HIP(levels());
+        return GC_OK;
+    }
+    }
+    return GC_E_ARG;
 }
 
 int gc_batch_garble(gc_batch *b, const uint8_t *key, size_t keylen, const void *d_rnd) {
@@ -1058,17 +1079,12 @@ int gc_batch_garble(gc_batch *b, const uint8_t *key, size_t keylen, const void *
     int rc = set_key(b, key, keylen);
     if (rc != GC_OK) return rc;
     b->r_known = false;  // (drawn on the device)
-    const Plan &p = b->circ->plan.p;
-    // the flattened fused kernel draws R and the input labels itself; the other schedules get them from a small
-    // initialisation kernel (outside the timed bracket)
-    const bool fused_init = uses_flat(b);
-    if (!fused_init) launch_init_garble((const uint4 *)d_rnd, p.info.ninputs, b->d_W, b->d_R, b->g, ctx->stream);
-    if (!ctx->capturing) GC_HIP(hipEventRecord(b->ev0, ctx->stream));
-    rc = run_levels(b, false, b->d_T, fused_init ? (const uint4 *)d_rnd : nullptr);
-    if (rc != GC_OK) return rc;
-    if (!ctx->capturing) GC_HIP(hipEventRecord(b->ev1, ctx->stream));
-    b->timed = !ctx->capturing;
-    return GC_OK;
+    // R and the input labels: drawn by the flattened kernel itself, on the other paths by a small initialisation kernel
+    // (outside the timed bracket)
+    const Path path = pass_path(b, false);
+    const bool in_kernel = kernel_draws_labels(b, path);
+    if (!in_kernel) launch_init_garble((const uint4 *)d_rnd, b->circ->plan.p.info.ninputs, b->d_W, b->d_R, b->g, ctx->stream);
+    return timed_pass(b, [&] { return run_levels(b, path, false, b->d_T, in_kernel ? (const uint4 *)d_rnd : nullptr); });
 }
 
 // two batches can exchange labels / tables only if their HBM layouts agree (same schedule class and tile size)
@@ -1103,12 +1119,7 @@ int gc_batch_eval(gc_batch *ev, const uint8_t *key, size_t keylen, const gc_batc
     GC_HIP(hipSetDevice(ctx->device));
     int rc = set_key(ev, key, keylen);
     if (rc != GC_OK) return rc;
-    if (!ctx->capturing) GC_HIP(hipEventRecord(ev->ev0, ctx->stream));
-    rc = run_levels(ev, true, tables->d_T);
-    if (rc != GC_OK) return rc;
-    if (!ctx->capturing) GC_HIP(hipEventRecord(ev->ev1, ctx->stream));
-    ev->timed = !ctx->capturing;
-    return GC_OK;
+    return timed_pass(ev, [&] { return run_levels(ev, pass_path(ev, true), true, tables->d_T); });
 }
 
 // ---- one AES key per instance (fused_flat_keyed_kernels.hip, fused_hbm_keyed_kernels.hip) -----------------------
@@ -1122,8 +1133,9 @@ static int keyed_path(const gc_batch *b, const char **why) {
         *why = "schedule 1 only";
         return 0;
     }
-    if (b->keyed_force == 2 || !b->g.lds_wires) return 2;
-    if (!uses_flat(b)) {
+    const Path path = batch_path(b, false);
+    if (b->keyed_force == 2 || path == Path::FusedHbm || path == Path::WideLevels) return 2;
+    if (!kernel_draws_labels(b, path)) {
         *why = "the batch keeps its wires in LDS without the flattened kernels";
         return 0;
     }
@@ -1135,12 +1147,9 @@ static int keyed_path(const gc_batch *b, const char **why) {
     return 1;
 }
 
-int gc_batch_keyed_path(const gc_batch *b) try {
+int gc_batch_keyed_path(const gc_batch *b) {
     const char *why;
     return b ? keyed_path(b, &why) : 0;
-} catch (...) {
-    (void)gc::on_exception();
-    return 0;
 }
 
 int gc_batch_keyed_supported(const gc_batch *b) { return gc_batch_keyed_path(b) != 0; }
@@ -1175,51 +1184,21 @@ static int run_keyed(gc_batch *b, bool eval, const void *d_keys, size_t keylen, 
     int rc = expand_keys(b, d_keys, rounds);
     if (rc != GC_OK) return rc;
     const Plan &p = b->circ->plan.p;
-    if (path == 2) {  // wires in HBM: R and the input labels from a kernel of their own, as in gc_batch_garble
-        if (!eval) launch_init_garble(rnd, p.info.ninputs, b->d_W, b->d_R, b->g, ctx->stream);
-        FusedArgs a{};
-        a.descs = b->circ->d_descs;
-        a.steps = b->circ->d_steps;
-        a.nsteps = (uint32_t)p.levels.size();
-        a.ninputs = p.info.ninputs;
-        a.W = b->d_W;
-        a.R = b->d_R;
-        a.T = const_cast<uint4 *>(T);
-        a.te0 = ctx->d_te0;
-        a.rounds = rounds;
-        if (!ctx->capturing) GC_HIP(hipEventRecord(b->ev0, ctx->stream));
-        GC_HIP(launch_fused_hbm_keyed(eval, a, b->d_keyed_rk, p.info.n_or != 0, b->g, ctx->stream));
-        if (!ctx->capturing) GC_HIP(hipEventRecord(b->ev1, ctx->stream));
-        b->timed = !ctx->capturing;
-        b->last_launches = 1;
-        b->have_all_wires = true;
+    // wires in HBM: R and the input labels from a kernel of their own, as in gc_batch_garble
+    if (path == 2 && !eval) launch_init_garble(rnd, p.info.ninputs, b->d_W, b->d_R, b->g, ctx->stream);
+    return timed_pass(b, [&]() -> int {
+        if (path == 2) {
+            GC_HIP(launch_fused_hbm_keyed(eval, fused_args(b, T, b->d_keyed_rk, rounds), b->d_keyed_rk, p.info.n_or != 0, b->g, ctx->stream));
+            b->last_launches = 1;
+            b->have_all_wires = true;
+            return GC_OK;
+        }
+        const FusedFlatArgs f = flat_args(b, T, b->d_keyed_rk, rounds, rnd);
+        GC_HIP(launch_fused_flat_keyed(eval, f, b->g, ctx->stream));
+        b->last_launches = f.nunits ? 1 : 0;
+        b->have_all_wires = false;
         return GC_OK;
-    }
-    FusedFlatArgs f{};
-    f.prog = b->circ->d_fl_prog;
-    f.units = b->circ->d_fl_units;
-    f.hgslot = b->circ->d_fl_hgslot;
-    f.ogslot = b->circ->d_fl_ogslot;
-    f.in_lds = b->circ->d_fl_in_lds;
-    f.nunits = (uint32_t)p.fl_units.size();
-    f.ninputs = p.info.ninputs;
-    f.nls = p.n_flat_slots;
-    f.ustride = p.fl_unit_stride;
-    f.W = b->d_W;
-    f.R = b->d_R;
-    f.T = const_cast<uint4 *>(T);
-    f.rk = b->d_keyed_rk;
-    f.te0 = ctx->d_te0;
-    f.rounds = rounds;
-    f.rnd = rnd;
-    f.has_or = p.info.n_or != 0;
-    if (!ctx->capturing) GC_HIP(hipEventRecord(b->ev0, ctx->stream));
-    GC_HIP(launch_fused_flat_keyed(eval, f, b->g, ctx->stream));
-    if (!ctx->capturing) GC_HIP(hipEventRecord(b->ev1, ctx->stream));
-    b->timed = !ctx->capturing;
-    b->last_launches = f.nunits ? 1 : 0;
-    b->have_all_wires = false;
-    return GC_OK;
+    });
 }
 
 int gc_batch_garble_keyed(gc_batch *b, const void *d_keys, size_t keylen, const void *d_rnd) try {
@@ -1747,7 +1726,7 @@ int gc_garble_labels_keep(gc_circ *c, const uint8_t *key, size_t keylen, const g
         if (p.info.ninputs) rc = write_scatter(b, inputs, p.info.ninputs, 0, p.info.ninputs, nullptr, 0, b->d_W, b->g.lw);
         if (rc != GC_OK) break;
         if ((rc = set_key(b, key, keylen)) != GC_OK) break;
-        if ((rc = run_levels(b, false, b->d_T)) != GC_OK) break;
+        if ((rc = run_levels(b, pass_path(b, false), false, b->d_T)) != GC_OK) break;
         if (out_l0 && (rc = gc_batch_read_outputs(b, out_l0)) != GC_OK) break;
     } while (0);
     if (rc != GC_OK) {
@@ -1840,11 +1819,13 @@ int gc_pass_dev(gc_circ *c, bool eval, const uint8_t *key, size_t keylen, const 
         // a cooperative pass exchanges the labels with the store itself (a kernel before and one behind it were 10 us
         // plus their gaps of a 230 us step)
         // (the caller has put the same pointers into *d_xchg, in device memory, with its other uploads)
-        const bool in_pass = d_xchg && wide_one_instance(b, eval) && coop_ready(ctx);
+        // (the path is decided once: the exchange here and the kernel in run_levels cannot disagree)
+        const Path path = pass_path(b, eval);
+        const bool in_pass = d_xchg && path == Path::WideCoop;
         if (!in_pass) launch_store_gather(b->d_W, (const uint4 *)d_store, d_in_idx, p.info.ninputs, ctx->stream);
         if ((rc = set_key(b, key, keylen)) != GC_OK) break;
         b->xchg = in_pass ? d_xchg : nullptr;
-        rc = run_levels(b, eval, b->d_T);
+        rc = run_levels(b, path, eval, b->d_T);
         b->xchg = nullptr;
         if (rc != GC_OK) break;
         if (!in_pass)

@@ -130,7 +130,7 @@ struct gc_circ {
 struct gc_graph_entry {
     bool eval;
     int rounds;
-    int schedule;
+    int kind;  // which launches (engine.cpp: kGraphLevels / kGraphWide)
     const uint4 *T;
     hipGraphExec_t exec;
 };
