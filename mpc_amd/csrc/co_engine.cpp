@@ -39,27 +39,7 @@ int launched() {
     return GC_OK;
 }
 
-// A host form is staging around the operation of its _dev form: one Staged per array, in the order of the operation's
-// arguments.  stage_in allocates EVERY device copy before it copies the first input; stage_out copies the outputs (a status
-// block is one of them) and waits, once.
-struct Staged {
-    const void *in;  // copied to the device before the operation, or NULL
-    void *out;       // copied back behind it, or NULL
-    size_t bytes;
-    DevBuf d;
-};
-int stage_in(Staged *io, size_t k, hipStream_t s) {
-    for (size_t j = 0; j < k; j++) GC_HIP(io[j].d.alloc(io[j].bytes));
-    for (size_t j = 0; j < k; j++)
-        if (io[j].in) GC_HIP(hipMemcpyAsync(io[j].d.p, io[j].in, io[j].bytes, hipMemcpyHostToDevice, s));
-    return GC_OK;
-}
-int stage_out(Staged *io, size_t k, hipStream_t s) {
-    for (size_t j = 0; j < k; j++)
-        if (io[j].out) GC_HIP(hipMemcpyAsync(io[j].out, io[j].d.p, io[j].bytes, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipStreamSynchronize(s));
-    return GC_OK;
-}
+// A host form is staging (host_staging.h: Staged, stage_in, stage_out) around the operation of its _dev form.
 
 Fe load_fe(const uint8_t *b) {
     Fe f;

@@ -11,31 +11,13 @@
 
 #include "../../include/gcengine.h"
 #include "aes_host.h"
+#include "host_staging.h"  // DevBuf, GC_HIP, gc::set_error; Staged, stage_in / stage_out
 #include "kernels.h"
 #include "plan.h"
 
 namespace gc {
 extern thread_local char tls_error[512];
-void set_error(const char *what, hipError_t e);
-
-// a temporary device buffer, freed on scope exit
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
 }  // namespace gc
-
-#define GC_HIP(expr)                                                   \
-    do {                                                               \
-        hipError_t e__ = (expr);                                       \
-        if (e__ != hipSuccess) {                                       \
-            gc::set_error(#expr, e__);                                 \
-            return e__ == hipErrorOutOfMemory ? GC_E_NOMEM : GC_E_HIP; \
-        }                                                              \
-    } while (0)
 
 struct gc_ctx {
     int device = 0;

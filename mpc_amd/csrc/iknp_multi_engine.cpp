@@ -1,9 +1,11 @@
 // iknp_multi_engine.cpp — C ABI of the multi-session IKNP extension and COT pad loops (gc_iknp_multi_*, gc_cot_multi_*):
 // S sessions of `per` OTs each, session-major, one kernel per call (iknp_multi_kernels.hip; layouts: iknp_multi.h), of
 // bit-COT on the same handle (gc_iknp_multi_*_bits*) and of the triple folds over S peers (gc_gmw_triples_multi_*;
-// iknp_multi_bits_kernels.hip, iknp_multi_bits.h).
+// iknp_multi_bits_kernels.hip, iknp_multi_bits.h).  A host form is staging (host_staging.h) around the operation of its _dev
+// form.
 #include <algorithm>
 #include <cstring>
+#include <iterator>
 #include <new>
 
 #include "engine.h"
@@ -103,6 +105,26 @@ int multi_call_args(const gc_iknp_multi *h, bool receiver, size_t per, MultiSize
     return GC_OK;
 }
 
+// The operations on device pointers, the device set: what a _dev form does behind its argument checks.  The stream position
+// is the caller's to advance.
+// the receiver's (d_choice_packed -> d_u_out, d_labels_out) or the sender's (d_u_in -> d_labels_out) extension
+int extend_run(gc_iknp_multi *h, size_t per, const void *d_choice_packed, const void *d_u_in, void *d_u_out, void *d_labels_out) {
+    GC_HIP(launch_iknp_multi(h->receiver, h->d_keys, h->d_delta, h->pos, h->S, per, (const uint8_t *)d_choice_packed,
+                             (const uint8_t *)d_u_in, (uint8_t *)d_u_out, (uint4 *)d_labels_out, h->ctx->d_te0, h->ctx->stream));
+    return GC_OK;
+}
+int cot_send_run(gc_ctx *ctx, const void *d_seed, const void *d_delta, const void *d_data, const void *d_wires, size_t S,
+                 size_t per, void *d_out) {
+    GC_HIP(launch_cot_multi_send((const uint4 *)d_seed, (const uint4 *)d_delta, (const uint4 *)d_data, (const uint4 *)d_wires, S,
+                                 per, (uint4 *)d_out, ctx->d_te0, ctx->stream));
+    return GC_OK;
+}
+int cot_recv_run(gc_ctx *ctx, const void *d_seed, const void *d_flags, const void *d_sent, void *d_result, size_t S, size_t per) {
+    GC_HIP(launch_cot_multi_recv((const uint4 *)d_seed, (const uint8_t *)d_flags, (const uint4 *)d_sent, (uint4 *)d_result, S,
+                                 per, ctx->d_te0, ctx->stream));
+    return GC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -148,10 +170,9 @@ int gc_iknp_multi_receive_dev(gc_iknp_multi *h, const void *d_choice_packed, siz
     if (!d_choice_packed || !d_u_out || !d_labels_out) return GC_E_ARG;
     gc_ctx *ctx = h->ctx;
     GC_HIP(hipSetDevice(ctx->device));
-    GC_HIP(launch_iknp_multi(true, h->d_keys, nullptr, h->pos, h->S, per, (const uint8_t *)d_choice_packed, nullptr,
-                             (uint8_t *)d_u_out, (uint4 *)d_labels_out, ctx->d_te0, ctx->stream));
-    h->pos += iknp_multi_advance(per);
-    return GC_OK;
+    rc = extend_run(h, per, d_choice_packed, nullptr, d_u_out, d_labels_out);
+    if (rc == GC_OK) h->pos += iknp_multi_advance(per);
+    return rc;
 }
 
 int gc_iknp_multi_send_dev(gc_iknp_multi *h, const void *d_u_in, size_t per, void *d_labels_out) {
@@ -162,10 +183,9 @@ int gc_iknp_multi_send_dev(gc_iknp_multi *h, const void *d_u_in, size_t per, voi
     if (!d_u_in || !d_labels_out) return GC_E_ARG;
     gc_ctx *ctx = h->ctx;
     GC_HIP(hipSetDevice(ctx->device));
-    GC_HIP(launch_iknp_multi(false, h->d_keys, h->d_delta, h->pos, h->S, per, nullptr, (const uint8_t *)d_u_in, nullptr,
-                             (uint4 *)d_labels_out, ctx->d_te0, ctx->stream));
-    h->pos += iknp_multi_advance(per);
-    return GC_OK;
+    rc = extend_run(h, per, nullptr, d_u_in, nullptr, d_labels_out);
+    if (rc == GC_OK) h->pos += iknp_multi_advance(per);
+    return rc;
 }
 
 int gc_iknp_multi_receive(gc_iknp_multi *h, const uint8_t *choice, size_t per, uint8_t *u_out, gc_label *labels_out) try {
@@ -174,27 +194,16 @@ int gc_iknp_multi_receive(gc_iknp_multi *h, const uint8_t *choice, size_t per, u
     if (rc != GC_OK) return rc;
     if (per == 0) return GC_OK;
     if (!choice || !u_out || !labels_out) return GC_E_ARG;
-    const size_t cb = (size_t)iknp_multi_choice_bytes(per);
-    std::vector<uint8_t> bbuf(z.choice, 0);  // iknp.go:472-477, per session
-    for (size_t s = 0; s < h->S; s++)
-        for (size_t j = 0; j < per; j++)
-            if (choice[s * per + j]) bbuf[s * cb + j / 8] |= (uint8_t)(1u << (j % 8));
+    const std::vector<uint8_t> bbuf = pack_rows(choice, h->S, per, (size_t)iknp_multi_choice_bytes(per));  // z.choice bytes
     gc_ctx *ctx = h->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_bits, d_u, d_lab;
-    GC_HIP(d_bits.alloc(z.choice));
-    GC_HIP(d_u.alloc(z.u));
-    GC_HIP(d_lab.alloc(z.labels));
-    hipStream_t st = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_bits.p, bbuf.data(), z.choice, hipMemcpyHostToDevice, st));
-    GC_HIP(launch_iknp_multi(true, h->d_keys, nullptr, h->pos, h->S, per, (const uint8_t *)d_bits.p, nullptr,
-                             (uint8_t *)d_u.p, (uint4 *)d_lab.p, ctx->d_te0, st));
-    GC_HIP(hipMemcpyAsync(u_out, d_u.p, z.u, hipMemcpyDeviceToHost, st));
-    GC_HIP(hipMemcpyAsync(labels_out, d_lab.p, z.labels, hipMemcpyDeviceToHost, st));
-    GC_HIP(hipStreamSynchronize(st));
-    h->pos += iknp_multi_advance(per);
-    return GC_OK;
+    Staged io[] = {{bbuf.data(), nullptr, z.choice}, {nullptr, u_out, z.u}, {nullptr, labels_out, z.labels}};
+    rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = extend_run(h, per, io[0].d.p, nullptr, io[1].d.p, io[2].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) h->pos += iknp_multi_advance(per);
+    return rc;
 } catch (...) {
     return gc::on_exception();
 }
@@ -208,17 +217,12 @@ int gc_iknp_multi_send(gc_iknp_multi *h, const uint8_t *u_in, size_t u_len, size
     gc_ctx *ctx = h->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_u, d_lab;
-    GC_HIP(d_u.alloc(z.u));
-    GC_HIP(d_lab.alloc(z.labels));
-    hipStream_t st = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_u.p, u_in, z.u, hipMemcpyHostToDevice, st));
-    GC_HIP(launch_iknp_multi(false, h->d_keys, h->d_delta, h->pos, h->S, per, nullptr, (const uint8_t *)d_u.p, nullptr,
-                             (uint4 *)d_lab.p, ctx->d_te0, st));
-    GC_HIP(hipMemcpyAsync(labels_out, d_lab.p, z.labels, hipMemcpyDeviceToHost, st));
-    GC_HIP(hipStreamSynchronize(st));
-    h->pos += iknp_multi_advance(per);
-    return GC_OK;
+    Staged io[] = {{u_in, nullptr, z.u}, {nullptr, labels_out, z.labels}};
+    rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = extend_run(h, per, nullptr, io[0].d.p, nullptr, io[1].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) h->pos += iknp_multi_advance(per);
+    return rc;
 } catch (...) {
     return gc::on_exception();
 }
@@ -232,9 +236,7 @@ int gc_cot_multi_send_pads_dev(gc_ctx *ctx, const void *d_seed, const void *d_de
     if (per == 0) return GC_OK;
     if (!d_seed || !d_delta || !d_data || !d_wires || !d_out) return GC_E_ARG;
     GC_HIP(hipSetDevice(ctx->device));
-    GC_HIP(launch_cot_multi_send((const uint4 *)d_seed, (const uint4 *)d_delta, (const uint4 *)d_data, (const uint4 *)d_wires, S,
-                                 per, (uint4 *)d_out, ctx->d_te0, ctx->stream));
-    return GC_OK;
+    return cot_send_run(ctx, d_seed, d_delta, d_data, d_wires, S, per, d_out);
 }
 
 int gc_cot_multi_receive_unpad_dev(gc_ctx *ctx, const void *d_seed, const void *d_flags, const void *d_sent, void *d_result,
@@ -244,9 +246,7 @@ int gc_cot_multi_receive_unpad_dev(gc_ctx *ctx, const void *d_seed, const void *
     if (per == 0) return GC_OK;
     if (!d_seed || !d_flags || !d_sent || !d_result) return GC_E_ARG;
     GC_HIP(hipSetDevice(ctx->device));
-    GC_HIP(launch_cot_multi_recv((const uint4 *)d_seed, (const uint8_t *)d_flags, (const uint4 *)d_sent, (uint4 *)d_result, S,
-                                 per, ctx->d_te0, ctx->stream));
-    return GC_OK;
+    return cot_recv_run(ctx, d_seed, d_flags, d_sent, d_result, S, per);
 }
 
 int gc_cot_multi_send_pads(gc_ctx *ctx, const gc_label *seed, const gc_label *delta, const gc_label *data,
@@ -257,22 +257,12 @@ int gc_cot_multi_send_pads(gc_ctx *ctx, const gc_label *seed, const gc_label *de
     if (!seed || !delta || !data || !wires || !out) return GC_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_seed, d_delta, d_data, d_w, d_out;
-    GC_HIP(d_seed.alloc(S * 16));
-    GC_HIP(d_delta.alloc(S * 16));
-    GC_HIP(d_data.alloc(z.n * 16));
-    GC_HIP(d_w.alloc(z.n * 32));
-    GC_HIP(d_out.alloc(z.n * 32));
-    hipStream_t st = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_seed.p, seed, S * 16, hipMemcpyHostToDevice, st));
-    GC_HIP(hipMemcpyAsync(d_delta.p, delta, S * 16, hipMemcpyHostToDevice, st));
-    GC_HIP(hipMemcpyAsync(d_data.p, data, z.n * 16, hipMemcpyHostToDevice, st));
-    GC_HIP(hipMemcpyAsync(d_w.p, wires, z.n * 32, hipMemcpyHostToDevice, st));
-    GC_HIP(launch_cot_multi_send((const uint4 *)d_seed.p, (const uint4 *)d_delta.p, (const uint4 *)d_data.p,
-                                 (const uint4 *)d_w.p, S, per, (uint4 *)d_out.p, ctx->d_te0, st));
-    GC_HIP(hipMemcpyAsync(out, d_out.p, z.n * 32, hipMemcpyDeviceToHost, st));
-    GC_HIP(hipStreamSynchronize(st));
-    return GC_OK;
+    Staged io[] = {{seed, nullptr, S * 16}, {delta, nullptr, S * 16}, {data, nullptr, z.n * 16}, {wires, nullptr, z.n * 32},
+                   {nullptr, out, z.n * 32}};
+    int rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = cot_send_run(ctx, io[0].d.p, io[1].d.p, io[2].d.p, io[3].d.p, S, per, io[4].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    return rc;
 } catch (...) {
     return gc::on_exception();
 }
@@ -285,21 +275,11 @@ int gc_cot_multi_receive_unpad(gc_ctx *ctx, const gc_label *seed, const uint8_t 
     if (!seed || !flags || !sent || !result) return GC_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_seed, d_f, d_s, d_r;
-    GC_HIP(d_seed.alloc(S * 16));
-    GC_HIP(d_f.alloc(z.n));
-    GC_HIP(d_s.alloc(z.n * 32));
-    GC_HIP(d_r.alloc(z.n * 16));
-    hipStream_t st = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_seed.p, seed, S * 16, hipMemcpyHostToDevice, st));
-    GC_HIP(hipMemcpyAsync(d_f.p, flags, z.n, hipMemcpyHostToDevice, st));
-    GC_HIP(hipMemcpyAsync(d_s.p, sent, z.n * 32, hipMemcpyHostToDevice, st));
-    GC_HIP(hipMemcpyAsync(d_r.p, result, z.n * 16, hipMemcpyHostToDevice, st));
-    GC_HIP(launch_cot_multi_recv((const uint4 *)d_seed.p, (const uint8_t *)d_f.p, (const uint4 *)d_s.p, (uint4 *)d_r.p, S, per,
-                                 ctx->d_te0, st));
-    GC_HIP(hipMemcpyAsync(result, d_r.p, z.n * 16, hipMemcpyDeviceToHost, st));
-    GC_HIP(hipStreamSynchronize(st));
-    return GC_OK;
+    Staged io[] = {{seed, nullptr, S * 16}, {flags, nullptr, z.n}, {sent, nullptr, z.n * 32}, {result, result, z.n * 16}};
+    int rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = cot_recv_run(ctx, io[0].d.p, io[1].d.p, io[2].d.p, io[3].d.p, S, per);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    return rc;
 } catch (...) {
     return gc::on_exception();
 }
@@ -324,6 +304,19 @@ bool bits_choice_span(size_t S, size_t per, size_t stride, size_t *span) {
     return true;
 }
 
+// the bits operations on device pointers, as extend_run.  u_session, u_chunk: where the sender finds column 0 of chunk c of
+// session s (launch_iknp_multi_send_bits)
+int recv_bits_run(gc_iknp_multi *h, size_t per, const void *d_choices, size_t choice_stride, void *d_u_out, void *d_result) {
+    GC_HIP(launch_iknp_multi_recv_bits(h->d_keys, h->pos, h->S, per, (const uint64_t *)d_choices, choice_stride,
+                                       (uint8_t *)d_u_out, (uint64_t *)d_result, h->ctx->d_te0, h->ctx->stream));
+    return GC_OK;
+}
+int send_bits_run(gc_iknp_multi *h, size_t per, const void *d_u_in, size_t u_session, size_t u_chunk, void *d_result) {
+    GC_HIP(launch_iknp_multi_send_bits(h->d_keys, h->d_delta, h->pos, h->S, per, (const uint8_t *)d_u_in, u_session, u_chunk,
+                                       (uint64_t *)d_result, h->ctx->d_te0, h->ctx->stream));
+    return GC_OK;
+}
+
 }  // namespace
 
 int gc_iknp_multi_receive_bits_dev(gc_iknp_multi *h, const void *d_choices, size_t choice_stride, size_t per, void *d_u_out,
@@ -336,10 +329,9 @@ int gc_iknp_multi_receive_bits_dev(gc_iknp_multi *h, const void *d_choices, size
     if (!d_choices || !d_u_out || !d_result || !bits_choice_span(h->S, per, choice_stride, &span)) return GC_E_ARG;
     gc_ctx *ctx = h->ctx;
     GC_HIP(hipSetDevice(ctx->device));
-    GC_HIP(launch_iknp_multi_recv_bits(h->d_keys, h->pos, h->S, per, (const uint64_t *)d_choices, choice_stride,
-                                       (uint8_t *)d_u_out, (uint64_t *)d_result, ctx->d_te0, ctx->stream));
-    h->pos += iknp_multi_advance(per);
-    return GC_OK;
+    rc = recv_bits_run(h, per, d_choices, choice_stride, d_u_out, d_result);
+    if (rc == GC_OK) h->pos += iknp_multi_advance(per);
+    return rc;
 }
 
 int gc_iknp_multi_send_bits_dev(gc_iknp_multi *h, const void *d_u_in, size_t per, void *d_result) {
@@ -351,10 +343,9 @@ int gc_iknp_multi_send_bits_dev(gc_iknp_multi *h, const void *d_u_in, size_t per
     if (!d_u_in || !d_result) return GC_E_ARG;
     gc_ctx *ctx = h->ctx;
     GC_HIP(hipSetDevice(ctx->device));
-    GC_HIP(launch_iknp_multi_send_bits(h->d_keys, h->d_delta, h->pos, h->S, per, (const uint8_t *)d_u_in,
-                                       (size_t)iknp_multi_u_bytes(per), 8192, (uint64_t *)d_result, ctx->d_te0, ctx->stream));
-    h->pos += iknp_multi_advance(per);
-    return GC_OK;
+    rc = send_bits_run(h, per, d_u_in, (size_t)iknp_multi_u_bytes(per), 8192, d_result);
+    if (rc == GC_OK) h->pos += iknp_multi_advance(per);
+    return rc;
 }
 
 int gc_iknp_multi_receive_bits(gc_iknp_multi *h, const uint64_t *choices, size_t choice_stride, size_t per, uint8_t *u_out,
@@ -368,19 +359,12 @@ int gc_iknp_multi_receive_bits(gc_iknp_multi *h, const uint64_t *choices, size_t
     gc_ctx *ctx = h->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_ch, d_u, d_res;
-    GC_HIP(d_ch.alloc(span * 8));
-    GC_HIP(d_u.alloc(z.u));
-    GC_HIP(d_res.alloc(words * 8));
-    hipStream_t st = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_ch.p, choices, span * 8, hipMemcpyHostToDevice, st));
-    GC_HIP(launch_iknp_multi_recv_bits(h->d_keys, h->pos, h->S, per, (const uint64_t *)d_ch.p, choice_stride,
-                                       (uint8_t *)d_u.p, (uint64_t *)d_res.p, ctx->d_te0, st));
-    GC_HIP(hipMemcpyAsync(u_out, d_u.p, z.u, hipMemcpyDeviceToHost, st));
-    GC_HIP(hipMemcpyAsync(result, d_res.p, words * 8, hipMemcpyDeviceToHost, st));
-    GC_HIP(hipStreamSynchronize(st));
-    h->pos += iknp_multi_advance(per);
-    return GC_OK;
+    Staged io[] = {{choices, nullptr, span * 8}, {nullptr, u_out, z.u}, {nullptr, result, words * 8}};
+    rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = recv_bits_run(h, per, io[0].d.p, choice_stride, io[1].d.p, io[2].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) h->pos += iknp_multi_advance(per);
+    return rc;
 } catch (...) {
     return gc::on_exception();
 }
@@ -401,17 +385,12 @@ int gc_iknp_multi_send_bits(gc_iknp_multi *h, const uint8_t *u_in, size_t u_len,
     gc_ctx *ctx = h->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_u, d_res;
-    GC_HIP(d_u.alloc(col0.size()));
-    GC_HIP(d_res.alloc(words * 8));
-    hipStream_t st = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_u.p, col0.data(), col0.size(), hipMemcpyHostToDevice, st));
-    GC_HIP(launch_iknp_multi_send_bits(h->d_keys, h->d_delta, h->pos, h->S, per, (const uint8_t *)d_u.p, row, 64,
-                                       (uint64_t *)d_res.p, ctx->d_te0, st));
-    GC_HIP(hipMemcpyAsync(result, d_res.p, words * 8, hipMemcpyDeviceToHost, st));
-    GC_HIP(hipStreamSynchronize(st));
-    h->pos += iknp_multi_advance(per);
-    return GC_OK;
+    Staged io[] = {{col0.data(), nullptr, col0.size()}, {nullptr, result, words * 8}};
+    rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = send_bits_run(h, per, io[0].d.p, row, 64, io[1].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) h->pos += iknp_multi_advance(per);
+    return rc;
 } catch (...) {
     return gc::on_exception();
 }

@@ -1,8 +1,9 @@
 // kos_multi_engine.cpp — C ABI of the multi-session KOS check (gc_kos_multi_*): the tags and the check of the malicious IKNP
 // variant for S sessions of `per` OTs each, session-major, one kernel per call (kos_multi_kernels.hip; layouts: kos_multi.h).
 // The _dev forms only reset the status block and launch: no allocation, no wait, nothing copied to the host, so they may be
-// captured.  The host forms stage their arrays the way the host forms of iknp_multi_engine.cpp do.
+// captured.  A host form is staging (host_staging.h) around the operation of its _dev form.
 #include <algorithm>
+#include <iterator>
 #include <new>
 #include <vector>
 
@@ -48,21 +49,6 @@ int check_run(gc_ctx *ctx, const void *d_seed2, const void *d_result, const void
     return GC_OK;
 }
 
-// one byte per choice -> rows of `row` bytes, packed LSB first (iknp.go:472-477), zero-padded
-std::vector<uint8_t> pack_rows(const uint8_t *b, size_t S, size_t per, size_t row) {
-    std::vector<uint8_t> out(S * row, 0);
-    for (size_t s = 0; s < S; s++)
-        for (size_t j = 0; j < per; j++)
-            if (b[s * per + j]) out[s * row + j / 8] |= (uint8_t)(1u << (j % 8));
-    return out;
-}
-
-int to_dev(DevBuf &d, const void *src, size_t bytes, hipStream_t st) {
-    GC_HIP(d.alloc(bytes));
-    if (src && bytes) GC_HIP(hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, st));
-    return GC_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -102,17 +88,12 @@ int gc_kos_multi_receiver_tags(gc_ctx *ctx, const gc_label *seed2, const gc_labe
     const std::vector<uint8_t> bits = pack_rows(b, S, per, z.choice_row), cbits = pack_rows(bcv, S, kKosCvLabels, kKosBcvRow);
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    DevBuf d_seed, d_res, d_bits, d_cv, d_cb, d_tags;
-    int rc = to_dev(d_seed, seed2, S * kLabel, st);
-    if (rc == GC_OK) rc = to_dev(d_res, result, z.n * kLabel, st);
-    if (rc == GC_OK) rc = to_dev(d_bits, bits.data(), bits.size(), st);
-    if (rc == GC_OK) rc = to_dev(d_cv, choice_vec, S * kKosCvLabels * kLabel, st);
-    if (rc == GC_OK) rc = to_dev(d_cb, cbits.data(), cbits.size(), st);
-    if (rc == GC_OK) rc = to_dev(d_tags, nullptr, S * 3 * kLabel, st);
-    if (rc == GC_OK) rc = tags_run(ctx, d_seed.p, d_res.p, d_bits.p, d_cv.p, d_cb.p, S, per, d_tags.p);
-    if (rc == GC_OK) GC_HIP(hipMemcpyAsync(tags_out, d_tags.p, S * 3 * kLabel, hipMemcpyDeviceToHost, st));
-    GC_HIP(hipStreamSynchronize(st));  // also on an error: a copy may be queued on what is freed next
+    Staged io[] = {{seed2, nullptr, S * kLabel}, {result, nullptr, z.n * kLabel}, {bits.data(), nullptr, bits.size()},
+                   {choice_vec, nullptr, S * kKosCvLabels * kLabel}, {cbits.data(), nullptr, cbits.size()},
+                   {nullptr, tags_out, S * 3 * kLabel}};
+    int rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = tags_run(ctx, io[0].d.p, io[1].d.p, io[2].d.p, io[3].d.p, io[4].d.p, S, per, io[5].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
     return rc;
 } catch (...) {
     return gc::on_exception();
@@ -130,19 +111,12 @@ int gc_kos_multi_sender_check(gc_ctx *ctx, const gc_label *seed2, const gc_label
     uint64_t status[2] = {0, 0};
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    DevBuf d_seed, d_res, d_cv, d_delta, d_tags, d_ok, d_status;
-    int rc = to_dev(d_seed, seed2, S * kLabel, st);
-    if (rc == GC_OK) rc = to_dev(d_res, result, z.n * kLabel, st);
-    if (rc == GC_OK) rc = to_dev(d_cv, choice_vec, S * kKosCvLabels * kLabel, st);
-    if (rc == GC_OK) rc = to_dev(d_delta, delta, S * kLabel, st);
-    if (rc == GC_OK) rc = to_dev(d_tags, tags, S * 3 * kLabel, st);
-    if (rc == GC_OK) rc = to_dev(d_ok, nullptr, S, st);
-    if (rc == GC_OK) rc = to_dev(d_status, nullptr, sizeof status, st);
-    if (rc == GC_OK) rc = check_run(ctx, d_seed.p, d_res.p, d_cv.p, d_delta.p, d_tags.p, S, per, d_ok.p, d_status.p);
-    if (rc == GC_OK) GC_HIP(hipMemcpyAsync(ok.data(), d_ok.p, S, hipMemcpyDeviceToHost, st));
-    if (rc == GC_OK) GC_HIP(hipMemcpyAsync(status, d_status.p, sizeof status, hipMemcpyDeviceToHost, st));
-    GC_HIP(hipStreamSynchronize(st));
+    Staged io[] = {{seed2, nullptr, S * kLabel}, {result, nullptr, z.n * kLabel},
+                   {choice_vec, nullptr, S * kKosCvLabels * kLabel}, {delta, nullptr, S * kLabel},
+                   {tags, nullptr, S * 3 * kLabel}, {nullptr, ok.data(), S}, {nullptr, status, sizeof status}};
+    int rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = check_run(ctx, io[0].d.p, io[1].d.p, io[2].d.p, io[3].d.p, io[4].d.p, S, per, io[5].d.p, io[6].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
     if (rc != GC_OK) return rc;
     if (ok_out) std::copy(ok.begin(), ok.end(), ok_out);
     if (bad_session) *bad_session = status[0] ? (size_t)status[1] : (size_t)-1;

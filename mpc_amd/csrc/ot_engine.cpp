@@ -1,6 +1,8 @@
-// ot_engine.cpp — C ABI for the IKNP OT extension, MITCCRH and the COT pad loops.
+// ot_engine.cpp — C ABI for the IKNP OT extension, MITCCRH and the COT pad loops.  A host form is staging (host_staging.h)
+// around the operation of its _dev form.
 #include <algorithm>
 #include <cstring>
+#include <iterator>
 #include <new>
 
 #include "engine.h"
@@ -121,36 +123,47 @@ size_t gc_iknp_u_bytes(size_t n) {
 
 static size_t stream_advance(size_t n) { return (n / 512) * 64 + ((n % 512) + 7) / 8; }
 
-// receive() with the choice bits already packed LSB-first, 64 bytes per chunk (bbuf[chunks*64])
+// bytes of the packed choice bits of a host receive: 64 per chunk and 16 of zeros behind them
+static size_t choice_buf_bytes(size_t n) { return ((n + 511) / 512) * 64 + 16; }
+
+// The extension on device pointers, the device set: what a _dev form does behind its argument checks, between its events,
+// and a host form between stage_in and stage_out.  The receiver's (d_choice_packed -> d_u_out, d_labels_out) or the
+// sender's (d_u_in -> d_labels_out); the stream position is the caller's to advance.
+static int extend_run(gc_iknp *k, size_t n, const void *d_choice_packed, const void *d_u_in, void *d_u_out, void *d_labels_out) {
+    GC_HIP(launch_iknp_fused(k->receiver, k->d_rk0, k->d_rk1, k->pos, n, (const uint8_t *)d_choice_packed,
+                             (const uint8_t *)d_u_in, k->delta, (uint8_t *)d_u_out, (uint4 *)d_labels_out, k->ctx->d_te0,
+                             k->ctx->stream));
+    return GC_OK;
+}
+// ... with the labels in the handle's workspace (iknp_ws: n labels at its start) and bit 0 of each packed into d_result
+static int extend_bits_run(gc_iknp *k, size_t n, const void *d_choice_packed, const void *d_u_in, void *d_u_out, void *d_result) {
+    const int rc = extend_run(k, n, d_choice_packed, d_u_in, d_u_out, k->d_ws);
+    if (rc != GC_OK) return rc;
+    launch_pack_label_bit0((const uint4 *)k->d_ws, n, (uint64_t *)d_result, k->ctx->stream);
+    GC_HIP(hipGetLastError());
+    return GC_OK;
+}
+
+// receive() with the choice bits already packed LSB-first, 64 bytes per chunk (bbuf[choice_buf_bytes(n)])
 static int iknp_receive_packed(gc_iknp *k, const std::vector<uint8_t> &bbuf, size_t n, uint8_t *u_out,
                                gc_label *labels_out) {
     gc_ctx *ctx = k->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    const size_t chunks = (n + 511) / 512, ub = gc_iknp_u_bytes(n);
-    DevBuf d_bits, d_u, d_lab;
-    GC_HIP(d_bits.alloc(chunks * 64 + 16));
-    GC_HIP(d_u.alloc(chunks * 8192));
-    GC_HIP(d_lab.alloc(n * sizeof(uint4)));
-    hipStream_t s = ctx->stream;
-    GC_HIP(hipMemsetAsync(d_bits.p, 0, chunks * 64 + 16, s));
-    GC_HIP(hipMemcpyAsync(d_bits.p, bbuf.data(), std::min(bbuf.size(), chunks * 64), hipMemcpyHostToDevice, s));
-    GC_HIP(launch_iknp_fused(true, k->d_rk0, k->d_rk1, k->pos, n, (const uint8_t *)d_bits.p, nullptr, k->delta,
-                             (uint8_t *)d_u.p, (uint4 *)d_lab.p, ctx->d_te0, s));
-    GC_HIP(hipMemcpyAsync(u_out, d_u.p, ub, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipMemcpyAsync(labels_out, d_lab.p, n * sizeof(uint4), hipMemcpyDeviceToHost, s));
-    GC_HIP(hipStreamSynchronize(s));
-    k->pos += stream_advance(n);
-    return GC_OK;
+    const size_t chunks = (n + 511) / 512;
+    Staged io[] = {{bbuf.data(), nullptr, bbuf.size()}, {nullptr, u_out, gc_iknp_u_bytes(n), chunks * 8192},
+                   {nullptr, labels_out, n * sizeof(uint4)}};
+    int rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = extend_run(k, n, io[0].d.p, nullptr, io[1].d.p, io[2].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) k->pos += stream_advance(n);
+    return rc;
 }
 
 int gc_iknp_receive(gc_iknp *k, const uint8_t *choice, size_t n, uint8_t *u_out, gc_label *labels_out) try {
     if (!k || !k->receiver || (n && (!choice || !u_out || !labels_out))) return GC_E_ARG;
     if (n == 0) return GC_OK;
-    std::vector<uint8_t> bbuf(((n + 511) / 512) * 64, 0);  // iknp.go:472-477
-    for (size_t i = 0; i < n; i++)
-        if (choice[i]) bbuf[i / 8] |= (uint8_t)(1u << (i % 8));
-    return iknp_receive_packed(k, bbuf, n, u_out, labels_out);
+    return iknp_receive_packed(k, pack_rows(choice, 1, n, choice_buf_bytes(n)), n, u_out, labels_out);
 } catch (...) {
     return gc::on_exception();
 }
@@ -163,7 +176,7 @@ int gc_iknp_receive_bits(gc_iknp *k, const uint64_t *choices, size_t n, uint8_t 
     for (size_t i = 0; i < (n + 63) / 64; i++) result[i] = 0;
     if (n == 0) return GC_OK;
     const size_t chunks = (n + 511) / 512;
-    std::vector<uint8_t> bbuf(chunks * 64, 0);
+    std::vector<uint8_t> bbuf(choice_buf_bytes(n), 0);
     for (size_t c = 0; c < chunks; c++) {
         const size_t ofs = c * 512, rows = std::min<size_t>(512, n - ofs), words = ((rows + 7) / 8) / 8;
         for (size_t w = 0; w < words; w++)
@@ -187,17 +200,12 @@ int gc_iknp_send(gc_iknp *k, const uint8_t *u_in, size_t u_len, size_t n, gc_lab
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
     const size_t chunks = (n + 511) / 512;
-    DevBuf d_u, d_lab;
-    GC_HIP(d_u.alloc(chunks * 8192));
-    GC_HIP(d_lab.alloc(n * sizeof(uint4)));
-    hipStream_t s = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_u.p, u_in, u_len, hipMemcpyHostToDevice, s));
-    GC_HIP(launch_iknp_fused(false, k->d_rk0, nullptr, k->pos, n, nullptr, (const uint8_t *)d_u.p, k->delta, nullptr,
-                             (uint4 *)d_lab.p, ctx->d_te0, s));
-    GC_HIP(hipMemcpyAsync(labels_out, d_lab.p, n * sizeof(uint4), hipMemcpyDeviceToHost, s));
-    GC_HIP(hipStreamSynchronize(s));
-    k->pos += stream_advance(n);
-    return GC_OK;
+    Staged io[] = {{u_in, nullptr, u_len, chunks * 8192}, {nullptr, labels_out, n * sizeof(uint4)}};
+    int rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = extend_run(k, n, nullptr, io[0].d.p, nullptr, io[1].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) k->pos += stream_advance(n);
+    return rc;
 } catch (...) {
     return gc::on_exception();
 }
@@ -230,8 +238,8 @@ int gc_iknp_receive_dev(gc_iknp *k, const void *d_choice_packed, size_t n, void 
     if (rc != GC_OK) return rc;
     hipStream_t s = ctx->stream;
     GC_HIP(hipEventRecord(k->ev0, s));
-    GC_HIP(launch_iknp_fused(true, k->d_rk0, k->d_rk1, k->pos, n, (const uint8_t *)d_choice_packed, nullptr, k->delta,
-                             (uint8_t *)d_u_out, (uint4 *)d_labels_out, ctx->d_te0, s));
+    rc = extend_run(k, n, d_choice_packed, nullptr, d_u_out, d_labels_out);
+    if (rc != GC_OK) return rc;
     GC_HIP(hipEventRecord(k->ev1, s));
     k->timed = true;
     k->pos += stream_advance(n);
@@ -249,8 +257,8 @@ int gc_iknp_send_dev(gc_iknp *k, const void *d_u_in, size_t n, void *d_labels_ou
     if (rc != GC_OK) return rc;
     hipStream_t s = ctx->stream;
     GC_HIP(hipEventRecord(k->ev0, s));
-    GC_HIP(launch_iknp_fused(false, k->d_rk0, nullptr, k->pos, n, nullptr, (const uint8_t *)d_u_in, k->delta, nullptr,
-                             (uint4 *)d_labels_out, ctx->d_te0, s));
+    rc = extend_run(k, n, nullptr, d_u_in, nullptr, d_labels_out);
+    if (rc != GC_OK) return rc;
     GC_HIP(hipEventRecord(k->ev1, s));
     k->timed = true;
     k->pos += stream_advance(n);
@@ -269,15 +277,12 @@ int gc_iknp_receive_bits_dev(gc_iknp *k, const void *d_choices, size_t n, void *
     const size_t chunks = (n + 511) / 512;
     int rc = iknp_ws(k, n * sizeof(uint4) + chunks * 64);
     if (rc != GC_OK) return rc;
-    uint4 *lab = (uint4 *)k->d_ws;
     uint64_t *bbuf = (uint64_t *)((uint8_t *)k->d_ws + n * sizeof(uint4));
     hipStream_t s = ctx->stream;
     GC_HIP(hipEventRecord(k->ev0, s));
     launch_fold_choice_words((const uint64_t *)d_choices, n, bbuf, s);
-    GC_HIP(launch_iknp_fused(true, k->d_rk0, k->d_rk1, k->pos, n, (const uint8_t *)bbuf, nullptr, k->delta,
-                             (uint8_t *)d_u_out, lab, ctx->d_te0, s));
-    launch_pack_label_bit0(lab, n, (uint64_t *)d_result, s);
-    GC_HIP(hipGetLastError());
+    rc = extend_bits_run(k, n, bbuf, nullptr, d_u_out, d_result);
+    if (rc != GC_OK) return rc;
     GC_HIP(hipEventRecord(k->ev1, s));
     k->timed = true;
     k->pos += stream_advance(n);
@@ -292,13 +297,10 @@ int gc_iknp_send_bits_dev(gc_iknp *k, const void *d_u_in, size_t n, void *d_resu
     GC_HIP(hipSetDevice(ctx->device));
     int rc = iknp_ws(k, n * sizeof(uint4));
     if (rc != GC_OK) return rc;
-    uint4 *lab = (uint4 *)k->d_ws;
     hipStream_t s = ctx->stream;
     GC_HIP(hipEventRecord(k->ev0, s));
-    GC_HIP(launch_iknp_fused(false, k->d_rk0, nullptr, k->pos, n, nullptr, (const uint8_t *)d_u_in, k->delta, nullptr, lab,
-                             ctx->d_te0, s));
-    launch_pack_label_bit0(lab, n, (uint64_t *)d_result, s);
-    GC_HIP(hipGetLastError());
+    rc = extend_bits_run(k, n, nullptr, d_u_in, nullptr, d_result);
+    if (rc != GC_OK) return rc;
     GC_HIP(hipEventRecord(k->ev1, s));
     k->timed = true;
     k->pos += stream_advance(n);
@@ -332,56 +334,41 @@ static void host_clmul128(const gc_label &a, const gc_label &b, uint64_t out[4])
         }
 }
 
-// acc[6] <- sums over (result, b) then (choice_vec, bcv); shared by both roles
-// chi-PRG + inner products over labels that are ALREADY on the device (d_res [n], d_bits [n] or null) plus the 256-label
-// choice vector from the host: two launches into one accumulator — chi labels are consecutive in the stream, results
-// first (counter 0..n-1), then the choice vector (n..n+255) (iknp.go:159-174)
-static int kos_sums_dev(gc_ctx *ctx, const gc_label *seed2, const uint4 *d_res, const uint8_t *d_bits, size_t n,
-                        const gc_label *choice_vec, const uint8_t *bcv, uint64_t acc[6]) {
+// acc[6] <- sums over (result, b) then (choice_vec, bcv); shared by both roles and both forms.  chi-PRG + inner products: two
+// launches into one accumulator — chi labels are consecutive in the stream, results first (counter 0..n-1), then the choice
+// vector (n..n+255) (iknp.go:159-174).  The n labels are staged from `result`, or lie at d_res already (the _dev forms:
+// result NULL); their choice bits likewise from b or at d_bits.  The 256-label choice vector comes from the host in both.
+static int kos_sums(gc_ctx *ctx, const gc_label *seed2, const gc_label *result, const void *d_res, const uint8_t *b,
+                    const void *d_bits, size_t n, const gc_label *choice_vec, const uint8_t *bcv, uint64_t acc[6]) {
     GC_HIP(hipSetDevice(ctx->device));
     uint32_t rk[44];
     expand_label_key(*seed2, rk);  // newPrg(seed2) (iknp.go:150, 411)
-    DevBuf d_rk, d_cv, d_cb, d_zero, d_acc;
-    GC_HIP(d_rk.alloc(sizeof rk));
-    GC_HIP(d_cv.alloc(256 * sizeof(uint4)));
-    GC_HIP(d_cb.alloc(256));
-    GC_HIP(d_acc.alloc(6 * sizeof(uint64_t)));
+    uint8_t cb[256] = {0};
+    if (bcv) std::memcpy(cb, bcv, sizeof cb);
+    const bool zeros = n && !b && !d_bits;  // the sender has no choice bits: x is not used, feed zeros
+    // the last two only where there is something to stage: the choice bits (or the zeros), then the labels
+    Staged io[] = {{rk, nullptr, sizeof rk}, {choice_vec, nullptr, 256 * sizeof(uint4)}, {cb, nullptr, sizeof cb},
+                   {nullptr, acc, 6 * sizeof(uint64_t)}, {b, nullptr, n}, {result, nullptr, n * sizeof(uint4)}};
+    const size_t k = (n && result) ? 6 : zeros ? 5 : 4;
     hipStream_t s = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_rk.p, rk, sizeof rk, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_cv.p, choice_vec, 256 * sizeof(uint4), hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemsetAsync(d_cb.p, 0, 256, s));
-    if (bcv) GC_HIP(hipMemcpyAsync(d_cb.p, bcv, 256, hipMemcpyHostToDevice, s));
-    if (n && !d_bits) {  // the sender has no choice bits: x is not used, feed zeros
-        GC_HIP(d_zero.alloc(n));
-        GC_HIP(hipMemsetAsync(d_zero.p, 0, n, s));
-        d_bits = (const uint8_t *)d_zero.p;
-    }
-    GC_HIP(hipMemsetAsync(d_acc.p, 0, 6 * sizeof(uint64_t), s));
-    launch_kos_accumulate((const uint32_t *)d_rk.p, 0, d_res, d_bits, n, (unsigned long long *)d_acc.p, ctx->d_te0, s);
-    launch_kos_accumulate((const uint32_t *)d_rk.p, n, (const uint4 *)d_cv.p, (const uint8_t *)d_cb.p, 256,
-                          (unsigned long long *)d_acc.p, ctx->d_te0, s);
+    const int rc = stage_in(io, k, s);
+    if (rc != GC_OK) return rc;
+    if (k == 6) d_res = io[5].d.p;
+    if (k >= 5) d_bits = io[4].d.p;
+    if (zeros) GC_HIP(hipMemsetAsync(io[4].d.p, 0, n, s));
+    GC_HIP(hipMemsetAsync(io[3].d.p, 0, 6 * sizeof(uint64_t), s));
+    const struct {
+        uint64_t idx0;
+        const void *v, *bits;
+        size_t n;
+    } parts[2] = {{0, d_res, d_bits, n}, {n, io[1].d.p, io[2].d.p, 256}};
+    for (const auto &part : parts)
+        launch_kos_accumulate((const uint32_t *)io[0].d.p, part.idx0, (const uint4 *)part.v, (const uint8_t *)part.bits, part.n,
+                              (unsigned long long *)io[3].d.p, ctx->d_te0, s);
     GC_HIP(hipGetLastError());
-    GC_HIP(hipMemcpyAsync(acc, d_acc.p, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    GC_HIP(hipStreamSynchronize(s));
-    return GC_OK;
+    return stage_out(io, k, s);
 }
 
-// host-buffer form: stage the labels (and choice bits), then as above
-static int kos_sums(gc_ctx *ctx, const gc_label *seed2, const gc_label *result, const uint8_t *b, size_t n,
-                    const gc_label *choice_vec, const uint8_t *bcv, uint64_t acc[6]) {
-    GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_v, d_b;
-    hipStream_t s = ctx->stream;
-    if (n) {
-        GC_HIP(d_v.alloc(n * sizeof(uint4)));
-        GC_HIP(hipMemcpyAsync(d_v.p, result, n * sizeof(uint4), hipMemcpyHostToDevice, s));
-        if (b) {
-            GC_HIP(d_b.alloc(n));
-            GC_HIP(hipMemcpyAsync(d_b.p, b, n, hipMemcpyHostToDevice, s));
-        }
-    }
-    return kos_sums_dev(ctx, seed2, (const uint4 *)d_v.p, b ? (const uint8_t *)d_b.p : nullptr, n, choice_vec, bcv, acc);
-}
 
 static int kos_finish_sender(const uint64_t acc[6], const gc_label *delta, const gc_label *x, const gc_label *t0,
                              const gc_label *t1) {
@@ -397,7 +384,7 @@ int gc_kos_receiver_tags_dev(gc_ctx *ctx, const gc_label *seed2, const void *d_r
     if (!ctx || !seed2 || !choice_vec || !bcv || !x || !t0 || !t1 || (n && (!d_result || !d_b))) return GC_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
     uint64_t acc[6];
-    int rc = kos_sums_dev(ctx, seed2, (const uint4 *)d_result, (const uint8_t *)d_b, n, choice_vec, bcv, acc);
+    int rc = kos_sums(ctx, seed2, nullptr, d_result, nullptr, d_b, n, choice_vec, bcv, acc);
     if (rc != GC_OK) return rc;
     *t0 = gc_label{acc[0], acc[1]};
     *t1 = gc_label{acc[2], acc[3]};
@@ -413,7 +400,7 @@ int gc_kos_sender_check_dev(gc_ctx *ctx, const gc_label *seed2, const void *d_re
     if (!ctx || !seed2 || !choice_vec || !delta || !x || !t0 || !t1 || !ok || (n && !d_result)) return GC_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
     uint64_t acc[6];
-    int rc = kos_sums_dev(ctx, seed2, (const uint4 *)d_result, nullptr, n, choice_vec, nullptr, acc);
+    int rc = kos_sums(ctx, seed2, nullptr, d_result, nullptr, nullptr, n, choice_vec, nullptr, acc);
     if (rc != GC_OK) return rc;
     *ok = kos_finish_sender(acc, delta, x, t0, t1);
     return GC_OK;
@@ -426,7 +413,7 @@ int gc_kos_receiver_tags(gc_ctx *ctx, const gc_label *seed2, const gc_label *res
     if (!ctx || !seed2 || !choice_vec || !bcv || !x || !t0 || !t1 || (n && (!result || !b))) return GC_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
     uint64_t acc[6];
-    int rc = kos_sums(ctx, seed2, result, b, n, choice_vec, bcv, acc);
+    int rc = kos_sums(ctx, seed2, result, nullptr, b, nullptr, n, choice_vec, bcv, acc);
     if (rc != GC_OK) return rc;
     *t0 = gc_label{acc[0], acc[1]};
     *t1 = gc_label{acc[2], acc[3]};
@@ -442,7 +429,7 @@ int gc_kos_sender_check(gc_ctx *ctx, const gc_label *seed2, const gc_label *resu
     if (!ctx || !seed2 || !choice_vec || !delta || !x || !t0 || !t1 || !ok || (n && !result)) return GC_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
     uint64_t acc[6];
-    int rc = kos_sums(ctx, seed2, result, nullptr, n, choice_vec, nullptr, acc);
+    int rc = kos_sums(ctx, seed2, result, nullptr, nullptr, nullptr, n, choice_vec, nullptr, acc);
     if (rc != GC_OK) return rc;
     *ok = kos_finish_sender(acc, delta, x, t0, t1);
     return GC_OK;
@@ -465,20 +452,38 @@ int gc_iknp_send_bits(gc_iknp *k, const uint8_t *u_in, size_t u_len, size_t n, u
     return gc::on_exception();
 }
 
+// ---- MITCCRH and the pad loops of COT and ROT ---------------------------------------------------------------------
+// The operations on device pointers, the device set: what a _dev form does behind its argument checks
+static int mitccrh_run(gc_ctx *ctx, const gc_label *seed, uint64_t gid0, void *d_blks, size_t n, uint32_t h) {
+    launch_mitccrh(to_u4(*seed), gid0, (uint4 *)d_blks, n, h, ctx->d_te0, ctx->stream);
+    GC_HIP(hipGetLastError());
+    return GC_OK;
+}
+// d_wires NULL: the ROT sender (below)
+static int cot_send_run(gc_ctx *ctx, const gc_label *seed, const gc_label *delta, const void *d_data, const void *d_wires,
+                        size_t n, void *d_out) {
+    launch_cot_send(to_u4(*seed), to_u4(*delta), (const uint4 *)d_data, (const uint4 *)d_wires, n, (uint4 *)d_out, ctx->d_te0,
+                    ctx->stream);
+    GC_HIP(hipGetLastError());
+    return GC_OK;
+}
+static int cot_recv_run(gc_ctx *ctx, const gc_label *seed, const void *d_flags, const void *d_sent, void *d_result, size_t n) {
+    launch_cot_recv(to_u4(*seed), (const uint8_t *)d_flags, (const uint4 *)d_sent, (uint4 *)d_result, n, ctx->d_te0,
+                    ctx->stream);
+    GC_HIP(hipGetLastError());
+    return GC_OK;
+}
+
 int gc_mitccrh_hash(gc_ctx *ctx, const gc_label *seed, uint64_t gid0, gc_label *blks, size_t n, uint32_t h) try {
     if (!ctx || !seed || (n && !blks)) return GC_E_ARG;
     if (n == 0 || h == 0) return GC_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d;
-    const size_t bytes = n * h * sizeof(uint4);
-    GC_HIP(d.alloc(bytes));
-    GC_HIP(hipMemcpyAsync(d.p, blks, bytes, hipMemcpyHostToDevice, ctx->stream));
-    launch_mitccrh(to_u4(*seed), gid0, (uint4 *)d.p, n, h, ctx->d_te0, ctx->stream);
-    GC_HIP(hipGetLastError());
-    GC_HIP(hipMemcpyAsync(blks, d.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    return GC_OK;
+    Staged io[] = {{blks, blks, n * h * sizeof(uint4)}};  // hashed in place
+    int rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = mitccrh_run(ctx, seed, gid0, io[0].d.p, n, h);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    return rc;
 } catch (...) {
     return gc::on_exception();
 }
@@ -489,19 +494,11 @@ int gc_cot_send_pads(gc_ctx *ctx, const gc_label *seed, const gc_label *delta, c
     if (n == 0) return GC_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_data, d_w, d_out;
-    GC_HIP(d_data.alloc(n * 16));
-    GC_HIP(d_w.alloc(n * 32));
-    GC_HIP(d_out.alloc(n * 32));
-    hipStream_t s = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_data.p, data, n * 16, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_w.p, wires, n * 32, hipMemcpyHostToDevice, s));
-    launch_cot_send(to_u4(*seed), to_u4(*delta), (const uint4 *)d_data.p, (const uint4 *)d_w.p, n, (uint4 *)d_out.p,
-                    ctx->d_te0, s);
-    GC_HIP(hipGetLastError());
-    GC_HIP(hipMemcpyAsync(out, d_out.p, n * 32, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipStreamSynchronize(s));
-    return GC_OK;
+    Staged io[] = {{data, nullptr, n * 16}, {wires, nullptr, n * 32}, {nullptr, out, n * 32}};
+    int rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = cot_send_run(ctx, seed, delta, io[0].d.p, io[1].d.p, n, io[2].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    return rc;
 } catch (...) {
     return gc::on_exception();
 }
@@ -512,19 +509,11 @@ int gc_cot_receive_unpad(gc_ctx *ctx, const gc_label *seed, const uint8_t *flags
     if (n == 0) return GC_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_f, d_s, d_r;
-    GC_HIP(d_f.alloc(n));
-    GC_HIP(d_s.alloc(n * 32));
-    GC_HIP(d_r.alloc(n * 16));
-    hipStream_t s = ctx->stream;
-    GC_HIP(hipMemcpyAsync(d_f.p, flags, n, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_s.p, sent, n * 32, hipMemcpyHostToDevice, s));
-    GC_HIP(hipMemcpyAsync(d_r.p, result, n * 16, hipMemcpyHostToDevice, s));
-    launch_cot_recv(to_u4(*seed), (const uint8_t *)d_f.p, (const uint4 *)d_s.p, (uint4 *)d_r.p, n, ctx->d_te0, s);
-    GC_HIP(hipGetLastError());
-    GC_HIP(hipMemcpyAsync(result, d_r.p, n * 16, hipMemcpyDeviceToHost, s));
-    GC_HIP(hipStreamSynchronize(s));
-    return GC_OK;
+    Staged io[] = {{flags, nullptr, n}, {sent, nullptr, n * 32}, {result, result, n * 16}};
+    int rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = cot_recv_run(ctx, seed, io[0].d.p, io[1].d.p, io[2].d.p, n);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    return rc;
 } catch (...) {
     return gc::on_exception();
 }
@@ -535,10 +524,7 @@ int gc_cot_send_pads_dev(gc_ctx *ctx, const gc_label *seed, const gc_label *delt
     if (!ctx || !seed || !delta || (n && (!d_data || !d_wires || !d_out))) return GC_E_ARG;
     if (n == 0) return GC_OK;
     GC_HIP(hipSetDevice(ctx->device));
-    launch_cot_send(to_u4(*seed), to_u4(*delta), (const uint4 *)d_data, (const uint4 *)d_wires, n, (uint4 *)d_out,
-                    ctx->d_te0, ctx->stream);
-    GC_HIP(hipGetLastError());
-    return GC_OK;
+    return cot_send_run(ctx, seed, delta, d_data, d_wires, n, d_out);
 }
 
 int gc_cot_receive_unpad_dev(gc_ctx *ctx, const gc_label *seed, const void *d_flags, const void *d_sent,
@@ -546,10 +532,7 @@ int gc_cot_receive_unpad_dev(gc_ctx *ctx, const gc_label *seed, const void *d_fl
     if (!ctx || !seed || (n && (!d_flags || !d_sent || !d_result))) return GC_E_ARG;
     if (n == 0) return GC_OK;
     GC_HIP(hipSetDevice(ctx->device));
-    launch_cot_recv(to_u4(*seed), (const uint8_t *)d_flags, (const uint4 *)d_sent, (uint4 *)d_result, n, ctx->d_te0,
-                    ctx->stream);
-    GC_HIP(hipGetLastError());
-    return GC_OK;
+    return cot_recv_run(ctx, seed, d_flags, d_sent, d_result, n);
 }
 
 // ---- ROT (ot/rot.go:132-202): the pad loops of ROT.Send / ROT.Receive --------------------------------------------
@@ -561,19 +544,14 @@ int gc_rot_send_dev(gc_ctx *ctx, const gc_label *seed, const gc_label *delta, co
     if (!ctx || !seed || !delta || (n && (!d_data || !d_wires_out))) return GC_E_ARG;
     if (n == 0) return GC_OK;
     GC_HIP(hipSetDevice(ctx->device));
-    launch_cot_send(to_u4(*seed), to_u4(*delta), (const uint4 *)d_data, nullptr, n, (uint4 *)d_wires_out, ctx->d_te0,
-                    ctx->stream);
-    GC_HIP(hipGetLastError());
-    return GC_OK;
+    return cot_send_run(ctx, seed, delta, d_data, nullptr, n, d_wires_out);
 }
 
 int gc_rot_receive_dev(gc_ctx *ctx, const gc_label *seed, void *d_result, size_t n) {
     if (!ctx || !seed || (n && !d_result)) return GC_E_ARG;
     if (n == 0) return GC_OK;
     GC_HIP(hipSetDevice(ctx->device));
-    launch_mitccrh(to_u4(*seed), 0, (uint4 *)d_result, n, 1, ctx->d_te0, ctx->stream);
-    GC_HIP(hipGetLastError());
-    return GC_OK;
+    return mitccrh_run(ctx, seed, 0, d_result, n, 1);
 }
 
 int gc_rot_send(gc_ctx *ctx, const gc_label *seed, const gc_label *delta, const gc_label *data, size_t n,
@@ -582,15 +560,11 @@ int gc_rot_send(gc_ctx *ctx, const gc_label *seed, const gc_label *delta, const 
     if (n == 0) return GC_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GC_HIP(hipSetDevice(ctx->device));
-    DevBuf d_data, d_out;
-    GC_HIP(d_data.alloc(n * 16));
-    GC_HIP(d_out.alloc(n * 32));
-    GC_HIP(hipMemcpyAsync(d_data.p, data, n * 16, hipMemcpyHostToDevice, ctx->stream));
-    launch_cot_send(to_u4(*seed), to_u4(*delta), (const uint4 *)d_data.p, nullptr, n, (uint4 *)d_out.p, ctx->d_te0, ctx->stream);
-    GC_HIP(hipGetLastError());
-    GC_HIP(hipMemcpyAsync(wires_out, d_out.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    return GC_OK;
+    Staged io[] = {{data, nullptr, n * 16}, {nullptr, wires_out, n * 32}};
+    int rc = stage_in(io, std::size(io), ctx->stream);
+    if (rc == GC_OK) rc = cot_send_run(ctx, seed, delta, io[0].d.p, nullptr, n, io[1].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), ctx->stream);
+    return rc;
 } catch (...) {
     return gc::on_exception();
 }
