@@ -576,6 +576,10 @@ int gc_stream_batch_get_wire(gc_stream_batch *, uint32_t w, gc_wire *out);
 /* {L0, L0 ^ R} of the named global wires as gc_wire [sessions][n] in device memory — what gc_cot_multi_send_pads_dev consumes
  * for the peer's inputs; asynchronous (ids[] may be reused on return) */
 int gc_stream_batch_gather_wires(gc_stream_batch *, const uint32_t *ids, uint32_t n, void *d_wires_out);
+/* read-only counters of the handle's circuit cache (any pointer may be NULL): entries / bytes = what it holds now, in the
+ * device bytes that count against GC_STREAM_BATCH_CACHE_BYTES; loads = steps whose circuit was not cached and was kept;
+ * evictions = entries freed to stay within the budget.  A refused step moves none of them. */
+int gc_stream_batch_cache_stats(const gc_stream_batch *, uint64_t *entries, uint64_t *bytes, uint64_t *loads, uint64_t *evictions);
 
 /* the evaluator's side: the store of circuit.StreamEval for `sessions` sessions; d_keys as above */
 gc_stream_eval_batch *gc_stream_eval_batch_create(gc_ctx *, uint32_t sessions, const void *d_keys, size_t keylen, int *status);
@@ -584,6 +588,9 @@ void gc_stream_eval_batch_free(gc_stream_eval_batch *);
 int gc_stream_eval_batch_set_wires(gc_stream_eval_batch *, const uint32_t *ids, uint32_t n, const void *d_labels);
 /* out[sessions]: the active label of wire w in every session; waits for the ctx stream */
 int gc_stream_eval_batch_get_wire(gc_stream_eval_batch *, uint32_t w, gc_label *out);
+/* the evaluator's counterpart of gc_stream_batch_cache_stats (its cache holds the circuits of the parsed blocks) */
+int gc_stream_eval_batch_cache_stats(const gc_stream_eval_batch *, uint64_t *entries, uint64_t *bytes, uint64_t *loads,
+                                     uint64_t *evictions);
 /* ONE OpCircuit block of every session (the per-gate loop of StreamEvaluator, stream_evaluator.go:270-432).  ref_block: a
  * HOST copy of any one session's block bytes; it is parsed and checked as gc_stream_eval_circuit parses a block, with the same
  * refusals (GC_E_GATE, GC_E_ROWS, GC_E_ARG) and the same size checks before anything is sized by the peer's data.  d_blocks:

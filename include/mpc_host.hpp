@@ -538,6 +538,15 @@ public:
     void GatherWires(const std::vector<uint32_t> &ids, void *d_wires_out) {
         check(gc_stream_batch_gather_wires(h_, ids.data(), (uint32_t)ids.size(), d_wires_out), "gc_stream_batch_gather_wires");
     }
+    // the circuit cache: what it holds now, and how often it loaded and evicted
+    struct CacheStats {
+        uint64_t entries = 0, bytes = 0, loads = 0, evictions = 0;
+    };
+    CacheStats GetCacheStats() const {
+        CacheStats c;
+        check(gc_stream_batch_cache_stats(h_, &c.entries, &c.bytes, &c.loads, &c.evictions), "gc_stream_batch_cache_stats");
+        return c;
+    }
 
 private:
     gc_stream_batch *h_ = nullptr;
@@ -569,6 +578,11 @@ public:
         check(gc_stream_eval_batch_circuit(h_, ngates, ntmp, nwires, ref.data(), ref.size(), d_blocks, stride, d_bad, &used),
               "gc_stream_eval_batch_circuit");
         return used;
+    }
+    StreamingBatch::CacheStats GetCacheStats() const {
+        StreamingBatch::CacheStats c;
+        check(gc_stream_eval_batch_cache_stats(h_, &c.entries, &c.bytes, &c.loads, &c.evictions), "gc_stream_eval_batch_cache_stats");
+        return c;
     }
 
 private:

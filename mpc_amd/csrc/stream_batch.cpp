@@ -138,6 +138,7 @@ struct SbCore {
     std::vector<std::unique_ptr<SbCirc>> cache;
     size_t cache_bytes = 0;
     uint64_t tick = 0;
+    uint64_t n_loads = 0, n_evictions = 0;  // misses that ended with an entry kept / entries the budget loop freed
     SbStage ring[kRing];
     uint32_t next = 0;
 
@@ -237,8 +238,10 @@ struct SbCore {
             gc_circ_free(cache[lru]->circ);
             cache_bytes -= cache[lru]->dev_bytes;
             cache.erase(cache.begin() + (long)lru);
+            n_evictions++;
         }
         cache_bytes += e->dev_bytes;
+        n_loads++;
         e->last_use = ++tick;
         *out = e.get();
         cache.push_back(std::move(e));
@@ -606,6 +609,15 @@ int eval_step(gc_stream_eval_batch *e, uint32_t ngates, uint32_t ntmp, uint32_t 
     return rc != GC_OK ? rc : rce;
 }
 
+int cache_stats(const SbCore *c, uint64_t *entries, uint64_t *bytes, uint64_t *loads, uint64_t *evictions) {
+    if (!c) return GC_E_ARG;
+    if (entries) *entries = c->cache.size();
+    if (bytes) *bytes = c->cache_bytes;
+    if (loads) *loads = c->n_loads;
+    if (evictions) *evictions = c->n_evictions;
+    return GC_OK;
+}
+
 // ids[] on the device for the length of one call (a host copy: the call waits for it)
 int ids_to_device(SbCore &c, const uint32_t *ids, uint32_t n, DevBuf *d) {
     GC_HIP(d->alloc(4 * (size_t)n));
@@ -722,6 +734,10 @@ int gc_stream_batch_gather_wires(gc_stream_batch *s, const uint32_t *ids, uint32
     return gc::on_exception();
 }
 
+int gc_stream_batch_cache_stats(const gc_stream_batch *s, uint64_t *entries, uint64_t *bytes, uint64_t *loads, uint64_t *evictions) {
+    return cache_stats(s, entries, bytes, loads, evictions);
+}
+
 gc_stream_eval_batch *gc_stream_eval_batch_create(gc_ctx *ctx, uint32_t sessions, const void *d_keys, size_t keylen, int *status) try {
     int rc = GC_OK;
     std::unique_ptr<gc_stream_eval_batch> e(new (std::nothrow) gc_stream_eval_batch);
@@ -773,6 +789,11 @@ int gc_stream_eval_batch_get_wire(gc_stream_eval_batch *e, uint32_t w, gc_label 
     return rc;
 } catch (...) {
     return gc::on_exception();
+}
+
+int gc_stream_eval_batch_cache_stats(const gc_stream_eval_batch *e, uint64_t *entries, uint64_t *bytes, uint64_t *loads,
+                                     uint64_t *evictions) {
+    return cache_stats(e, entries, bytes, loads, evictions);
 }
 
 int gc_stream_eval_batch_circuit(gc_stream_eval_batch *e, uint32_t ngates, uint32_t ntmp, uint32_t nwires, const uint8_t *ref_block,

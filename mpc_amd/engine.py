@@ -131,6 +131,8 @@ def lib():
         "gc_stream_batch_garble": (i32, [vp, vp, u32, u32, vp, u32, vp, u32, vp, sz, C.POINTER(C.c_size_t)]),
         "gc_stream_batch_get_wire": (i32, [vp, u32, vp]),
         "gc_stream_batch_gather_wires": (i32, [vp, vp, u32, vp]),
+        "gc_stream_batch_cache_stats": (i32, [vp] + [C.POINTER(C.c_uint64)] * 4),
+        "gc_stream_eval_batch_cache_stats": (i32, [vp] + [C.POINTER(C.c_uint64)] * 4),
         "gc_stream_eval_batch_create": (vp, [vp, u32, vp, sz, ip]),
         "gc_stream_eval_batch_free": (None, [vp]),
         "gc_stream_eval_batch_set_wires": (i32, [vp, vp, u32, vp]),
@@ -1076,6 +1078,12 @@ class StreamBatch:
         i = np.ascontiguousarray(ids, dtype=np.uint32)
         _check(lib().gc_stream_batch_gather_wires(self.h, _p(i), len(i), _dp(d_wires_out)), "gc_stream_batch_gather_wires")
 
+    def cache_stats(self):
+        """the circuit cache (gc_stream_batch_cache_stats): (entries, device bytes, loads, evictions)"""
+        v = [C.c_uint64(0) for _ in range(4)]
+        _check(lib().gc_stream_batch_cache_stats(self.h, *[C.byref(x) for x in v]), "gc_stream_batch_cache_stats")
+        return tuple(int(x.value) for x in v)
+
     def close(self):
         if self.h:
             lib().gc_stream_batch_free(self.h)
@@ -1111,6 +1119,12 @@ class StreamEvalBatch:
         _check(lib().gc_stream_eval_batch_circuit(self.h, ngates, ntmp, nwires, _p(b), len(ref_block), _dp(d_blocks), stride,
                                                   _dp(d_bad), C.byref(n)), "gc_stream_eval_batch_circuit")
         return n.value
+
+    def cache_stats(self):
+        """the circuit cache (gc_stream_eval_batch_cache_stats): (entries, device bytes, loads, evictions)"""
+        v = [C.c_uint64(0) for _ in range(4)]
+        _check(lib().gc_stream_eval_batch_cache_stats(self.h, *[C.byref(x) for x in v]), "gc_stream_eval_batch_cache_stats")
+        return tuple(int(x.value) for x in v)
 
     def close(self):
         if self.h:
