@@ -746,7 +746,6 @@ int eval_block(gc_stream_eval *e, uint32_t ngates, uint32_t ntmp, uint32_t nwire
     }
     // keep the skeleton: the next block of this circuit is matched byte-wise instead of parsed
     e->n_parsed++;
-    constexpr size_t kSkelVariants = 32;
     constexpr size_t kSkelCap = (size_t)1 << 30;  // beyond 1 GiB of reference blocks every new circuit is parsed each time
     if (e->use_skels && rec_ok && e->skel_bytes + 2 * pos <= kSkelCap) {
         auto &v = e->skels[((uint64_t)ngates << 32) | ntmp];

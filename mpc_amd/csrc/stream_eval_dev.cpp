@@ -104,7 +104,7 @@ __global__ __launch_bounds__(512) void k_eval_verify(VerifyArgs a) {
     uint32_t verdict = 0;
     if (!__syncthreads_or((int)(diff != 0))) {
         uint32_t s = it.skel;
-        for (uint32_t tries = 0; tries < 64; tries++) {  // the guessed skeleton first, then its mates
+        for (uint32_t tries = 0; tries < kMateTries; tries++) {  // the guessed skeleton first, then its mates
             int bad = k.nuniq > kUniqLds;
             if (!bad) {
                 for (uint32_t f = tid; f < k.ngf; f += 512) {

@@ -88,6 +88,13 @@ uint32_t stream_max_wires();
 bool eval_adopt_ids(gc_stream_eval *e, const EvalSkel &sk, const uint32_t *ids, uint32_t nwires);
 
 // ---- device-side match (stream_eval_dev.cpp) ----------------------------------------------------------------------------------
+// The byte layouts kept per (gates, tmp wires) key (stream_eval.cpp: the least recently matched one goes) and the skeletons a
+// device verdict tries for one block: the guessed one, then its mates.  A ring of mates holds live layouts of ONE key only, so
+// it is never longer than kSkelVariants: with at least as many tries the walk comes back to the guess — the ring is closed —
+// before it runs out, and no mate is left untried whatever the ring's order.
+constexpr size_t kSkelVariants = 32;
+constexpr uint32_t kMateTries = 64;
+static_assert(kSkelVariants <= kMateTries, "a verdict's walk must reach every mate of the guessed skeleton");
 // every complete OpCircuit block at the head of buf[0, len) that the DEVICE recognises (or the host parser takes when the device
 // does not know it): *pos = bytes taken, *n = blocks; what is left — a cut-off block, another operation — is the caller's
 int evdev_blocks(gc_stream_eval *e, const uint8_t *buf, size_t len, size_t *pos, uint32_t *n);

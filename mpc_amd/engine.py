@@ -1005,7 +1005,8 @@ class StreamEval:
         return a.value, b.value
 
     def dev_stats(self):
-        """(blocks the DEVICE recognised in read buffers handed to gc_stream_eval_blocks, of those: parsed by the host after all)"""
+        """(blocks of read buffers handed to gc_stream_eval_blocks that were scheduled on a DEVICE verdict, blocks the device was
+        asked about that went to the host's matcher / parser after all): disjoint counts"""
         a, b = C.c_uint64(0), C.c_uint64(0)
         _check(lib().gc_stream_eval_dev_stats(self.h, C.byref(a), C.byref(b)), "gc_stream_eval_dev_stats")
         return a.value, b.value

@@ -12,6 +12,7 @@ import pytest
 import oracle
 from mpc_amd import engine
 from mpc_amd.circuit import adder, bitwise, multiplier, subtractor, synthetic_levelised
+from tests.stream_eval_dev_cases import framed_stream as _framed_stream
 from tests.util import drbg
 
 pytestmark = pytest.mark.gpu
@@ -291,12 +292,6 @@ def test_default_planning_in_the_background_keeps_the_bytes(monkeypatch):
     _, gf, ef = _run(ctx, steps, prim, key, rnd, 300)
     assert gf[2] == 0 and ef[2] == 0  # everything that repeats is planned by now
     ctx.close()
-
-
-def _framed_stream(steps, blocks):
-    import struct
-    return b"".join(struct.pack(">5I", 1, k, c.NumGates, c.NumWires, max(max(in_), max(out_)) + 1) + bytes(b)
-                    for k, ((c, in_, out_), b) in enumerate(zip(steps, blocks))) + struct.pack(">I", 2)
 
 
 @pytest.mark.parametrize("pinned,piece", [(True, 1 << 20), (False, 1 << 20), (True, 150_000), (False, 70_000)])
