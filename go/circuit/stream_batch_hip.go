@@ -178,3 +178,179 @@ func (e *StreamEvalBatch) EvalBlock(numGates, numTmpWires, numWires int, ref []b
 	}
 	return int(used), nil
 }
+
+// SelectLabels writes the garbler's own input labels (compiler/ssa/streamer.go:79-102: L1 if inputs.Bit(i), else L0) of every
+// session into dst as ot.Label [sessions][len(ws)]; bits holds one byte per input, [sessions][len(ws)], non-zero = 1.  Queued.
+func (s *StreamingBatch) SelectLabels(ws []Wire, bits, dst *DevBuf) error {
+	if bits.Size() < s.sessions*len(ws) || dst.Size() < s.sessions*len(ws)*16 {
+		return fmt.Errorf("SelectLabels: %d bits, %d label bytes for %d x %d wires", bits.Size(), dst.Size(), s.sessions, len(ws))
+	}
+	p := wireIDs(ws)
+	if st := C.gc_stream_batch_select_labels_dev(s.h, p, C.uint32_t(len(ws)), bits.Ptr(), dst.Ptr()); st != C.GC_OK {
+		return statusError(st)
+	}
+	return nil
+}
+
+// SelectLabelsHost is SelectLabels for host slices: bits [sessions][len(ws)], the labels in the same order.
+func (s *StreamingBatch) SelectLabelsHost(ws []Wire, bits []byte) ([]ot.Label, error) {
+	if len(ws) == 0 || len(bits) != s.sessions*len(ws) {
+		return nil, fmt.Errorf("SelectLabelsHost: %d bits for %d x %d wires", len(bits), s.sessions, len(ws))
+	}
+	out := make([]ot.Label, len(bits))
+	p := wireIDs(ws)
+	st := C.gc_stream_batch_select_labels(s.h, p, C.uint32_t(len(ws)), (*C.uint8_t)(unsafe.Pointer(&bits[0])),
+		(*C.gc_label)(unsafe.Pointer(&out[0])))
+	if st != C.GC_OK {
+		return nil, statusError(st)
+	}
+	return out, nil
+}
+
+// Decode is the result loop of streamer.go:563-579 for every session: labels holds ot.Label [sessions][len(ws)] as the peers
+// sent them; bitsOut receives 0, 1 or 0xff ("unknown label") per label and bad one u32 per session, its number of 0xff.  Queued.
+func (s *StreamingBatch) Decode(ws []Wire, labels, bitsOut, bad *DevBuf) error {
+	if labels.Size() < s.sessions*len(ws)*16 || bitsOut.Size() < s.sessions*len(ws) || bad.Size() < 4*s.sessions {
+		return fmt.Errorf("Decode: buffers too small for %d x %d labels", s.sessions, len(ws))
+	}
+	p := wireIDs(ws)
+	if st := C.gc_stream_batch_decode_dev(s.h, p, C.uint32_t(len(ws)), labels.Ptr(), bitsOut.Ptr(), bad.Ptr()); st != C.GC_OK {
+		return statusError(st)
+	}
+	return nil
+}
+
+// DecodeHost is Decode for host slices; it returns the bits [sessions][len(ws)] and the count of unknown labels per session.
+func (s *StreamingBatch) DecodeHost(ws []Wire, labels []ot.Label) ([]byte, []uint32, error) {
+	if len(ws) == 0 || len(labels) != s.sessions*len(ws) {
+		return nil, nil, fmt.Errorf("DecodeHost: %d labels for %d x %d wires", len(labels), s.sessions, len(ws))
+	}
+	bits := make([]byte, len(labels))
+	bad := make([]uint32, s.sessions)
+	p := wireIDs(ws)
+	st := C.gc_stream_batch_decode(s.h, p, C.uint32_t(len(ws)), (*C.gc_label)(unsafe.Pointer(&labels[0])),
+		(*C.uint8_t)(unsafe.Pointer(&bits[0])), (*C.uint32_t)(unsafe.Pointer(&bad[0])))
+	if st != C.GC_OK {
+		return nil, nil, statusError(st)
+	}
+	return bits, bad, nil
+}
+
+// ErrWindowsBusy is GC_E_BUSY of (*StreamingBatchOut).Garble: no window is free and nothing has happened.
+var ErrWindowsBusy = fmt.Errorf("stream batch: no free output window")
+
+// StreamingBatchOut writes the steps of a StreamingBatch into a ring of windows whose bytes arrive in pinned host memory
+// while the next window fills: what conn.WriteBuf is to one session (compiler/ssa/streamer.go:679-693 writes the OpCircuit
+// header that Garble takes as prefix).  One goroutine may call Garble / Flush while one other calls Next / Release.
+type StreamingBatchOut struct {
+	h        *C.gc_stream_batch_out
+	sessions int
+}
+
+// NewStreamingBatchOut makes nwindows (>= 2) windows of windowBytes per session; Close it before its StreamingBatch.
+func NewStreamingBatchOut(s *StreamingBatch, windowBytes, nwindows int) (*StreamingBatchOut, error) {
+	var st C.int
+	h := C.gc_stream_batch_out_create(s.h, C.size_t(windowBytes), C.uint32_t(nwindows), &st)
+	if h == nil {
+		return nil, statusError(st)
+	}
+	return &StreamingBatchOut{h: h, sessions: s.sessions}, nil
+}
+
+// Close waits for the copies in flight and frees the windows.
+func (o *StreamingBatchOut) Close() {
+	if o.h != nil {
+		C.gc_stream_batch_out_free(o.h)
+		o.h = nil
+	}
+}
+
+// Garble queues prefix (at most 64 bytes) and the step's bytes for every session and returns their number per session.
+// ErrWindowsBusy: release a window and call again.
+func (o *StreamingBatchOut) Garble(prefix []byte, c *Circuit, in, out []Wire) (int, error) {
+	if len(c.Gates) == 0 {
+		return 0, nil
+	}
+	pre := append([]byte{}, prefix...)
+	pre = append(pre, 0)
+	pi := wireIDs(in)
+	po := wireIDs(out)
+	var n C.size_t
+	st := C.gc_stream_batch_out_garble(o.h, (*C.uint8_t)(unsafe.Pointer(&pre[0])), C.size_t(len(prefix)),
+		(*C.gc_gate)(unsafe.Pointer(&c.Gates[0])), C.uint32_t(len(c.Gates)), C.uint32_t(c.NumWires), pi, C.uint32_t(len(in)), po,
+		C.uint32_t(len(out)), &n)
+	if st == C.GC_E_BUSY {
+		return 0, ErrWindowsBusy
+	}
+	if st != C.GC_OK {
+		return int(n), statusError(st)
+	}
+	return int(n), nil
+}
+
+// Flush seals the filling window if it holds any byte.
+func (o *StreamingBatchOut) Flush() error {
+	if st := C.gc_stream_batch_out_flush(o.h); st != C.GC_OK {
+		return statusError(st)
+	}
+	return nil
+}
+
+// Next hands out the oldest sealed window, its copy complete: session k's bytes are base[k*stride : k*stride+n].  n == 0:
+// nothing is sealed.  The memory is the handle's and valid until Release.
+func (o *StreamingBatchOut) Next() (base unsafe.Pointer, stride, n int, err error) {
+	var p *C.uint8_t
+	var cs, cn C.size_t
+	if st := C.gc_stream_batch_out_next(o.h, &p, &cs, &cn); st != C.GC_OK {
+		return nil, 0, 0, statusError(st)
+	}
+	return unsafe.Pointer(p), int(cs), int(cn), nil
+}
+
+// Release returns the oldest handed-out window to the ring.
+func (o *StreamingBatchOut) Release() error {
+	if st := C.gc_stream_batch_out_release(o.h); st != C.GC_OK {
+		return statusError(st)
+	}
+	return nil
+}
+
+// Stats returns the windows sealed, the bytes per session, the windows grown and the ErrWindowsBusy answers so far.
+func (o *StreamingBatchOut) Stats() (sealed, bytesPerSession, grown, busy uint64, err error) {
+	var a, b, c, d C.uint64_t
+	if st := C.gc_stream_batch_out_stats(o.h, &a, &b, &c, &d); st != C.GC_OK {
+		return 0, 0, 0, 0, statusError(st)
+	}
+	return uint64(a), uint64(b), uint64(c), uint64(d), nil
+}
+
+// EvalBlockHost is EvalBlock with every session's block in host memory: session k's at unsafe.Add(blocks, k*stride), n bytes
+// each — a window of the garbler's StreamingBatchOut, or what S connections delivered.  Session refSession's bytes are the
+// reference block.  Pinned memory (AllocPinned) is read by DMA and must stay untouched until UploadsWait or Bad returns.
+func (e *StreamEvalBatch) EvalBlockHost(numGates, numTmpWires, numWires int, blocks unsafe.Pointer, stride, n, refSession int) (int, error) {
+	var used C.size_t
+	st := C.gc_stream_eval_batch_circuit_host(e.h, C.uint32_t(numGates), C.uint32_t(numTmpWires), C.uint32_t(numWires),
+		(*C.uint8_t)(blocks), C.size_t(stride), C.size_t(n), C.uint32_t(refSession), &used)
+	if st != C.GC_OK {
+		return 0, statusError(st)
+	}
+	return int(used), nil
+}
+
+// UploadsWait returns when every block handed to EvalBlockHost has left the caller's memory.
+func (e *StreamEvalBatch) UploadsWait() error {
+	if st := C.gc_stream_eval_batch_uploads_wait(e.h); st != C.GC_OK {
+		return statusError(st)
+	}
+	return nil
+}
+
+// Bad waits and returns, per session, the structure bytes that differed from the reference block in any EvalBlockHost so
+// far: a session that differed once stays marked and is run again through StreamEval.evalBlock by the caller.
+func (e *StreamEvalBatch) Bad() ([]uint32, error) {
+	bad := make([]uint32, e.sessions)
+	if st := C.gc_stream_eval_batch_bad(e.h, (*C.uint32_t)(unsafe.Pointer(&bad[0]))); st != C.GC_OK {
+		return nil, statusError(st)
+	}
+	return bad, nil
+}

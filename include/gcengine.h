@@ -46,7 +46,8 @@ enum {
     GC_E_HIP = -6,     /* HIP runtime failure (no device, launch error); see gc_last_error() */
     GC_E_NOMEM = -7,   /* device or host allocation failed */
     GC_E_WIRE = -8,    /* gate reads a wire that no input/gate has written, or wire id >= nwires */
-    GC_E_POINT = -9    /* ot.ErrPointNotOnCurve: "ot: point not on curve" (co_helpers.go:17, :179-188) */
+    GC_E_POINT = -9,   /* ot.ErrPointNotOnCurve: "ot: point not on curve" (co_helpers.go:17, :179-188) */
+    GC_E_BUSY = -10    /* gc_stream_batch_out_garble: every output window is sealed or handed out; nothing has happened */
 };
 
 const char *gc_strerror(int status);
@@ -604,6 +605,75 @@ int gc_stream_eval_batch_cache_stats(const gc_stream_eval_batch *, uint64_t *ent
  * block whose circuit is outside gc_batch_keyed_supported. */
 int gc_stream_eval_batch_circuit(gc_stream_eval_batch *, uint32_t ngates, uint32_t ntmp, uint32_t nwires, const uint8_t *ref_block,
                                  size_t len, const void *d_blocks, size_t stride, void *d_bad, size_t *consumed);
+
+/* ---- the other two phases of a session and the way to host memory (additive).  Every rule above holds: not
+ * inside a pipeline capture (GC_E_ARG), GC_E_ARG for a wire id >= GC_STREAM_MAX_WIRES, the store grows with the largest id
+ * as in gc_stream_batch_gather_wires. ---- */
+/* The garbler's own input labels (compiler/ssa/streamer.go:79-102: L1 if inputs.Bit(i), else L0) for all sessions:
+ *  d_bits        u8 [sessions][n], a non-zero byte is 1 (as gc_batch_select_inputs reads its bits)
+ *  d_labels_out  gc_label [sessions][n] = L0 of wire ids[j] in session s, ^ R[s] where the bit is 1
+ * A wire never set gives 0 or R[s] (the label form of gc_stream_batch_gather_wires).  ids may repeat; n = 0 is GC_OK.
+ * Asynchronous on the ctx stream; ids[] may be reused on return. */
+int gc_stream_batch_select_labels_dev(gc_stream_batch *, const uint32_t *ids, uint32_t n, const void *d_bits, void *d_labels_out);
+/* The result (streamer.go:563-579: label.Equal(wire.L0) -> 0, wire.L1 -> 1, else "unknown label") for all sessions:
+ *  d_labels    gc_label [sessions][n], what the peers sent back for the wires ids[0 .. n)
+ *  d_bits_out  u8 [sessions][n]: 0, 1, or 0xff where the label is neither (as gc_batch_decode writes its bits)
+ *  d_bad       u32 [sessions], zeroed by the call: the number of session s's 0xff entries
+ * ids may repeat; n = 0 zeroes d_bad and is GC_OK.  Asynchronous on the ctx stream; ids[] may be reused on return. */
+int gc_stream_batch_decode_dev(gc_stream_batch *, const uint32_t *ids, uint32_t n, const void *d_labels, void *d_bits_out, void *d_bad);
+/* the host forms of the two: host pointers, synchronous, staged as the host forms of the OT family are */
+int gc_stream_batch_select_labels(gc_stream_batch *, const uint32_t *ids, uint32_t n, const uint8_t *bits, gc_label *labels_out);
+int gc_stream_batch_decode(gc_stream_batch *, const uint32_t *ids, uint32_t n, const gc_label *labels, uint8_t *bits_out,
+                           uint32_t *bad_out);
+
+/* The garbler's stream bytes in windows of pinned host memory.  All sessions of a handle write the same number of bytes per
+ * step, so their streams advance in lock step: a window is a device array [sessions][cap] plus a pinned host array of the same
+ * shape, cap = window_bytes rounded up to 16; nwindows >= 2 (else GC_E_ARG).  The steps fill one window after the other; a
+ * window is SEALED when it is exactly full, when the next step does not fit behind what it holds, or by _flush if it holds any
+ * byte.  Sealing records an event on the ctx stream; a second stream of the handle waits for it and copies the window's used
+ * columns to the host (GC_STREAM_BATCH_OUT_WHOLE_ROWS=1: the whole array in one piece) while the ctx stream goes on into the
+ * next free window.  A step is never split over two windows.
+ *  _create   NULL + *status on failure (GC_E_ARG, GC_E_NOMEM, GC_E_HIP)
+ *  _free     waits for its copies; free it before the gc_stream_batch
+ *  _garble   gc_stream_batch_garble with d_out = the filling window at its running offset and stride = cap.  prefix[0 ..
+ *            prefix_len), prefix_len 0 .. 64 (else GC_E_ARG), is written to every session in front of the step's bytes — the
+ *            20-byte OpCircuit header of streamer.go:679-693, so that a window is what goes onto a socket; *written includes
+ *            it.  A step larger than cap grows the EMPTY filling window alone, to the step rounded up to 4 096 (counted in
+ *            `grown`); a failed allocation there is GC_E_NOMEM and nothing has changed.  When no window is free it returns
+ *            GC_E_BUSY: nothing has happened — the store is unchanged, nothing is queued, `busy` is counted — and the caller
+ *            releases a window and repeats the call.  It never waits for the caller, only for the device.
+ *  _flush    seals the filling window if it holds any byte (else nothing)
+ *  _next     hands out the oldest sealed window not yet handed out and waits for its copy: session s's next *len bytes are at
+ *            *base + s * *stride.  With nothing sealed: GC_OK with *len = 0, without waiting.
+ *  _release  returns the oldest handed-out window to the ring; several may be out at once and they come back in order.  With
+ *            nothing handed out: GC_E_ARG.
+ *  _stats    windows sealed, bytes per session accepted by _garble, windows grown, GC_E_BUSY answers (any pointer may be NULL)
+ * One thread on _garble / _flush and one other on _next / _release may use a handle at the same time (_next waits outside the
+ * handle's lock).  gc_stream_batch_garble on the same gc_stream_batch stays legal meanwhile; its bytes go where its caller says
+ * and are part of no window. */
+typedef struct gc_stream_batch_out gc_stream_batch_out;
+gc_stream_batch_out *gc_stream_batch_out_create(gc_stream_batch *, size_t window_bytes, uint32_t nwindows, int *status);
+void gc_stream_batch_out_free(gc_stream_batch_out *);
+int gc_stream_batch_out_garble(gc_stream_batch_out *, const uint8_t *prefix, size_t prefix_len, const gc_gate *gates, uint32_t ngates,
+                               uint32_t nwires, const uint32_t *in, uint32_t nin, const uint32_t *out, uint32_t nout, size_t *written);
+int gc_stream_batch_out_flush(gc_stream_batch_out *);
+int gc_stream_batch_out_next(gc_stream_batch_out *, const uint8_t **base, size_t *stride, size_t *len);
+int gc_stream_batch_out_release(gc_stream_batch_out *);
+int gc_stream_batch_out_stats(const gc_stream_batch_out *, uint64_t *sealed, uint64_t *bytes_per_session, uint64_t *grown, uint64_t *busy);
+
+/* gc_stream_eval_batch_circuit with the blocks in HOST memory: session s's block at blocks + s * stride, any stride >= len (the
+ * layout of a garbler window: *base + offset of gc_stream_batch_out_next is a valid argument).  Session ref_session's bytes
+ * are the reference block, parsed and refused exactly as there; the rest of the step is the same.  The blocks go into a ring
+ * of two device buffers of the handle on a stream of their own, so block k + 1 uploads while block k evaluates.  Pinned
+ * memory (gc_host_is_pinned) is copied by DMA straight from the caller's pages: it must stay valid and unchanged until
+ * gc_stream_eval_batch_uploads_wait, _bad or _free returns.  Pageable memory goes through pinned staging of the handle, and
+ * the call returns when `blocks` may be reused.  The count of differing structure bytes is ADDED into an array of the handle:
+ * _bad waits and returns the sums since create (bad_out[sessions]); a session that differed once stays marked, and its later
+ * labels are unspecified. */
+int gc_stream_eval_batch_circuit_host(gc_stream_eval_batch *, uint32_t ngates, uint32_t ntmp, uint32_t nwires, const uint8_t *blocks,
+                                      size_t stride, size_t len, uint32_t ref_session, size_t *consumed);
+int gc_stream_eval_batch_uploads_wait(gc_stream_eval_batch *);
+int gc_stream_eval_batch_bad(gc_stream_eval_batch *, uint32_t *bad_out /* [sessions] */);
 
 /* ------------------------------------------------------------------------------------------
  * IKNP OT extension + MITCCRH (ot/iknp.go, ot/mitccrh.go, ot/cot.go)

@@ -547,10 +547,89 @@ public:
         check(gc_stream_batch_cache_stats(h_, &c.entries, &c.bytes, &c.loads, &c.evictions), "gc_stream_batch_cache_stats");
         return c;
     }
+    // the garbler's own input labels (streamer.go:79-102): d_labels_out gc_label [sessions][ids] = L0, ^ R where d_bits (u8
+    // [sessions][ids]) is not zero; asynchronous
+    void SelectLabelsDev(const std::vector<uint32_t> &ids, const void *d_bits, void *d_labels_out) {
+        check(gc_stream_batch_select_labels_dev(h_, ids.data(), (uint32_t)ids.size(), d_bits, d_labels_out),
+              "gc_stream_batch_select_labels_dev");
+    }
+    // ... from host bits [sessions][ids], synchronous
+    std::vector<gc_label> SelectLabels(const std::vector<uint32_t> &ids, const std::vector<uint8_t> &bits) {
+        if (bits.size() != (size_t)sessions_ * ids.size()) throw Error("SelectLabels: bits must be [sessions][ids]");
+        std::vector<gc_label> out(bits.size());
+        check(gc_stream_batch_select_labels(h_, ids.data(), (uint32_t)ids.size(), bits.data(), out.data()),
+              "gc_stream_batch_select_labels");
+        return out;
+    }
+    // the result (streamer.go:563-579): d_bits_out u8 [sessions][ids] = 0 / 1 / 0xff ("unknown label"), d_bad u32 [sessions] =
+    // the 0xff entries of a session; asynchronous
+    void DecodeDev(const std::vector<uint32_t> &ids, const void *d_labels, void *d_bits_out, void *d_bad) {
+        check(gc_stream_batch_decode_dev(h_, ids.data(), (uint32_t)ids.size(), d_labels, d_bits_out, d_bad),
+              "gc_stream_batch_decode_dev");
+    }
+    // ... of host labels [sessions][ids], synchronous; bad: [sessions]
+    std::vector<uint8_t> Decode(const std::vector<uint32_t> &ids, const std::vector<gc_label> &labels, std::vector<uint32_t> *bad) {
+        if (labels.size() != (size_t)sessions_ * ids.size() || !bad) throw Error("Decode: labels must be [sessions][ids]");
+        std::vector<uint8_t> bits(labels.size());
+        bad->assign(sessions_, 0);
+        check(gc_stream_batch_decode(h_, ids.data(), (uint32_t)ids.size(), labels.data(), bits.data(), bad->data()),
+              "gc_stream_batch_decode");
+        return bits;
+    }
+    gc_stream_batch *handle() const { return h_; }
+    uint32_t sessions() const { return sessions_; }
 
 private:
     gc_stream_batch *h_ = nullptr;
     uint32_t sessions_;
+};
+
+// The steps of a StreamingBatch in windows of pinned host memory (gc_stream_batch_out_*): destroy it before its StreamingBatch.
+// One thread may call Garble / Flush while one other calls Next / Release.
+class StreamingBatchOut {
+public:
+    StreamingBatchOut(StreamingBatch &sb, size_t window_bytes, uint32_t nwindows) {
+        int st = GC_OK;
+        h_ = gc_stream_batch_out_create(sb.handle(), window_bytes, nwindows, &st);
+        if (!h_) check(st, "gc_stream_batch_out_create");
+    }
+    ~StreamingBatchOut() { gc_stream_batch_out_free(h_); }
+    StreamingBatchOut(const StreamingBatchOut &) = delete;
+    StreamingBatchOut &operator=(const StreamingBatchOut &) = delete;
+    // false: no window is free (GC_E_BUSY) — nothing has happened; release one and call again.  *written: bytes per session,
+    // the prefix (the OpCircuit header, streamer.go:679-693) included
+    bool Garble(const std::vector<uint8_t> &prefix, const std::vector<gc_gate> &gates, uint32_t nwires,
+                const std::vector<uint32_t> &in, const std::vector<uint32_t> &out, size_t *written) {
+        size_t n = 0;
+        const int st = gc_stream_batch_out_garble(h_, prefix.data(), prefix.size(), gates.data(), (uint32_t)gates.size(), nwires,
+                                                  in.data(), (uint32_t)in.size(), out.data(), (uint32_t)out.size(), &n);
+        if (written) *written = n;
+        if (st == GC_E_BUSY) return false;
+        check(st, "gc_stream_batch_out_garble");
+        return true;
+    }
+    void Flush() { check(gc_stream_batch_out_flush(h_), "gc_stream_batch_out_flush"); }
+    struct Window {
+        const uint8_t *base = nullptr;  // session s's bytes: base + s * stride
+        size_t stride = 0, len = 0;     // len == 0: nothing is sealed
+    };
+    Window Next() {
+        Window w;
+        check(gc_stream_batch_out_next(h_, &w.base, &w.stride, &w.len), "gc_stream_batch_out_next");
+        return w;
+    }
+    void Release() { check(gc_stream_batch_out_release(h_), "gc_stream_batch_out_release"); }
+    struct Stats {
+        uint64_t sealed = 0, bytes_per_session = 0, grown = 0, busy = 0;
+    };
+    Stats GetStats() const {
+        Stats s;
+        check(gc_stream_batch_out_stats(h_, &s.sealed, &s.bytes_per_session, &s.grown, &s.busy), "gc_stream_batch_out_stats");
+        return s;
+    }
+
+private:
+    gc_stream_batch_out *h_ = nullptr;
 };
 
 class StreamEvalBatch {
@@ -578,6 +657,22 @@ public:
         check(gc_stream_eval_batch_circuit(h_, ngates, ntmp, nwires, ref.data(), ref.size(), d_blocks, stride, d_bad, &used),
               "gc_stream_eval_batch_circuit");
         return used;
+    }
+    // EvalBlock with every session's block in HOST memory, `stride` apart (a window of StreamingBatchOut: base + offset);
+    // session ref_session's is the reference block.  Pinned memory stays untouched until UploadsWait / Bad returns.
+    size_t EvalBlockHost(uint32_t ngates, uint32_t ntmp, uint32_t nwires, const uint8_t *blocks, size_t stride, size_t len,
+                         uint32_t ref_session = 0) {
+        size_t used = 0;
+        check(gc_stream_eval_batch_circuit_host(h_, ngates, ntmp, nwires, blocks, stride, len, ref_session, &used),
+              "gc_stream_eval_batch_circuit_host");
+        return used;
+    }
+    void UploadsWait() { check(gc_stream_eval_batch_uploads_wait(h_), "gc_stream_eval_batch_uploads_wait"); }
+    // per session the structure bytes that differed in any EvalBlockHost since construction (waits)
+    std::vector<uint32_t> Bad() {
+        std::vector<uint32_t> bad(sessions_);
+        check(gc_stream_eval_batch_bad(h_, bad.data()), "gc_stream_eval_batch_bad");
+        return bad;
     }
     StreamingBatch::CacheStats GetCacheStats() const {
         StreamingBatch::CacheStats c;

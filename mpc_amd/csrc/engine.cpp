@@ -253,6 +253,7 @@ const char *gc_strerror(int status) {
     case GC_E_NOMEM: return "out of memory";
     case GC_E_WIRE: return "gate input wire not set";
     case GC_E_POINT: return "ot: point not on curve";
+    case GC_E_BUSY: return "no free output window: release one and repeat the call";
     default: return "unknown status";
     }
 }

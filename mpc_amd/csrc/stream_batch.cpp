@@ -8,13 +8,16 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
+#include <mutex>
 #include <new>
 #include <unordered_map>
 #include <vector>
 
 #include "engine.h"
 #include "stream_batch.h"
+#include "stream_batch_windows.h"
 
 namespace gcs {
 uint32_t stream_max_wires();  // stream_eval.cpp (GC_STREAM_MAX_WIRES)
@@ -346,6 +349,33 @@ struct gc_stream_eval_batch : SbCore {
     std::vector<uint32_t> row_off, in_ids, out_ids;
     std::vector<uint64_t> last_t, last_w;  // who wrote (tmp / global) wire last: generation << 32 | id
     uint32_t gen = 0;
+    // ---- gc_stream_eval_batch_circuit_host: blocks from host memory (all lazily made)
+    struct BlockBuf {  // one device block buffer [S][pitch] and the pinned staging for pageable callers
+        uint8_t *dev = nullptr, *pin = nullptr;
+        size_t dev_cap = 0, pin_cap = 0;
+        hipEvent_t uploaded = nullptr, consumed = nullptr;  // on the upload stream / on the ctx stream
+        bool in_flight = false, in_use = false;             // `uploaded` / `consumed` has been recorded
+    };
+    static constexpr int kBlockBufs = 2;  // block k + 1 uploads while block k evaluates
+    BlockBuf blk[kBlockBufs];
+    hipStream_t up = nullptr;
+    uint32_t nblk = 0;
+    uint32_t *d_badsum = nullptr;  // [S]: differing structure bytes since create
+    ~gc_stream_eval_batch() {
+        if (ctx) {
+            (void)hipSetDevice(ctx->device);
+            if (up) (void)hipStreamSynchronize(up);
+            (void)hipStreamSynchronize(ctx->stream);
+        }
+        for (auto &b : blk) {
+            if (b.dev) (void)hipFree(b.dev);
+            if (b.pin) (void)hipHostFree(b.pin);
+            if (b.uploaded) (void)hipEventDestroy(b.uploaded);
+            if (b.consumed) (void)hipEventDestroy(b.consumed);
+        }
+        if (up) (void)hipStreamDestroy(up);
+        if (d_badsum) (void)hipFree(d_badsum);
+    }
 };
 
 namespace {
@@ -390,8 +420,14 @@ bool rewrite_aliased(gc_stream_batch *s, const gc_gate **gates, uint32_t ngates,
     return true;
 }
 
+// where a step's bytes go once their number is known: the caller's place, or a window of a gc_stream_batch_out.  Called
+// when nothing can refuse the step any more and before anything of it is queued.
+using Placer = std::function<int(size_t nbytes, void **d_out, size_t *stride)>;
+
+// prefix: bytes in front of every session's step (they join the skeleton: the same for all sessions)
 int garble_step(gc_stream_batch *s, const gc_gate *gates, uint32_t ngates, uint32_t nwires, const uint32_t *in, uint32_t nin,
-                const uint32_t *out, uint32_t nout, void *d_out, size_t stride, size_t *written) {
+                const uint32_t *out, uint32_t nout, void *d_out, size_t stride, size_t *written, const uint8_t *prefix = nullptr,
+                size_t prefix_len = 0, const Placer *place = nullptr) {
     static const char *const what = "gc_stream_batch_garble";
     if (!s || !written || (ngates && !gates) || (nin && !in) || (nout && !out)) return GC_E_ARG;
     *written = 0;
@@ -409,10 +445,16 @@ int garble_step(gc_stream_batch *s, const gc_gate *gates, uint32_t ngates, uint3
     GC_HIP(hipSetDevice(s->ctx->device));
     // the bytes are those of the caller's gate list; the pass runs the list with in-place reads redirected
     s->skel.clear(), s->row_off.clear();
-    const size_t nbytes = step_skeleton(gates, ngates, nwires, in, nin, out, nout, &s->skel, &s->row_off);
+    size_t nbytes = step_skeleton(gates, ngates, nwires, in, nin, out, nout, &s->skel, &s->row_off);
+    if (prefix_len) {
+        s->skel.insert(s->skel.begin(), prefix, prefix + prefix_len);
+        for (uint32_t &off : s->row_off) off += (uint32_t)prefix_len;
+        nbytes += prefix_len;
+    }
     *written = nbytes;
     if (nbytes >= 0x7fffffffu) return refuse(what, "a step of 2 GiB or more");
-    if (!d_out || stride % 4 != 0 || stride < nbytes) return refuse(what, "stride must be a multiple of 4 and >= the step's bytes");
+    if (!place && (!d_out || stride % 4 != 0 || stride < nbytes))
+        return refuse(what, "stride must be a multiple of 4 and >= the step's bytes");
     const gc_gate *run = gates;
     std::unordered_map<uint32_t, uint32_t> latest;
     rewrite_aliased(s, &run, ngates, nwires, in, nin, out, nout, &latest);
@@ -435,6 +477,10 @@ int garble_step(gc_stream_batch *s, const gc_gate *gates, uint32_t ngates, uint3
     for (uint32_t j = 0; j < nout; j++) {
         auto it = latest.find(out[j]);
         if (it != latest.end()) s->out_marked[j] = it->second == nwires - nout + j ? out[j] : kNone;
+    }
+    if (place) {
+        rc = (*place)(nbytes, &d_out, &stride);
+        if (rc != GC_OK) return rc;
     }
     StepBlob b;
     b.plan(nin, nout, s->row_off.size(), nbytes);
@@ -558,8 +604,12 @@ int parse_block(gc_stream_eval_batch *e, uint32_t ngates, uint32_t ntmp, uint32_
     return GC_OK;
 }
 
+// the blocks of a step whose reference block has been accepted, in device memory: the caller's, or an upload of the handle's
+using Supplier = std::function<int(size_t nbytes, const void **d_blocks, size_t *stride)>;
+
+// supply: d_bad is the handle's running sum (not zeroed) and the blocks come from *supply
 int eval_step(gc_stream_eval_batch *e, uint32_t ngates, uint32_t ntmp, uint32_t nwires, const uint8_t *ref, size_t len,
-              const void *d_blocks, size_t stride, void *d_bad, size_t *consumed) {
+              const void *d_blocks, size_t stride, void *d_bad, size_t *consumed, const Supplier *supply = nullptr) {
     static const char *const what = "gc_stream_eval_batch_circuit";
     if (!e || !consumed || (!ref && len) || !d_bad) return GC_E_ARG;
     *consumed = 0;
@@ -569,13 +619,13 @@ int eval_step(gc_stream_eval_batch *e, uint32_t ngates, uint32_t ntmp, uint32_t 
     if (e->ctx->capturing) return GC_E_ARG;
     GC_HIP(hipSetDevice(e->ctx->device));
     hipStream_t q = e->ctx->stream;
-    GC_HIP(hipMemsetAsync(d_bad, 0, (size_t)e->S * sizeof(uint32_t), q));
+    if (!supply) GC_HIP(hipMemsetAsync(d_bad, 0, (size_t)e->S * sizeof(uint32_t), q));
     if (ngates == 0) return GC_OK;
     size_t pos = 0;
     int rc = parse_block(e, ngates, ntmp, nwires, ref, len, &pos);
     if (rc != GC_OK) return rc;
     if (pos >= 0x7fffffffu) return refuse(what, "a block of 2 GiB or more");
-    if (!d_blocks || stride % 4 != 0 || stride < len) return refuse(what, "stride must be a multiple of 4 and >= len");
+    if (!supply && (!d_blocks || stride % 4 != 0 || stride < len)) return refuse(what, "stride must be a multiple of 4 and >= len");
     const uint32_t nin = (uint32_t)e->in_ids.size(), nout = (uint32_t)e->out_ids.size();
     SbCirc *ent = nullptr;
     rc = e->find_or_load(e->gates.data(), ngates, nin + ngates, nin, nout, what, &ent);
@@ -585,6 +635,10 @@ int eval_step(gc_stream_eval_batch *e, uint32_t ngates, uint32_t ntmp, uint32_t 
     for (uint32_t id : e->out_ids) mx = std::max(mx, id == kNone ? 0u : id);
     rc = e->ensure(mx);
     if (rc != GC_OK) return rc;
+    if (supply) {
+        rc = (*supply)(pos, &d_blocks, &stride);
+        if (rc != GC_OK) return rc;
+    }
     StepBlob b;
     b.plan(nin, nout, e->row_off.size(), pos);
     SbStage *st = nullptr;
@@ -799,6 +853,419 @@ int gc_stream_eval_batch_cache_stats(const gc_stream_eval_batch *e, uint64_t *en
 int gc_stream_eval_batch_circuit(gc_stream_eval_batch *e, uint32_t ngates, uint32_t ntmp, uint32_t nwires, const uint8_t *ref_block,
                                  size_t len, const void *d_blocks, size_t stride, void *d_bad, size_t *consumed) try {
     return eval_step(e, ngates, ntmp, nwires, ref_block, len, d_blocks, stride, d_bad, consumed);
+} catch (...) {
+    return gc::on_exception();
+}
+
+}  // extern "C"
+
+// ================================================================================================================================
+// Inputs, results and the host-memory paths of the two handles: the garbler's own input labels and the
+// decoded result on the device, windows of stream bytes in pinned host memory, and the evaluator's blocks from host memory.
+// ================================================================================================================================
+
+// One window: a device array [S][cap] the steps write into and a pinned host array of the same shape.  The ring state (which
+// window fills, seals, is handed out) is gcsb::WindowRing; this handle adds the memory, the events and the copy stream.
+struct gc_stream_batch_out {
+    struct Win {
+        uint8_t *dev = nullptr, *pin = nullptr;
+        hipEvent_t sealed = nullptr, copied = nullptr;  // on the ctx stream / on the copy stream
+    };
+    gc_stream_batch *sb = nullptr;
+    mutable std::mutex mu;  // the ring and the windows' pointers; never held across a wait for a copy
+    gcsb::WindowRing ring;
+    std::vector<Win> win;
+    hipStream_t copy = nullptr;
+    bool whole_rows = false;  // copy [S][cap] in one piece instead of the used columns (GC_STREAM_BATCH_OUT_WHOLE_ROWS)
+
+    static void drop(Win &w) {
+        if (w.dev) (void)hipFree(w.dev);
+        if (w.pin) (void)hipHostFree(w.pin);
+        w.dev = w.pin = nullptr;
+    }
+    // both arrays or neither; the device array starts as zeros (a whole-row copy moves bytes no step wrote)
+    int make(size_t cap, Win *w) const {
+        const size_t bytes = (size_t)sb->S * cap;
+        hipError_t e = hipMalloc((void **)&w->dev, bytes);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&w->pin, bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMemsetAsync(w->dev, 0, bytes, sb->ctx->stream);
+        if (e != hipSuccess) {
+            drop(*w);
+            GC_HIP(e);
+        }
+        return GC_OK;
+    }
+    // the window's first n columns are complete in program order of the ctx stream: queue their way to the host
+    int seal(uint32_t k, size_t n) {
+        Win &w = win[k];
+        const size_t cap = ring.cap[k];
+        GC_HIP(hipEventRecord(w.sealed, sb->ctx->stream));
+        GC_HIP(hipStreamWaitEvent(copy, w.sealed, 0));
+        if (whole_rows || n == cap)
+            GC_HIP(hipMemcpyAsync(w.pin, w.dev, (size_t)sb->S * cap, hipMemcpyDeviceToHost, copy));
+        else
+            GC_HIP(hipMemcpy2DAsync(w.pin, cap, w.dev, cap, n, sb->S, hipMemcpyDeviceToHost, copy));
+        GC_HIP(hipEventRecord(w.copied, copy));
+        return GC_OK;
+    }
+    ~gc_stream_batch_out() {
+        if (sb) {
+            (void)hipSetDevice(sb->ctx->device);
+            if (copy) (void)hipStreamSynchronize(copy);
+            (void)hipStreamSynchronize(sb->ctx->stream);
+        }
+        for (auto &w : win) {
+            drop(w);
+            if (w.sealed) (void)hipEventDestroy(w.sealed);
+            if (w.copied) (void)hipEventDestroy(w.copied);
+        }
+        if (copy) (void)hipStreamDestroy(copy);
+    }
+};
+
+namespace {
+
+// the ids of a select / decode call: checked, the store grown to hold them, and sent through the staging ring
+int io_ids(gc_stream_batch *s, const char *what, const uint32_t *ids, uint32_t n, SbStage **st, const uint32_t **d_ids) {
+    if (s->ctx->capturing) return GC_E_ARG;
+    uint32_t mx = 0;
+    for (uint32_t i = 0; i < n; i++) mx = std::max(mx, ids[i]);
+    if (mx >= gcs::stream_max_wires()) return refuse(what, "a wire id >= GC_STREAM_MAX_WIRES");
+    GC_HIP(hipSetDevice(s->ctx->device));
+    int rc = s->ensure(mx);  // (a wire never set reads as 0: its labels are 0 and R)
+    if (rc != GC_OK) return rc;
+    StepBlob b;
+    b.plan(n, 0, 0, 0);
+    gcsb::StepDev dev{};
+    rc = send_step(*s, b, ids, n, nullptr, 0, {}, nullptr, 0, st, &dev);
+    if (rc == GC_OK) *d_ids = (const uint32_t *)((*st)->dev + b.o_in);
+    return rc;
+}
+
+int select_dev(gc_stream_batch *s, const uint32_t *ids, uint32_t n, const void *d_bits, void *d_labels_out) {
+    if (!s || (n && (!ids || !d_bits || !d_labels_out))) return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    SbStage *st = nullptr;
+    const uint32_t *d_ids = nullptr;
+    int rc = io_ids(s, "gc_stream_batch_select_labels_dev", ids, n, &st, &d_ids);
+    if (rc != GC_OK) return rc;
+    gcsb::launch_select(s->d_store, s->bstride, d_ids, n, s->d_R, (const uint8_t *)d_bits, (uint4 *)d_labels_out, s->S, s->ctx->stream);
+    const hipError_t e = hipGetLastError();
+    rc = step_sent(*s, st);
+    GC_HIP(e);
+    return rc;
+}
+
+int decode_dev(gc_stream_batch *s, const uint32_t *ids, uint32_t n, const void *d_labels, void *d_bits_out, void *d_bad) {
+    if (!s || !d_bad || (n && (!ids || !d_labels || !d_bits_out))) return GC_E_ARG;
+    if (s->ctx->capturing) return GC_E_ARG;
+    GC_HIP(hipSetDevice(s->ctx->device));
+    GC_HIP(hipMemsetAsync(d_bad, 0, (size_t)s->S * sizeof(uint32_t), s->ctx->stream));
+    if (n == 0) return GC_OK;
+    SbStage *st = nullptr;
+    const uint32_t *d_ids = nullptr;
+    int rc = io_ids(s, "gc_stream_batch_decode_dev", ids, n, &st, &d_ids);
+    if (rc != GC_OK) return rc;
+    gcsb::launch_decode_labels(s->d_store, s->bstride, d_ids, n, s->d_R, (const uint4 *)d_labels, (uint8_t *)d_bits_out,
+                               (uint32_t *)d_bad, s->S, s->ctx->stream);
+    const hipError_t e = hipGetLastError();
+    rc = step_sent(*s, st);
+    GC_HIP(e);
+    return rc;
+}
+
+int out_garble(gc_stream_batch_out *h, const uint8_t *prefix, size_t prefix_len, const gc_gate *gates, uint32_t ngates,
+               uint32_t nwires, const uint32_t *in, uint32_t nin, const uint32_t *out, uint32_t nout, size_t *written) {
+    if (!h || !written || prefix_len > 64 || (prefix_len && !prefix) || (ngates && !gates) || (nin && !in) || (nout && !out))
+        return GC_E_ARG;
+    *written = 0;
+    gc_stream_batch *s = h->sb;
+    // a full ring is known from the step's size alone: answer before the step touches anything (a step that is refused by
+    // its shape is left to garble_step, which says why).  The size is worked out before the lock is taken, so that a caller
+    // who repeats a busy call does not keep the lock from the thread that would release a window.
+    int shape = GC_OK;
+    size_t size = 0;
+    if (ngates && !s->ctx->capturing && !step_refused(gates, ngates, nwires, nin, nout, &shape))
+        size = step_skeleton(gates, ngates, nwires, in, nin, out, nout, nullptr, nullptr) + prefix_len;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (size && h->ring.plan_step(size).is_busy) {
+        h->ring.note_busy();
+        return GC_E_BUSY;
+    }
+    GC_HIP(hipSetDevice(s->ctx->device));
+    uint32_t seal_after = gcsb::WindowRing::kNoWindow;
+    size_t seal_len = 0;
+    const Placer place = [&](size_t n, void **d_out, size_t *stride) -> int {
+        const gcsb::WindowRing::Step p = h->ring.plan_step(n);
+        if (p.is_busy) {
+            h->ring.note_busy();
+            return GC_E_BUSY;
+        }
+        gc_stream_batch_out::Win bigger;
+        if (p.grow_to) {  // (the window is empty and free: nothing on the device or on the link uses its arrays)
+            const int rc = h->make(p.grow_to, &bigger);
+            if (rc != GC_OK) return rc;
+        }
+        if (p.seal_before != gcsb::WindowRing::kNoWindow) {
+            const int rc = h->seal(p.seal_before, p.seal_len);
+            if (rc != GC_OK) {
+                gc_stream_batch_out::drop(bigger);
+                return rc;
+            }
+        }
+        if (p.grow_to) {
+            gc_stream_batch_out::drop(h->win[p.win]);
+            h->win[p.win].dev = bigger.dev, h->win[p.win].pin = bigger.pin;
+        }
+        h->ring.commit(p, n);
+        if (p.seal_after) seal_after = p.win, seal_len = p.at + n;
+        *d_out = h->win[p.win].dev + p.at;
+        *stride = h->ring.cap[p.win];
+        return GC_OK;
+    };
+    const int rc = garble_step(s, gates, ngates, nwires, in, nin, out, nout, nullptr, 0, written, prefix, prefix_len, &place);
+    // (the ring has the window as sealed whatever became of the step's launches: its events must exist)
+    const int rcs = seal_after != gcsb::WindowRing::kNoWindow ? h->seal(seal_after, seal_len) : GC_OK;
+    return rc != GC_OK ? rc : rcs;
+}
+
+// the handle's upload stream, running sum and events, made by the first call that needs them
+int eval_host_setup(gc_stream_eval_batch *e) {
+    GC_HIP(hipSetDevice(e->ctx->device));
+    if (!e->up) GC_HIP(hipStreamCreateWithFlags(&e->up, hipStreamNonBlocking));
+    for (auto &b : e->blk) {
+        if (!b.uploaded) GC_HIP(hipEventCreateWithFlags(&b.uploaded, hipEventDisableTiming));
+        if (!b.consumed) GC_HIP(hipEventCreateWithFlags(&b.consumed, hipEventDisableTiming));
+    }
+    if (!e->d_badsum) {
+        GC_HIP(hipMalloc((void **)&e->d_badsum, (size_t)e->S * sizeof(uint32_t)));
+        GC_HIP(hipMemsetAsync(e->d_badsum, 0, (size_t)e->S * sizeof(uint32_t), e->ctx->stream));
+    }
+    return GC_OK;
+}
+
+int eval_host(gc_stream_eval_batch *e, uint32_t ngates, uint32_t ntmp, uint32_t nwires, const uint8_t *blocks, size_t stride,
+              size_t len, uint32_t ref_session, size_t *consumed) {
+    if (!e || !consumed || (!blocks && len) || ref_session >= e->S || (e->S > 1 && stride < len)) return GC_E_ARG;
+    *consumed = 0;
+    if (e->ctx->capturing) return GC_E_ARG;
+    int rc = eval_host_setup(e);
+    if (rc != GC_OK) return rc;
+    gc_stream_eval_batch::BlockBuf *used = nullptr;
+    const Supplier supply = [&](size_t nbytes, const void **d_blocks, size_t *pitch_out) -> int {
+        gc_stream_eval_batch::BlockBuf &b = e->blk[e->nblk++ % gc_stream_eval_batch::kBlockBufs];
+        const size_t pitch = up16(nbytes), need = (size_t)e->S * pitch;
+        const bool pinned = gc_host_is_pinned(blocks) != 0;
+        if (b.dev_cap < need) {  // (freed only when the block before has been ingested)
+            if (b.in_flight) GC_HIP(hipEventSynchronize(b.uploaded));
+            if (b.in_use) GC_HIP(hipEventSynchronize(b.consumed));
+            if (b.dev) (void)hipFree(b.dev);
+            b.dev = nullptr, b.dev_cap = 0;
+            GC_HIP(hipMalloc((void **)&b.dev, need + need / 2));
+            b.dev_cap = need + need / 2;
+        } else if (b.in_use) {
+            GC_HIP(hipStreamWaitEvent(e->up, b.consumed, 0));
+        }
+        if (pinned) {  // DMA straight from the caller's memory, row by row at the caller's stride
+            // (one session: its stride is not looked at, and a source pitch below the width would be refused)
+            GC_HIP(hipMemcpy2DAsync(b.dev, pitch, blocks, e->S > 1 ? stride : nbytes, nbytes, e->S, hipMemcpyHostToDevice, e->up));
+        } else {
+            if (b.in_flight) GC_HIP(hipEventSynchronize(b.uploaded));  // (the staging's previous block has left)
+            if (b.pin_cap < need) {
+                if (b.pin) (void)hipHostFree(b.pin);
+                b.pin = nullptr, b.pin_cap = 0;
+                GC_HIP(hipHostMalloc((void **)&b.pin, need + need / 2, hipHostMallocDefault));
+                b.pin_cap = need + need / 2;
+            }
+            for (uint32_t s = 0; s < e->S; s++) std::memcpy(b.pin + (size_t)s * pitch, blocks + (size_t)s * stride, nbytes);
+            GC_HIP(hipMemcpyAsync(b.dev, b.pin, need, hipMemcpyHostToDevice, e->up));
+        }
+        GC_HIP(hipEventRecord(b.uploaded, e->up));
+        b.in_flight = true;
+        GC_HIP(hipStreamWaitEvent(e->ctx->stream, b.uploaded, 0));
+        used = &b;
+        *d_blocks = b.dev, *pitch_out = pitch;
+        return GC_OK;
+    };
+    rc = eval_step(e, ngates, ntmp, nwires, blocks ? blocks + (size_t)ref_session * stride : nullptr, len, nullptr, 0, e->d_badsum,
+                   consumed, &supply);
+    if (used) {  // what reads the buffer is queued (or was not: then the event completes at once)
+        const hipError_t err = hipEventRecord(used->consumed, e->ctx->stream);
+        used->in_use = err == hipSuccess;
+        if (rc == GC_OK) GC_HIP(err);
+    }
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gc_stream_batch_select_labels_dev(gc_stream_batch *s, const uint32_t *ids, uint32_t n, const void *d_bits, void *d_labels_out) try {
+    return select_dev(s, ids, n, d_bits, d_labels_out);
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_stream_batch_decode_dev(gc_stream_batch *s, const uint32_t *ids, uint32_t n, const void *d_labels, void *d_bits_out,
+                               void *d_bad) try {
+    return decode_dev(s, ids, n, d_labels, d_bits_out, d_bad);
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_stream_batch_select_labels(gc_stream_batch *s, const uint32_t *ids, uint32_t n, const uint8_t *bits, gc_label *labels_out) try {
+    if (!s || (n && (!ids || !bits || !labels_out))) return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    if (s->ctx->capturing) return GC_E_ARG;
+    std::lock_guard<std::mutex> lock(s->ctx->mu);  // (a host form: §17)
+    GC_HIP(hipSetDevice(s->ctx->device));
+    const size_t cells = (size_t)s->S * n;
+    Staged io[] = {{bits, nullptr, cells}, {nullptr, labels_out, cells * sizeof(gc_label)}};
+    int rc = stage_in(io, std::size(io), s->ctx->stream);
+    if (rc == GC_OK) rc = select_dev(s, ids, n, io[0].d.p, io[1].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), s->ctx->stream);
+    return rc;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_stream_batch_decode(gc_stream_batch *s, const uint32_t *ids, uint32_t n, const gc_label *labels, uint8_t *bits_out,
+                           uint32_t *bad_out) try {
+    if (!s || !bad_out || (n && (!ids || !labels || !bits_out))) return GC_E_ARG;
+    if (s->ctx->capturing) return GC_E_ARG;
+    std::lock_guard<std::mutex> lock(s->ctx->mu);  // (a host form: §17)
+    GC_HIP(hipSetDevice(s->ctx->device));
+    const size_t cells = (size_t)s->S * n;
+    Staged io[] = {{labels, nullptr, cells * sizeof(gc_label)}, {nullptr, bits_out, cells}, {nullptr, bad_out, (size_t)s->S * sizeof(uint32_t)}};
+    int rc = stage_in(io, std::size(io), s->ctx->stream);
+    if (rc == GC_OK) rc = decode_dev(s, ids, n, io[0].d.p, io[1].d.p, io[2].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), s->ctx->stream);
+    return rc;
+} catch (...) {
+    return gc::on_exception();
+}
+
+gc_stream_batch_out *gc_stream_batch_out_create(gc_stream_batch *s, size_t window_bytes, uint32_t nwindows, int *status) try {
+    int rc = GC_OK;
+    std::unique_ptr<gc_stream_batch_out> h(new (std::nothrow) gc_stream_batch_out);
+    if (!h) rc = GC_E_NOMEM;
+    if (rc == GC_OK && (!s || window_bytes == 0 || window_bytes > ((size_t)1 << 40) || nwindows > 4096)) rc = GC_E_ARG;
+    if (rc == GC_OK && !h->ring.init(window_bytes, nwindows)) rc = GC_E_ARG;
+    auto setup = [&]() -> int {
+        h->sb = s;
+        const char *e = std::getenv("GC_STREAM_BATCH_OUT_WHOLE_ROWS");
+        h->whole_rows = e && *e && *e != '0';
+        GC_HIP(hipSetDevice(s->ctx->device));
+        GC_HIP(hipStreamCreateWithFlags(&h->copy, hipStreamNonBlocking));
+        h->win.resize(nwindows);
+        for (uint32_t k = 0; k < nwindows; k++) {
+            GC_HIP(hipEventCreateWithFlags(&h->win[k].sealed, hipEventDisableTiming));
+            GC_HIP(hipEventCreateWithFlags(&h->win[k].copied, hipEventDisableTiming));
+            const int r = h->make(h->ring.cap[k], &h->win[k]);
+            if (r != GC_OK) return r;
+        }
+        return GC_OK;
+    };
+    if (rc == GC_OK) rc = setup();
+    if (status) *status = rc;
+    return rc == GC_OK ? h.release() : nullptr;
+} catch (...) {
+    const int rc__ = gc::on_exception();
+    if (status) *status = rc__;
+    return nullptr;
+}
+
+void gc_stream_batch_out_free(gc_stream_batch_out *h) { delete h; }
+
+int gc_stream_batch_out_garble(gc_stream_batch_out *h, const uint8_t *prefix, size_t prefix_len, const gc_gate *gates, uint32_t ngates,
+                               uint32_t nwires, const uint32_t *in, uint32_t nin, const uint32_t *out, uint32_t nout,
+                               size_t *written) try {
+    return out_garble(h, prefix, prefix_len, gates, ngates, nwires, in, nin, out, nout, written);
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_stream_batch_out_flush(gc_stream_batch_out *h) try {
+    if (!h) return GC_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    size_t n = 0;
+    const uint32_t w = h->ring.plan_flush(&n);
+    if (w == gcsb::WindowRing::kNoWindow) return GC_OK;
+    GC_HIP(hipSetDevice(h->sb->ctx->device));
+    const int rc = h->seal(w, n);
+    if (rc == GC_OK) h->ring.commit_flush();
+    return rc;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_stream_batch_out_next(gc_stream_batch_out *h, const uint8_t **base, size_t *stride, size_t *len) try {
+    if (!h || !base || !stride || !len) return GC_E_ARG;
+    *base = nullptr, *stride = 0, *len = 0;
+    hipEvent_t copied = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(h->mu);
+        size_t n = 0;
+        const uint32_t w = h->ring.next(&n);
+        if (w == gcsb::WindowRing::kNoWindow) return GC_OK;
+        *base = h->win[w].pin, *stride = h->ring.cap[w], *len = n;
+        copied = h->win[w].copied;
+    }
+    GC_HIP(hipSetDevice(h->sb->ctx->device));
+    GC_HIP(hipEventSynchronize(copied));
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_stream_batch_out_release(gc_stream_batch_out *h) try {
+    if (!h) return GC_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    return h->ring.release() == gcsb::WindowRing::kNoWindow ? GC_E_ARG : GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_stream_batch_out_stats(const gc_stream_batch_out *h, uint64_t *sealed, uint64_t *bytes_per_session, uint64_t *grown,
+                              uint64_t *busy) try {
+    if (!h) return GC_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (sealed) *sealed = h->ring.sealed;
+    if (bytes_per_session) *bytes_per_session = h->ring.bytes_per_session;
+    if (grown) *grown = h->ring.grown;
+    if (busy) *busy = h->ring.busy;
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_stream_eval_batch_circuit_host(gc_stream_eval_batch *e, uint32_t ngates, uint32_t ntmp, uint32_t nwires, const uint8_t *blocks,
+                                      size_t stride, size_t len, uint32_t ref_session, size_t *consumed) try {
+    return eval_host(e, ngates, ntmp, nwires, blocks, stride, len, ref_session, consumed);
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_stream_eval_batch_uploads_wait(gc_stream_eval_batch *e) try {
+    if (!e) return GC_E_ARG;
+    GC_HIP(hipSetDevice(e->ctx->device));
+    if (e->up) GC_HIP(hipStreamSynchronize(e->up));
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_stream_eval_batch_bad(gc_stream_eval_batch *e, uint32_t *bad_out) try {
+    if (!e || !bad_out) return GC_E_ARG;
+    GC_HIP(hipSetDevice(e->ctx->device));
+    if (e->up) GC_HIP(hipStreamSynchronize(e->up));
+    if (e->d_badsum)
+        GC_HIP(hipMemcpyAsync(bad_out, e->d_badsum, (size_t)e->S * sizeof(uint32_t), hipMemcpyDeviceToHost, e->ctx->stream));
+    else
+        std::memset(bad_out, 0, (size_t)e->S * sizeof(uint32_t));
+    GC_HIP(hipStreamSynchronize(e->ctx->stream));
+    return GC_OK;
 } catch (...) {
     return gc::on_exception();
 }

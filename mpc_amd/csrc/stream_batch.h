@@ -44,4 +44,14 @@ void launch_serialise(const StepDev &d, const uint4 *T, const gc::Layout &lt, ui
 void launch_ingest(const StepDev &d, uint4 *T, const gc::Layout &lt, const uint8_t *in, size_t stride, uint32_t S, uint32_t *bad,
                    hipStream_t s);
 
+// the tile of the two movers below: ids x sessions, and the most tiles along the ids that one grid holds (more are swept)
+constexpr uint32_t kIoIds = 64, kIoSessions = 32, kIoMaxTiles = 1024;
+// out [S][n] = store[ids[j]][s] ^ (bits[s][n] ? R[s] : 0): the garbler's label for a bit (streamer.go:79-102)
+void launch_select(const uint4 *store, uint32_t bstride, const uint32_t *ids, uint32_t n, const uint4 *R, const uint8_t *bits,
+                   uint4 *out, uint32_t S, hipStream_t s);
+// bits_out [S][n] = 0 / 1 / 0xff for labels [S][n] equal to store[ids[j]][s] / that ^ R[s] / neither (streamer.go:563-579), and
+// bad[s] += session s's 0xff entries (one add per wave that saw any)
+void launch_decode_labels(const uint4 *store, uint32_t bstride, const uint32_t *ids, uint32_t n, const uint4 *R, const uint4 *labels,
+                          uint8_t *bits_out, uint32_t *bad, uint32_t S, hipStream_t s);
+
 }  // namespace gcsb

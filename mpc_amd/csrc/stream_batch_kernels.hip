@@ -152,7 +152,92 @@ __global__ __launch_bounds__(kThreads) void k_sb_ingest(StepDev d, uint4 *__rest
     if ((threadIdx.x & 63) == 0 && diff) atomicAdd(bad + s, diff);
 }
 
+// ---- inputs and results (gc_stream_batch_select_labels_dev / _decode_dev) ----------------------------------------------------
+// The store is [wire id][bstride], the callers' arrays are [session][n].  A tile of kIoIds ids x kIoSessions sessions is read
+// with the lanes along the sessions (512 contiguous bytes of a store row), turned in LDS as k_gather turns its tile, and used
+// with the lanes along the ids: a wave owns one session's 64 consecutive entries, 1 KiB of labels or 64 bytes of bits.  The
+// tiles along the ids are swept (gridDim.x is capped), so any n runs.
+__device__ __forceinline__ void io_tile_in(uint4 (*tile)[kIoSessions + 1], const uint4 *__restrict__ store, uint32_t bstride,
+                                           const uint32_t *__restrict__ ids, uint32_t n, uint32_t S, uint32_t j0, uint32_t i0) {
+    const uint32_t tx = threadIdx.x & (kIoSessions - 1), ty = threadIdx.x / kIoSessions;
+    const uint32_t i = i0 + tx;
+    for (uint32_t r = ty; r < kIoIds; r += kThreads / kIoSessions) {
+        const uint32_t j = j0 + r;
+        if (j < n && i < S) tile[r][tx] = store[(size_t)ids[j] * bstride + i];
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_sb_select(const uint4 *__restrict__ store, uint32_t bstride,
+                                                        const uint32_t *__restrict__ ids, uint32_t n, const uint4 *__restrict__ R,
+                                                        const uint8_t *__restrict__ bits, uint4 *__restrict__ out, uint32_t S) {
+    __shared__ uint4 tile[kIoIds][kIoSessions + 1];
+    const uint32_t i0 = blockIdx.y * kIoSessions, ntiles = (n + kIoIds - 1) / kIoIds;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const uint32_t j0 = t * kIoIds, j = j0 + lane;
+        io_tile_in(tile, store, bstride, ids, n, S, j0, i0);
+        __syncthreads();
+        for (uint32_t r = wave; r < kIoSessions; r += kThreads / 64) {
+            const uint32_t i = i0 + r;
+            if (j < n && i < S) {
+                const size_t at = (size_t)i * n + j;
+                const uint32_t m = bits[at] ? 0xffffffffu : 0u;
+                const uint4 v = tile[lane][r], rr = R[i];
+                out[at] = make_uint4(v.x ^ (rr.x & m), v.y ^ (rr.y & m), v.z ^ (rr.z & m), v.w ^ (rr.w & m));
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_sb_decode(const uint4 *__restrict__ store, uint32_t bstride,
+                                                        const uint32_t *__restrict__ ids, uint32_t n, const uint4 *__restrict__ R,
+                                                        const uint4 *__restrict__ labels, uint8_t *__restrict__ bits_out,
+                                                        uint32_t *__restrict__ bad, uint32_t S) {
+    __shared__ uint4 tile[kIoIds][kIoSessions + 1];
+    const uint32_t i0 = blockIdx.y * kIoSessions, ntiles = (n + kIoIds - 1) / kIoIds;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const uint32_t j0 = t * kIoIds, j = j0 + lane;
+        io_tile_in(tile, store, bstride, ids, n, S, j0, i0);
+        __syncthreads();
+        for (uint32_t r = wave; r < kIoSessions; r += kThreads / 64) {  // (uniform per wave: one session at a time)
+            const uint32_t i = i0 + r;
+            uint32_t unknown = 0;
+            if (j < n && i < S) {
+                const size_t at = (size_t)i * n + j;
+                const uint4 l0 = tile[lane][r], rr = R[i], lab = labels[at];
+                const uint4 d = make_uint4(lab.x ^ l0.x, lab.y ^ l0.y, lab.z ^ l0.z, lab.w ^ l0.w);
+                uint8_t bit = 0xff;  // BitFromLabel's "unknown label" (streamer.go:563-579)
+                if ((d.x | d.y | d.z | d.w) == 0) bit = 0;
+                else if (((d.x ^ rr.x) | (d.y ^ rr.y) | (d.z ^ rr.z) | (d.w ^ rr.w)) == 0) bit = 1;
+                bits_out[at] = bit;
+                unknown = bit == 0xff;
+            }
+            for (int o = 32; o > 0; o >>= 1) unknown += __shfl_down(unknown, o, 64);
+            if (lane == 0 && unknown) atomicAdd(bad + i, unknown);
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace
+
+void launch_select(const uint4 *store, uint32_t bstride, const uint32_t *ids, uint32_t n, const uint4 *R, const uint8_t *bits,
+                   uint4 *out, uint32_t S, hipStream_t s) {
+    if (n == 0 || S == 0) return;
+    const uint32_t ntiles = (n + kIoIds - 1) / kIoIds;
+    hipLaunchKernelGGL(k_sb_select, dim3(ntiles < kIoMaxTiles ? ntiles : kIoMaxTiles, (S + kIoSessions - 1) / kIoSessions),
+                       dim3(kThreads), 0, s, store, bstride, ids, n, R, bits, out, S);
+}
+
+void launch_decode_labels(const uint4 *store, uint32_t bstride, const uint32_t *ids, uint32_t n, const uint4 *R, const uint4 *labels,
+                          uint8_t *bits_out, uint32_t *bad, uint32_t S, hipStream_t s) {
+    if (n == 0 || S == 0) return;
+    const uint32_t ntiles = (n + kIoIds - 1) / kIoIds;
+    hipLaunchKernelGGL(k_sb_decode, dim3(ntiles < kIoMaxTiles ? ntiles : kIoMaxTiles, (S + kIoSessions - 1) / kIoSessions),
+                       dim3(kThreads), 0, s, store, bstride, ids, n, R, labels, bits_out, bad, S);
+}
 
 void launch_rnd_form(uint4 *rnd, const uint4 *R, uint32_t S, uint32_t n1, hipStream_t s) {
     const size_t n = (size_t)S * n1;

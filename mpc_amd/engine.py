@@ -20,6 +20,7 @@ HEADER = os.path.join(os.path.dirname(HERE), "include", "gcengine.h")
 ABI_VERSION = 2  # GC_ABI_VERSION of include/gcengine.h
 GC_OK, GC_E_KEYSIZE, GC_E_RAND, GC_E_GATE, GC_E_ROWS, GC_E_ARG, GC_E_HIP, GC_E_NOMEM, GC_E_WIRE, GC_E_POINT = (
     0, -1, -2, -3, -4, -5, -6, -7, -8, -9)
+GC_E_BUSY = -10  # gc_stream_batch_out_garble: no free window
 
 
 class EngineError(RuntimeError):
@@ -138,6 +139,20 @@ def lib():
         "gc_stream_eval_batch_set_wires": (i32, [vp, vp, u32, vp]),
         "gc_stream_eval_batch_get_wire": (i32, [vp, u32, vp]),
         "gc_stream_eval_batch_circuit": (i32, [vp, u32, u32, u32, vp, sz, vp, sz, vp, C.POINTER(C.c_size_t)]),
+        "gc_stream_batch_select_labels_dev": (i32, [vp, vp, u32, vp, vp]),
+        "gc_stream_batch_decode_dev": (i32, [vp, vp, u32, vp, vp, vp]),
+        "gc_stream_batch_select_labels": (i32, [vp, vp, u32, vp, vp]),
+        "gc_stream_batch_decode": (i32, [vp, vp, u32, vp, vp, vp]),
+        "gc_stream_batch_out_create": (vp, [vp, sz, u32, ip]),
+        "gc_stream_batch_out_free": (None, [vp]),
+        "gc_stream_batch_out_garble": (i32, [vp, vp, sz, vp, u32, u32, vp, u32, vp, u32, C.POINTER(C.c_size_t)]),
+        "gc_stream_batch_out_flush": (i32, [vp]),
+        "gc_stream_batch_out_next": (i32, [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+        "gc_stream_batch_out_release": (i32, [vp]),
+        "gc_stream_batch_out_stats": (i32, [vp] + [C.POINTER(C.c_uint64)] * 4),
+        "gc_stream_eval_batch_circuit_host": (i32, [vp, u32, u32, u32, vp, sz, sz, u32, C.POINTER(C.c_size_t)]),
+        "gc_stream_eval_batch_uploads_wait": (i32, [vp]),
+        "gc_stream_eval_batch_bad": (i32, [vp, vp]),
         "gc_batch_create": (vp, [vp, u32, ip]),
         "gc_batch_free": (None, [vp]),
         "gc_ctx_capture_begin": (i32, [vp]),
@@ -1079,6 +1094,42 @@ class StreamBatch:
         i = np.ascontiguousarray(ids, dtype=np.uint32)
         _check(lib().gc_stream_batch_gather_wires(self.h, _p(i), len(i), _dp(d_wires_out)), "gc_stream_batch_gather_wires")
 
+    def select_labels(self, ids, bits, labels_out=None):
+        """the garbler's own input labels: L0 of wire ids[j], ^ R where the bit is not zero.  bits: a DeviceBuffer u8
+        [S][len(ids)] with labels_out a DeviceBuffer gc_label [S][len(ids)] (gc_stream_batch_select_labels_dev, asynchronous), or
+        a host array, which returns LABEL [S, len(ids)] (gc_stream_batch_select_labels, synchronous)"""
+        i = np.ascontiguousarray(ids, dtype=np.uint32)
+        if isinstance(bits, DeviceBuffer):
+            _check(lib().gc_stream_batch_select_labels_dev(self.h, _p(i), len(i), _dp(bits), _dp(labels_out)),
+                   "gc_stream_batch_select_labels_dev")
+            return labels_out
+        b = np.ascontiguousarray(bits, dtype=np.uint8)
+        if b.shape != (self.sessions, len(i)):
+            raise EngineError(GC_E_ARG, "select_labels: bits must be u8 [sessions, len(ids)]")
+        out = np.zeros((self.sessions, len(i)), LABEL)
+        _check(lib().gc_stream_batch_select_labels(self.h, _p(i), len(i), _p(b), _p(out)), "gc_stream_batch_select_labels")
+        return out
+
+    def decode(self, ids, labels, bits_out=None, d_bad=None):
+        """the result: 0 / 1 / 0xff per label equal to L0 / L1 / neither of wire ids[j], and per session the number of 0xff.
+        labels: a DeviceBuffer gc_label [S][len(ids)] with bits_out (u8 [S][len(ids)]) and d_bad (u32 [S]) DeviceBuffers
+        (gc_stream_batch_decode_dev, asynchronous), or a host LABEL array, which returns (bits [S, len(ids)], bad [S])"""
+        i = np.ascontiguousarray(ids, dtype=np.uint32)
+        if isinstance(labels, DeviceBuffer):
+            _check(lib().gc_stream_batch_decode_dev(self.h, _p(i), len(i), _dp(labels), _dp(bits_out), _dp(d_bad)),
+                   "gc_stream_batch_decode_dev")
+            return bits_out, d_bad
+        lab = np.ascontiguousarray(labels, dtype=LABEL)
+        if lab.shape != (self.sessions, len(i)):
+            raise EngineError(GC_E_ARG, "decode: labels must be LABEL [sessions, len(ids)]")
+        bits, bad = np.zeros((self.sessions, len(i)), np.uint8), np.zeros(self.sessions, np.uint32)
+        _check(lib().gc_stream_batch_decode(self.h, _p(i), len(i), _p(lab), _p(bits), _p(bad)), "gc_stream_batch_decode")
+        return bits, bad
+
+    def out(self, window_bytes, nwindows):
+        """a StreamBatchOut of this handle: windows of stream bytes in pinned host memory; close it before this handle"""
+        return StreamBatchOut(self, window_bytes, nwindows)
+
     def cache_stats(self):
         """the circuit cache (gc_stream_batch_cache_stats): (entries, device bytes, loads, evictions)"""
         v = [C.c_uint64(0) for _ in range(4)]
@@ -1088,6 +1139,63 @@ class StreamBatch:
     def close(self):
         if self.h:
             lib().gc_stream_batch_free(self.h)
+            self.h = None
+
+
+class StreamBatchOut:
+    """gc_stream_batch_out: the steps of a StreamBatch written into a ring of windows [S][cap] whose bytes arrive in pinned
+    host memory while the next window fills.  One thread may garble / flush while one other takes windows and releases them."""
+
+    def __init__(self, sb, window_bytes, nwindows):
+        self.sessions = sb.sessions
+        st = C.c_int(0)
+        self.h = lib().gc_stream_batch_out_create(sb.h, window_bytes, nwindows, C.byref(st))
+        if not self.h:
+            raise EngineError(st.value, "gc_stream_batch_out_create")
+
+    def garble(self, prefix, gates, nwires, in_, out_):
+        """one step behind `prefix` (bytes, at most 64) for every session; returns the bytes written per session.  Raises
+        EngineError with code GC_E_BUSY when no window is free: release one and call again"""
+        g = np.ascontiguousarray(gates, dtype=GATE)
+        i = np.ascontiguousarray(in_, dtype=np.uint32)
+        o = np.ascontiguousarray(out_, dtype=np.uint32)
+        pre = bytes(prefix)
+        pb = np.frombuffer(pre, np.uint8) if pre else np.zeros(1, np.uint8)
+        n = C.c_size_t(0)
+        _check(lib().gc_stream_batch_out_garble(self.h, _p(pb), len(pre), _p(g), len(g), nwires, _p(i), len(i), _p(o), len(o),
+                                                C.byref(n)), "gc_stream_batch_out_garble")
+        return n.value
+
+    def flush(self):
+        _check(lib().gc_stream_batch_out_flush(self.h), "gc_stream_batch_out_flush")
+
+    def next(self):
+        """the oldest sealed window, its copy complete: (address of session 0's bytes, stride, len), or None"""
+        base, stride, n = C.c_void_p(0), C.c_size_t(0), C.c_size_t(0)
+        _check(lib().gc_stream_batch_out_next(self.h, C.byref(base), C.byref(stride), C.byref(n)), "gc_stream_batch_out_next")
+        return (base.value, stride.value, n.value) if n.value else None
+
+    def next_view(self):
+        """next() as a numpy view u8 [S, len] of the pinned window (valid until it is released), or None"""
+        w = self.next()
+        if w is None:
+            return None
+        base, stride, n = w
+        raw = (C.c_uint8 * (self.sessions * stride)).from_address(base)
+        return np.frombuffer(raw, np.uint8).reshape(self.sessions, stride)[:, :n]
+
+    def release(self):
+        _check(lib().gc_stream_batch_out_release(self.h), "gc_stream_batch_out_release")
+
+    def stats(self):
+        """(windows sealed, bytes per session, windows grown, GC_E_BUSY answers)"""
+        v = [C.c_uint64(0) for _ in range(4)]
+        _check(lib().gc_stream_batch_out_stats(self.h, *[C.byref(x) for x in v]), "gc_stream_batch_out_stats")
+        return tuple(int(x.value) for x in v)
+
+    def close(self):
+        if self.h:
+            lib().gc_stream_batch_out_free(self.h)
             self.h = None
 
 
@@ -1120,6 +1228,25 @@ class StreamEvalBatch:
         _check(lib().gc_stream_eval_batch_circuit(self.h, ngates, ntmp, nwires, _p(b), len(ref_block), _dp(d_blocks), stride,
                                                   _dp(d_bad), C.byref(n)), "gc_stream_eval_batch_circuit")
         return n.value
+
+    def circuit_host(self, ngates, ntmp, nwires, blocks, stride, length, ref_session=0):
+        """one OpCircuit block of every session from HOST memory: blocks = the address of session 0's block (an int, e.g. a
+        window's base + offset) or a numpy u8 array, session s's block `stride` bytes further; session ref_session's is the
+        reference block.  Pinned memory must stay unchanged until uploads_wait() / bad() / close(); returns the bytes used"""
+        addr = blocks if isinstance(blocks, int) else blocks.ctypes.data
+        n = C.c_size_t(0)
+        _check(lib().gc_stream_eval_batch_circuit_host(self.h, ngates, ntmp, nwires, C.c_void_p(addr), stride, length, ref_session,
+                                                       C.byref(n)), "gc_stream_eval_batch_circuit_host")
+        return n.value
+
+    def uploads_wait(self):
+        _check(lib().gc_stream_eval_batch_uploads_wait(self.h), "gc_stream_eval_batch_uploads_wait")
+
+    def bad(self):
+        """u32 [S]: differing structure bytes per session over every circuit_host since create (waits)"""
+        out = np.zeros(self.sessions, np.uint32)
+        _check(lib().gc_stream_eval_batch_bad(self.h, _p(out)), "gc_stream_eval_batch_bad")
+        return out
 
     def cache_stats(self):
         """the circuit cache (gc_stream_eval_batch_cache_stats): (entries, device bytes, loads, evictions)"""

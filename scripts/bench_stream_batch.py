@@ -21,7 +21,17 @@ ingester's bytes per second against 8 TB/s.
 --program big130_16: a program of WIDE steps instead — the first 16 steps of bench_stream.py's big130 (131 072 gates per step,
 64 levels of 2 048, four circuits in turn), whose circuits keep their wires in HBM and take the keyed HBM-wire kernels
 (k_garble_hbm_keyed / k_eval_hbm_keyed); the parent refused them.  Its four batches are larger than the default cache of a
-handle together, so the run raises GC_STREAM_BATCH_CACHE_BYTES to 16 GiB unless the caller set it."""
+handle together, so the run raises GC_STREAM_BATCH_CACHE_BYTES to 16 GiB unless the caller set it.
+
+--egress: the way of the garbler's bytes to HOST memory instead, one JSON line per S.  Windows of 1 MiB per
+session; four forms alternate after an untimed pass of each, a window is one whole pass between two gc_ctx_sync:
+  (a) device   today's device-only pass above: the reused buffer, nothing leaves
+  (b) sync     what a host had before gc_stream_batch_out_*: the steps appended in a device window [S][1 MiB], and a synchronous
+               gc_dev_download of the window into pinned memory whenever the next step does not fit
+  (c) windows  gc_stream_batch_out_* with three windows, a 20-byte prefix per step and a consumer thread that only releases
+  copy         (b)'s downloads alone, no garbling: the link
+The criterion: all (c) windows below all (b) windows.  GC_STREAM_BATCH_OUT_WHOLE_ROWS=1 in the environment makes (c) copy whole
+windows in one piece instead of the used columns."""
 import argparse
 import csv
 import ctypes as C
@@ -162,6 +172,137 @@ def measure(ctx, prog, S, reps, sample):
     return row
 
 
+EGRESS_WINDOW = 1 << 20
+EGRESS_WINDOWS = 3
+
+
+class Egress:
+    """forms (b), (c) and the copy alone beside a Batch's form (a), on the Batch's garbler handle"""
+
+    def __init__(self, ctx, prog, b):
+        import threading
+        self.threading = threading
+        self.ctx, self.prog, self.b, self.S = ctx, prog, b, b.S
+        self.cap = EGRESS_WINDOW
+        assert max(prog.sizes) + 20 <= self.cap
+        self.d_win = engine.DeviceBuffer(ctx, shape=self.S * self.cap)
+        self.pin = engine.PinnedArray(self.S * self.cap, np.uint8)
+        self.out = b.sb.out(self.cap, EGRESS_WINDOWS)
+        self.prefix = np.arange(20, dtype=np.uint8)
+        self.n = C.c_size_t(0)
+        # where (b) downloads: before the first step that does not fit behind the ones in the window, and at the end
+        self.cuts, at = [], 0
+        for k, n in enumerate(prog.sizes):
+            if at + n > self.cap:
+                self.cuts.append(k)
+                at = 0
+            at += n
+        self.downloads = len(self.cuts) + 1
+
+    def download(self):
+        rc = engine.lib().gc_dev_download(self.ctx.h, C.c_void_p(self.pin.ptr), C.c_void_p(self.d_win.ptr), self.S * self.cap)
+        if rc:
+            raise engine.EngineError(rc, "gc_dev_download")
+
+    def run_sync(self):
+        L, pn, h = engine.lib(), C.byref(self.n), self.b.sb.h
+        garble, cuts, at = L.gc_stream_batch_garble, set(self.cuts), 0
+        for k, a in enumerate(self.prog.args.begin):
+            if k in cuts:
+                self.download()
+                at = 0
+            rc = garble(h, *a, C.c_void_p(self.d_win.ptr + at), self.cap, pn)
+            if rc:
+                raise engine.EngineError(rc, "gc_stream_batch_garble(step %d)" % k)
+            at += self.n.value
+        self.download()
+
+    def run_copy(self):
+        for _ in range(self.downloads):
+            self.download()
+
+    def run_windows(self):
+        L, pn, h = engine.lib(), C.byref(self.n), self.out.h
+        garble, pre = L.gc_stream_batch_out_garble, self.prefix.ctypes.data_as(C.c_void_p)
+        flushed, taken = self.threading.Event(), [0]
+
+        def consumer():
+            while True:
+                last = flushed.is_set()
+                if self.out.next() is None:
+                    if last:
+                        return
+                    time.sleep(0.0001)
+                    continue
+                taken[0] += 1
+                self.out.release()
+
+        t = self.threading.Thread(target=consumer)
+        t.start()
+        try:
+            for k, a in enumerate(self.prog.args.begin):
+                while True:
+                    rc = garble(h, pre, 20, *a, pn)
+                    if rc != engine.GC_E_BUSY:
+                        break
+                    time.sleep(0.00005)  # (no window is free: let the consumer run)
+                if rc:
+                    raise engine.EngineError(rc, "gc_stream_batch_out_garble(step %d)" % k)
+            self.out.flush()
+        finally:
+            flushed.set()
+            t.join()
+        return taken[0]
+
+    def window(self, run):
+        self.ctx.sync()
+        t0 = time.perf_counter()
+        run()
+        self.ctx.sync()
+        return time.perf_counter() - t0
+
+    def close(self):
+        self.out.close()
+        self.pin.close()
+        self.d_win.close()
+
+
+def egress(ctx, prog, S, reps):
+    ref_stream = np.zeros(prog.bytes, np.uint8)  # (the evaluator is not run here)
+    b = Batch(ctx, prog, S, ref_stream)
+    try:
+        e = Egress(ctx, prog, b)
+    except engine.EngineError as err:
+        b.close()
+        return {"bench": "stream_batch_egress", "program": PROGRAM, "sessions": S, "skipped": "windows not allocated: %s" % err}
+    forms = {"device": lambda: b.run(False), "sync": e.run_sync, "windows": e.run_windows, "copy": e.run_copy}
+    for run in forms.values():
+        e.window(run)
+    sealed0, busy0 = e.out.stats()[0], e.out.stats()[3]
+    t = {k: [] for k in forms}
+    for _ in range(reps):
+        for k, run in forms.items():
+            t[k].append(e.window(run))
+    sealed, _, grown, busy = e.out.stats()
+    med = {k: statistics.median(v) for k, v in t.items()}
+    bound = max(med["device"], med["copy"])
+    moved = (prog.bytes + 20 * len(prog.steps)) * S
+    row = {
+        "bench": "stream_batch_egress", "program": PROGRAM, "sessions": S, "key_bytes": 32, "steps": len(prog.steps),
+        "bytes_per_session": prog.bytes, "window_bytes": e.cap, "windows": EGRESS_WINDOWS, "reps": reps,
+        "whole_rows": bool(os.environ.get("GC_STREAM_BATCH_OUT_WHOLE_ROWS", "0") not in ("", "0")),
+        "device_s": med["device"], "sync_s": med["sync"], "windows_s": med["windows"], "copy_s": med["copy"],
+        "copy_bytes_per_s": e.downloads * S * e.cap / med["copy"], "windows_stream_bytes_per_s": moved / med["windows"],
+        "windows_below_sync_in_all_rounds": max(t["windows"]) < min(t["sync"]),
+        "windows_over_max_device_copy": med["windows"] / bound, "sync_over_device_plus_copy": med["sync"] / (med["device"] + med["copy"]),
+        "pinned_bytes_of_the_handle": EGRESS_WINDOWS * S * e.cap, "windows_sealed_per_pass": (sealed - sealed0) / reps,
+        "sync_downloads_per_pass": e.downloads, "grown": grown, "busy_answers_per_pass": (busy - busy0) / reps, "seconds_all": t,
+    }
+    e.close()
+    b.close()
+    return row
+
+
 def once(ctx, prog, S):
     """one garble+eval pass and nothing else timed: the run a kernel trace is taken of"""
     _, _, ref_stream, _ = one_session(ctx, prog, bytes(range(32)), bs.stream_rnd(PROGRAM, len(prog.prim)), evaluate=False)
@@ -202,6 +343,8 @@ def main():
     ap.add_argument("--once", type=int, default=None, help="one garble+eval pass at this many sessions (for a kernel trace)")
     ap.add_argument("--kernel-stats", default=None, help="kernel-stats csv of a traced --once run: print its split (with --sessions S)")
     ap.add_argument("--out", default=None, help="also append the lines to this file")
+    ap.add_argument("--egress", action="store_true", help="the garbler's bytes to host memory: device-only, synchronous download, "
+                                                          "gc_stream_batch_out_* windows, the copy alone")
     ap.add_argument("--program", default=PROGRAM, choices=sorted(PROGRAMS), help="big130_16: wide steps, wires in HBM")
     a = ap.parse_args()
     PROGRAM = a.program
@@ -222,6 +365,9 @@ def main():
     ctx = engine.Context(0)
     if a.once:
         once(ctx, prog, a.once)
+    elif a.egress:
+        for S in a.sessions:
+            emit(egress(ctx, prog, S, a.reps))
     else:
         for S in a.sessions:
             emit(measure(ctx, prog, S, a.reps, a.sample))
