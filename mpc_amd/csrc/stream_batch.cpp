@@ -18,6 +18,7 @@
 #include "engine.h"
 #include "stream_batch.h"
 #include "stream_batch_windows.h"
+#include "stream_wire.h"
 
 namespace gcs {
 uint32_t stream_max_wires();  // stream_eval.cpp (GC_STREAM_MAX_WIRES)
@@ -51,37 +52,16 @@ inline size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
 // in their 16- or 32-bit form, and 16 zero bytes per table row.  bytes / row_off may be null (the size alone).
 size_t step_skeleton(const gc_gate *gates, uint32_t ngates, uint32_t nwires, const uint32_t *in, uint32_t nin, const uint32_t *out,
                      uint32_t nout, std::vector<uint8_t> *bytes, std::vector<uint32_t> *row_off) {
-    const uint32_t first_tmp = nin, first_out = nwires - nout;
     size_t pos = 0;
     for (uint32_t g = 0; g < ngates; g++) {
         const gc_gate &q = gates[g];
-        uint32_t flags = q.op;
-        auto get = [&](uint32_t w, uint32_t bit) -> uint32_t {  // Get / Set through in[] first (:131-157), else a tmp wire
-            if (w < first_tmp) return in[w];
-            if (w >= first_out) return out[w - first_out];
-            flags |= bit;
-            return w;
-        };
-        const uint32_t bi = q.op != GC_INV ? get(q.in1, 0x40) : 0;
-        const uint32_t ai = get(q.in0, 0x80), ci = get(q.out, 0x20);
-        const bool shortf = ai <= 0xffff && bi <= 0xffff && ci <= 0xffff;
-        const uint32_t wc = q.op == GC_INV ? 2 : 3;
-        const uint32_t rows = q.op == GC_AND ? 2 : q.op == GC_OR ? 3 : q.op == GC_INV ? 1 : 0;
-        const size_t size = 1 + (shortf ? 2u : 4u) * wc + 16u * rows;
+        const gcw::GateForm f = gcw::gate_form(q.op, q.in0, q.in1, q.out, nin, nwires - nout, in, out);
         if (bytes) {
-            bytes->resize(pos + size, 0);
-            uint8_t *p = bytes->data() + pos;
-            *p++ = (uint8_t)(flags | (shortf ? 0x10 : 0));
-            auto put = [&](uint32_t v) {
-                if (!shortf) *p++ = (uint8_t)(v >> 24), *p++ = (uint8_t)(v >> 16);
-                *p++ = (uint8_t)(v >> 8), *p++ = (uint8_t)v;
-            };
-            put(ai);
-            if (wc == 3) put(bi);
-            put(ci);
-            for (uint32_t r = 0; r < rows; r++) row_off->push_back((uint32_t)(pos + size - 16u * (rows - r)));
+            bytes->resize(pos + f.size, 0);
+            const size_t row0 = (size_t)(gcw::put_gate_head(bytes->data() + pos, f) - bytes->data());
+            for (uint32_t r = 0; r < f.rows; r++) row_off->push_back((uint32_t)(row0 + 16u * r));
         }
-        pos += size;
+        pos += f.size;
     }
     return pos;
 }
@@ -285,9 +265,10 @@ struct StepBlob {
     }
 };
 
-// fills the stage, sends it, and describes it to the kernels
-int send_step(SbCore &c, const StepBlob &b, const uint32_t *in, uint32_t nin, const uint32_t *out, uint32_t nout,
+// lays the blob out (b), fills the stage, sends it, and describes it to the kernels
+int send_step(SbCore &c, StepBlob &b, const uint32_t *in, uint32_t nin, const uint32_t *out, uint32_t nout,
               const std::vector<uint32_t> &row_off, const uint8_t *skel, size_t nbytes, SbStage **stp, gcsb::StepDev *dev) {
+    b.plan(nin, nout, row_off.size(), nbytes);
     SbStage *st = nullptr;
     int rc = c.stage(b.total, &st);
     if (rc != GC_OK) return rc;
@@ -314,6 +295,13 @@ int send_step(SbCore &c, const StepBlob &b, const uint32_t *in, uint32_t nin, co
 int step_sent(SbCore &c, SbStage *st) {
     GC_HIP(hipEventRecord(st->done, c.ctx->stream));
     return GC_OK;
+}
+// behind the one launch of a call that sent only ids (io_ids): the launch's error, and the stage's event whatever it was
+int ids_launched(SbCore &c, SbStage *st) {
+    const hipError_t e = hipGetLastError();
+    const int rc = step_sent(c, st);
+    GC_HIP(e);
+    return rc;
 }
 
 // out[] with all but the LAST of equal ids marked "not stored" (Set in order: the last one wins)
@@ -346,9 +334,9 @@ struct gc_stream_batch : SbCore {
 struct gc_stream_eval_batch : SbCore {
     std::vector<gc_gate> gates;
     std::vector<uint8_t> skel;
-    std::vector<uint32_t> row_off, in_ids, out_ids;
-    std::vector<uint64_t> last_t, last_w;  // who wrote (tmp / global) wire last: generation << 32 | id
-    uint32_t gen = 0;
+    std::vector<uint32_t> row_off, out_ids;
+    gcw::WireStamps stamps;  // who wrote a (tmp / global) wire last
+    gcw::BlockIo io;         // the block's inputs (io.inputs: the in[] of its step) and global writers
     // ---- gc_stream_eval_batch_circuit_host: blocks from host memory (all lazily made)
     struct BlockBuf {  // one device block buffer [S][pitch] and the pinned staging for pageable callers
         uint8_t *dev = nullptr, *pin = nullptr;
@@ -483,7 +471,6 @@ int garble_step(gc_stream_batch *s, const gc_gate *gates, uint32_t ngates, uint3
         if (rc != GC_OK) return rc;
     }
     StepBlob b;
-    b.plan(nin, nout, s->row_off.size(), nbytes);
     SbStage *st = nullptr;
     gcsb::StepDev dev{};
     rc = send_step(*s, b, in, nin, s->out_marked.data(), nout, s->row_off, s->skel.data(), nbytes, &st, &dev);
@@ -508,96 +495,32 @@ int garble_step(gc_stream_batch *s, const gc_gate *gates, uint32_t ngates, uint3
     return rc != GC_OK ? rc : rce;
 }
 
-// One OpCircuit block as the peer sent it, parsed into a single-assignment gate list — the gate loop of stream_eval.cpp's
-// eval_block (stream_evaluator.go:272-345) with the same refusals, restated for a handle without that stream's skeleton
-// and queue state.  Wire ids of the device circuit: [0, nin) the global wires read before the block writes them, in order
-// of first use; then one id per gate, first the gates that write a tmp wire, last the gates that write a global wire: those
-// are the outputs.  skel = the block's bytes with its rows zeroed.
+// One OpCircuit block as the peer sent it, parsed into a single-assignment gate list: gcw::walk_block (stream_wire.h — the
+// gate loop and the refusals of stream_eval.cpp's evaluator) with a sink that keeps the gates and where the rows are.
+// e->gates / io.inputs / out_ids: the device circuit and the global wires it reads and stores (kNone: a later gate of the
+// block writes the same wire); skel = the block's bytes with its rows zeroed.
+struct BatchSink {
+    std::vector<gcw::ParsedGate> gates;
+    std::vector<uint32_t> &row_off;
+    uint32_t global_field(size_t, bool) { return 0; }
+    void gate(uint32_t g, uint32_t in0, uint32_t in1, uint32_t op, bool writes_tmp) { gates[g] = gcw::ParsedGate{in0, in1, op, writes_tmp}; }
+    void rows(size_t at, uint32_t n) {
+        for (uint32_t r = 0; r < n; r++) row_off.push_back((uint32_t)(at + 16u * r));
+    }
+};
 int parse_block(gc_stream_eval_batch *e, uint32_t ngates, uint32_t ntmp, uint32_t nwires, const uint8_t *buf, size_t len, size_t *used) {
-    if (e->last_t.size() < ntmp) e->last_t.resize(ntmp, 0);
-    if (++e->gen == 0) {
-        std::fill(e->last_t.begin(), e->last_t.end(), 0);
-        std::fill(e->last_w.begin(), e->last_w.end(), 0);
-        e->gen = 1;
-    }
-    const uint64_t gen = e->gen;
-    struct Parsed {
-        uint32_t in0, in1, op;
-        bool tmp;
-    };
-    std::vector<Parsed> ps(ngates);
-    std::vector<std::pair<uint32_t, uint32_t>> glob;  // (gate, global wire) of the gates that write a global wire
-    e->in_ids.clear(), e->row_off.clear();
-    static const uint8_t kRowsOf[5] = {0, 0, 2, 3, 1}, kWiresOf[5] = {3, 3, 3, 3, 2};
-    auto touch_w = [&](uint32_t idx) {
-        if (idx >= e->last_w.size()) e->last_w.resize((size_t)idx + 1 + e->last_w.size() / 2, 0);
-    };
+    e->row_off.clear();
+    BatchSink sink{std::vector<gcw::ParsedGate>(ngates), e->row_off};
     size_t pos = 0;
-    for (uint32_t g = 0; g < ngates; g++) {
-        if (pos + 1 > len) return GC_E_ROWS;
-        uint8_t gop = buf[pos++];
-        const bool at = gop & 0x80, bt = gop & 0x40, ct = gop & 0x20, shortf = gop & 0x10;
-        gop &= 0x0f;
-        if (gop > GC_INV) return GC_E_GATE;  // "invalid operation"
-        const int nw = kWiresOf[gop];
-        const uint32_t rows = kRowsOf[gop], idsz = shortf ? 2u : 4u;
-        if (pos + (size_t)idsz * nw + 16 * (size_t)rows > len) return GC_E_ROWS;
-        uint32_t w[3] = {0, 0, 0};
-        for (int i = 0; i < nw; i++, pos += idsz)
-            w[i] = shortf ? ((uint32_t)buf[pos] << 8) | buf[pos + 1]
-                          : ((uint32_t)buf[pos] << 24) | ((uint32_t)buf[pos + 1] << 16) | ((uint32_t)buf[pos + 2] << 8) | buf[pos + 3];
-        int err = GC_OK;
-        auto use = [&](bool t, uint32_t idx) -> uint32_t {  // current id of a wire; bit 31: a circuit input
-            if (t) {
-                if (idx >= ntmp || (e->last_t[idx] >> 32) != gen) {  // tmp wires are private to their block
-                    err = GC_E_ARG;
-                    return 0;
-                }
-                return (uint32_t)e->last_t[idx];
-            }
-            if (idx >= nwires) {
-                err = GC_E_ARG;
-                return 0;
-            }
-            touch_w(idx);
-            if ((e->last_w[idx] >> 32) == gen) return (uint32_t)e->last_w[idx];
-            const uint32_t id = 0x80000000u | (uint32_t)e->in_ids.size();
-            e->in_ids.push_back(idx);
-            e->last_w[idx] = (gen << 32) | id;
-            return id;
-        };
-        Parsed &k = ps[g];
-        k.in0 = use(at, w[0]);
-        k.in1 = nw == 3 ? use(bt, w[1]) : k.in0;
-        if (err != GC_OK) return err;
-        k.op = gop, k.tmp = ct;
-        const uint32_t ci = w[nw - 1];
-        if (ct) {
-            if (ci >= ntmp) return GC_E_ARG;
-            e->last_t[ci] = (gen << 32) | g;
-        } else {
-            if (ci >= nwires) return GC_E_ARG;
-            touch_w(ci);
-            e->last_w[ci] = (gen << 32) | g;
-            glob.emplace_back(g, ci);
-        }
-        for (uint32_t r = 0; r < rows; r++, pos += 16) e->row_off.push_back((uint32_t)pos);
-    }
-    const uint32_t nin = (uint32_t)e->in_ids.size(), nout = (uint32_t)glob.size(), n_tmp = ngates - nout;
-    std::vector<uint32_t> id_of(ngates);
-    uint32_t kt = 0, kg = 0;
-    for (uint32_t g = 0; g < ngates; g++) id_of[g] = ps[g].tmp ? nin + kt++ : nin + n_tmp + kg++;
-    auto fix = [&](uint32_t v) { return (v & 0x80000000u) ? (v & 0x7fffffffu) : id_of[v]; };
-    e->gates.assign(ngates, gc_gate{});
-    for (uint32_t g = 0; g < ngates; g++) {
-        e->gates[g].in0 = fix(ps[g].in0);
-        e->gates[g].in1 = ps[g].op == GC_INV ? 0 : fix(ps[g].in1);
-        e->gates[g].out = id_of[g];
-        e->gates[g].op = (uint8_t)ps[g].op;
-    }
-    // only the LAST gate of the block that writes a global wire stores it (streaming.Set in gate order)
+    const int rc = gcw::walk_block(buf, len, ngates, ntmp, nwires, e->stamps, e->io, sink, &pos);
+    if (rc != GC_OK) return rc;
+    const uint32_t nout = (uint32_t)e->io.writers.size();
+    std::vector<uint32_t> id_of;
+    gcw::ssa_gate_list(sink.gates, (uint32_t)e->io.inputs.size(), nout, [](const gcw::ParsedGate &g) { return g.writes_tmp; }, &id_of, &e->gates);
+    std::vector<uint8_t> live;
+    gcw::live_outputs(e->stamps, e->io, &live);
     e->out_ids.resize(nout);
-    for (uint32_t k = 0; k < nout; k++) e->out_ids[k] = (uint32_t)e->last_w[glob[k].second] == glob[k].first ? glob[k].second : kNone;
+    for (uint32_t k = 0; k < nout; k++) e->out_ids[k] = live[k] ? (uint32_t)e->io.writers[k] : kNone;
     e->skel.assign(buf, buf + pos);
     for (uint32_t off : e->row_off) std::memset(e->skel.data() + off, 0, 16);
     *used = pos;
@@ -626,12 +549,12 @@ int eval_step(gc_stream_eval_batch *e, uint32_t ngates, uint32_t ntmp, uint32_t 
     if (rc != GC_OK) return rc;
     if (pos >= 0x7fffffffu) return refuse(what, "a block of 2 GiB or more");
     if (!supply && (!d_blocks || stride % 4 != 0 || stride < len)) return refuse(what, "stride must be a multiple of 4 and >= len");
-    const uint32_t nin = (uint32_t)e->in_ids.size(), nout = (uint32_t)e->out_ids.size();
+    const uint32_t nin = (uint32_t)e->io.inputs.size(), nout = (uint32_t)e->out_ids.size();
     SbCirc *ent = nullptr;
     rc = e->find_or_load(e->gates.data(), ngates, nin + ngates, nin, nout, what, &ent);
     if (rc != GC_OK) return rc;
     uint32_t mx = 0;
-    for (uint32_t id : e->in_ids) mx = std::max(mx, id);
+    for (uint32_t id : e->io.inputs) mx = std::max(mx, id);
     for (uint32_t id : e->out_ids) mx = std::max(mx, id == kNone ? 0u : id);
     rc = e->ensure(mx);
     if (rc != GC_OK) return rc;
@@ -640,10 +563,9 @@ int eval_step(gc_stream_eval_batch *e, uint32_t ngates, uint32_t ntmp, uint32_t 
         if (rc != GC_OK) return rc;
     }
     StepBlob b;
-    b.plan(nin, nout, e->row_off.size(), pos);
     SbStage *st = nullptr;
     gcsb::StepDev dev{};
-    rc = send_step(*e, b, e->in_ids.data(), nin, e->out_ids.data(), nout, e->row_off, e->skel.data(), pos, &st, &dev);
+    rc = send_step(*e, b, e->io.inputs.data(), nin, e->out_ids.data(), nout, e->row_off, e->skel.data(), pos, &st, &dev);
     if (rc != GC_OK) return rc;
     const uint32_t *d_in = (const uint32_t *)(st->dev + b.o_in), *d_outi = (const uint32_t *)(st->dev + b.o_out);
     gc_batch *bt = ent->batch;
@@ -688,6 +610,24 @@ int read_column(SbCore &c, uint32_t w, std::vector<gc_label> *col) {
                               c.ctx->stream));
     GC_HIP(hipStreamSynchronize(c.ctx->stream));
     return GC_OK;
+}
+
+// the ids of a select / decode / gather / set call: checked, the store grown to hold them (a wire never set reads as 0: its
+// labels are 0 and R), and sent through the staging ring — `send` in their place, if given (set: all but the last of equal ids)
+int io_ids(SbCore &c, const char *what, bool refuse_capture, const uint32_t *ids, uint32_t n, SbStage **st, const uint32_t **d_ids,
+           const uint32_t *send = nullptr) {
+    if (refuse_capture && c.ctx->capturing) return GC_E_ARG;
+    uint32_t mx = 0;
+    for (uint32_t i = 0; i < n; i++) mx = std::max(mx, ids[i]);
+    if (mx >= gcs::stream_max_wires()) return refuse(what, "a wire id >= GC_STREAM_MAX_WIRES");
+    GC_HIP(hipSetDevice(c.ctx->device));
+    int rc = c.ensure(mx);
+    if (rc != GC_OK) return rc;
+    StepBlob b;
+    gcsb::StepDev dev{};
+    rc = send_step(c, b, send ? send : ids, n, nullptr, 0, {}, nullptr, 0, st, &dev);
+    if (rc == GC_OK) *d_ids = (const uint32_t *)((*st)->dev + b.o_in);
+    return rc;
 }
 
 }  // namespace
@@ -766,24 +706,13 @@ int gc_stream_batch_get_wire(gc_stream_batch *s, uint32_t w, gc_wire *out) try {
 int gc_stream_batch_gather_wires(gc_stream_batch *s, const uint32_t *ids, uint32_t n, void *d_wires_out) try {
     if (!s || (n && (!ids || !d_wires_out))) return GC_E_ARG;
     if (n == 0) return GC_OK;
-    uint32_t mx = 0;
-    for (uint32_t i = 0; i < n; i++) mx = std::max(mx, ids[i]);
-    if (mx >= gcs::stream_max_wires()) return refuse("gc_stream_batch_gather_wires", "a wire id >= GC_STREAM_MAX_WIRES");
-    GC_HIP(hipSetDevice(s->ctx->device));
-    int rc = s->ensure(mx);  // (a wire never set reads as (0, R))
-    if (rc != GC_OK) return rc;
-    StepBlob b;
-    b.plan(n, 0, 0, 0);
     SbStage *st = nullptr;
-    gcsb::StepDev dev{};
-    rc = send_step(*s, b, ids, n, nullptr, 0, {}, nullptr, 0, &st, &dev);
+    const uint32_t *d_ids = nullptr;
+    int rc = io_ids(*s, "gc_stream_batch_gather_wires", false, ids, n, &st, &d_ids);  // (a wire never set reads as (0, R))
     if (rc != GC_OK) return rc;
-    launch_gather(s->d_store, s->store_layout(), 0, (const uint32_t *)(st->dev + b.o_in), 0, n, s->d_R, 1, (uint4 *)d_wires_out,
+    launch_gather(s->d_store, s->store_layout(), 0, d_ids, 0, n, s->d_R, 1, (uint4 *)d_wires_out,
                   2 * (size_t)n, s->S, s->ctx->stream);
-    const hipError_t e = hipGetLastError();
-    rc = step_sent(*s, st);
-    GC_HIP(e);
-    return rc;
+    return ids_launched(*s, st);
 } catch (...) {
     return gc::on_exception();
 }
@@ -811,26 +740,15 @@ void gc_stream_eval_batch_free(gc_stream_eval_batch *e) { delete e; }
 int gc_stream_eval_batch_set_wires(gc_stream_eval_batch *e, const uint32_t *ids, uint32_t n, const void *d_labels) try {
     if (!e || (n && (!ids || !d_labels))) return GC_E_ARG;
     if (n == 0) return GC_OK;
-    uint32_t mx = 0;
-    for (uint32_t i = 0; i < n; i++) mx = std::max(mx, ids[i]);
-    if (mx >= gcs::stream_max_wires()) return refuse("gc_stream_eval_batch_set_wires", "a wire id >= GC_STREAM_MAX_WIRES");
-    GC_HIP(hipSetDevice(e->ctx->device));
-    int rc = e->ensure(mx);
-    if (rc != GC_OK) return rc;
     std::vector<uint32_t> marked;
     last_wins(ids, n, &marked);
-    StepBlob b;
-    b.plan(n, 0, 0, 0);
     SbStage *st = nullptr;
-    gcsb::StepDev dev{};
-    rc = send_step(*e, b, marked.data(), n, nullptr, 0, {}, nullptr, 0, &st, &dev);
+    const uint32_t *d_ids = nullptr;
+    int rc = io_ids(*e, "gc_stream_eval_batch_set_wires", false, ids, n, &st, &d_ids, marked.data());
     if (rc != GC_OK) return rc;
-    launch_scatter((const uint4 *)d_labels, n, n, (const uint32_t *)(st->dev + b.o_in), 0, e->d_store, e->store_layout(), 0, e->S,
+    launch_scatter((const uint4 *)d_labels, n, n, d_ids, 0, e->d_store, e->store_layout(), 0, e->S,
                    e->ctx->stream);
-    const hipError_t err = hipGetLastError();
-    rc = step_sent(*e, st);
-    GC_HIP(err);
-    return rc;
+    return ids_launched(*e, st);
 } catch (...) {
     return gc::on_exception();
 }
@@ -925,35 +843,15 @@ struct gc_stream_batch_out {
 
 namespace {
 
-// the ids of a select / decode call: checked, the store grown to hold them, and sent through the staging ring
-int io_ids(gc_stream_batch *s, const char *what, const uint32_t *ids, uint32_t n, SbStage **st, const uint32_t **d_ids) {
-    if (s->ctx->capturing) return GC_E_ARG;
-    uint32_t mx = 0;
-    for (uint32_t i = 0; i < n; i++) mx = std::max(mx, ids[i]);
-    if (mx >= gcs::stream_max_wires()) return refuse(what, "a wire id >= GC_STREAM_MAX_WIRES");
-    GC_HIP(hipSetDevice(s->ctx->device));
-    int rc = s->ensure(mx);  // (a wire never set reads as 0: its labels are 0 and R)
-    if (rc != GC_OK) return rc;
-    StepBlob b;
-    b.plan(n, 0, 0, 0);
-    gcsb::StepDev dev{};
-    rc = send_step(*s, b, ids, n, nullptr, 0, {}, nullptr, 0, st, &dev);
-    if (rc == GC_OK) *d_ids = (const uint32_t *)((*st)->dev + b.o_in);
-    return rc;
-}
-
 int select_dev(gc_stream_batch *s, const uint32_t *ids, uint32_t n, const void *d_bits, void *d_labels_out) {
     if (!s || (n && (!ids || !d_bits || !d_labels_out))) return GC_E_ARG;
     if (n == 0) return GC_OK;
     SbStage *st = nullptr;
     const uint32_t *d_ids = nullptr;
-    int rc = io_ids(s, "gc_stream_batch_select_labels_dev", ids, n, &st, &d_ids);
+    int rc = io_ids(*s, "gc_stream_batch_select_labels_dev", true, ids, n, &st, &d_ids);
     if (rc != GC_OK) return rc;
     gcsb::launch_select(s->d_store, s->bstride, d_ids, n, s->d_R, (const uint8_t *)d_bits, (uint4 *)d_labels_out, s->S, s->ctx->stream);
-    const hipError_t e = hipGetLastError();
-    rc = step_sent(*s, st);
-    GC_HIP(e);
-    return rc;
+    return ids_launched(*s, st);
 }
 
 int decode_dev(gc_stream_batch *s, const uint32_t *ids, uint32_t n, const void *d_labels, void *d_bits_out, void *d_bad) {
@@ -964,14 +862,11 @@ int decode_dev(gc_stream_batch *s, const uint32_t *ids, uint32_t n, const void *
     if (n == 0) return GC_OK;
     SbStage *st = nullptr;
     const uint32_t *d_ids = nullptr;
-    int rc = io_ids(s, "gc_stream_batch_decode_dev", ids, n, &st, &d_ids);
+    int rc = io_ids(*s, "gc_stream_batch_decode_dev", true, ids, n, &st, &d_ids);
     if (rc != GC_OK) return rc;
     gcsb::launch_decode_labels(s->d_store, s->bstride, d_ids, n, s->d_R, (const uint4 *)d_labels, (uint8_t *)d_bits_out,
                                (uint32_t *)d_bad, s->S, s->ctx->stream);
-    const hipError_t e = hipGetLastError();
-    rc = step_sent(*s, st);
-    GC_HIP(e);
-    return rc;
+    return ids_launched(*s, st);
 }
 
 int out_garble(gc_stream_batch_out *h, const uint8_t *prefix, size_t prefix_len, const gc_gate *gates, uint32_t ngates,

@@ -175,23 +175,38 @@ uint32_t stream_max_wires() {
     return v;
 }
 
-bool eval_adopt_ids(gc_stream_eval *e, const EvalSkel &sk, const uint32_t *ids, uint32_t nwires) {
-    if (++e->gen == 0) {
-        std::fill(e->last_t.begin(), e->last_t.end(), 0);
-        std::fill(e->last_w.begin(), e->last_w.end(), 0);
-        e->gen = 1;
+// the global id fields gf_off (byte offset | 1 << 31 for the 4-byte form) of the block at buf
+static void read_global_ids(const uint8_t *buf, const std::vector<uint32_t> &gf_off, std::vector<uint32_t> *ids) {
+    ids->resize(gf_off.size());
+    for (size_t f = 0; f < gf_off.size(); f++) {
+        const uint8_t *q = buf + (gf_off[f] & 0x7fffffffu);
+        (*ids)[f] = (gf_off[f] >> 31) ? ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3]
+                                      : ((uint32_t)q[0] << 8) | q[1];
     }
-    const uint64_t stamp = (uint64_t)e->gen << 32;
-    const uint32_t nf = (uint32_t)sk.gf_off.size();
+}
+
+// repeat pattern of a block's global ids: per field, the index of the first field naming the same wire (stamps in last_w
+// under a generation of their own).  false: an id >= nwires, or a pattern other than expect[] (if given)
+static bool canon_of(gc_stream_eval *e, const uint32_t *ids, uint32_t nf, uint32_t nwires, const uint32_t *expect,
+                     std::vector<uint32_t> *canon) {
+    gcw::WireStamps &st = e->stamps;
+    const uint64_t gen = st.next_gen(), stamp = gen << 32;
+    if (canon) canon->resize(nf);
     for (uint32_t f = 0; f < nf; f++) {
         const uint32_t id = ids[f];
         if (id >= nwires) return false;
-        if (id >= e->last_w.size()) e->last_w.resize((size_t)id + 1 + e->last_w.size() / 2, 0);
+        st.touch_w(id);
         uint32_t first = f;
-        if ((e->last_w[id] >> 32) == e->gen) first = (uint32_t)e->last_w[id];
-        else e->last_w[id] = stamp | f;
-        if (sk.gf_canon[f] != first) return false;
+        if ((st.last_w[id] >> 32) == gen) first = (uint32_t)st.last_w[id];
+        else st.last_w[id] = stamp | f;
+        if (expect && expect[f] != first) return false;
+        if (canon) (*canon)[f] = first;
     }
+    return true;
+}
+
+bool eval_adopt_ids(gc_stream_eval *e, const EvalSkel &sk, const uint32_t *ids, uint32_t nwires) {
+    if (!canon_of(e, ids, (uint32_t)sk.gf_off.size(), nwires, sk.gf_canon.data(), nullptr)) return false;
     const uint32_t nin = sk.nin, nout = sk.nout;
     e->io_host.resize((size_t)nin + nout + 1);
     for (uint32_t k = 0; k < nin; k++) e->io_host[k] = ids[sk.in_gf[k]];
@@ -203,7 +218,6 @@ bool eval_adopt_ids(gc_stream_eval *e, const EvalSkel &sk, const uint32_t *ids, 
     return true;
 }
 
-// One OpCircuit block (gc_stream_eval_circuit; block after block in gc_stream_eval_blocks)
 // the row buffer of the block being taken in: a small block (candidate for a step group) parses its rows into plain host
 // scratch — they are copied into the group's pinned upload region when the block is queued —, a big block uses the next entry
 // of the pinned ring
@@ -457,9 +471,10 @@ int eval_schedule(gc_stream_eval *e, const BlockIn &in, size_t *consumed) {
     return eval_big_block(e, in, tr, consumed);
 }
 
-int eval_block(gc_stream_eval *e, uint32_t ngates, uint32_t ntmp, uint32_t nwires, const uint8_t *buf, size_t len,
-               size_t *consumed) {
-    *consumed = 0;
+namespace {
+
+// the sizes of a block's header, and the store grown to the block's numWires
+int check_block_header(gc_stream_eval *e, uint32_t ngates, uint32_t ntmp, uint32_t nwires, size_t len) {
     // The block comes from the peer: bound it before anything is sized by it.  A gate is at least 5 bytes (op + two
     // 16-bit ids), so a header that announces more gates than the bytes can hold is a truncated stream; global wire
     // ids must stay below the numWires of the block's own header (the reference indexes its store with them,
@@ -471,216 +486,89 @@ int eval_block(gc_stream_eval *e, uint32_t ngates, uint32_t ntmp, uint32_t nwire
     if ((uint64_t)ntmp > 64ull * ngates + (1u << 20) || nwires > stream_max_wires()) return GC_E_ARG;
     if ((size_t)ngates > len / 5) return GC_E_ROWS;
     e->store.ensure(nwires);  // InitCircuit(numWires, numTmpWires)
-    if (ngates == 0) return GC_OK;
-    StreamTrace tr;
-    // Parse the gate stream (stream_evaluator.go:272-345) into an SSA gate list.  Wire ids of the device circuit:
-    //   [0, nin)            wires read before this circuit writes them, in order of first use
-    //   then one id per gate: first the gates that write a tmp wire, last the gates that write a global wire —
-    //   those are the circuit's outputs and the only labels that come back (streaming.Set, :346-432).
-    // "Who wrote (tmp, idx) last" is an array look-up with a generation stamp (no clearing between circuits).
-    // A tmp wire is private to its OpCircuit block (stream_garble.go:131-157 gives every non-input, non-output
-    // wire of the circuit a tmp id, written by a gate before any gate reads it): a block that reads a tmp it has
-    // not written is rejected instead of evaluated on a stale label.
-    if (e->last_t.size() < ntmp) {
-        e->last_t.resize(ntmp, 0);
+    return GC_OK;
+}
+
+// ---- a block seen before, up to its rows and global ids?  Fills b (circuit, sizes, where the rows are), e->io_host, e->wr_ids.
+bool match_known_skeleton(gc_stream_eval *e, uint32_t ntmp, uint32_t nwires, size_t len, BlockIn *b) {
+    if (!e->use_skels) return false;
+    auto it = e->skels.find(((uint64_t)b->ngates << 32) | ntmp);
+    if (it == e->skels.end()) return false;
+    for (size_t si = 0; si < it->second.size(); si++) {
+        const EvalSkel &sk = *it->second[si];
+        if (sk.nbytes > len) continue;
+        if (!e->pool.match(sk, b->buf, b->small_block ? nullptr : b->slab)) continue;
+        // the skeleton's bookkeeping for a block that equals it byte-wise: the ids at their known offsets, in the skeleton's
+        // repeat pattern?
+        read_global_ids(b->buf, sk.gf_off, &e->gf_ids);
+        if (!eval_adopt_ids(e, sk, e->gf_ids.data(), nwires)) continue;
+        b->ent = sk.ent, b->nin = sk.nin, b->nout = sk.nout;
+        b->nrows = sk.nrows, b->pos = sk.nbytes;
+        // (a small block's rows are copied ONCE, into the upload region of the group it joins — eval_queue_block)
+        if (b->small_block) b->rows_from = &sk;
+        // most recently matched first: the variants of a circuit (which operands have 16-bit ids, which repeat) are
+        // tried in that order and the least recently matched one goes when there are too many
+        if (si) std::rotate(it->second.begin(), it->second.begin() + (long)si, it->second.begin() + (long)si + 1);
+        return true;
     }
-    std::vector<CircKey> &gates = e->keys;
-    bool small_block = false;
-    uint32_t sb = 0;
-    gc_label *slab = nullptr;
-    {
-        int rcb = eval_rows_buffer(e, ngates, &small_block, &sb, &slab);
-        if (rcb != GC_OK) return rcb;
-    }
-    size_t nrows = 0;
-    tr.lap("eval: row buffer free");
-    auto load_be64 = [](const uint8_t *p) {
+    return false;
+}
+
+// What gcw::walk_block (stream_wire.h) tells the evaluator about a block it has not seen: the gates as the cache keys them,
+// their hash, the rows into the slab, and the block's skeleton recorded on the way (e->rec: compare runs, global id fields).
+// (The hooks are forced inline: a first-seen block is parsed on the host's critical path.)
+struct EvalSink {
+    const uint8_t *buf;
+    EvalSkel &rec;
+    std::vector<CircKey> &gates;
+    gc_label *slab;
+    CircuitHash ph;
+    size_t nrows = 0, run_start = 0;
+    static __forceinline__ uint64_t load_be64(const uint8_t *p) {
         uint64_t v;
         std::memcpy(&v, p, 8);
         return __builtin_bswap64(v);
-    };
-    auto field_id = [&](uint32_t f) -> uint32_t {  // global id field (offset | 1 << 31 for the 4-byte form)
-        const uint8_t *q = buf + (f & 0x7fffffffu);
-        return (f >> 31) ? ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3]
-                         : ((uint32_t)q[0] << 8) | q[1];
-    };
-    // repeat pattern of a block's global ids: per field, the index of the first field naming the same wire
-    // (stamps in last_w under a generation of their own)
-    auto canon_of = [&](const std::vector<uint32_t> &gf_off, std::vector<uint32_t> *ids, const uint32_t *expect,
-                        std::vector<uint32_t> *canon) -> bool {
-        if (++e->gen == 0) {
-            std::fill(e->last_t.begin(), e->last_t.end(), 0);
-            std::fill(e->last_w.begin(), e->last_w.end(), 0);
-            e->gen = 1;
-        }
-        const uint64_t stamp = (uint64_t)e->gen << 32;
-        ids->resize(gf_off.size());
-        if (canon) canon->resize(gf_off.size());
-        for (uint32_t f = 0; f < gf_off.size(); f++) {
-            const uint32_t id = field_id(gf_off[f]);
-            if (id >= nwires) return false;
-            if (id >= e->last_w.size()) e->last_w.resize((size_t)id + 1 + e->last_w.size() / 2, 0);
-            uint32_t first = f;
-            if ((e->last_w[id] >> 32) == e->gen) first = (uint32_t)e->last_w[id];
-            else e->last_w[id] = stamp | f;
-            if (expect && expect[f] != first) return false;
-            if (canon) (*canon)[f] = first;
-            (*ids)[f] = id;
-        }
-        return true;
-    };
-    CircEntry *ent = nullptr;
-    const EvalSkel *rows_from = nullptr;  // a matched small block whose rows are still in buf
-    uint32_t nin = 0, nout = 0;
-    size_t pos = 0;
-    std::vector<uint32_t> &gf_ids = e->gf_ids, &wr_ids = e->wr_ids;
-    // ---- a block seen before, up to its rows and global ids?
-    {
-        // the skeleton's bookkeeping for a block that equals it byte-wise: the ids at their known offsets, in the skeleton's
-        // repeat pattern?
-        auto adopt = [&](const EvalSkel &sk) {
-            if (!canon_of(sk.gf_off, &gf_ids, sk.gf_canon.data(), nullptr)) return false;
-            ent = sk.ent;
-            nin = sk.nin, nout = sk.nout;
-            nrows = sk.nrows;
-            pos = sk.nbytes;
-            e->io_host.resize((size_t)nin + nout + 1);
-            for (uint32_t k = 0; k < nin; k++) e->io_host[k] = gf_ids[sk.in_gf[k]];
-            wr_ids.resize(nout);
-            for (uint32_t k = 0; k < nout; k++) {
-                wr_ids[k] = gf_ids[sk.out_gf[k]];
-                e->io_host[nin + k] = sk.out_live[k] ? wr_ids[k] : 0xffffffffu;
-            }
-            // (a small block's rows are copied ONCE, into the upload region of the group it joins — below)
-            if (small_block) rows_from = &sk;
-            return true;
-        };
-        auto it = e->skels.end();
-        if (e->use_skels && (it = e->skels.find(((uint64_t)ngates << 32) | ntmp)) != e->skels.end()) {
-            for (size_t si = 0; si < it->second.size(); si++) {
-                const EvalSkel &sk = *it->second[si];
-                if (sk.nbytes > len) continue;
-                if (!e->pool.match(sk, buf, small_block ? nullptr : slab) || !adopt(sk)) continue;
-                // most recently matched first: the variants of a circuit (which operands have 16-bit ids, which repeat) are
-                // tried in that order and the least recently matched one goes when there are too many
-                if (si) std::rotate(it->second.begin(), it->second.begin() + (long)si, it->second.begin() + (long)si + 1);
-                break;
-            }
-        }
     }
-    if (ent) {
-        e->n_matched++;
-        tr.lap("eval: skeleton match");
-    }
-    if (!ent) {
-    if (++e->gen == 0) {  // stamp wrap-around
-        std::fill(e->last_t.begin(), e->last_t.end(), 0);
-        std::fill(e->last_w.begin(), e->last_w.end(), 0);
-        e->gen = 1;
-    }
-    const uint32_t gen = e->gen;
-    gates.resize(ngates);
-    // The cache is keyed on the block AS PARSED — {in0, in1, writes-a-tmp, op} per gate, operands named by the gate
-    // that wrote them (bit 31: the k-th distinct input) — which fixes the device circuit completely; its wire ids
-    // (inputs, tmp-writing gates, global-writing gates) are only worked out when the cache does not know the block.
-    std::vector<uint64_t> &glob = e->dst_pack;  // (gate << 32 | global wire) of the gates that write a global wire
-    std::vector<uint32_t> &inputs = e->in_idx;  // no per-call allocation: a block has ~10^5 gates
-    glob.clear();
-    inputs.clear();
-    EvalSkel &rec = e->rec;  // the block's skeleton, recorded on the way
-    rec.chunks.clear(), rec.gf_off.clear(), rec.in_gf.clear(), rec.out_gf.clear();
-    size_t run_start = 0;
-    bool rec_ok = len < 0x7fffffffu;
-    auto cut = [&](size_t at, uint32_t skip, uint32_t rows) {  // the compare run ends at `at`: a global id or rows follow
+    __forceinline__ void cut(size_t at, uint32_t skip, uint32_t rows) {  // the compare run ends at `at`: a global id or rows follow
         rec.chunks.push_back(EvalSkel::Chunk{(uint32_t)(at - run_start), (uint16_t)skip, (uint16_t)rows});
         run_start = at + skip + 16u * (size_t)rows;
-    };
-    CircuitHash ph(ngates, 0, 0, 0);
-    static const uint8_t kRowsOf[5] = {0, 0, 2, 3, 1}, kWiresOf[5] = {3, 3, 3, 3, 2};
-    for (uint32_t g = 0; g < ngates; g++) {
-        if (pos + 1 > len) return GC_E_ROWS;
-        uint8_t gop = buf[pos++];
-        const bool at = gop & 0x80, bt = gop & 0x40, ct = gop & 0x20, shortf = gop & 0x10;
-        gop &= 0x0f;
-        if (gop > GC_INV) return GC_E_GATE;  // "invalid operation"
-        const int nw = kWiresOf[gop];
-        const uint32_t rows = kRowsOf[gop];
-        uint32_t w[3] = {0, 0, 0};
-        const size_t idpos = pos;
-        const uint32_t idsz = shortf ? 2u : 4u;
-        if (shortf) {
-            if (pos + 2 * (size_t)nw + 16 * (size_t)rows > len) return GC_E_ROWS;
-            for (int i = 0; i < nw; i++) w[i] = ((uint32_t)buf[pos + 2 * i] << 8) | buf[pos + 2 * i + 1];
-            pos += 2 * (size_t)nw;
-        } else {
-            if (pos + 4 * (size_t)nw + 16 * (size_t)rows > len) return GC_E_ROWS;
-            for (int i = 0; i < nw; i++) {
-                uint32_t v;
-                std::memcpy(&v, buf + pos + 4 * i, 4);
-                w[i] = __builtin_bswap32(v);
-            }
-            pos += 4 * (size_t)nw;
-        }
-        auto global_field = [&](int i) -> uint32_t {  // field i of this gate names a global wire: its field number
-            const size_t o = idpos + (size_t)idsz * i;
-            cut(o, idsz, 0);
-            rec.gf_off.push_back((uint32_t)o | (shortf ? 0u : 0x80000000u));
-            return (uint32_t)rec.gf_off.size() - 1;
-        };
-        int err = GC_OK;
-        auto use = [&](bool t, uint32_t idx, int field) -> uint32_t {  // current id of a wire; bit 31: a circuit input
-            if (t) {
-                if (idx >= ntmp || (e->last_t[idx] >> 32) != gen) {
-                    err = GC_E_ARG;
-                    return 0;
-                }
-                return (uint32_t)e->last_t[idx];
-            }
-            if (idx >= nwires) {
-                err = GC_E_ARG;
-                return 0;
-            }
-            const uint32_t f = global_field(field);
-            if (idx >= e->last_w.size()) e->last_w.resize((size_t)idx + 1 + e->last_w.size() / 2, 0);
-            if ((e->last_w[idx] >> 32) == gen) return (uint32_t)e->last_w[idx];
-            const uint32_t id = 0x80000000u | (uint32_t)inputs.size();
-            inputs.push_back(idx);
-            rec.in_gf.push_back(f);
-            e->last_w[idx] = ((uint64_t)gen << 32) | id;
-            return id;
-        };
-        CircKey &k = gates[g];
-        k.in0 = use(at, w[0], 0);
-        k.in1 = nw == 3 ? use(bt, w[1], 1) : k.in0;
-        if (err != GC_OK) return err;
-        k.op = gop;
-        k.out = ct ? 1u : 0u;
-        ph.mix(g, k);
-        const uint32_t ci = w[nw - 1];
-        if (ct) {
-            if (ci >= ntmp) return GC_E_ARG;
-            e->last_t[ci] = ((uint64_t)gen << 32) | g;
-        } else {
-            if (ci >= nwires) return GC_E_ARG;
-            rec.out_gf.push_back(global_field(nw - 1));
-            if (ci >= e->last_w.size()) e->last_w.resize((size_t)ci + 1 + e->last_w.size() / 2, 0);
-            e->last_w[ci] = ((uint64_t)gen << 32) | g;
-            glob.push_back(((uint64_t)g << 32) | ci);
-        }
-        if (rows) cut(pos, 0, rows);
-        for (uint32_t r = 0; r < rows; r++) {
-            slab[nrows++] = gc_label{load_be64(buf + pos), load_be64(buf + pos + 8)};
-            pos += 16;
-        }
     }
-    cut(pos, 0, 0);
-    tr.lap("eval: parse");
-    nin = (uint32_t)inputs.size(), nout = (uint32_t)glob.size();
-    const uint32_t n_tmp = ngates - nout;
-    const uint32_t cw = nin + ngates;
-    const uint64_t h = ((ph.done() ^ nin) * CircuitHash::kPrime ^ nout) * CircuitHash::kPrime;
-    // device circuit, cached by content
-    ent = cache_find_keys(e->cache, h, gates, cw, nin, nout);
+    __forceinline__ uint32_t global_field(size_t o, bool is_short) {  // the id field at o names a global wire: its field number
+        cut(o, is_short ? 2u : 4u, 0);
+        rec.gf_off.push_back((uint32_t)o | (is_short ? 0u : 0x80000000u));
+        return (uint32_t)rec.gf_off.size() - 1;
+    }
+    __forceinline__ void gate(uint32_t g, uint32_t in0, uint32_t in1, uint32_t op, bool writes_tmp) {
+        gates[g] = CircKey{in0, in1, writes_tmp ? 1u : 0u, op};
+        ph.mix(g, gates[g]);
+    }
+    __forceinline__ void rows(size_t at, uint32_t n) {
+        cut(at, 0, n);
+        for (uint32_t r = 0; r < n; r++, at += 16) slab[nrows++] = gc_label{load_be64(buf + at), load_be64(buf + at + 8)};
+    }
+};
+
+// Parse the gate stream (stream_evaluator.go:272-345): e->keys = the block AS PARSED — {in0, in1, writes-a-tmp, op} per gate,
+// operands named by the gate that wrote them (bit 31: the k-th distinct input) — which fixes the device circuit completely
+// and is what the cache is keyed on (*hash); its wire ids are only worked out when the cache does not know the block
+// (load_or_find_circuit).  e->io: the inputs and the global writers; the rows into b->slab.  The refusals are walk_block's.
+int parse_new_block(gc_stream_eval *e, uint32_t ntmp, uint32_t nwires, size_t len, BlockIn *b, uint64_t *hash) {
+    e->keys.resize(b->ngates);  // (no per-call allocation: a block has ~10^5 gates)
+    e->rec.chunks.clear(), e->rec.gf_off.clear();
+    EvalSink sink{b->buf, e->rec, e->keys, b->slab, CircuitHash(b->ngates, 0, 0, 0)};
+    const int rc = gcw::walk_block(b->buf, len, b->ngates, ntmp, nwires, e->stamps, e->io, sink, &b->pos);
+    if (rc != GC_OK) return rc;
+    sink.cut(b->pos, 0, 0);
+    b->nrows = sink.nrows, b->nin = (uint32_t)e->io.inputs.size(), b->nout = (uint32_t)e->io.writers.size();
+    *hash = ((sink.ph.done() ^ b->nin) * CircuitHash::kPrime ^ b->nout) * CircuitHash::kPrime;
+    return GC_OK;
+}
+
+// the device circuit of the parsed block (e->keys), cached by content
+int load_or_find_circuit(gc_stream_eval *e, BlockIn *b, uint64_t h) {
+    const uint32_t ngates = b->ngates, nin = b->nin, nout = b->nout, cw = nin + ngates;
+    std::vector<CircKey> &gates = e->keys;
+    CircEntry *ent = cache_find_keys(e->cache, h, gates, cw, nin, nout);
     if (!ent) {
         if (e->cache_gates + ngates + 1 > e->cache_budget && !e->cache.empty()) {
             // The cache is bounded (the blocks are the peer's data: a stream of ever new circuits must not grow host and
@@ -710,70 +598,93 @@ int eval_block(gc_stream_eval *e, uint32_t ngates, uint32_t ntmp, uint32_t nwire
         }
         // wire ids of the device circuit: inputs, then the tmp-writing gates, then the global-writing gates
         int st = GC_OK;
-        std::vector<uint32_t> &id_of = e->id_of;
-        id_of.resize(ngates);
-        uint32_t kt = 0, kg = 0;
-        for (uint32_t g = 0; g < ngates; g++) id_of[g] = gates[g].out ? nin + kt++ : nin + n_tmp + kg++;
-        std::vector<gc_gate> &full = e->gates;
-        full.assign(ngates, gc_gate{});
-        auto fix = [&](uint32_t v) { return (v & 0x80000000u) ? (v & 0x7fffffffu) : id_of[v]; };
-        for (uint32_t g = 0; g < ngates; g++) {
-            full[g].in0 = fix(gates[g].in0);
-            full[g].in1 = gates[g].op == GC_INV ? 0 : fix(gates[g].in1);
-            full[g].out = id_of[g];
-            full[g].op = (uint8_t)gates[g].op;
-        }
-        gc_circ *nc = gc_circ_load(e->ctx, full.data(), ngates, cw, nin, nout, &st);
+        gcw::ssa_gate_list(gates, nin, nout, [](const CircKey &k) { return k.out != 0; }, &e->id_of, &e->gates);
+        gc_circ *nc = gc_circ_load(e->ctx, e->gates.data(), ngates, cw, nin, nout, &st);
         if (!nc) return st;
         ent = cache_put_keys(e->cache, h, nc, gates, cw, nin, nout);
         e->cache_gates += ent->cost;
         ent->eval_form = true;  // (chain fusion: `gates` holds the block as parsed; its ctx-wide identity)
         ent->uid = fuse_register(e->ctx, true, h, ent->gates, cw, nin, nout);
     }
-    tr.lap("eval: hash + cache");
-    // Input labels are gathered from, output labels scattered into, the device-resident store: nothing waits for the
-    // GPU, so the parsing of the next block overlaps the evaluation of this one.  Only the LAST gate of the block that
-    // writes a global wire stores it (streaming.Set in gate order, :346-432: the last write wins).
+    b->ent = ent;
+    return GC_OK;
+}
+
+// Input labels are gathered from, output labels scattered into, the device-resident store: nothing waits for the
+// GPU, so the parsing of the next block overlaps the evaluation of this one.  Only the LAST gate of the block that
+// writes a global wire stores it (streaming.Set in gate order, :346-432: the last write wins).  (Reads the stamps of the
+// block's walk: before anything takes a new generation.)
+void bind_parsed_wires(gc_stream_eval *e, const BlockIn &b) {
+    const uint32_t nin = b.nin, nout = b.nout;
     e->io_host.resize((size_t)nin + nout + 1);
-    for (uint32_t i = 0; i < nin; i++) e->io_host[i] = inputs[i];
-    wr_ids.resize(nout);
-    rec.out_live.resize(nout);
+    for (uint32_t i = 0; i < nin; i++) e->io_host[i] = e->io.inputs[i];
+    e->wr_ids.resize(nout);
+    gcw::live_outputs(e->stamps, e->io, &e->rec.out_live);
     for (uint32_t k = 0; k < nout; k++) {
-        const uint32_t g = (uint32_t)(glob[k] >> 32), idx = (uint32_t)glob[k];
-        wr_ids[k] = idx;
-        rec.out_live[k] = (uint32_t)e->last_w[idx] == g;
-        e->io_host[nin + k] = rec.out_live[k] ? idx : 0xffffffffu;
+        const uint32_t idx = e->wr_ids[k] = (uint32_t)e->io.writers[k];
+        e->io_host[nin + k] = e->rec.out_live[k] ? idx : 0xffffffffu;
     }
-    // keep the skeleton: the next block of this circuit is matched byte-wise instead of parsed
-    e->n_parsed++;
+}
+
+// keep the skeleton: the next block of this circuit is matched byte-wise instead of parsed
+void record_skeleton(gc_stream_eval *e, uint32_t ntmp, uint32_t nwires, size_t len, const BlockIn &b) {
     constexpr size_t kSkelCap = (size_t)1 << 30;  // beyond 1 GiB of reference blocks every new circuit is parsed each time
-    if (e->use_skels && rec_ok && e->skel_bytes + 2 * pos <= kSkelCap) {
-        auto &v = e->skels[((uint64_t)ngates << 32) | ntmp];
-        // one circuit serialises differently with the widths of the ids it is bound to (per gate: 16-bit ids if all of the
-        // gate's are <= 0xffff) and with operands that repeat: an adder of a mixed program shows up in a dozen forms
-        if (v.size() >= kSkelVariants) {
-            evdev_drop(e, v.back().get());
-            e->skel_bytes -= std::min(e->skel_bytes, v.back()->held());
-            v.pop_back();
-        }
-        std::unique_ptr<EvalSkel> sk(new EvalSkel);
-        sk->nbytes = pos;
-        sk->key = ((uint64_t)ngates << 32) | ntmp;
-        sk->nrows = (uint32_t)nrows, sk->nin = nin, sk->nout = nout;
-        sk->ent = ent;
-        sk->bytes.assign(buf, buf + pos);
-        sk->build(rec.chunks);
-        sk->gf_off = rec.gf_off;
-        sk->in_gf = rec.in_gf, sk->out_gf = rec.out_gf, sk->out_live = rec.out_live;
-        if (canon_of(sk->gf_off, &gf_ids, nullptr, &sk->gf_canon)) {
-            sk->shape_hash();
-            e->skel_bytes += sk->held();
-            evdev_add(e, sk.get());
-            v.insert(v.begin(), std::move(sk));
-        }
+    if (!e->use_skels || len >= 0x7fffffffu || e->skel_bytes + 2 * b.pos > kSkelCap) return;
+    auto &v = e->skels[((uint64_t)b.ngates << 32) | ntmp];
+    // one circuit serialises differently with the widths of the ids it is bound to (per gate: 16-bit ids if all of the
+    // gate's are <= 0xffff) and with operands that repeat: an adder of a mixed program shows up in a dozen forms
+    if (v.size() >= kSkelVariants) {
+        evdev_drop(e, v.back().get());
+        e->skel_bytes -= std::min(e->skel_bytes, v.back()->held());
+        v.pop_back();
     }
-    }  // parsed
-    return eval_schedule(e, BlockIn{ent, ngates, nin, nout, nrows, pos, small_block, sb, slab, rows_from, buf}, consumed);
+    std::unique_ptr<EvalSkel> sk(new EvalSkel);
+    sk->nbytes = b.pos, sk->key = ((uint64_t)b.ngates << 32) | ntmp;
+    sk->nrows = (uint32_t)b.nrows, sk->nin = b.nin, sk->nout = b.nout, sk->ent = b.ent;
+    sk->bytes.assign(b.buf, b.buf + b.pos);
+    sk->build(e->rec.chunks);
+    sk->gf_off = e->rec.gf_off;
+    sk->in_gf = e->io.in_field, sk->out_gf = e->io.out_field, sk->out_live = e->rec.out_live;
+    read_global_ids(b.buf, sk->gf_off, &e->gf_ids);
+    if (canon_of(e, e->gf_ids.data(), (uint32_t)sk->gf_off.size(), nwires, nullptr, &sk->gf_canon)) {
+        sk->shape_hash();
+        e->skel_bytes += sk->held();
+        evdev_add(e, sk.get());
+        v.insert(v.begin(), std::move(sk));
+    }
+}
+
+}  // namespace
+
+// One OpCircuit block (gc_stream_eval_circuit; block after block in gc_stream_eval_blocks): bounded, then recognised by its
+// byte skeleton or parsed, its circuit found or loaded and its skeleton kept, then scheduled.
+int eval_block(gc_stream_eval *e, uint32_t ngates, uint32_t ntmp, uint32_t nwires, const uint8_t *buf, size_t len,
+               size_t *consumed) {
+    *consumed = 0;
+    int rc = check_block_header(e, ngates, ntmp, nwires, len);
+    if (rc != GC_OK || ngates == 0) return rc;
+    StreamTrace tr;
+    BlockIn b{};
+    b.ngates = ngates, b.buf = buf;
+    rc = eval_rows_buffer(e, ngates, &b.small_block, &b.sb, &b.slab);
+    if (rc != GC_OK) return rc;
+    tr.lap("eval: row buffer free");
+    if (match_known_skeleton(e, ntmp, nwires, len, &b)) {
+        e->n_matched++;
+        tr.lap("eval: skeleton match");
+    } else {
+        uint64_t h = 0;
+        rc = parse_new_block(e, ntmp, nwires, len, &b, &h);
+        if (rc != GC_OK) return rc;
+        tr.lap("eval: parse");
+        rc = load_or_find_circuit(e, &b, h);
+        if (rc != GC_OK) return rc;
+        tr.lap("eval: hash + cache");
+        bind_parsed_wires(e, b);
+        e->n_parsed++;
+        record_skeleton(e, ntmp, nwires, len, b);
+    }
+    return eval_schedule(e, b, consumed);
 }
 
 }  // namespace gcs

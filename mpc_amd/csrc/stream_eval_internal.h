@@ -4,6 +4,7 @@
 
 #include "stream_internal.h"
 #include "stream_skel.h"
+#include "stream_wire.h"
 
 namespace gcs {
 struct EvalDev;  // stream_eval_dev.cpp
@@ -16,13 +17,13 @@ struct gc_stream_eval : StreamCore {  // (the core: what the evaluator shares wi
     std::vector<uint32_t> io_host;  // indices of this block's inputs, then of its global outputs (0xffffffff: superseded)
     uint32_t *d_io = nullptr;
     size_t io_cap = 0;
-    // per-circuit scratch, kept across calls: last writer of every tmp / global wire with a generation stamp
-    std::vector<uint64_t> last_t, last_w;  // per tmp / global wire: generation stamp << 32 | current id (one load per look-up)
-    uint32_t gen = 0;
+    // per-circuit scratch, kept across calls: last writer of every tmp / global wire with a generation stamp (one load per
+    // look-up), the inputs and global writers of the block being parsed
+    gcw::WireStamps stamps;
+    gcw::BlockIo io;
     std::vector<gc_gate> gates;       // only materialised for a circuit the cache does not know
     std::vector<CircKey> keys;        // the block's gates as packed records {in0, in1, out, op}
-    std::vector<uint64_t> dst_pack;   // per gate: destination index | tmp flag << 32 (parser scratch, kept across calls)
-    std::vector<uint32_t> in_idx, id_of;
+    std::vector<uint32_t> id_of;
     // by (ngates, ntmp); a few byte layouts per key, most recently matched first (behind pointers: the order changes often)
     std::unordered_map<uint64_t, std::vector<std::unique_ptr<EvalSkel>>> skels;
     std::vector<uint32_t> gf_ids, wr_ids;   // scratch: the block's global ids by field / the wires it writes

@@ -3,49 +3,17 @@
 // byte for byte, written by the GPU at scanned byte offsets (the per-gate host loop was 4 ms for a 131 072-gate step, ten
 // times the garbling itself).
 #include "stream_internal.h"
+#include "stream_wire.h"
 
 namespace gcs {
 
 namespace {
-struct SerGate {
-    uint32_t ai, bi, ci, size;
-    uint8_t op, wc, rows, shortf;
-};
-__device__ __forceinline__ SerGate ser_gate(const SerArgs &a, uint32_t i) {
-    SerGate g{};
-    const uint32_t op = a.ops[i];
-    const uint32_t w0 = a.gw[3 * i], w1 = a.gw[3 * i + 1], w2 = a.gw[3 * i + 2];
-    uint32_t flags = op;
-    auto get = [&](uint32_t w, uint32_t bit) -> uint32_t {  // Get/Set indirection (:131-157) + the tmp flag
-        if (w < a.first_tmp) return a.in[w];
-        if (w >= a.first_out) return a.out[w - a.first_out];
-        flags |= bit;
-        return w;
-    };
-    g.bi = op != GC_INV ? get(w1, 0x40) : 0;
-    g.ai = get(w0, 0x80);
-    g.ci = get(w2, 0x20);
-    g.wc = op == GC_INV ? 2 : 3;
-    g.rows = op == GC_AND ? 2 : op == GC_OR ? 3 : op == GC_INV ? 1 : 0;
-    g.shortf = g.ai <= 0xffff && g.bi <= 0xffff && g.ci <= 0xffff;
-    g.op = (uint8_t)(flags | (g.shortf ? 0x10 : 0));
-    g.size = 1 + (g.shortf ? 2u : 4u) * g.wc + 16u * g.rows;
-    return g;
+__device__ __forceinline__ gcw::GateForm ser_gate(const SerArgs &a, uint32_t i) {
+    return gcw::gate_form(a.ops[i], a.gw[3 * i], a.gw[3 * i + 1], a.gw[3 * i + 2], a.first_tmp, a.first_out, a.in, a.out);
 }
-// one gate at p: op byte, 2-3 wire ids (BE u16 if all fit, else BE u32), rows as BE(D0)||BE(D1); T = the dense slab
-__device__ __forceinline__ void ser_put(uint8_t *p, const SerGate &q, uint32_t r0, const uint4 *T, const Layout &lt) {
-    *p++ = q.op;
-    auto put = [&](uint32_t v) {
-        if (!q.shortf) {
-            *p++ = (uint8_t)(v >> 24);
-            *p++ = (uint8_t)(v >> 16);
-        }
-        *p++ = (uint8_t)(v >> 8);
-        *p++ = (uint8_t)v;
-    };
-    put(q.ai);
-    if (q.wc == 3) put(q.bi);
-    put(q.ci);
+// one gate at p (stream_wire.h), its rows as BE(D0)||BE(D1); T = the dense slab
+__device__ __forceinline__ void ser_put(uint8_t *p, const gcw::GateForm &q, uint32_t r0, const uint4 *T, const Layout &lt) {
+    p = gcw::put_gate_head(p, q);
     for (uint32_t r = 0; r < q.rows; r++) {
         const uint4 v = T[lt.at(r0 + r, 0)];  // uint4 label: (x, y) = D0 low / high, (z, w) = D1 low / high
         const uint32_t w4[4] = {v.y, v.x, v.w, v.z};
@@ -124,11 +92,11 @@ __global__ __launch_bounds__(kSerThreads) void k_ser_write(SerArgs a, const uint
                                                            uint8_t *buf) {
     __shared__ uint32_t wsum[kSerThreads / 64];
     __shared__ __attribute__((aligned(16))) uint8_t stage[kSerGates * kMaxGateBytes + 16];
-    SerGate g[kSerPer];
+    gcw::GateForm g[kSerPer];
     uint32_t mine = 0;
     for (uint32_t k = 0; k < kSerPer; k++) {
         const uint32_t i = blockIdx.x * kSerGates + threadIdx.x * kSerPer + k;
-        g[k] = SerGate{};
+        g[k] = gcw::GateForm{};
         if (i < a.ngates) g[k] = ser_gate(a, i);
         mine += g[k].size;
     }
@@ -172,7 +140,7 @@ __global__ __launch_bounds__(kFinGates) void k_stream_serialise(const FinJob *jo
     uint32_t before = 0;
     for (uint32_t i = threadIdx.x; i < lo; i += kFinGates) before += ser_gate(j.a, i).size;
     const uint32_t i = lo + threadIdx.x;
-    SerGate q{};
+    gcw::GateForm q{};
     if (i < j.a.ngates) q = ser_gate(j.a, i);
     uint32_t incl = q.size;
     const uint32_t lane = threadIdx.x & 63;
