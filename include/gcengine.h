@@ -1147,6 +1147,87 @@ int gc_gmw_triples_multi_sender_fold_dev(gc_ctx *, const void *d_s, const void *
                                          size_t S, size_t words);
 int gc_gmw_triples_multi_receiver_fold_dev(gc_ctx *, const void *d_r, void *d_c, size_t S, size_t words);
 
+/* ------------------------------------------------------------------------------------------
+ * The four rounds of sha2pc for S sessions per call (sha2pc/garbler.go, evaluator.go, encoding.go; additive)
+ * Session s of a call is byte for byte what GarblerRound1 / EvaluatorRound2 / GarblerRound3 / EvaluatorRound4 and
+ * EncodeRound1 / 2 / 3 give for that session alone.  Randomness is the caller's, in the reference's consumption order: the
+ * sender's scalar a and the session id (Round 1), the receiver's scalars (Round 2), the key and then R and the L0 of every
+ * input wire (Round 3: d_rnd is that of gc_batch_garble).
+ *   Geometry.  A handle serves one 2-party circuit: ng garbler inputs (wires 0 .. ng), ne evaluator inputs (the next ne),
+ *   nout outputs, rows = the plan's slab_rows.  Encoded lengths (gc_sha2pc_layout; index 0 .. 2 = Round 1 .. 3):
+ *     Round 1   "R1" sid[8] "\x05P-256" Ax[32] Ay[32]                                   80
+ *     Round 2   "R2" sid[8] "\x05P-256" ne x X[32], ceil(ne / 8) sign bytes             16 + 32 ne + ceil(ne / 8)
+ *     Round 3   "R3" sid[8] key[32], rows labels, ng labels, nout x (L0, L1), ne x (ct0, ct1)
+ *                                                                              42 + 16 rows + 16 ng + 32 nout + 32 ne
+ *   (sha256xor: 80, 8 240, 707 146; a 32-byte digest).  A DEVICE array of payloads is [S][stride] bytes, 16-byte aligned,
+ *   stride a multiple of 16 and >= lead + len; payload s begins at byte `lead` of its slot: 0 for Rounds 1 and 2, 6 for Round
+ *   3, which puts its tables at byte 48 and every label of it on a multiple of 16.  A caller sends and receives slot + lead.
+ *   The HOST forms take and give packed arrays [S][len].  Per-OT arrays are session-major as in gc_co_multi_*: OT j of
+ *   session s is element s * ne + j, with id j.  d_sid is [S][8] bytes (8-byte aligned), d_keys [S][32], d_a [S][32],
+ *   d_scalars [S][ne][32], d_A / d_AaInv [S] gc_p256_point, bits one byte each (non-zero: 1), the digest
+ *   [S][ceil(nout / 8)] bytes, bit i of the output in bit i % 8 of byte i / 8; all other device arrays 16-byte aligned.
+ *   Create.  The handle owns one keyed gc_batch of S instances (schedule 1) and every scratch array of its rounds, and
+ *   uploads G's window table if the ctx has none; synchronous, not between gc_ctx_capture_begin and _end.  NULL and *status =
+ *   GC_E_ARG with a gc_last_error() text when gc_batch_keyed_supported is 0 for that batch, when ng + ne is not the
+ *   circuit's input count (or ne or the output count is 0), or when a size does not fit size_t (S must fit uint32_t).  One
+ *   call at a time per handle; free waits for the ctx stream first (free a handle before its circuit and its ctx); NULL is
+ *   a no-op.
+ *   _dev calls allocate nothing and wait for nothing: a fixed sequence of launches on the ctx stream.
+ *   d_verdict: u32 [S] in device memory, written by every call for every session.  0: good.  Otherwise code | index << 8,
+ *   the first check the reference would fail:
+ *     GC_SHA2PC_MAGIC    wrong magic
+ *     GC_SHA2PC_CURVE    curve chunk other than "\x05P-256"
+ *     GC_SHA2PC_SESSION  the payload's sid is not the session's own (garbler.go:91, evaluator.go:73)
+ *     GC_SHA2PC_SETUP    a = 0 mod N, or an A / AaInv that is not VALID as gc_co_multi_* define it
+ *     GC_SHA2PC_POINT    choice point `index` does not decode: X >= p, or x^3 - 3x + b is no square (lowest index)
+ *     GC_SHA2PC_LABEL    output label `index` is neither hint (BitFromLabel; lowest index)
+ *   in the order Round 2: MAGIC, CURVE, SETUP; Round 3: MAGIC, CURVE, POINT, SESSION, SETUP; Round 4: MAGIC, SESSION,
+ *   SETUP, LABEL; Round 1: SETUP.  A bad session gets zero bytes in every output of that call (a payload over its len
+ *   bytes, not the slot's padding) and changes nothing in any other session.
+ *   Host forms: host pointers, packed payloads, synchronous, staged.  Every good session is written; with a bad session
+ *   the call returns GC_E_POINT (POINT; SETUP in the evaluator's calls) or GC_E_ARG (everything else) for the LOWEST bad
+ *   session and *bad_session = its number (verdict [S] and bad_session may be NULL).
+ *   Not offered: sessions on different circuits in one handle, other curves, Encode*Session (persistence stays in Go). */
+typedef struct gc_sha2pc_garbler gc_sha2pc_garbler;
+typedef struct gc_sha2pc_evaluator gc_sha2pc_evaluator;
+enum {
+    GC_SHA2PC_MAGIC = 1,
+    GC_SHA2PC_CURVE = 2,
+    GC_SHA2PC_SESSION = 3,
+    GC_SHA2PC_SETUP = 4,
+    GC_SHA2PC_POINT = 5,
+    GC_SHA2PC_LABEL = 6
+};
+gc_sha2pc_garbler *gc_sha2pc_garbler_create(gc_ctx *, gc_circ *, uint32_t ng, uint32_t ne, size_t S, int *status);
+gc_sha2pc_evaluator *gc_sha2pc_evaluator_create(gc_ctx *, gc_circ *, uint32_t ng, uint32_t ne, size_t S, int *status);
+void gc_sha2pc_garbler_free(gc_sha2pc_garbler *);
+void gc_sha2pc_evaluator_free(gc_sha2pc_evaluator *);
+/* len[3], lead[3] of Rounds 1 .. 3 and the digest's bytes (any pointer may be NULL); GC_E_ARG as create.  The _plan form
+ * needs no device. */
+int gc_sha2pc_layout(const gc_circ *, uint32_t ng, uint32_t ne, size_t len[3], size_t lead[3], size_t *digest_bytes);
+int gc_sha2pc_layout_plan(const gc_plan *, uint32_t ng, uint32_t ne, size_t len[3], size_t lead[3], size_t *digest_bytes);
+
+int gc_sha2pc_garbler_round1_dev(gc_sha2pc_garbler *, const void *d_a, const void *d_sid, void *d_A_out, void *d_AaInv_out,
+                                 void *d_r1_out, size_t stride1, void *d_verdict);
+int gc_sha2pc_evaluator_round2_dev(gc_sha2pc_evaluator *, const void *d_r1, size_t stride1, const void *d_scalars,
+                                   const void *d_bits, void *d_A_out, void *d_sid_out, void *d_r2_out, size_t stride2,
+                                   void *d_verdict);
+int gc_sha2pc_garbler_round3_dev(gc_sha2pc_garbler *, const void *d_a, const void *d_AaInv, const void *d_sid,
+                                 const void *d_r2, size_t stride2, const void *d_keys, const void *d_rnd, const void *d_bits,
+                                 void *d_r3_out, size_t stride3, void *d_verdict);
+int gc_sha2pc_evaluator_round4_dev(gc_sha2pc_evaluator *, const void *d_A, const void *d_sid, const void *d_scalars,
+                                   const void *d_bits, const void *d_r3, size_t stride3, void *d_digest_out, void *d_verdict);
+int gc_sha2pc_garbler_round1(gc_sha2pc_garbler *, const uint8_t *a, const uint8_t *sid, gc_p256_point *A_out,
+                             gc_p256_point *AaInv_out, uint8_t *r1_out, uint32_t *verdict, size_t *bad_session);
+int gc_sha2pc_evaluator_round2(gc_sha2pc_evaluator *, const uint8_t *r1, const uint8_t *scalars, const uint8_t *bits,
+                               gc_p256_point *A_out, uint8_t *sid_out, uint8_t *r2_out, uint32_t *verdict, size_t *bad_session);
+int gc_sha2pc_garbler_round3(gc_sha2pc_garbler *, const uint8_t *a, const gc_p256_point *AaInv, const uint8_t *sid,
+                             const uint8_t *r2, const uint8_t *keys, const uint8_t *rnd, const uint8_t *bits, uint8_t *r3_out,
+                             uint32_t *verdict, size_t *bad_session);
+int gc_sha2pc_evaluator_round4(gc_sha2pc_evaluator *, const gc_p256_point *A, const uint8_t *sid, const uint8_t *scalars,
+                               const uint8_t *bits, const uint8_t *r3, uint8_t *digest_out, uint32_t *verdict,
+                               size_t *bad_session);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@
 //   Circuit::Garble / Circuit::Eval / Garbled circuit/garble.go:162-183,248-308, circuit/eval.go:17-115
 //   mpc::circuit::ParseBristol                circuit/parser.go:265-494
 //   mpc::circuit::Streaming                   circuit/stream_garble.go:41-192
+//   mpc::sha2pc::GarblerBatch / EvaluatorBatch sha2pc/garbler.go:37-136, evaluator.go:27-113 for S sessions per call
 //
 // Go `error` returns become exceptions of type mpc::Error whose what() carries the reference's message.
 // Go io.Reader becomes mpc::Reader.  Everything compute-heavy goes through libgcengine.so; there is no
@@ -797,4 +798,98 @@ private:
 };
 
 }  // namespace circuit
+
+// The four rounds of the reference's sha2pc package for S sessions per call (sha2pc/garbler.go, evaluator.go, encoding.go;
+// gcengine.h: gc_sha2pc_*), on packed encoded payloads [S][len].  A check of the reference that a session fails is reported
+// in verdict[s] (GC_SHA2PC_* | index << 8) with zero bytes for that session's outputs; the calls throw only for their own
+// failures.  Randomness is the caller's, in the reference's consumption order.
+namespace sha2pc {
+
+struct Layout {
+    size_t len[3], lead[3], digest_bytes;
+};
+
+inline Layout RoundLayout(const gc_circ *circ, uint32_t ng, uint32_t ne) {
+    Layout l{};
+    check(gc_sha2pc_layout(circ, ng, ne, l.len, l.lead, &l.digest_bytes), "gc_sha2pc_layout");
+    return l;
+}
+
+// a bad session is the verdicts' to report
+inline void check_round(int st, size_t bad, const char *what) {
+    if ((st == GC_E_ARG || st == GC_E_POINT) && bad != (size_t)-1) return;
+    check(st, what);
+}
+
+class GarblerBatch {
+public:
+    GarblerBatch(Context &ctx, gc_circ *circ, uint32_t ng, uint32_t ne, size_t S) : S_(S), l_(RoundLayout(circ, ng, ne)) {
+        int st = GC_OK;
+        h_ = gc_sha2pc_garbler_create(ctx.handle(), circ, ng, ne, S, &st);
+        check(st, "gc_sha2pc_garbler_create");
+    }
+    ~GarblerBatch() { gc_sha2pc_garbler_free(h_); }
+    GarblerBatch(const GarblerBatch &) = delete;
+    GarblerBatch &operator=(const GarblerBatch &) = delete;
+    const Layout &layout() const { return l_; }
+    gc_sha2pc_garbler *handle() { return h_; }
+    // GarblerRound1 + EncodeRound1: a [S][32], sid [S][8] -> A, AaInv [S], r1 [S][80]
+    void Round1(const uint8_t *a, const uint8_t *sid, std::vector<gc_p256_point> &A, std::vector<gc_p256_point> &AaInv,
+                std::vector<uint8_t> &r1, std::vector<uint32_t> &verdict) {
+        A.resize(S_), AaInv.resize(S_), r1.resize(S_ * l_.len[0]), verdict.resize(S_);
+        size_t bad = (size_t)-1;
+        check_round(gc_sha2pc_garbler_round1(h_, a, sid, A.data(), AaInv.data(), r1.data(), verdict.data(), &bad), bad,
+                    "gc_sha2pc_garbler_round1");
+    }
+    // DecodeRound2 + GarblerRound3 + EncodeRound3
+    void Round3(const uint8_t *a, const gc_p256_point *AaInv, const uint8_t *sid, const uint8_t *r2, const uint8_t *keys,
+                const uint8_t *rnd, const uint8_t *bits, std::vector<uint8_t> &r3, std::vector<uint32_t> &verdict) {
+        r3.resize(S_ * l_.len[2]), verdict.resize(S_);
+        size_t bad = (size_t)-1;
+        check_round(gc_sha2pc_garbler_round3(h_, a, AaInv, sid, r2, keys, rnd, bits, r3.data(), verdict.data(), &bad), bad,
+                    "gc_sha2pc_garbler_round3");
+    }
+
+private:
+    gc_sha2pc_garbler *h_ = nullptr;
+    size_t S_;
+    Layout l_;
+};
+
+class EvaluatorBatch {
+public:
+    EvaluatorBatch(Context &ctx, gc_circ *circ, uint32_t ng, uint32_t ne, size_t S) : S_(S), l_(RoundLayout(circ, ng, ne)) {
+        int st = GC_OK;
+        h_ = gc_sha2pc_evaluator_create(ctx.handle(), circ, ng, ne, S, &st);
+        check(st, "gc_sha2pc_evaluator_create");
+    }
+    ~EvaluatorBatch() { gc_sha2pc_evaluator_free(h_); }
+    EvaluatorBatch(const EvaluatorBatch &) = delete;
+    EvaluatorBatch &operator=(const EvaluatorBatch &) = delete;
+    const Layout &layout() const { return l_; }
+    gc_sha2pc_evaluator *handle() { return h_; }
+    // DecodeRound1 + EvaluatorRound2 + EncodeRound2: scalars [S][ne][32], bits [S][ne] -> A [S], sid [S][8], r2 [S][len]
+    void Round2(const uint8_t *r1, const uint8_t *scalars, const uint8_t *bits, std::vector<gc_p256_point> &A,
+                std::vector<uint8_t> &sid, std::vector<uint8_t> &r2, std::vector<uint32_t> &verdict) {
+        A.resize(S_), sid.resize(S_ * 8), r2.resize(S_ * l_.len[1]), verdict.resize(S_);
+        size_t bad = (size_t)-1;
+        check_round(gc_sha2pc_evaluator_round2(h_, r1, scalars, bits, A.data(), sid.data(), r2.data(), verdict.data(), &bad),
+                    bad, "gc_sha2pc_evaluator_round2");
+    }
+    // DecodeRound3 + EvaluatorRound4 -> digests [S][digest_bytes]
+    void Round4(const gc_p256_point *A, const uint8_t *sid, const uint8_t *scalars, const uint8_t *bits, const uint8_t *r3,
+                std::vector<uint8_t> &digests, std::vector<uint32_t> &verdict) {
+        digests.resize(S_ * l_.digest_bytes), verdict.resize(S_);
+        size_t bad = (size_t)-1;
+        check_round(gc_sha2pc_evaluator_round4(h_, A, sid, scalars, bits, r3, digests.data(), verdict.data(), &bad), bad,
+                    "gc_sha2pc_evaluator_round4");
+    }
+
+private:
+    gc_sha2pc_evaluator *h_ = nullptr;
+    size_t S_;
+    Layout l_;
+};
+
+}  // namespace sha2pc
 }  // namespace mpc

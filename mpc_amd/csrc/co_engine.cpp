@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "sha2pc.h"
 
 using namespace gc;
 
@@ -463,6 +464,13 @@ int multi_decrypt_run(gc_ctx *ctx, const void *d_A, const void *d_scalars, const
 }
 
 }  // namespace
+
+// sha2pc.h: G's table on the device before the first round of a gc_sha2pc_* handle
+int gc::co_multi_prepare(gc_ctx *ctx) try {
+    return ctx ? multi_g_table(ctx) : GC_E_ARG;
+} catch (...) {
+    return gc::on_exception();
+}
 
 extern "C" {
 

@@ -321,6 +321,22 @@ def lib():
         "gc_kos_multi_receiver_tags_dev": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, vp]),
         "gc_kos_multi_sender_check": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp]),
         "gc_kos_multi_sender_check_dev": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp]),
+        "gc_sha2pc_garbler_create": (vp, [vp, vp, C.c_uint32, C.c_uint32, sz, ip]),
+        "gc_sha2pc_evaluator_create": (vp, [vp, vp, C.c_uint32, C.c_uint32, sz, ip]),
+        "gc_sha2pc_garbler_free": (None, [vp]),
+        "gc_sha2pc_evaluator_free": (None, [vp]),
+        "gc_sha2pc_layout": (i32, [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                   C.POINTER(C.c_size_t)]),
+        "gc_sha2pc_layout_plan": (i32, [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                        C.POINTER(C.c_size_t)]),
+        "gc_sha2pc_garbler_round1_dev": (i32, [vp, vp, vp, vp, vp, vp, sz, vp]),
+        "gc_sha2pc_evaluator_round2_dev": (i32, [vp, vp, sz, vp, vp, vp, vp, vp, sz, vp]),
+        "gc_sha2pc_garbler_round3_dev": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, sz, vp]),
+        "gc_sha2pc_evaluator_round4_dev": (i32, [vp, vp, vp, vp, vp, vp, sz, vp, vp]),
+        "gc_sha2pc_garbler_round1": (i32, [vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_size_t)]),
+        "gc_sha2pc_evaluator_round2": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_size_t)]),
+        "gc_sha2pc_garbler_round3": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_size_t)]),
+        "gc_sha2pc_evaluator_round4": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_size_t)]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -2299,3 +2315,144 @@ def kos_multi_sender_check_dev(ctx, d_seed2, d_result, d_choice_vec, d_delta, d_
     failing session (all ones: none)}"""
     _check(lib().gc_kos_multi_sender_check_dev(ctx.h, _dp(d_seed2), _dp(d_result), _dp(d_choice_vec), _dp(d_delta), _dp(d_tags),
                                                S, per, _dp(d_ok), _dp(d_status)), "gc_kos_multi_sender_check_dev")
+
+
+# ---- the sha2pc rounds for S sessions per call (gc_sha2pc_*) -----------------------------------------------------------------
+
+SHA2PC_MAGIC, SHA2PC_CURVE, SHA2PC_SESSION, SHA2PC_SETUP, SHA2PC_POINT, SHA2PC_LABEL = 1, 2, 3, 4, 5, 6
+
+
+class Sha2pcSessionError(EngineError):
+    """a bad session of a gc_sha2pc_* host call: .bad_session = the lowest one, .verdict = u32 [S] (code | index << 8),
+    .out = the outputs all the same (zeros in the bad sessions)"""
+
+    def __init__(self, code, what, bad_session, verdict, out):
+        super().__init__(code, what)
+        self.bad_session, self.verdict, self.out = bad_session, verdict, out
+
+
+def sha2pc_layout(plan_or_circ, ng, ne):
+    """gc_sha2pc_layout / _layout_plan -> (len [3], lead [3], digest bytes) of Rounds 1 .. 3; a Plan needs no device"""
+    ln, ld, db = (C.c_size_t * 3)(), (C.c_size_t * 3)(), C.c_size_t(0)
+    if isinstance(plan_or_circ, DeviceCircuit):
+        rc = lib().gc_sha2pc_layout(plan_or_circ.h, ng, ne, ln, ld, C.byref(db))
+    else:
+        rc = lib().gc_sha2pc_layout_plan(plan_or_circ.h if plan_or_circ is not None else None, ng, ne, ln, ld, C.byref(db))
+    _check(rc, "gc_sha2pc_layout")
+    return list(ln), list(ld), db.value
+
+
+class _Sha2pc:
+    """what the two handles share: geometry, the strides of device payload arrays, the verdict of a host call"""
+
+    def __init__(self, dcirc, ng, ne, S, create, free, what):
+        self.ctx, self.dc, self.ng, self.ne, self.S = dcirc.ctx, dcirc, int(ng), int(ne), int(S)
+        self._free, self.h = free, None
+        st = C.c_int(0)
+        self.h = create(self.ctx.h, dcirc.h, ng, ne, S, C.byref(st))
+        if not self.h:
+            raise EngineError(st.value, what)
+        self.len, self.lead, self.digest_bytes = sha2pc_layout(dcirc, ng, ne)
+        self.stride = [(ld + ln + 15) // 16 * 16 for ln, ld in zip(self.len, self.lead)]
+
+    def _host(self, rc, what, verdict, bad, out):
+        if rc in (GC_E_ARG, GC_E_POINT) and _bad(bad) is not None:
+            raise Sha2pcSessionError(rc, what, bad.value, verdict, out)
+        _check(rc, what)
+        return out
+
+    def close(self):
+        """free the handle BEFORE its circuit and its ctx; behind either the handle is dropped unfreed (its free would wait
+        for a stream that is gone)"""
+        if self.h and self.dc.h and self.ctx.h:
+            self._free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _bytes2(a, S, per):
+    a = np.ascontiguousarray(a, dtype=np.uint8).reshape(S, -1)
+    assert a.shape[1] == per, (a.shape, per)
+    return a
+
+
+class Sha2pcGarbler(_Sha2pc):
+    """gc_sha2pc_garbler: GarblerRound1 / GarblerRound3 with EncodeRound1 / EncodeRound3 for S sessions per call"""
+
+    def __init__(self, dcirc, ng, ne, S):
+        super().__init__(dcirc, ng, ne, S, lib().gc_sha2pc_garbler_create, lib().gc_sha2pc_garbler_free,
+                         "gc_sha2pc_garbler_create")
+
+    def round1_dev(self, d_a, d_sid, d_A_out, d_AaInv_out, d_r1_out, stride1, d_verdict):
+        _check(lib().gc_sha2pc_garbler_round1_dev(self.h, _dp(d_a), _dp(d_sid), _dp(d_A_out), _dp(d_AaInv_out), _dp(d_r1_out),
+                                                  stride1, _dp(d_verdict)), "gc_sha2pc_garbler_round1_dev")
+
+    def round3_dev(self, d_a, d_AaInv, d_sid, d_r2, stride2, d_keys, d_rnd, d_bits, d_r3_out, stride3, d_verdict):
+        _check(lib().gc_sha2pc_garbler_round3_dev(self.h, _dp(d_a), _dp(d_AaInv), _dp(d_sid), _dp(d_r2), stride2, _dp(d_keys),
+                                                  _dp(d_rnd), _dp(d_bits), _dp(d_r3_out), stride3, _dp(d_verdict)),
+               "gc_sha2pc_garbler_round3_dev")
+
+    def round1(self, a, sid):
+        """a u8 [S, 32], sid u8 [S, 8] -> (A [S, 64], AaInv [S, 64], r1 [S, 80]); raises Sha2pcSessionError"""
+        S = self.S
+        a, sid = _bytes2(a, S, 32), _bytes2(sid, S, 8)
+        A, ainv, r1 = np.zeros((S, 64), np.uint8), np.zeros((S, 64), np.uint8), np.zeros((S, self.len[0]), np.uint8)
+        v, bad = np.zeros(S, np.uint32), C.c_size_t(_NONE)
+        rc = lib().gc_sha2pc_garbler_round1(self.h, _p(a), _p(sid), _p(A), _p(ainv), _p(r1), _p(v), C.byref(bad))
+        return self._host(rc, "gc_sha2pc_garbler_round1", v, bad, (A, ainv, r1))
+
+    def round3(self, a, AaInv, sid, r2, keys, rnd, bits):
+        """packed r2 u8 [S, len2], keys [S, 32], rnd [S, 16 * (1 + ng + ne)], bits u8 [S, ng] -> r3 u8 [S, len3]"""
+        S = self.S
+        a, ai, sid, keys = _bytes2(a, S, 32), _bytes2(AaInv, S, 64), _bytes2(sid, S, 8), _bytes2(keys, S, 32)
+        r2, rnd = _bytes2(r2, S, self.len[1]), _bytes2(rnd, S, 16 * (1 + self.ng + self.ne))
+        bits = np.ascontiguousarray(bits, dtype=np.uint8).reshape(S, self.ng)
+        r3 = np.zeros((S, self.len[2]), np.uint8)
+        v, bad = np.zeros(S, np.uint32), C.c_size_t(_NONE)
+        rc = lib().gc_sha2pc_garbler_round3(self.h, _p(a), _p(ai), _p(sid), _p(r2), _p(keys), _p(rnd),
+                                            _p(bits) if self.ng else None, _p(r3), _p(v), C.byref(bad))
+        return self._host(rc, "gc_sha2pc_garbler_round3", v, bad, r3)
+
+
+class Sha2pcEvaluator(_Sha2pc):
+    """gc_sha2pc_evaluator: EvaluatorRound2 / EvaluatorRound4 with EncodeRound2 for S sessions per call"""
+
+    def __init__(self, dcirc, ng, ne, S):
+        super().__init__(dcirc, ng, ne, S, lib().gc_sha2pc_evaluator_create, lib().gc_sha2pc_evaluator_free,
+                         "gc_sha2pc_evaluator_create")
+
+    def round2_dev(self, d_r1, stride1, d_scalars, d_bits, d_A_out, d_sid_out, d_r2_out, stride2, d_verdict):
+        _check(lib().gc_sha2pc_evaluator_round2_dev(self.h, _dp(d_r1), stride1, _dp(d_scalars), _dp(d_bits), _dp(d_A_out),
+                                                    _dp(d_sid_out), _dp(d_r2_out), stride2, _dp(d_verdict)),
+               "gc_sha2pc_evaluator_round2_dev")
+
+    def round4_dev(self, d_A, d_sid, d_scalars, d_bits, d_r3, stride3, d_digest_out, d_verdict):
+        _check(lib().gc_sha2pc_evaluator_round4_dev(self.h, _dp(d_A), _dp(d_sid), _dp(d_scalars), _dp(d_bits), _dp(d_r3),
+                                                    stride3, _dp(d_digest_out), _dp(d_verdict)),
+               "gc_sha2pc_evaluator_round4_dev")
+
+    def round2(self, r1, scalars, bits):
+        """packed r1 u8 [S, 80], scalars u8 [S, ne, 32], bits u8 [S, ne] -> (A [S, 64], sid [S, 8], r2 [S, len2])"""
+        S = self.S
+        r1, sc = _bytes2(r1, S, self.len[0]), _bytes2(scalars, S, 32 * self.ne)
+        bits = np.ascontiguousarray(bits, dtype=np.uint8).reshape(S, self.ne)
+        A, sid, r2 = np.zeros((S, 64), np.uint8), np.zeros((S, 8), np.uint8), np.zeros((S, self.len[1]), np.uint8)
+        v, bad = np.zeros(S, np.uint32), C.c_size_t(_NONE)
+        rc = lib().gc_sha2pc_evaluator_round2(self.h, _p(r1), _p(sc), _p(bits), _p(A), _p(sid), _p(r2), _p(v), C.byref(bad))
+        return self._host(rc, "gc_sha2pc_evaluator_round2", v, bad, (A, sid, r2))
+
+    def round4(self, A, sid, scalars, bits, r3):
+        """packed r3 u8 [S, len3] -> digests u8 [S, digest_bytes]"""
+        S = self.S
+        A, sid, sc = _bytes2(A, S, 64), _bytes2(sid, S, 8), _bytes2(scalars, S, 32 * self.ne)
+        bits = np.ascontiguousarray(bits, dtype=np.uint8).reshape(S, self.ne)
+        r3 = _bytes2(r3, S, self.len[2])
+        dg = np.zeros((S, self.digest_bytes), np.uint8)
+        v, bad = np.zeros(S, np.uint32), C.c_size_t(_NONE)
+        rc = lib().gc_sha2pc_evaluator_round4(self.h, _p(A), _p(sid), _p(sc), _p(bits), _p(r3), _p(dg), _p(v), C.byref(bad))
+        return self._host(rc, "gc_sha2pc_evaluator_round4", v, bad, dg)
