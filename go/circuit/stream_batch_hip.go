@@ -9,6 +9,7 @@ import "C"
 
 import (
 	"fmt"
+	"io"
 	"unsafe"
 
 	"github.com/markkurossi/mpc/ot"
@@ -353,4 +354,182 @@ func (e *StreamEvalBatch) Bad() ([]uint32, error) {
 		return nil, statusError(st)
 	}
 	return bad, nil
+}
+
+// ReturnLabels is the OpReturn handler (stream_evaluator.go:434-461) for every session at once: the active label of each
+// wire of ids, labels[k*len(ids)+j] for session k — one label per id, in the order the garbler named them; a wire never set
+// gives the zero label, as streaming.Get does on a fresh store.  It waits for the evaluation queued so far.
+func (e *StreamEvalBatch) ReturnLabels(ids []Wire) ([]ot.Label, error) {
+	if len(ids) == 0 {
+		return nil, nil
+	}
+	labels := make([]ot.Label, e.sessions*len(ids))
+	st := C.gc_stream_eval_batch_return_labels(e.h, wireIDs(ids), C.uint32_t(len(ids)), (*C.gc_label)(unsafe.Pointer(&labels[0])))
+	if st != C.GC_OK {
+		return nil, statusError(st)
+	}
+	return labels, nil
+}
+
+// ReturnLabelsDev leaves the same array in device memory, where StreamingBatch.DecodeDev of a garbler on the same GPU reads
+// it; asynchronous.
+func (e *StreamEvalBatch) ReturnLabelsDev(ids []Wire, labels *DevBuf) error {
+	if labels.Size() < e.sessions*len(ids)*16 {
+		return fmt.Errorf("ReturnLabelsDev: the buffer is shorter than %d sessions x %d labels", e.sessions, len(ids))
+	}
+	if st := C.gc_stream_eval_batch_return_labels_dev(e.h, wireIDs(ids), C.uint32_t(len(ids)), labels.Ptr()); st != C.GC_OK {
+		return statusError(st)
+	}
+	return nil
+}
+
+// StreamEvalBatchIn drives a StreamEvalBatch from S connections: it reads what each of them has to give, in chunks that
+// respect no step boundary, and hands the chunks to gc_stream_eval_batch_in_feed, which evaluates every complete OpCircuit
+// message (the loop of stream_evaluator.go:227-249) and keeps an unfinished one.  The sessions run one program in lock
+// step: every reader delivers the same number of bytes per message.
+type StreamEvalBatchIn struct {
+	e       *StreamEvalBatch
+	h       *C.gc_stream_eval_batch_in
+	readers []io.Reader
+	chunk   []byte // [sessions][chunkBytes], filled up to `have` per session, of which `at` are consumed
+	stride  int
+	have    int
+	at      int
+	fed     uint64 // bytes per session that Feed has taken
+}
+
+// NewStreamEvalBatchIn wraps one reader per session.  refSession's bytes are the ones the framing is read from;
+// maxMessageBytes bounds what the handle keeps of one unfinished message; chunkBytes is how much is read per session and call.
+func (e *StreamEvalBatch) NewStreamEvalBatchIn(readers []io.Reader, refSession, maxMessageBytes, chunkBytes int) (*StreamEvalBatchIn, error) {
+	if len(readers) != e.sessions || chunkBytes < 4 {
+		return nil, fmt.Errorf("NewStreamEvalBatchIn: %d readers for %d sessions, chunks of %d bytes", len(readers), e.sessions, chunkBytes)
+	}
+	var st C.int
+	h := C.gc_stream_eval_batch_in_create(e.h, C.uint32_t(refSession), C.size_t(maxMessageBytes), &st)
+	if h == nil {
+		return nil, statusError(st)
+	}
+	return &StreamEvalBatchIn{e: e, h: h, readers: readers, chunk: make([]byte, e.sessions*chunkBytes), stride: chunkBytes}, nil
+}
+
+// Close waits for the uploads in flight and frees the intake; close it before its StreamEvalBatch.
+func (in *StreamEvalBatchIn) Close() {
+	if in.h != nil {
+		C.gc_stream_eval_batch_in_free(in.h)
+		in.h = nil
+	}
+}
+
+// Feed hands the next n bytes of every session (session k's at chunk[k*stride:]) to the handle.  taken: the bytes of the
+// chunk that were consumed; nextOp: OpCircuit while all of them were, else the op word the feed stopped in front of.
+func (in *StreamEvalBatchIn) Feed(chunk []byte, stride, n int) (taken int, nextOp uint32, err error) {
+	if n == 0 {
+		return 0, uint32(OpCircuit), nil
+	}
+	var t C.size_t
+	var op C.uint32_t
+	st := C.gc_stream_eval_batch_in_feed(in.h, (*C.uint8_t)(unsafe.Pointer(&chunk[0])), C.size_t(stride), C.size_t(n), &t, &op)
+	in.fed += uint64(t)
+	if st != C.GC_OK {
+		return int(t), uint32(op), statusError(st)
+	}
+	return int(t), uint32(op), nil
+}
+
+// Stats returns the messages evaluated, their bytes per session, the chunks uploaded and the bytes kept over the feeds.
+func (in *StreamEvalBatchIn) Stats() (steps, bytesPerSession, uploads, carried uint64, err error) {
+	var a, b, c, d C.uint64_t
+	if st := C.gc_stream_eval_batch_in_stats(in.h, &a, &b, &c, &d); st != C.GC_OK {
+		return 0, 0, 0, 0, statusError(st)
+	}
+	return uint64(a), uint64(b), uint64(c), uint64(d), nil
+}
+
+// Run reads and feeds until a message that is not OpCircuit stands at the head of every stream, and returns its op.  The
+// bytes behind the op word stay with the intake: ReadUint32s reads them.  Every session must deliver as many bytes as the
+// reference session does; io.EOF in front of a complete op word is an error.
+func (in *StreamEvalBatchIn) Run() (uint32, error) {
+	for {
+		if in.at == in.have {
+			n, err := in.fill()
+			if err != nil {
+				return 0, err
+			}
+			in.at, in.have = 0, n
+		}
+		taken, op, err := in.Feed(in.chunk[in.at:], in.stride, in.have-in.at)
+		if err != nil {
+			return 0, err
+		}
+		in.at += taken
+		if op == uint32(OpCircuit) {
+			continue
+		}
+		// the word: all four bytes lie in this chunk, or its first ones went with earlier feeds and were dropped there
+		_, evaluated, _, _, err := in.Stats()
+		if err != nil {
+			return 0, err
+		}
+		in.at += 4 - int(in.fed-evaluated)
+		in.fed = evaluated
+		return op, nil
+	}
+}
+
+// fill reads the next chunk of every session: as many bytes as session 0 has to give, at most one chunk.
+func (in *StreamEvalBatchIn) fill() (int, error) {
+	n, err := in.readers[0].Read(in.chunk[:in.stride])
+	if n == 0 {
+		if err == nil {
+			err = io.ErrNoProgress
+		}
+		return 0, err
+	}
+	for k := 1; k < len(in.readers); k++ {
+		if _, err := io.ReadFull(in.readers[k], in.chunk[k*in.stride:k*in.stride+n]); err != nil {
+			return 0, err
+		}
+	}
+	return n, nil
+}
+
+// ReadUint32s reads count big-endian words of every session from behind the stop (the wire ids of OpReturn) and returns
+// session 0's; a session whose words differ is an error.
+func (in *StreamEvalBatchIn) ReadUint32s(count int) ([]uint32, error) {
+	out := make([]uint32, count)
+	var word [4]byte
+	for i := range out {
+		for b := 0; b < 4; b++ {
+			if in.at == in.have {
+				n, err := in.fill()
+				if err != nil {
+					return nil, err
+				}
+				in.at, in.have = 0, n
+			}
+			word[b] = in.chunk[in.at]
+			for k := 1; k < len(in.readers); k++ {
+				if in.chunk[k*in.stride+in.at] != word[b] {
+					return nil, fmt.Errorf("session %d names other wires than session 0", k)
+				}
+			}
+			in.at++
+		}
+		out[i] = uint32(word[0])<<24 | uint32(word[1])<<16 | uint32(word[2])<<8 | uint32(word[3])
+	}
+	return out, nil
+}
+
+// Return answers OpReturn for every session: it reads numOutputs wire ids from behind the op word and returns
+// labels[k*numOutputs+j], the label session k sends back for the j-th id (behind OpResult, one SendLabel each).
+func (in *StreamEvalBatchIn) Return(numOutputs int) ([]ot.Label, error) {
+	ids, err := in.ReadUint32s(numOutputs)
+	if err != nil {
+		return nil, err
+	}
+	ws := make([]Wire, len(ids))
+	for i, id := range ids {
+		ws[i] = Wire(id)
+	}
+	return in.e.ReturnLabels(ws)
 }

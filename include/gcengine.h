@@ -675,6 +675,54 @@ int gc_stream_eval_batch_circuit_host(gc_stream_eval_batch *, uint32_t ngates, u
 int gc_stream_eval_batch_uploads_wait(gc_stream_eval_batch *);
 int gc_stream_eval_batch_bad(gc_stream_eval_batch *, uint32_t *bad_out /* [sessions] */);
 
+/* The evaluator driven from what arrives on a wire (additive): the result labels and the chunked intake. */
+
+/* OpReturn (circuit/stream_evaluator.go:434-461: one label per output wire id) for all sessions:
+ *  d_labels_out  gc_label [sessions][n] = the active label of global wire ids[j] in session s — the array
+ *                gc_stream_batch_decode_dev reads
+ * A wire never set gives what gc_stream_eval_batch_get_wire gives for it (zero).  ids may repeat; n = 0 is GC_OK.  Not inside
+ * a pipeline capture and no id >= GC_STREAM_MAX_WIRES (GC_E_ARG); the store grows as in gc_stream_eval_batch_set_wires.
+ * Asynchronous on the ctx stream; ids[] may be reused on return.  The second form takes a host pointer and is synchronous,
+ * staged as the host forms of the OT family are. */
+int gc_stream_eval_batch_return_labels_dev(gc_stream_eval_batch *, const uint32_t *ids, uint32_t n, void *d_labels_out);
+int gc_stream_eval_batch_return_labels(gc_stream_eval_batch *, const uint32_t *ids, uint32_t n, gc_label *labels_out);
+
+/* The intake: the next bytes of every session's stream, in chunks that respect no step boundary.  The streams are in lock step
+ * (one program, the same number of bytes per step in every session), so the message loop of stream_evaluator.go:227-249 runs
+ * once, over session ref_session's bytes: BE32 op, and for OpCircuit (1) BE32 step, numGates, numTmpWires, numWires and the
+ * block.  Every complete OpCircuit message in the bytes held so far is evaluated, in stream order, exactly as
+ * gc_stream_eval_batch_circuit_host evaluates it: the same refusals and size checks before anything is sized by peer data,
+ * every offset from the reference session, the per-session count of differing structure bytes — the 20 header bytes
+ * included — added into the sums of gc_stream_eval_batch_bad.
+ *  _create  max_message_bytes (20 .. 2^31 - 2, else GC_E_ARG) bounds what the handle holds of ONE unfinished message, header
+ *           included; NULL + *status on failure
+ *  _free    waits for its uploads; free it before the gc_stream_eval_batch
+ *  _feed    session s's next len bytes are at chunk + s * stride, any stride >= len (*base of gc_stream_batch_out_next is a
+ *           valid argument); pinned and pageable memory follow the rules of gc_stream_eval_batch_circuit_host.  The chunk is
+ *           uploaded ONCE, on the handle's upload stream, behind the bytes of the unfinished message of earlier feeds, and
+ *           its blocks are ingested in place.  A message that the chunk does not complete — it may end in the header, in a
+ *           gate's op byte, in an id or in a row, and span any number of feeds — is no error: its bytes are kept, *taken = len
+ *           and *next_op = 1.  At the first complete op word that is not OpCircuit the feed stops in front of it: *next_op =
+ *           that word, *taken = the bytes of this chunk in front of it, and nothing is kept; the caller reads that message
+ *           itself (OpReturn: gc_stream_eval_batch_return_labels) and feeds again from the next op word.  (A word that began
+ *           in an earlier chunk gives *taken = 0; the bytes of it that earlier feeds took — the sum of their *taken minus
+ *           bytes_per_session of _stats — are dropped.)  An op the reference would refuse is reported the same way, not
+ *           judged.  A message the parser refuses returns the code of gc_stream_eval_batch_circuit_host (GC_E_GATE,
+ *           GC_E_ARG, GC_E_ROWS for a header whose numGates cannot fit under max_message_bytes, or when the kept bytes would
+ *           exceed it): the messages before it stay evaluated, *taken = the bytes of this chunk in front of it, nothing is
+ *           kept and the handle stays usable.  Nothing is allocated from numGates before the bytes are there.
+ *  _stats   messages evaluated, their bytes per session, chunks uploaded, bytes per session kept at the end of a feed summed
+ *           over the feeds (any pointer may be NULL)
+ * One thread feeds a handle at a time.  gc_stream_eval_batch_circuit_host stays legal on the same gc_stream_eval_batch while no
+ * intake holds an unfinished message; _bad and _uploads_wait also wait for the intake's uploads. */
+typedef struct gc_stream_eval_batch_in gc_stream_eval_batch_in;
+gc_stream_eval_batch_in *gc_stream_eval_batch_in_create(gc_stream_eval_batch *, uint32_t ref_session, size_t max_message_bytes, int *status);
+void gc_stream_eval_batch_in_free(gc_stream_eval_batch_in *);
+int gc_stream_eval_batch_in_feed(gc_stream_eval_batch_in *, const uint8_t *chunk, size_t stride, size_t len, size_t *taken,
+                                 uint32_t *next_op);
+int gc_stream_eval_batch_in_stats(const gc_stream_eval_batch_in *, uint64_t *steps, uint64_t *bytes_per_session, uint64_t *uploads,
+                                  uint64_t *carried_bytes);
+
 /* ------------------------------------------------------------------------------------------
  * IKNP OT extension + MITCCRH (ot/iknp.go, ot/mitccrh.go, ot/cot.go)
  * ------------------------------------------------------------------------------------------ */

@@ -680,10 +680,63 @@ public:
         check(gc_stream_eval_batch_cache_stats(h_, &c.entries, &c.bytes, &c.loads, &c.evictions), "gc_stream_eval_batch_cache_stats");
         return c;
     }
+    // OpReturn (stream_evaluator.go:434-461): gc_label [sessions][ids.size()] in device memory, what StreamingBatch's decode
+    // reads; asynchronous
+    void ReturnLabelsDev(const std::vector<uint32_t> &ids, void *d_labels_out) {
+        check(gc_stream_eval_batch_return_labels_dev(h_, ids.data(), (uint32_t)ids.size(), d_labels_out),
+              "gc_stream_eval_batch_return_labels_dev");
+    }
+    // ... the same into host memory: [s * ids.size() + j] = the active label of wire ids[j] in session s (waits)
+    std::vector<gc_label> ReturnLabels(const std::vector<uint32_t> &ids) {
+        std::vector<gc_label> out((size_t)sessions_ * ids.size());
+        check(gc_stream_eval_batch_return_labels(h_, ids.data(), (uint32_t)ids.size(), out.data()), "gc_stream_eval_batch_return_labels");
+        return out;
+    }
+    gc_stream_eval_batch *handle() { return h_; }
+    uint32_t sessions() const { return sessions_; }
 
 private:
     gc_stream_eval_batch *h_ = nullptr;
     uint32_t sessions_;
+};
+
+// The intake of a StreamEvalBatch (gc_stream_eval_batch_in_*): chunks of the S byte streams that respect no step boundary in,
+// evaluated steps out.  Destroy it before its StreamEvalBatch; one thread feeds it at a time.
+class StreamEvalBatchIn {
+public:
+    StreamEvalBatchIn(StreamEvalBatch &e, uint32_t ref_session, size_t max_message_bytes) {
+        int st = GC_OK;
+        h_ = gc_stream_eval_batch_in_create(e.handle(), ref_session, max_message_bytes, &st);
+        if (!h_) check(st, "gc_stream_eval_batch_in_create");
+    }
+    ~StreamEvalBatchIn() { gc_stream_eval_batch_in_free(h_); }
+    StreamEvalBatchIn(const StreamEvalBatchIn &) = delete;
+    StreamEvalBatchIn &operator=(const StreamEvalBatchIn &) = delete;
+    struct Fed {
+        size_t taken = 0;      // bytes of the chunk that were taken
+        uint32_t next_op = 1;  // 1 (OpCircuit): all of them; else the op word the feed stopped in front of
+        int status = GC_OK;    // GC_E_GATE / GC_E_ROWS / GC_E_ARG: the message at `taken` was refused by the parser
+    };
+    // session s's next len bytes at chunk + s * stride.  A refused message is reported in Fed::status (the handle stays
+    // usable); any other failure throws.
+    Fed Feed(const uint8_t *chunk, size_t stride, size_t len) {
+        Fed f;
+        f.status = gc_stream_eval_batch_in_feed(h_, chunk, stride, len, &f.taken, &f.next_op);
+        if (f.status != GC_E_GATE && f.status != GC_E_ROWS && f.status != GC_E_ARG) check(f.status, "gc_stream_eval_batch_in_feed");
+        return f;
+    }
+    struct Stats {
+        uint64_t steps = 0, bytes_per_session = 0, uploads = 0, carried_bytes = 0;
+    };
+    Stats GetStats() const {
+        Stats s;
+        check(gc_stream_eval_batch_in_stats(h_, &s.steps, &s.bytes_per_session, &s.uploads, &s.carried_bytes),
+              "gc_stream_eval_batch_in_stats");
+        return s;
+    }
+
+private:
+    gc_stream_eval_batch_in *h_ = nullptr;
 };
 
 // ParseBristol (parser.go:265-494), same validation messages

@@ -17,6 +17,7 @@
 
 #include "engine.h"
 #include "stream_batch.h"
+#include "stream_batch_intake.h"
 #include "stream_batch_windows.h"
 #include "stream_wire.h"
 
@@ -614,8 +615,9 @@ int read_column(SbCore &c, uint32_t w, std::vector<gc_label> *col) {
 
 // the ids of a select / decode / gather / set call: checked, the store grown to hold them (a wire never set reads as 0: its
 // labels are 0 and R), and sent through the staging ring — `send` in their place, if given (set: all but the last of equal ids)
+// nsend: `send` is a list of its own length (n == 0: no wire ids, a list of offsets — gc_stream_eval_batch_in_feed)
 int io_ids(SbCore &c, const char *what, bool refuse_capture, const uint32_t *ids, uint32_t n, SbStage **st, const uint32_t **d_ids,
-           const uint32_t *send = nullptr) {
+           const uint32_t *send = nullptr, uint32_t nsend = 0) {
     if (refuse_capture && c.ctx->capturing) return GC_E_ARG;
     uint32_t mx = 0;
     for (uint32_t i = 0; i < n; i++) mx = std::max(mx, ids[i]);
@@ -625,7 +627,7 @@ int io_ids(SbCore &c, const char *what, bool refuse_capture, const uint32_t *ids
     if (rc != GC_OK) return rc;
     StepBlob b;
     gcsb::StepDev dev{};
-    rc = send_step(c, b, send ? send : ids, n, nullptr, 0, {}, nullptr, 0, st, &dev);
+    rc = send_step(c, b, send ? send : ids, nsend ? nsend : n, nullptr, 0, {}, nullptr, 0, st, &dev);
     if (rc == GC_OK) *d_ids = (const uint32_t *)((*st)->dev + b.o_in);
     return rc;
 }
@@ -841,6 +843,39 @@ struct gc_stream_batch_out {
     }
 };
 
+// The intake of S byte streams.  What is held and where the next message starts is gcsb::Intake; this handle
+// adds two device buffers [S][pitch] that read [the kept tail | the fed chunk], the pinned staging of pageable callers, the
+// reference session's copy of the tail on the host, and the events between the handle's upload stream and the ctx stream.
+struct gc_stream_eval_batch_in {
+    struct Buf {
+        uint8_t *dev = nullptr, *pin = nullptr;
+        size_t pitch = 0, dev_cap = 0, pin_cap = 0;
+        hipEvent_t uploaded = nullptr, consumed = nullptr;  // on the upload stream / on the ctx stream
+        bool in_flight = false, in_use = false;             // `uploaded` / `consumed` has been recorded
+    };
+    gc_stream_eval_batch *e = nullptr;
+    uint32_t ref = 0;
+    gcsb::Intake st;
+    Buf buf[2];
+    uint32_t cur = 0;              // the buffer whose front holds the tail
+    size_t tail_at = 0;            // ... at this column
+    std::vector<uint8_t> ref_buf;  // the reference session's [tail | chunk] while a tail is held
+    std::vector<uint32_t> msg_off;
+    ~gc_stream_eval_batch_in() {
+        if (e) {
+            (void)hipSetDevice(e->ctx->device);
+            if (e->up) (void)hipStreamSynchronize(e->up);
+            (void)hipStreamSynchronize(e->ctx->stream);
+        }
+        for (auto &b : buf) {
+            if (b.dev) (void)hipFree(b.dev);
+            if (b.pin) (void)hipHostFree(b.pin);
+            if (b.uploaded) (void)hipEventDestroy(b.uploaded);
+            if (b.consumed) (void)hipEventDestroy(b.consumed);
+        }
+    }
+};
+
 namespace {
 
 int select_dev(gc_stream_batch *s, const uint32_t *ids, uint32_t n, const void *d_bits, void *d_labels_out) {
@@ -990,6 +1025,140 @@ int eval_host(gc_stream_eval_batch *e, uint32_t ngates, uint32_t ntmp, uint32_t 
         if (rc == GC_OK) GC_HIP(err);
     }
     return rc;
+}
+
+int return_dev(gc_stream_eval_batch *e, const uint32_t *ids, uint32_t n, void *d_labels_out) {
+    if (!e || (n && (!ids || !d_labels_out))) return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    SbStage *st = nullptr;
+    const uint32_t *d_ids = nullptr;
+    int rc = io_ids(*e, "gc_stream_eval_batch_return_labels_dev", true, ids, n, &st, &d_ids);  // (a wire never set reads as 0)
+    if (rc != GC_OK) return rc;
+    gcsb::launch_return_labels(e->d_store, e->bstride, d_ids, n, (uint4 *)d_labels_out, e->S, e->ctx->stream);
+    return ids_launched(*e, st);
+}
+
+// the buffer of a feed: [keep bytes from the buffer before | the chunk], on the handle's upload stream
+int in_upload(gc_stream_eval_batch_in *h, const gcsb::Intake::Feed &f, const uint8_t *chunk, size_t stride,
+              gc_stream_eval_batch_in::Buf **out) {
+    gc_stream_eval_batch *e = h->e;
+    gc_stream_eval_batch_in::Buf &prev = h->buf[h->cur], &b = h->buf[h->cur ^ 1u];
+    const size_t pitch = up16(f.width), need = (size_t)e->S * pitch;
+    if (b.dev_cap < need) {  // (freed only when what read it has run: the copy of its tail into `prev`, its ingesters)
+        if (b.in_flight) GC_HIP(hipStreamSynchronize(e->up));
+        if (b.in_use) GC_HIP(hipEventSynchronize(b.consumed));
+        uint8_t *nw = nullptr;
+        const size_t cap = std::max<size_t>(need + need / 2, (size_t)1 << 16);
+        GC_HIP(hipMalloc((void **)&nw, cap));
+        if (b.dev) (void)hipFree(b.dev);
+        b.dev = nw, b.dev_cap = cap, b.in_use = false;
+    } else if (b.in_use) {
+        GC_HIP(hipStreamWaitEvent(e->up, b.consumed, 0));
+    }
+    const bool pinned = gc_host_is_pinned(chunk) != 0;
+    if (!pinned) {
+        const size_t pneed = (size_t)e->S * f.n;
+        if (b.in_flight) GC_HIP(hipEventSynchronize(b.uploaded));  // (the staging's previous chunk has left)
+        if (b.pin_cap < pneed) {
+            uint8_t *nw = nullptr;
+            const size_t cap = std::max<size_t>(pneed + pneed / 2, (size_t)1 << 16);
+            GC_HIP(hipHostMalloc((void **)&nw, cap, hipHostMallocDefault));
+            if (b.pin) (void)hipHostFree(b.pin);
+            b.pin = nw, b.pin_cap = cap;
+        }
+    }
+    // ---- nothing below allocates
+    b.pitch = pitch;
+    if (f.keep)  // the tail moves to the front: the open message is contiguous wherever it is evaluated
+        GC_HIP(hipMemcpy2DAsync(b.dev, pitch, prev.dev + h->tail_at, prev.pitch, f.keep, e->S, hipMemcpyDeviceToDevice, e->up));
+    if (pinned) {  // (one session: its stride is not looked at, and a source pitch below the width would be refused)
+        GC_HIP(hipMemcpy2DAsync(b.dev + f.keep, pitch, chunk, e->S > 1 ? stride : f.n, f.n, e->S, hipMemcpyHostToDevice, e->up));
+    } else {
+        for (uint32_t s = 0; s < e->S; s++) std::memcpy(b.pin + (size_t)s * f.n, chunk + (size_t)s * stride, f.n);
+        GC_HIP(hipMemcpy2DAsync(b.dev + f.keep, pitch, b.pin, f.n, f.n, e->S, hipMemcpyHostToDevice, e->up));
+    }
+    GC_HIP(hipEventRecord(b.uploaded, e->up));
+    b.in_flight = true;
+    GC_HIP(hipStreamWaitEvent(e->ctx->stream, b.uploaded, 0));
+    *out = &b;
+    return GC_OK;
+}
+
+int in_feed(gc_stream_eval_batch_in *h, const uint8_t *chunk, size_t stride, size_t len, size_t *taken, uint32_t *next_op) {
+    if (!h || !taken || !next_op || (len && !chunk)) return GC_E_ARG;
+    *taken = 0, *next_op = gcsb::Intake::kOpCircuit;
+    gc_stream_eval_batch *e = h->e;
+    if (e->S > 1 && stride < len) return GC_E_ARG;
+    if (e->ctx->capturing) return GC_E_ARG;
+    if (len == 0) return GC_OK;
+    if (len >= 0x7fffffffu || h->st.held + len >= 0x7fffffffu) return refuse("gc_stream_eval_batch_in_feed", "a chunk of 2 GiB or more");
+    GC_HIP(hipSetDevice(e->ctx->device));
+    gcsb::Intake::Feed f = h->st.plan_feed(len);
+    gc_stream_eval_batch_in::Buf *b = nullptr;
+    int rc = in_upload(h, f, chunk, stride, &b);
+    if (rc != GC_OK) return rc;  // (nothing has changed: the tail is where it was)
+    // the reference session's bytes, contiguous: the caller's own while nothing is held
+    const uint8_t *ref = chunk + (size_t)h->ref * stride;
+    if (f.keep) {
+        h->ref_buf.resize(f.width);
+        std::memcpy(h->ref_buf.data() + f.keep, ref, len);
+        ref = h->ref_buf.data();
+    }
+    h->msg_off.clear();
+    int hip_rc = GC_OK;
+    for (;;) {
+        gcsb::Intake::Header hd;
+        gcsb::Intake::Found x = h->st.frame(ref + f.at, gcsb::Intake::avail(f), &hd);
+        if (x.kind == gcsb::Intake::kMessage) {
+            const size_t at = f.at + gcsb::Intake::kHeader;
+            const Supplier supply = [&](size_t, const void **d_blocks, size_t *pitch_out) -> int {
+                *d_blocks = b->dev + at, *pitch_out = b->pitch;
+                return GC_OK;
+            };
+            size_t used = 0;
+            rc = eval_step(e, hd.ngates, hd.ntmp, hd.nwires, ref + at, f.width - at, nullptr, 0, e->d_badsum, &used, &supply);
+            if (rc == GC_OK) {
+                h->msg_off.push_back((uint32_t)f.at);
+                x.len = gcsb::Intake::kHeader + used;
+            } else if (rc == GC_E_ROWS) {  // the bytes end inside the block: wait for more
+                x.kind = gcsb::Intake::kMore;
+            } else {
+                x.kind = gcsb::Intake::kRefused, x.rc = rc;
+                if (rc == GC_E_HIP || rc == GC_E_NOMEM) hip_rc = rc;
+            }
+        }
+        if (!h->st.apply(f, x)) break;
+    }
+    // the headers of the evaluated messages against the reference session's, in one launch; then the buffer is the ingesters'
+    if (!h->msg_off.empty()) {
+        SbStage *stg = nullptr;
+        const uint32_t *d_off = nullptr;
+        const int rcf = io_ids(*e, "gc_stream_eval_batch_in_feed", false, nullptr, 0, &stg, &d_off, h->msg_off.data(), (uint32_t)h->msg_off.size());
+        if (rcf == GC_OK) {
+            gcsb::launch_frames(b->dev, b->pitch, d_off, (uint32_t)h->msg_off.size(), e->S, h->ref, e->d_badsum, e->ctx->stream);
+            const int rcl = ids_launched(*e, stg);
+            if (rcl != GC_OK && hip_rc == GC_OK) hip_rc = rcl;
+        } else if (hip_rc == GC_OK) {
+            hip_rc = rcf;
+        }
+    }
+    const hipError_t err = hipEventRecord(b->consumed, e->ctx->stream);
+    b->in_use = err == hipSuccess;
+    // the tail: in this buffer from f.at on, and the reference session's on the host
+    if (f.carry) {
+        if (ref == h->ref_buf.data()) {
+            std::memmove(h->ref_buf.data(), h->ref_buf.data() + f.at, f.carry);
+        } else {
+            h->ref_buf.resize(f.carry);
+            std::memcpy(h->ref_buf.data(), ref + f.at, f.carry);
+        }
+    }
+    h->cur ^= 1u, h->tail_at = f.at;  // (not before: a parser that throws leaves the tail in the buffer before)
+    h->st.commit(f, true);
+    *taken = f.taken, *next_op = f.next_op;
+    if (hip_rc != GC_OK) return hip_rc;
+    GC_HIP(err);
+    return f.rc;
 }
 
 }  // namespace
@@ -1163,6 +1332,71 @@ int gc_stream_eval_batch_bad(gc_stream_eval_batch *e, uint32_t *bad_out) try {
     return GC_OK;
 } catch (...) {
     return gc::on_exception();
+}
+
+int gc_stream_eval_batch_return_labels_dev(gc_stream_eval_batch *e, const uint32_t *ids, uint32_t n, void *d_labels_out) try {
+    return return_dev(e, ids, n, d_labels_out);
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_stream_eval_batch_return_labels(gc_stream_eval_batch *e, const uint32_t *ids, uint32_t n, gc_label *labels_out) try {
+    if (!e || (n && (!ids || !labels_out))) return GC_E_ARG;
+    if (n == 0) return GC_OK;
+    if (e->ctx->capturing) return GC_E_ARG;
+    std::lock_guard<std::mutex> lock(e->ctx->mu);  // (a host form: §17)
+    GC_HIP(hipSetDevice(e->ctx->device));
+    Staged io[] = {{nullptr, labels_out, (size_t)e->S * n * sizeof(gc_label)}};
+    int rc = stage_in(io, std::size(io), e->ctx->stream);
+    if (rc == GC_OK) rc = return_dev(e, ids, n, io[0].d.p);
+    if (rc == GC_OK) rc = stage_out(io, std::size(io), e->ctx->stream);
+    return rc;
+} catch (...) {
+    return gc::on_exception();
+}
+
+gc_stream_eval_batch_in *gc_stream_eval_batch_in_create(gc_stream_eval_batch *e, uint32_t ref_session, size_t max_message_bytes,
+                                                        int *status) try {
+    int rc = GC_OK;
+    std::unique_ptr<gc_stream_eval_batch_in> h(new (std::nothrow) gc_stream_eval_batch_in);
+    if (!h) rc = GC_E_NOMEM;
+    if (rc == GC_OK && (!e || ref_session >= e->S || max_message_bytes >= 0x7fffffffu || !h->st.init(max_message_bytes))) rc = GC_E_ARG;
+    auto setup = [&]() -> int {
+        const int r = eval_host_setup(e);
+        if (r != GC_OK) return r;
+        for (auto &b : h->buf) {
+            GC_HIP(hipEventCreateWithFlags(&b.uploaded, hipEventDisableTiming));
+            GC_HIP(hipEventCreateWithFlags(&b.consumed, hipEventDisableTiming));
+        }
+        h->e = e, h->ref = ref_session;
+        return GC_OK;
+    };
+    if (rc == GC_OK) rc = setup();
+    if (status) *status = rc;
+    return rc == GC_OK ? h.release() : nullptr;
+} catch (...) {
+    const int rc__ = gc::on_exception();
+    if (status) *status = rc__;
+    return nullptr;
+}
+
+void gc_stream_eval_batch_in_free(gc_stream_eval_batch_in *h) { delete h; }
+
+int gc_stream_eval_batch_in_feed(gc_stream_eval_batch_in *h, const uint8_t *chunk, size_t stride, size_t len, size_t *taken,
+                                 uint32_t *next_op) try {
+    return in_feed(h, chunk, stride, len, taken, next_op);
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_stream_eval_batch_in_stats(const gc_stream_eval_batch_in *h, uint64_t *steps, uint64_t *bytes_per_session, uint64_t *uploads,
+                                  uint64_t *carried_bytes) {
+    if (!h) return GC_E_ARG;
+    if (steps) *steps = h->st.steps;
+    if (bytes_per_session) *bytes_per_session = h->st.bytes_per_session;
+    if (uploads) *uploads = h->st.uploads;
+    if (carried_bytes) *carried_bytes = h->st.carried_bytes;
+    return GC_OK;
 }
 
 }  // extern "C"

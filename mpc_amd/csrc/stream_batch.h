@@ -54,4 +54,15 @@ void launch_select(const uint4 *store, uint32_t bstride, const uint32_t *ids, ui
 void launch_decode_labels(const uint4 *store, uint32_t bstride, const uint32_t *ids, uint32_t n, const uint4 *R, const uint4 *labels,
                           uint8_t *bits_out, uint32_t *bad, uint32_t S, hipStream_t s);
 
+// out [S][n] = store[ids[j]][s]: the evaluator's active labels in the order gc_stream_batch_decode_dev reads them
+// (stream_evaluator.go:434-461)
+void launch_return_labels(const uint4 *store, uint32_t bstride, const uint32_t *ids, uint32_t n, uint4 *out, uint32_t S, hipStream_t s);
+
+// the OpCircuit header in front of a block: BE32 op, step, numGates, numTmpWires, numWires (streamer.go:679-693)
+constexpr uint32_t kFrameBytes = 20;
+// bad[s] += the bytes of [off[m], off[m] + kFrameBytes) that differ between row s and row `ref` of buf [S][pitch], summed over
+// m < nmsg (one add per wave that saw a difference).  Reads those bytes and nothing else.
+void launch_frames(const uint8_t *buf, size_t pitch, const uint32_t *off, uint32_t nmsg, uint32_t S, uint32_t ref, uint32_t *bad,
+                   hipStream_t s);
+
 }  // namespace gcsb

@@ -221,6 +221,47 @@ __global__ __launch_bounds__(kThreads) void k_sb_decode(const uint4 *__restrict_
     }
 }
 
+// the evaluator's result labels (gc_stream_eval_batch_return_labels_dev): the same tile and the same turn as k_sb_select, with
+// nothing to add to the label — no R and no bits
+__global__ __launch_bounds__(kThreads) void k_sb_return(const uint4 *__restrict__ store, uint32_t bstride,
+                                                        const uint32_t *__restrict__ ids, uint32_t n, uint4 *__restrict__ out,
+                                                        uint32_t S) {
+    __shared__ uint4 tile[kIoIds][kIoSessions + 1];
+    const uint32_t i0 = blockIdx.y * kIoSessions, ntiles = (n + kIoIds - 1) / kIoIds;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const uint32_t j0 = t * kIoIds, j = j0 + lane;
+        io_tile_in(tile, store, bstride, ids, n, S, j0, i0);
+        __syncthreads();
+        for (uint32_t r = wave; r < kIoSessions; r += kThreads / 64) {
+            const uint32_t i = i0 + r;
+            if (j < n && i < S) out[(size_t)i * n + j] = tile[lane][r];
+        }
+        __syncthreads();
+    }
+}
+
+// ---- the framing of a fed chunk (gc_stream_eval_batch_in_feed) ---------------------------------------------------------------
+// The 20 header bytes of message m of session s against the reference session's, for every (message, session) pair of a chunk:
+// a wave owns one session and its lanes the messages, so that a session's count is one sum over a wave.  off[m] comes from
+// the reference session's bytes (the host walked them); no byte of any session is used as an index.  The honest path has no
+// atomic: a wave that saw no difference adds nothing.
+__global__ __launch_bounds__(kThreads) void k_sb_frames(const uint8_t *__restrict__ buf, size_t pitch, const uint32_t *__restrict__ off,
+                                                        uint32_t nmsg, uint32_t S, uint32_t ref, uint32_t *__restrict__ bad) {
+    const uint32_t lane = threadIdx.x & 63, s = blockIdx.y * (kThreads / 64) + (threadIdx.x >> 6);
+    if (s >= S) return;  // (uniform per wave)
+    const uint8_t *mine = buf + (size_t)s * pitch, *theirs = buf + (size_t)ref * pitch;
+    uint32_t diff = 0;
+    for (uint32_t m = blockIdx.x * 64 + lane; m < nmsg; m += gridDim.x * 64) {
+        const uint32_t at = off[m];
+#pragma unroll
+        for (uint32_t k = 0; k < kFrameBytes; k++) diff += mine[at + k] != theirs[at + k];
+    }
+    if (__ballot(diff != 0) == 0) return;
+    for (int o = 32; o > 0; o >>= 1) diff += __shfl_down(diff, o, 64);
+    if (lane == 0) atomicAdd(bad + s, diff);
+}
+
 }  // namespace
 
 void launch_select(const uint4 *store, uint32_t bstride, const uint32_t *ids, uint32_t n, const uint4 *R, const uint8_t *bits,
@@ -237,6 +278,21 @@ void launch_decode_labels(const uint4 *store, uint32_t bstride, const uint32_t *
     const uint32_t ntiles = (n + kIoIds - 1) / kIoIds;
     hipLaunchKernelGGL(k_sb_decode, dim3(ntiles < kIoMaxTiles ? ntiles : kIoMaxTiles, (S + kIoSessions - 1) / kIoSessions),
                        dim3(kThreads), 0, s, store, bstride, ids, n, R, labels, bits_out, bad, S);
+}
+
+void launch_return_labels(const uint4 *store, uint32_t bstride, const uint32_t *ids, uint32_t n, uint4 *out, uint32_t S, hipStream_t s) {
+    if (n == 0 || S == 0) return;
+    const uint32_t ntiles = (n + kIoIds - 1) / kIoIds;
+    hipLaunchKernelGGL(k_sb_return, dim3(ntiles < kIoMaxTiles ? ntiles : kIoMaxTiles, (S + kIoSessions - 1) / kIoSessions),
+                       dim3(kThreads), 0, s, store, bstride, ids, n, out, S);
+}
+
+void launch_frames(const uint8_t *buf, size_t pitch, const uint32_t *off, uint32_t nmsg, uint32_t S, uint32_t ref, uint32_t *bad,
+                   hipStream_t s) {
+    if (nmsg == 0 || S == 0) return;
+    const uint32_t nx = (nmsg + 63) / 64;
+    hipLaunchKernelGGL(k_sb_frames, dim3(nx < kIoMaxTiles ? nx : kIoMaxTiles, (S + kThreads / 64 - 1) / (kThreads / 64)), dim3(kThreads),
+                       0, s, buf, pitch, off, nmsg, S, ref, bad);
 }
 
 void launch_rnd_form(uint4 *rnd, const uint4 *R, uint32_t S, uint32_t n1, hipStream_t s) {

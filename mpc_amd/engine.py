@@ -153,6 +153,12 @@ def lib():
         "gc_stream_eval_batch_circuit_host": (i32, [vp, u32, u32, u32, vp, sz, sz, u32, C.POINTER(C.c_size_t)]),
         "gc_stream_eval_batch_uploads_wait": (i32, [vp]),
         "gc_stream_eval_batch_bad": (i32, [vp, vp]),
+        "gc_stream_eval_batch_return_labels_dev": (i32, [vp, vp, u32, vp]),
+        "gc_stream_eval_batch_return_labels": (i32, [vp, vp, u32, vp]),
+        "gc_stream_eval_batch_in_create": (vp, [vp, u32, sz, ip]),
+        "gc_stream_eval_batch_in_free": (None, [vp]),
+        "gc_stream_eval_batch_in_feed": (i32, [vp, vp, sz, sz, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
+        "gc_stream_eval_batch_in_stats": (i32, [vp] + [C.POINTER(C.c_uint64)] * 4),
         "gc_batch_create": (vp, [vp, u32, ip]),
         "gc_batch_free": (None, [vp]),
         "gc_ctx_capture_begin": (i32, [vp]),
@@ -1264,6 +1270,26 @@ class StreamEvalBatch:
         _check(lib().gc_stream_eval_batch_bad(self.h, _p(out)), "gc_stream_eval_batch_bad")
         return out
 
+    def return_labels(self, ids, labels_out=None):
+        """OpReturn: the active label of wire ids[j] in every session as gc_label [S][len(ids)], what StreamBatch.decode reads.
+        labels_out: a DeviceBuffer (gc_stream_eval_batch_return_labels_dev, asynchronous) or None, which returns LABEL
+        [S, len(ids)] (gc_stream_eval_batch_return_labels, synchronous)"""
+        i = np.ascontiguousarray(ids, dtype=np.uint32)
+        if isinstance(labels_out, DeviceBuffer):
+            _check(lib().gc_stream_eval_batch_return_labels_dev(self.h, _p(i), len(i), _dp(labels_out)),
+                   "gc_stream_eval_batch_return_labels_dev")
+            return labels_out
+        out = np.zeros((self.sessions, len(i)), LABEL)
+        _check(lib().gc_stream_eval_batch_return_labels(self.h, _p(i), len(i), _p(out)), "gc_stream_eval_batch_return_labels")
+        return out
+
+    def return_labels_dev(self, ids, d_labels_out):
+        return self.return_labels(ids, d_labels_out)
+
+    def intake(self, ref_session=0, max_message_bytes=1 << 26):
+        """a StreamEvalBatchIn of this handle: chunks of the S byte streams in, evaluated steps out; close it before this handle"""
+        return StreamEvalBatchIn(self, ref_session, max_message_bytes)
+
     def cache_stats(self):
         """the circuit cache (gc_stream_eval_batch_cache_stats): (entries, device bytes, loads, evictions)"""
         v = [C.c_uint64(0) for _ in range(4)]
@@ -1273,6 +1299,52 @@ class StreamEvalBatch:
     def close(self):
         if self.h:
             lib().gc_stream_eval_batch_free(self.h)
+            self.h = None
+
+
+class StreamEvalBatchIn:
+    """gc_stream_eval_batch_in: the message loop of StreamEvaluator over S byte streams that arrive in chunks of any size.
+    Every complete OpCircuit message is evaluated as StreamEvalBatch.circuit_host evaluates it; an unfinished one is kept."""
+
+    def __init__(self, se, ref_session=0, max_message_bytes=1 << 26):
+        self.sessions = se.sessions
+        self.fed = 0  # bytes per session that feed() has taken
+        st = C.c_int(0)
+        self.h = lib().gc_stream_eval_batch_in_create(se.h, ref_session, max_message_bytes, C.byref(st))
+        if not self.h:
+            raise EngineError(st.value, "gc_stream_eval_batch_in_create")
+
+    def feed(self, chunk, stride=None, length=None):
+        """the next `length` bytes of every session: chunk = the address of session 0's bytes (an int, e.g. a window's base)
+        with stride and length, or a numpy u8 array [S, length].  Returns (taken, next_op): next_op == 1 and taken == length
+        while the messages are OpCircuit, else the op word the feed stopped in front of.  Raises EngineError with the
+        parser's code for a refused message; self.taken then says where in the chunk it began"""
+        if isinstance(chunk, int):
+            addr = chunk
+        else:
+            if chunk.dtype != np.uint8 or chunk.ndim != 2 or chunk.shape[0] != self.sessions or chunk.strides[1] != 1:
+                raise EngineError(GC_E_ARG, "feed: chunk must be u8 [sessions, length] with contiguous rows")
+            addr, stride, length = chunk.ctypes.data, (chunk.strides[0] if self.sessions > 1 else chunk.shape[1]), chunk.shape[1]
+        taken, op = C.c_size_t(0), C.c_uint32(0)
+        rc = lib().gc_stream_eval_batch_in_feed(self.h, C.c_void_p(addr), stride, length, C.byref(taken), C.byref(op))
+        self.taken = taken.value
+        self.fed += taken.value
+        _check(rc, "gc_stream_eval_batch_in_feed")
+        return taken.value, op.value
+
+    def word_bytes_taken(self):
+        """after a stop or a refusal with taken == 0: the bytes of that word or message that earlier feeds took (and dropped)"""
+        return self.fed - self.stats()[1]
+
+    def stats(self):
+        """(messages evaluated, their bytes per session, chunks uploaded, bytes per session kept over the feeds)"""
+        v = [C.c_uint64(0) for _ in range(4)]
+        _check(lib().gc_stream_eval_batch_in_stats(self.h, *[C.byref(x) for x in v]), "gc_stream_eval_batch_in_stats")
+        return tuple(int(x.value) for x in v)
+
+    def close(self):
+        if self.h:
+            lib().gc_stream_eval_batch_in_free(self.h)
             self.h = None
 
 

@@ -31,13 +31,22 @@ session; four forms alternate after an untimed pass of each, a window is one who
   (c) windows  gc_stream_batch_out_* with three windows, a 20-byte prefix per step and a consumer thread that only releases
   copy         (b)'s downloads alone, no garbling: the link
 The criterion: all (c) windows below all (b) windows.  GC_STREAM_BATCH_OUT_WHOLE_ROWS=1 in the environment makes (c) copy whole
-windows in one piece instead of the used columns."""
+windows in one piece instead of the used columns.
+
+--intake: the evaluator driven from the garbler's windows, one JSON line per S.  The program is garbled ONCE
+through gc_stream_batch_out_* behind real OpCircuit headers, windows of 1 MiB per session, and every window is kept in pinned
+memory.  Two forms alternate after an untimed pass of each, which also checks that both leave the same store
+(gc_stream_eval_batch_return_labels of the program's last outputs); a window is one whole pass between two gc_ctx_sync:
+  (a) per step  the header read on the host from session 0, one gc_stream_eval_batch_circuit_host per step
+  (b) intake    one gc_stream_eval_batch_in_feed per window
+--intake-once S runs one pass of (b) and nothing else timed: the run a kernel trace is taken of."""
 import argparse
 import csv
 import ctypes as C
 import json
 import os
 import statistics
+import struct
 import sys
 import time
 
@@ -303,6 +312,137 @@ def egress(ctx, prog, S, reps):
     return row
 
 
+class Intake:
+    """the garbler's windows of a Batch in pinned memory, and the two ways of an evaluator through them"""
+
+    def __init__(self, ctx, prog, b):
+        self.ctx, self.prog, self.b, self.S = ctx, prog, b, b.S
+        out = b.sb.out(EGRESS_WINDOW, EGRESS_WINDOWS)
+        n = C.c_size_t(0)
+        self.windows, self.msgs, self.pinned_bytes = [], [], 0
+
+        def drain():
+            while True:
+                v = out.next_view()
+                if v is None:
+                    return
+                p = engine.PinnedArray(v.shape, np.uint8)
+                p.a[:] = v
+                self.windows.append(p)
+                self.pinned_bytes += v.size
+                out.release()
+
+        for k, (a, ev) in enumerate(zip(prog.args.begin, prog.eval_args)):
+            hdr = np.frombuffer(struct.pack(">5I", 1, k, *ev), np.uint8)
+            while True:
+                rc = engine.lib().gc_stream_batch_out_garble(out.h, hdr.ctypes.data_as(C.c_void_p), 20, *a, C.byref(n))
+                if rc != engine.GC_E_BUSY:
+                    break
+                drain()
+            if rc:
+                raise engine.EngineError(rc, "gc_stream_batch_out_garble(step %d)" % k)
+        out.flush()
+        drain()
+        out.close()
+        self.bytes_per_session = sum(w.a.shape[1] for w in self.windows)
+        assert self.bytes_per_session == prog.bytes + 20 * len(prog.steps)
+        # a second evaluator with the same input labels: (a) runs on the Batch's, (b) on this one
+        self.se_b = engine.StreamEvalBatch(ctx, self.S, b.d_keys, 32)
+        d_w = engine.DeviceBuffer(ctx, shape=(self.S, len(prog.prim)), dtype=engine.WIRE)
+        b.sb.gather_wires(prog.prim, d_w)
+        self.se_b.set_wires(prog.prim, engine.DeviceBuffer(ctx, data=np.ascontiguousarray(d_w.numpy()["l0"])))
+        self.it = self.se_b.intake(0, EGRESS_WINDOW)
+        self.n, self.op = C.c_size_t(0), C.c_uint32(0)
+
+    def run_steps(self):
+        """the parent's route: the caller reads the framing of session 0 and makes one call, and one upload, per step"""
+        L, e, pn = engine.lib(), self.b.se.h, C.byref(self.n)
+        call, unpack = L.gc_stream_eval_batch_circuit_host, struct.Struct(">5I").unpack_from
+        calls = 0
+        for w in self.windows:
+            row0, base, (_, width) = w.a[0], w.ptr, w.a.shape
+            at = 0
+            while at < width:
+                op, _, ngates, ntmp, nwires = unpack(row0, at)
+                assert op == 1
+                rc = call(e, ngates, ntmp, nwires, C.c_void_p(base + at + 20), width, width - at - 20, 0, pn)
+                if rc:
+                    raise engine.EngineError(rc, "gc_stream_eval_batch_circuit_host")
+                at += 20 + self.n.value
+                calls += 1
+        return calls
+
+    def run_feed(self):
+        L, h, pn, po = engine.lib(), self.it.h, C.byref(self.n), C.byref(self.op)
+        for w in self.windows:
+            width = w.a.shape[1]
+            rc = L.gc_stream_eval_batch_in_feed(h, C.c_void_p(w.ptr), width, width, pn, po)
+            if rc or self.n.value != width or self.op.value != 1:
+                raise engine.EngineError(rc, "gc_stream_eval_batch_in_feed: taken %d of %d, next op %d" % (self.n.value, width, self.op.value))
+        return len(self.windows)
+
+    def window(self, run):
+        self.ctx.sync()
+        t0 = time.perf_counter()
+        run()
+        self.ctx.sync()
+        return time.perf_counter() - t0
+
+    def check(self):
+        """both routes leave the same labels on the outputs of the last steps, all of them the garbler's L0 or L1; no
+        structure byte differed"""
+        outs = [o for _, _, out_ in self.prog.steps[-8:] for o in out_]
+        la, lb = self.b.se.return_labels(outs), self.se_b.return_labels(outs)
+        assert (la == lb).all() and (self.b.se.bad() == 0).all() and (self.se_b.bad() == 0).all()
+        for j in (0, len(outs) - 1):
+            wire = self.b.sb.get(outs[j])
+            assert ((lb[:, j] == wire["l0"]) | (lb[:, j] == wire["l1"])).all(), outs[j]
+
+    def close(self):
+        self.it.close()
+        self.se_b.close()
+        for w in self.windows:
+            w.close()
+
+
+def intake(ctx, prog, S, reps, once_only=False):
+    b = Batch(ctx, prog, S, np.zeros(prog.bytes, np.uint8))
+    try:
+        x = Intake(ctx, prog, b)
+    except engine.EngineError as err:
+        b.close()
+        return {"bench": "stream_batch_intake", "program": PROGRAM, "sessions": S, "skipped": "windows not kept: %s" % err}
+    if once_only:
+        x.window(x.run_feed)
+        x.close(), b.close()
+        return None
+    calls = x.run_steps()
+    ctx.sync()
+    x.window(x.run_feed)
+    x.check()
+    t = {"per_step": [], "intake": []}
+    for _ in range(reps):
+        t["per_step"].append(x.window(x.run_steps))
+        t["intake"].append(x.window(x.run_feed))
+    x.check()
+    steps, nbytes, uploads, carried = x.it.stats()
+    med = {k: statistics.median(v) for k, v in t.items()}
+    row = {
+        "bench": "stream_batch_intake", "program": PROGRAM, "sessions": S, "key_bytes": 32, "steps": len(prog.steps),
+        "bytes_per_session": x.bytes_per_session, "window_bytes": EGRESS_WINDOW, "windows": len(x.windows), "reps": reps,
+        "pinned_bytes": x.pinned_bytes, "per_step_calls_per_pass": calls, "feeds_per_pass": len(x.windows),
+        "per_step_s": med["per_step"], "intake_s": med["intake"], "intake_over_per_step": med["intake"] / med["per_step"],
+        "per_step_spread_s": max(t["per_step"]) - min(t["per_step"]),
+        "intake_not_slower_beyond_the_spread_of_per_step": med["intake"] <= max(t["per_step"]),
+        "upload_bytes_per_s_intake": x.bytes_per_session * S / med["intake"],
+        "intake_steps_per_pass": steps / (reps + 1), "intake_uploads_per_pass": uploads / (reps + 1), "intake_carried_bytes": carried,
+        "intake_bytes_per_session_per_pass": nbytes / (reps + 1), "seconds_all": t,
+    }
+    x.close()
+    b.close()
+    return row
+
+
 def once(ctx, prog, S):
     """one garble+eval pass and nothing else timed: the run a kernel trace is taken of"""
     _, _, ref_stream, _ = one_session(ctx, prog, bytes(range(32)), bs.stream_rnd(PROGRAM, len(prog.prim)), evaluate=False)
@@ -345,6 +485,9 @@ def main():
     ap.add_argument("--out", default=None, help="also append the lines to this file")
     ap.add_argument("--egress", action="store_true", help="the garbler's bytes to host memory: device-only, synchronous download, "
                                                           "gc_stream_batch_out_* windows, the copy alone")
+    ap.add_argument("--intake", action="store_true", help="the evaluator through the garbler's windows: one call per step beside "
+                                                          "one gc_stream_eval_batch_in_feed per window")
+    ap.add_argument("--intake-once", type=int, default=None, help="one intake pass at this many sessions (for a kernel trace)")
     ap.add_argument("--program", default=PROGRAM, choices=sorted(PROGRAMS), help="big130_16: wide steps, wires in HBM")
     a = ap.parse_args()
     PROGRAM = a.program
@@ -365,6 +508,11 @@ def main():
     ctx = engine.Context(0)
     if a.once:
         once(ctx, prog, a.once)
+    elif a.intake_once:
+        intake(ctx, prog, a.intake_once, 0, once_only=True)
+    elif a.intake:
+        for S in a.sessions:
+            emit(intake(ctx, prog, S, a.reps))
     elif a.egress:
         for S in a.sessions:
             emit(egress(ctx, prog, S, a.reps))
