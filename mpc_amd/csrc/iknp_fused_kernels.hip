@@ -17,8 +17,8 @@
 // costs 2 x 128) and writes the labels back through the same 8 KiB of LDS so that the global store is coalesced.
 // LDS: 64 KiB table | 22 KiB (44 KiB) round keys | 8 (4) chunk buffers of 8 448 bytes.
 #include "aes_device.h"
+#include "iknp_chunk.h"
 #include "kernels.h"
-#include <cstdlib>
 
 namespace gc {
 
@@ -26,36 +26,6 @@ namespace {
 
 constexpr int IKT = kIknpThreads;
 constexpr uint32_t kKeyBytes = 128 * 176;  // [column][11 round keys][16 bytes]
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-using lds_u4 = __attribute__((address_space(3))) u32x4;
-using lds_w32 = __attribute__((address_space(3))) uint32_t;
-
-__device__ __forceinline__ uint4 lds_ld4(uint32_t addr) {
-    const u32x4 v = *(lds_u4 *)(uintptr_t)addr;
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void lds_st4(uint32_t addr, uint4 v) {
-    u32x4 w;
-    w.x = v.x, w.y = v.y, w.z = v.z, w.w = v.w;
-    *(lds_u4 *)(uintptr_t)addr = w;
-}
-__device__ __forceinline__ uint32_t lds_ld1(uint32_t addr) { return *(lds_w32 *)(uintptr_t)addr; }
-__device__ __forceinline__ void lds_st1(uint32_t addr, uint32_t v) { *(lds_w32 *)(uintptr_t)addr = v; }
-
-// Position (in dwords) of dword rd of column col inside a chunk buffer (kChunkBuf bytes).  Chosen so that
-//   * the lane = column ds_write_b128 of a keystream quarter hits 8 distinct 16-byte bank slots per 8 lanes,
-//   * the transposing wave (lane = rd * 4 + column group) reads dword rd of column (cg * 32 + k) from 32 distinct
-//     banks per 32 lanes for every k, and
-//   * for a fixed lane the 32 read addresses are one of FOUR bases plus the immediate 64 k (4 address registers
-//     instead of 32).
-constexpr uint32_t kCgStride = 520;              // dwords per column group: 32 columns x 16 + 8 (bank skew)
-constexpr uint32_t kChunkBuf = 512 * 16 + 16 * 16;  // 8 448 bytes: >= 4 * kCgStride * 4 for the columns, and room for the
-                                                   // 512 labels with one 16-byte pad per 32 labels on the way out
-__device__ __forceinline__ uint32_t chunk_pos(uint32_t col, uint32_t rd) {
-    const uint32_t cg = col >> 5, k = col & 31u;
-    return cg * kCgStride + k * 16u + (((rd >> 2) ^ ((k >> 1) & 3u)) << 2) + (rd & 3u);
-}
 
 // What a lane (= one column key) keeps for the whole kernel: the counter blocks of a column are (0, 0, j_hi, j_lo), so
 // after the first AddRoundKey the state columns 0 and 1 are the key words themselves — half of round 1's sixteen
@@ -243,36 +213,6 @@ __device__ __forceinline__ void column_stream(uint64_t p, uint32_t sh, uint32_t 
     }
 }
 
-__device__ __forceinline__ uint32_t load_u8s(const uint8_t *src, uint32_t nbytes) {  // up to 4 bytes, little-endian
-    uint32_t v = 0;
-    for (uint32_t b = 0; b < nbytes; b++) v |= (uint32_t)src[b] << (8 * b);
-    return v;
-}
-
-// bytes [16q, 16q+16) of a column of byte_rows (<= 64) bytes: full chunks are 16-byte aligned (col * 64), the last,
-// shorter chunk of a call goes byte by byte
-__device__ __forceinline__ uint4 load_quarter(const uint8_t *src, uint32_t byte_rows, uint32_t q) {
-    if (byte_rows == 64) return ((const uint4 *)src)[q];
-    uint32_t v[4];
-#pragma unroll
-    for (uint32_t i = 0; i < 4; i++) {
-        const uint32_t o = 16u * q + 4u * i;
-        v[i] = o < byte_rows ? load_u8s(src + o, byte_rows - o < 4 ? byte_rows - o : 4) : 0;
-    }
-    return make_uint4(v[0], v[1], v[2], v[3]);
-}
-__device__ __forceinline__ void store_quarter(uint8_t *dst, uint32_t byte_rows, uint32_t q, uint4 x) {
-    if (byte_rows == 64) {
-        ((uint4 *)dst)[q] = x;
-        return;
-    }
-    const uint32_t v[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-    for (uint32_t i = 0; i < 4; i++)
-        for (uint32_t b = 0; b < 4; b++)
-            if (16u * q + 4u * i + b < byte_rows) dst[16 * q + 4 * i + b] = (uint8_t)(v[i] >> (8 * b));
-}
-
 template <bool RECV, bool MISALIGNED, bool HI0>
 __global__ __launch_bounds__(IKT) void k_iknp_fused(const uint32_t *__restrict__ rk0, const uint32_t *__restrict__ rk1,
                                                     uint64_t pos0, size_t n, const uint8_t *__restrict__ bbuf,
@@ -307,24 +247,24 @@ __global__ __launch_bounds__(IKT) void k_iknp_fused(const uint32_t *__restrict__
         const size_t ofs = chunk * 512;
         const uint32_t rows = valid ? (uint32_t)((n - ofs) < 512 ? (n - ofs) : 512) : 0;
         const uint32_t byte_rows = (rows + 7) / 8;
+        // full chunks are 16-byte aligned (col * 64) and go as whole quarters; the last, shorter chunk of a call goes byte
+        // by byte whatever its length, so a call of less than one chunk asks no alignment of the caller's u
+        const bool whole = byte_rows == 64;
         uint32_t t[16];
         if (valid) column_stream<MISALIGNED, HI0>(pos0 + 64 * (uint64_t)chunk, sh, keyaddr, lo0, ck, t);
         const size_t at = chunk * 8192 + (size_t)col * byte_rows;  // column-major message layout (iknp.go:490-499)
         if (RECV) {
-            if (valid && stream == 1) {
-#pragma unroll
-                for (uint32_t q = 0; q < 4; q++)
-                    lds_st4(bufaddr + 4 * chunk_pos(col, 4 * q), make_uint4(t[4 * q], t[4 * q + 1], t[4 * q + 2], t[4 * q + 3]));
-            }
+            if (valid && stream == 1) chunk_put_quarters(bufaddr, col, t, 4);
             __syncthreads();
             if (valid && stream == 0) {
 #pragma unroll
                 for (uint32_t q = 0; q < 4; q++) {
-                    const uint4 b = load_quarter(bbuf + ofs / 8, byte_rows, q);  // choice bytes, same for every column
+                    const uint4 b = load_quarter(bbuf + ofs / 8, byte_rows, q, whole);  // choice bytes, same for every column
                     const uint4 t1 = lds_ld4(bufaddr + 4 * chunk_pos(col, 4 * q));
                     store_quarter(u_out + at, byte_rows, q,
                                   make_uint4(t[4 * q] ^ t1.x ^ b.x, t[4 * q + 1] ^ t1.y ^ b.y, t[4 * q + 2] ^ t1.z ^ b.z,
-                                             t[4 * q + 3] ^ t1.w ^ b.w));
+                                             t[4 * q + 3] ^ t1.w ^ b.w),
+                                  whole);
                 }
             }
         } else if (valid) {
@@ -333,19 +273,17 @@ __global__ __launch_bounds__(IKT) void k_iknp_fused(const uint32_t *__restrict__
             if ((word >> (col & 31u)) & 1u) {
 #pragma unroll
                 for (uint32_t q = 0; q < 4; q++) {
-                    const uint4 u = load_quarter(u_in + at, byte_rows, q);
+                    const uint4 u = load_quarter(u_in + at, byte_rows, q, whole);
                     t[4 * q] ^= u.x, t[4 * q + 1] ^= u.y, t[4 * q + 2] ^= u.z, t[4 * q + 3] ^= u.w;
                 }
             }
         }
-        if (valid && stream == 0) {
-#pragma unroll
-            for (uint32_t q = 0; q < 4; q++)
-                lds_st4(bufaddr + 4 * chunk_pos(col, 4 * q), make_uint4(t[4 * q], t[4 * q + 1], t[4 * q + 2], t[4 * q + 3]));
-        }
+        if (valid && stream == 0) chunk_put_quarters(bufaddr, col, t, 4);
         __syncthreads();
         // createLabels: wave w transposes chunk w of the group; lane = (rd, cg): dword rd (OTs 32rd .. 32rd+31) of the
         // 32 columns of group cg
+        // (the unguarded twin of chunk_create_labels in iknp_chunk.h, which k_iknp_multi calls: see there why this kernel
+        // keeps its own; keep the two in step)
         if (wave < NCH && grp * NCH + wave < chunks) {
             const size_t wofs = (grp * NCH + wave) * 512;
             const uint32_t wrows = (uint32_t)((n - wofs) < 512 ? (n - wofs) : 512);
@@ -399,34 +337,16 @@ hipError_t launch_iknp_fused(bool recv, const uint32_t *rk0, const uint32_t *rk1
     const unsigned grid = (unsigned)(groups < kIknpGrid ? groups : kIknpGrid);
     const size_t lds = kTeDualBytes + (recv ? 2 : 1) * kKeyBytes + (size_t)nch * kChunkBuf;
     const bool mis = (pos0 & 15u) != 0;
-    // every counter this launch encrypts below 2^32 blocks (64 GiB of keystream per column): the cheaper first round
-    // (GC_IKNP_GENERIC=1 forces the general first round: the only way to exercise it short of 64 GiB of stream)
-    const char *gen = getenv("GC_IKNP_GENERIC");
-    const bool hi0 = ((pos0 >> 4) + 4 * (uint64_t)chunks + 8) < (1ull << 32) && !(gen && gen[0] == '1');
-    hipError_t e = hipSuccess;
-#define GC_IK(R, M, H)                                                                                              \
-    do {                                                                                                            \
-        e = hipFuncSetAttribute((const void *)k_iknp_fused<R, M, H>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                (int)lds);                                                                          \
-        if (e == hipSuccess)                                                                                        \
-            hipLaunchKernelGGL((k_iknp_fused<R, M, H>), dim3(grid), dim3(IKT), lds, s, rk0, rk1, pos0, n, bbuf,     \
-                               u_in, delta, u_out, labels, te0);                                                    \
-    } while (0)
-#define GC_IK2(R, M)            \
-    do {                        \
-        if (hi0) GC_IK(R, M, true); \
-        else GC_IK(R, M, false);    \
-    } while (0)
+    const bool hi0 = iknp_counters_fit_32(pos0, chunks);
+    auto go = [&](auto kern) {
+        return launch_with_lds(kern, grid, IKT, lds, s, rk0, rk1, pos0, n, bbuf, u_in, delta, u_out, labels, te0);
+    };
     if (recv) {
-        if (mis) GC_IK2(true, true);
-        else GC_IK2(true, false);
-    } else {
-        if (mis) GC_IK2(false, true);
-        else GC_IK2(false, false);
+        if (mis) return hi0 ? go(k_iknp_fused<true, true, true>) : go(k_iknp_fused<true, true, false>);
+        return hi0 ? go(k_iknp_fused<true, false, true>) : go(k_iknp_fused<true, false, false>);
     }
-#undef GC_IK2
-#undef GC_IK
-    return e != hipSuccess ? e : hipGetLastError();
+    if (mis) return hi0 ? go(k_iknp_fused<false, true, true>) : go(k_iknp_fused<false, true, false>);
+    return hi0 ? go(k_iknp_fused<false, false, true>) : go(k_iknp_fused<false, false, false>);
 }
 
 }  // namespace gc

@@ -15,7 +15,6 @@
 // k_iknp_multi_send_bits computes column 0 only.  The other 127 column streams just advance, which is the handle's `pos`.
 // A lane makes 16 result bytes: one AES block on a block boundary, two with the byte shift off it.
 #include <algorithm>
-#include <cstdlib>
 
 #include "iknp_multi_bits.h"
 #include "iknp_multi_stream.h"
@@ -56,6 +55,9 @@ __global__ __launch_bounds__(IKT) void k_iknp_multi_recv_bits(const uint4 *__res
         const IknpMultiItem m = iknp_multi_item(valid ? it : 0, per, pos0);
         const uint32_t byte_rows = valid ? m.byte_rows : 0;
         const uint32_t nq = (byte_rows + 15u) / 16u;  // quarters of the column that hold bytes
+        // a column whose length is a multiple of 16 starts 16-byte aligned (col * byte_rows behind an offset that is a
+        // multiple of 128) and goes as whole quarters
+        const bool whole = (byte_rows & 15u) == 0;
         uint32_t t[16];
         if (valid) {
             const uint4 kl = keys[(m.session * 128 + col) * 2 + stream];
@@ -83,7 +85,8 @@ __global__ __launch_bounds__(IKT) void k_iknp_multi_recv_bits(const uint4 *__res
                     const uint4 t1 = lds_ld4(hand + q * 2048u);
                     store_quarter(u_out + at, byte_rows, q,
                                   make_uint4(t[4 * q] ^ t1.x ^ (uint32_t)b0, t[4 * q + 1] ^ t1.y ^ (uint32_t)(b0 >> 32),
-                                             t[4 * q + 2] ^ t1.z ^ (uint32_t)b1, t[4 * q + 3] ^ t1.w ^ (uint32_t)(b1 >> 32)));
+                                             t[4 * q + 2] ^ t1.z ^ (uint32_t)b1, t[4 * q + 3] ^ t1.w ^ (uint32_t)(b1 >> 32)),
+                                  whole);
                 }
             if (col == 0) {  // labelsBuf[row].Bit(0) is bit `row` of column 0 (iknp.go:601-611)
 #pragma unroll
@@ -170,20 +173,6 @@ __global__ __launch_bounds__(kGmwMultiFoldThreads) void k_gmw_multi_fold(const u
     }
 }
 
-// every counter of the launch below 2^32 blocks; GC_IKNP_GENERIC=1 forces the general form, as in launch_iknp_multi
-bool counters_fit_32(uint64_t pos0, size_t per) {
-    const char *gen = getenv("GC_IKNP_GENERIC");
-    return ((pos0 >> 4) + 4 * iknp_multi_chunks(per) + 8) < (1ull << 32) && !(gen && gen[0] == '1');
-}
-
-template <typename K, typename... A>
-hipError_t launch_with_lds(K kern, unsigned grid, unsigned threads, size_t lds, hipStream_t s, A... args) {
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, args...);
-    return hipGetLastError();
-}
-
 unsigned fold_grid(uint64_t n) {
     return (unsigned)std::min<uint64_t>((n + kGmwMultiFoldThreads - 1) / kGmwMultiFoldThreads, kGmwMultiFoldGrid);
 }
@@ -196,13 +185,13 @@ hipError_t launch_iknp_multi_recv_bits(const uint4 *keys, uint64_t pos0, size_t 
     const uint64_t steps = iknp_multi_steps(iknp_multi_items(S, per), kIknpRecvChunks);
     const unsigned grid = (unsigned)std::min<uint64_t>(steps, kIknpMultiGrid);
     const size_t lds = kTeDualBytes + 2 * (size_t)kIknpRecvChunks * kHandBuf;
-    const bool mis = (pos0 & 15u) != 0, hi0 = counters_fit_32(pos0, per);
-#define GC_IKB(M, H)                                                                                                    \
-    launch_with_lds(k_iknp_multi_recv_bits<M, H>, grid, IKT, lds, s, keys, pos0, (uint64_t)S, (uint64_t)per, choices, \
-                    (uint64_t)stride, u_out, result, te0)
-    if (mis) return hi0 ? GC_IKB(true, true) : GC_IKB(true, false);
-    return hi0 ? GC_IKB(false, true) : GC_IKB(false, false);
-#undef GC_IKB
+    const bool mis = (pos0 & 15u) != 0, hi0 = iknp_counters_fit_32(pos0, iknp_multi_chunks(per));
+    auto go = [&](auto kern) {
+        return launch_with_lds(kern, grid, IKT, lds, s, keys, pos0, (uint64_t)S, (uint64_t)per, choices, (uint64_t)stride, u_out,
+                               result, te0);
+    };
+    if (mis) return hi0 ? go(k_iknp_multi_recv_bits<true, true>) : go(k_iknp_multi_recv_bits<true, false>);
+    return hi0 ? go(k_iknp_multi_recv_bits<false, true>) : go(k_iknp_multi_recv_bits<false, false>);
 }
 
 hipError_t launch_iknp_multi_send_bits(const uint4 *keys, const uint4 *delta, uint64_t pos0, size_t S, size_t per,
@@ -211,12 +200,11 @@ hipError_t launch_iknp_multi_send_bits(const uint4 *keys, const uint4 *delta, ui
     if (S == 0 || per == 0) return hipSuccess;
     const uint64_t lanes = iknp_bits_send_lanes(S, per);
     const unsigned grid = (unsigned)std::min<uint64_t>((lanes + kIknpBitsSendThreads - 1) / kIknpBitsSendThreads, kIknpBitsSendGrid);
-#define GC_IKB(H)                                                                                                   \
-    launch_with_lds(k_iknp_multi_send_bits<H>, grid, kIknpBitsSendThreads, kTeDualBytes, s, keys,                   \
-                    (const uint32_t *)delta, pos0, (uint64_t)S, (uint64_t)per, u_in, (uint64_t)u_session, (uint64_t)u_chunk, \
-                    result, te0)
-    return counters_fit_32(pos0, per) ? GC_IKB(true) : GC_IKB(false);
-#undef GC_IKB
+    auto go = [&](auto kern) {
+        return launch_with_lds(kern, grid, kIknpBitsSendThreads, kTeDualBytes, s, keys, (const uint32_t *)delta, pos0, (uint64_t)S,
+                               (uint64_t)per, u_in, (uint64_t)u_session, (uint64_t)u_chunk, result, te0);
+    };
+    return iknp_counters_fit_32(pos0, iknp_multi_chunks(per)) ? go(k_iknp_multi_send_bits<true>) : go(k_iknp_multi_send_bits<false>);
 }
 
 hipError_t launch_gmw_multi_sender_u(const uint4 *delta, const uint64_t *a, uint64_t *u, size_t S, size_t words, hipStream_t s) {

@@ -17,8 +17,8 @@
 // k_cot_multi is k_cot_dual's body (ot_kernels.hip) with the seed and delta of the lane's session read from arrays and the
 // MITCCRH key index restarting at 0 in every session; a wave may span sessions.
 #include <algorithm>
-#include <cstdlib>
 
+#include "cot_lane.h"
 #include "iknp_multi.h"
 #include "iknp_multi_stream.h"
 #include "kernels.h"
@@ -28,14 +28,6 @@ namespace gc {
 namespace {
 
 constexpr int IKT = kIknpThreads;
-
-// The chunk buffer of k_iknp_fused (see there for the choice of the swizzle): position in dwords of dword rd of column col
-constexpr uint32_t kCgStride = 520;                 // dwords per column group: 32 columns x 16 + 8 (bank skew)
-constexpr uint32_t kChunkBuf = 512 * 16 + 16 * 16;  // 8 448 bytes
-__device__ __forceinline__ uint32_t chunk_pos(uint32_t col, uint32_t rd) {
-    const uint32_t cg = col >> 5, k = col & 31u;
-    return cg * kCgStride + k * 16u + (((rd >> 2) ^ ((k >> 1) & 3u)) << 2) + (rd & 3u);
-}
 
 // keys: the handle's base labels, [S][128] uint4 (sender: k0) or [S][128][2] (receiver: l0, l1 of every pair);
 // delta: [S] uint4 (sender).  choice / u_in / u_out / labels: the arrays of the call, laid out as iknp_multi.h says.
@@ -66,6 +58,9 @@ __global__ __launch_bounds__(IKT) void k_iknp_multi(const uint4 *__restrict__ ke
         const IknpMultiItem m = iknp_multi_item(valid ? it : 0, per, pos0);
         const uint32_t byte_rows = valid ? m.byte_rows : 0;
         const uint32_t nq = (byte_rows + 15u) / 16u;  // quarters of the column that hold bytes
+        // a column whose length is a multiple of 16 starts 16-byte aligned (col * byte_rows behind an offset that is a
+        // multiple of 128) and goes as whole quarters
+        const bool whole = (byte_rows & 15u) == 0;
         uint32_t t[16];
         if (valid) {
             const uint4 kl = keys[(m.session * 128 + col) * (RECV ? 2 : 1) + stream];
@@ -74,12 +69,7 @@ __global__ __launch_bounds__(IKT) void k_iknp_multi(const uint4 *__restrict__ ke
         }
         const uint64_t at = m.u_off + (uint64_t)col * byte_rows;  // column-major message layout (iknp.go:490-499)
         if (RECV) {
-            if (valid && stream == 1) {
-#pragma unroll
-                for (uint32_t q = 0; q < 4; q++)
-                    if (q < nq)
-                        lds_st4(bufaddr + 4 * chunk_pos(col, 4 * q), make_uint4(t[4 * q], t[4 * q + 1], t[4 * q + 2], t[4 * q + 3]));
-            }
+            if (valid && stream == 1) chunk_put_quarters(bufaddr, col, t, nq);
             __syncthreads();
             if (valid && stream == 0) {
 #pragma unroll
@@ -92,7 +82,8 @@ __global__ __launch_bounds__(IKT) void k_iknp_multi(const uint4 *__restrict__ ke
                         const uint4 t1 = lds_ld4(bufaddr + 4 * chunk_pos(col, 4 * q));
                         store_quarter(u_out + at, byte_rows, q,
                                       make_uint4(t[4 * q] ^ t1.x ^ b.x, t[4 * q + 1] ^ t1.y ^ b.y, t[4 * q + 2] ^ t1.z ^ b.z,
-                                                 t[4 * q + 3] ^ t1.w ^ b.w));
+                                                 t[4 * q + 3] ^ t1.w ^ b.w),
+                                      whole);
                     }
             }
         } else if (valid) {
@@ -102,68 +93,21 @@ __global__ __launch_bounds__(IKT) void k_iknp_multi(const uint4 *__restrict__ ke
 #pragma unroll
                 for (uint32_t q = 0; q < 4; q++)
                     if (q < nq) {
-                        const uint4 u = load_quarter(u_in + at, byte_rows, q);
+                        const uint4 u = load_quarter(u_in + at, byte_rows, q, whole);
                         t[4 * q] ^= u.x, t[4 * q + 1] ^= u.y, t[4 * q + 2] ^= u.z, t[4 * q + 3] ^= u.w;
                     }
             }
         }
-        if (valid && stream == 0) {
-#pragma unroll
-            for (uint32_t q = 0; q < 4; q++)
-                if (q < nq)
-                    lds_st4(bufaddr + 4 * chunk_pos(col, 4 * q), make_uint4(t[4 * q], t[4 * q + 1], t[4 * q + 2], t[4 * q + 3]));
-        }
+        if (valid && stream == 0) chunk_put_quarters(bufaddr, col, t, nq);
         __syncthreads();
-        // createLabels: wave w transposes item w of the step; lane = (rd, cg): dword rd (OTs 32rd .. 32rd+31) of the 32
-        // columns of group cg.  A dword row without an OT was not written above and is not read here.
+        // createLabels: wave w transposes item w of the step.  A dword row without an OT was not written above and is not
+        // read there.
         if (wave < NCH && step * NCH + wave < items) {
             const IknpMultiItem wm = iknp_multi_item(step * NCH + wave, per, pos0);
-            const uint32_t wrows = wm.rows;
-            const uint32_t wbuf = kBuf + wave * kChunkBuf;
-            const uint32_t rd = lane >> 2, cg = lane & 3u;
-            if (32u * rd < wrows) {
-                uint32_t base[4];
-#pragma unroll
-                for (uint32_t h = 0; h < 4; h++)
-                    base[h] = wbuf + 4 * (cg * kCgStride + (((rd >> 2) ^ h) << 2) + (rd & 3u));  // chunk_pos without 16 k
-                uint32_t x[32];
-#pragma unroll
-                for (uint32_t k = 0; k < 32; k++) x[k] = lds_ld1(base[(k >> 1) & 3u] + 64u * k);
-                // 32 x 32 bit transpose (masked swaps): afterwards x[i] bit k = column (cg*32+k), OT 32rd+i
-                uint32_t msk = 0x0000ffffu;
-#pragma unroll
-                for (uint32_t j = 16; j != 0; j >>= 1, msk ^= msk << j) {
-#pragma unroll
-                    for (uint32_t k = 0; k < 32; k = ((k | j) + 1) & ~j) {
-                        const uint32_t tt = ((x[k] >> j) ^ x[k | j]) & msk;
-                        x[k] ^= tt << j;
-                        x[k | j] ^= tt;
-                    }
-                }
-                // labels back through the same buffer (a wave's DS operations execute in order and every write depends
-                // on the lane's 32 reads); label r sits at 16 * (r + r / 32)
-                const uint32_t wbase = wbuf + 16 * (33 * rd) + 4 * cg;
-#pragma unroll
-                for (uint32_t i = 0; i < 32; i++) lds_st1(wbase + 16 * i, x[i]);
-            }
-            const uint32_t rbase = wbuf + 16 * (lane + (lane >> 5));
-#pragma unroll
-            for (uint32_t mth = 0; mth < 8; mth++) {
-                const uint32_t r = lane + 64 * mth;  // label r was written by the lanes of dword row r / 32 < ceil(wrows / 32)
-                if (r < wrows) labels[wm.label_off + r] = lds_ld4(rbase + 16 * 66 * mth);
-            }
+            chunk_create_labels(kBuf + wave * kChunkBuf, lane, wm.rows, labels + wm.label_off);
         }
         __syncthreads();
     }
-}
-
-// MITCCRH key of OT index gid: BE(Label{D0:gid, D1:0} ^ seed)   (mitccrh.go:70-82)
-__device__ __forceinline__ void mitccrh_key(uint4 seed, uint64_t gid, uint32_t (&k)[4]) {
-    const uint64_t d0 = (((uint64_t)seed.y << 32) | seed.x) ^ gid;
-    k[0] = (uint32_t)(d0 >> 32);
-    k[1] = (uint32_t)d0;
-    k[2] = seed.w;
-    k[3] = seed.z;
 }
 
 // SEND: COT.Send pads   (cot.go:160-181): out[2i] = H_j(x_i) ^ L0_i, out[2i+1] = H_j(x_i ^ delta_s) ^ L1_i
@@ -194,20 +138,12 @@ __global__ __launch_bounds__(kCotThreads) void k_cot_multi(const uint4 *__restri
             x[0] = out[i];
             pad[0] = data[2 * i + (flags[i] ? 1 : 0)];
         }
-        uint32_t st[NB][4];
+        uint4 h[NB];
+        mitccrh_pads<NB>(x, k, lo0, h);
 #pragma unroll
         for (int b = 0; b < NB; b++) {
-            st[b][0] = x[b].y;
-            st[b][1] = x[b].x;
-            st[b][2] = x[b].w;
-            st[b][3] = x[b].z;
-        }
-        aes128_otf_dual<NB>(st, k, lo0);
-#pragma unroll
-        for (int b = 0; b < NB; b++) {
-            const uint4 h = lxor(lxor(x[b], cols_to_label(st[b])), pad[b]);
-            if (SEND) out[2 * i + b] = h;
-            else out[i] = h;
+            if (SEND) out[2 * i + b] = lxor(h[b], pad[b]);
+            else out[i] = lxor(h[b], pad[b]);
         }
     }
 }
@@ -223,45 +159,25 @@ hipError_t launch_iknp_multi(bool recv, const uint4 *keys, const uint4 *delta, u
     const unsigned grid = (unsigned)std::min<uint64_t>(steps, kIknpMultiGrid);
     const size_t lds = kTeDualBytes + (size_t)nch * kChunkBuf;
     const bool mis = (pos0 & 15u) != 0;
-    // every counter this launch encrypts below 2^32 blocks (64 GiB of keystream per column); GC_IKNP_GENERIC=1 forces the
-    // general form, as in launch_iknp_fused
-    const char *gen = getenv("GC_IKNP_GENERIC");
-    const bool hi0 = ((pos0 >> 4) + 4 * iknp_multi_chunks(per) + 8) < (1ull << 32) && !(gen && gen[0] == '1');
-    hipError_t e = hipSuccess;
-#define GC_IKM(R, M, H)                                                                                             \
-    do {                                                                                                            \
-        e = hipFuncSetAttribute((const void *)k_iknp_multi<R, M, H>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                (int)lds);                                                                          \
-        if (e == hipSuccess)                                                                                        \
-            hipLaunchKernelGGL((k_iknp_multi<R, M, H>), dim3(grid), dim3(IKT), lds, s, keys, (const uint32_t *)delta, \
-                               pos0, (uint64_t)S, (uint64_t)per, choice, u_in, u_out, labels, te0);                 \
-    } while (0)
-#define GC_IKM2(R, M)                \
-    do {                             \
-        if (hi0) GC_IKM(R, M, true); \
-        else GC_IKM(R, M, false);    \
-    } while (0)
+    const bool hi0 = iknp_counters_fit_32(pos0, iknp_multi_chunks(per));
+    auto go = [&](auto kern) {
+        return launch_with_lds(kern, grid, IKT, lds, s, keys, (const uint32_t *)delta, pos0, (uint64_t)S, (uint64_t)per, choice,
+                               u_in, u_out, labels, te0);
+    };
     if (recv) {
-        if (mis) GC_IKM2(true, true);
-        else GC_IKM2(true, false);
-    } else {
-        if (mis) GC_IKM2(false, true);
-        else GC_IKM2(false, false);
+        if (mis) return hi0 ? go(k_iknp_multi<true, true, true>) : go(k_iknp_multi<true, true, false>);
+        return hi0 ? go(k_iknp_multi<true, false, true>) : go(k_iknp_multi<true, false, false>);
     }
-#undef GC_IKM2
-#undef GC_IKM
-    return e != hipSuccess ? e : hipGetLastError();
+    if (mis) return hi0 ? go(k_iknp_multi<false, true, true>) : go(k_iknp_multi<false, true, false>);
+    return hi0 ? go(k_iknp_multi<false, false, true>) : go(k_iknp_multi<false, false, false>);
 }
 
 template <typename K>
 static hipError_t launch_cot_multi(K kern, const uint4 *seeds, const uint4 *deltas, const uint4 *data, const uint4 *wires,
                                    const uint8_t *flags, uint4 *out, size_t n, size_t per, const uint32_t *te0, hipStream_t s) {
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kTeDualBytes);
-    if (e != hipSuccess) return e;
     const unsigned grid = (unsigned)std::min<size_t>(kCotGrid, (n + kCotThreads - 1) / kCotThreads);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kCotThreads), kTeDualBytes, s, seeds, deltas, data, wires, flags, out,
-                       (uint64_t)n, (uint64_t)per, te0);
-    return hipGetLastError();
+    return launch_with_lds(kern, grid, kCotThreads, kTeDualBytes, s, seeds, deltas, data, wires, flags, out, (uint64_t)n,
+                           (uint64_t)per, te0);
 }
 
 hipError_t launch_cot_multi_send(const uint4 *seeds, const uint4 *deltas, const uint4 *data, const uint4 *wires, size_t S,

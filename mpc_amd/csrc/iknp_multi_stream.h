@@ -1,28 +1,14 @@
 // iknp_multi_stream.h — what a lane of the multi-session IKNP kernels (iknp_multi_kernels.hip, iknp_multi_bits_kernels.hip)
-// does with its column: the AES-128-CTR keystream of a base label from a byte position on, the byte-granular loads and
-// stores of a column of the u message, and the 16-byte LDS accesses of the chunk buffers.  Device code only.
+// does with its column: the AES-128-CTR keystream of a base label from a byte position on, the key schedule in the lane.
+// What these kernels share with k_iknp_fused (LDS accesses, chunk buffer, transposing wave, the loads and stores of a column
+// of the u message) is in iknp_chunk.h, included here.  Device code only.
 #pragma once
 
 #include "aes_device.h"
 #include "aes_otf_dual.h"
+#include "iknp_chunk.h"
 
 namespace gc {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-using lds_u4 = __attribute__((address_space(3))) u32x4;
-using lds_w32 = __attribute__((address_space(3))) uint32_t;
-
-__device__ __forceinline__ uint4 lds_ld4(uint32_t addr) {
-    const u32x4 v = *(lds_u4 *)(uintptr_t)addr;
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void lds_st4(uint32_t addr, uint4 v) {
-    u32x4 w;
-    w.x = v.x, w.y = v.y, w.z = v.z, w.w = v.w;
-    *(lds_u4 *)(uintptr_t)addr = w;
-}
-__device__ __forceinline__ uint32_t lds_ld1(uint32_t addr) { return *(lds_w32 *)(uintptr_t)addr; }
-__device__ __forceinline__ void lds_st1(uint32_t addr, uint32_t v) { *(lds_w32 *)(uintptr_t)addr = v; }
 
 // Keystream block j of the lane's column as four little-endian dwords.  The key schedule runs again for every block
 // (aes128_otf_dual consumes its key), and the blocks go one at a time: the case this kernel is for needs one, and two in
@@ -75,37 +61,6 @@ __device__ __forceinline__ void column_stream(uint64_t p, uint32_t sh, uint32_t 
             }
         }
     }
-}
-
-__device__ __forceinline__ uint32_t load_u8s(const uint8_t *src, uint32_t nbytes) {  // up to 4 bytes, little-endian
-    uint32_t v = 0;
-    for (uint32_t b = 0; b < nbytes; b++) v |= (uint32_t)src[b] << (8 * b);
-    return v;
-}
-
-// bytes [16q, 16q + 16) of a column of byte_rows (<= 64) bytes, 16q < byte_rows; bytes past byte_rows read as zero and are
-// not written.  A column whose length is a multiple of 16 starts 16-byte aligned (col * byte_rows behind an offset that is a
-// multiple of 128) and goes as whole quarters; any other goes byte by byte.
-__device__ __forceinline__ uint4 load_quarter(const uint8_t *src, uint32_t byte_rows, uint32_t q) {
-    if ((byte_rows & 15u) == 0) return ((const uint4 *)src)[q];
-    uint32_t v[4];
-#pragma unroll
-    for (uint32_t i = 0; i < 4; i++) {
-        const uint32_t o = 16u * q + 4u * i;
-        v[i] = o < byte_rows ? load_u8s(src + o, byte_rows - o < 4 ? byte_rows - o : 4) : 0;
-    }
-    return make_uint4(v[0], v[1], v[2], v[3]);
-}
-__device__ __forceinline__ void store_quarter(uint8_t *dst, uint32_t byte_rows, uint32_t q, uint4 x) {
-    if ((byte_rows & 15u) == 0) {
-        ((uint4 *)dst)[q] = x;
-        return;
-    }
-    const uint32_t v[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-    for (uint32_t i = 0; i < 4; i++)
-        for (uint32_t b = 0; b < 4; b++)
-            if (16u * q + 4u * i + b < byte_rows) dst[16 * q + 4 * i + b] = (uint8_t)(v[i] >> (8 * b));
 }
 
 }  // namespace gc

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdlib>
 
 #include "co_multi_table.h"
 #include "co_table.h"
@@ -319,6 +320,23 @@ constexpr int kIknpRecvChunks = 4;    // ... chunks of 512 OTs per group and tri
 constexpr int kIknpSendChunks = 8;    // ... and as sender
 constexpr int kCotThreads = 1024;     // k_cot_dual, k_kos_accumulate: one lane = one OT per trip
 constexpr int kCotGrid = 256;         // ... at most this many workgroups (j += gridDim.x * kCotThreads)
+// Every counter block a launch of the IKNP kernels encrypts is below 2^32 (64 GiB of keystream per column): the cheaper
+// first round, HI0.  pos0: bytes every column stream has produced; chunks: of 512 OTs, per column stream.
+// GC_IKNP_GENERIC=1 forces the general first round: the only way to exercise it short of 64 GiB of stream.
+inline bool iknp_counters_fit_32(uint64_t pos0, uint64_t chunks) {
+    const char *gen = std::getenv("GC_IKNP_GENERIC");
+    return ((pos0 >> 4) + 4 * chunks + 8) < (1ull << 32) && !(gen && gen[0] == '1');
+}
+#if defined(__HIPCC__)
+// a kernel with `lds` bytes of dynamic LDS: set the size, launch, return the first error
+template <typename K, typename... A>
+hipError_t launch_with_lds(K kern, unsigned grid, unsigned threads, size_t lds, hipStream_t s, A... args) {
+    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, args...);
+    return hipGetLastError();
+}
+#endif
 // IKNP OT extension, fused (iknp_fused_kernels.hip): column AES-128-CTR PRG + u-matrix / delta fold + createLabels.
 // rk0/rk1: [128][44] expanded column keys (big-endian words); pos0: bytes every column stream has already
 // produced; n OTs in chunks of 512.
@@ -336,12 +354,12 @@ void launch_pack_label_bit0(const uint4 *labels, size_t n, uint64_t *result, hip
 void launch_kos_accumulate(const uint32_t *rk, uint64_t idx0, const uint4 *v, const uint8_t *bits, size_t n,
                            unsigned long long *acc, const uint32_t *te0, hipStream_t s);
 // blk[j*h + t] ^= AES_{key(gid0+j)}(blk[j*h+t])
-void launch_mitccrh(uint4 seed, uint64_t gid0, uint4 *blks, size_t n, uint32_t h, const uint32_t *te0,
-                    hipStream_t s);
-void launch_cot_send(uint4 seed, uint4 delta, const uint4 *data, const uint4 *wires /*[n][2]*/, size_t n, uint4 *out,
-                     const uint32_t *te0, hipStream_t s);
-void launch_cot_recv(uint4 seed, const uint8_t *flags, const uint4 *sent, uint4 *result, size_t n,
-                     const uint32_t *te0, hipStream_t s);
+hipError_t launch_mitccrh(uint4 seed, uint64_t gid0, uint4 *blks, size_t n, uint32_t h, const uint32_t *te0,
+                          hipStream_t s);
+hipError_t launch_cot_send(uint4 seed, uint4 delta, const uint4 *data, const uint4 *wires /*[n][2]*/, size_t n, uint4 *out,
+                           const uint32_t *te0, hipStream_t s);
+hipError_t launch_cot_recv(uint4 seed, const uint8_t *flags, const uint4 *sent, uint4 *result, size_t n,
+                           const uint32_t *te0, hipStream_t s);
 
 // ---- S sessions of equal length per launch (iknp_multi_kernels.hip; the items and their offsets: iknp_multi.h) ----
 constexpr int kIknpMultiGrid = 256;   // k_iknp_multi: at most this many workgroups of kIknpThreads lanes, each walking steps of

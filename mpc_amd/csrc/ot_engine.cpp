@@ -455,22 +455,19 @@ int gc_iknp_send_bits(gc_iknp *k, const uint8_t *u_in, size_t u_len, size_t n, u
 // ---- MITCCRH and the pad loops of COT and ROT ---------------------------------------------------------------------
 // The operations on device pointers, the device set: what a _dev form does behind its argument checks
 static int mitccrh_run(gc_ctx *ctx, const gc_label *seed, uint64_t gid0, void *d_blks, size_t n, uint32_t h) {
-    launch_mitccrh(to_u4(*seed), gid0, (uint4 *)d_blks, n, h, ctx->d_te0, ctx->stream);
-    GC_HIP(hipGetLastError());
+    GC_HIP(launch_mitccrh(to_u4(*seed), gid0, (uint4 *)d_blks, n, h, ctx->d_te0, ctx->stream));
     return GC_OK;
 }
 // d_wires NULL: the ROT sender (below)
 static int cot_send_run(gc_ctx *ctx, const gc_label *seed, const gc_label *delta, const void *d_data, const void *d_wires,
                         size_t n, void *d_out) {
-    launch_cot_send(to_u4(*seed), to_u4(*delta), (const uint4 *)d_data, (const uint4 *)d_wires, n, (uint4 *)d_out, ctx->d_te0,
-                    ctx->stream);
-    GC_HIP(hipGetLastError());
+    GC_HIP(launch_cot_send(to_u4(*seed), to_u4(*delta), (const uint4 *)d_data, (const uint4 *)d_wires, n, (uint4 *)d_out,
+                           ctx->d_te0, ctx->stream));
     return GC_OK;
 }
 static int cot_recv_run(gc_ctx *ctx, const gc_label *seed, const void *d_flags, const void *d_sent, void *d_result, size_t n) {
-    launch_cot_recv(to_u4(*seed), (const uint8_t *)d_flags, (const uint4 *)d_sent, (uint4 *)d_result, n, ctx->d_te0,
-                    ctx->stream);
-    GC_HIP(hipGetLastError());
+    GC_HIP(launch_cot_recv(to_u4(*seed), (const uint8_t *)d_flags, (const uint4 *)d_sent, (uint4 *)d_result, n, ctx->d_te0,
+                           ctx->stream));
     return GC_OK;
 }
 

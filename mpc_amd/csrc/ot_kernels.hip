@@ -11,7 +11,7 @@
 #include <cstdlib>
 
 #include "aes_device.h"
-#include "aes_otf_dual.h"
+#include "cot_lane.h"
 #include "kernels.h"
 #include "kos_clmul.h"
 
@@ -93,15 +93,6 @@ __device__ __forceinline__ void aes128_otf(uint32_t (&s)[N][4], uint32_t k0, uin
             }
         }
     }
-}
-
-// MITCCRH key of OT index gid: BE(Label{D0:gid, D1:0} ^ seed)   (mitccrh.go:70-82)
-__device__ __forceinline__ void mitccrh_key(uint4 seed, uint64_t gid, uint32_t (&k)[4]) {
-    const uint64_t d0 = (((uint64_t)seed.y << 32) | seed.x) ^ gid;
-    k[0] = (uint32_t)(d0 >> 32);
-    k[1] = (uint32_t)d0;
-    k[2] = seed.w;
-    k[3] = seed.z;
 }
 
 // N labels hashed under one key: x ^= AES_key(x)  (mitccrh.go:107-127)
@@ -233,22 +224,13 @@ __global__ __launch_bounds__(kCotThreads) void k_cot_dual(uint4 seed, uint4 delt
         } else if (MODE == 2) {
             pad[0] = data[2 * j + (flags[j] ? 1 : 0)];  // data = the 2n labels received
         }
-        uint32_t s[NB][4];
+        uint4 h[NB];
+        mitccrh_pads<NB>(x, k, lo0, h);
 #pragma unroll
         for (int b = 0; b < NB; b++) {
-            s[b][0] = x[b].y;
-            s[b][1] = x[b].x;
-            s[b][2] = x[b].w;
-            s[b][3] = x[b].z;
-        }
-        aes128_otf_dual<NB>(s, k, lo0);
-#pragma unroll
-        for (int b = 0; b < NB; b++) {
-            uint4 h = lxor(x[b], cols_to_label(s[b]));
-            if (MODE != 0) h = lxor(h, pad[b]);
-            if (MODE == 0) out[j * NB + b] = h;
-            else if (MODE == 1) out[2 * j + b] = h;
-            else out[j] = h;
+            if (MODE == 0) out[j * NB + b] = h[b];
+            else if (MODE == 1) out[2 * j + b] = lxor(h[b], pad[b]);
+            else out[j] = lxor(h[b], pad[b]);
         }
     }
 }
@@ -259,11 +241,10 @@ static bool cot_classic() {
 }
 
 template <typename K>
-static void launch_cot_dual(K kern, size_t n, hipStream_t s, uint4 seed, uint4 delta, uint64_t gid0, const uint4 *data,
-                            const uint4 *wires, const uint8_t *flags, uint4 *out, const uint32_t *te0) {
-    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kTeDualBytes);
+static hipError_t launch_cot_dual(K kern, size_t n, hipStream_t s, uint4 seed, uint4 delta, uint64_t gid0, const uint4 *data,
+                                  const uint4 *wires, const uint8_t *flags, uint4 *out, const uint32_t *te0) {
     const unsigned grid = (unsigned)std::min<size_t>(kCotGrid, (n + kCotThreads - 1) / kCotThreads);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kCotThreads), kTeDualBytes, s, seed, delta, gid0, data, wires, flags, out, n, te0);
+    return launch_with_lds(kern, grid, kCotThreads, kTeDualBytes, s, seed, delta, gid0, data, wires, flags, out, n, te0);
 }
 
 // ---- KOS consistency check (ot/iknp.go:138-194, 373-465; ot/gf128.go:14-27; ot/mul128_generic.go) --------
@@ -341,26 +322,35 @@ void launch_kos_accumulate(const uint32_t *rk, uint64_t idx0, const uint4 *v, co
     hipLaunchKernelGGL(k_kos_accumulate, dim3(grid), dim3(kCotThreads), kTeDualBytes, s, rk, idx0, v, bits, n, acc, te0);
 }
 
-void launch_mitccrh(uint4 seed, uint64_t gid0, uint4 *blks, size_t n, uint32_t h, const uint32_t *te0, hipStream_t s) {
-    if (n == 0 || h == 0) return;
+hipError_t launch_mitccrh(uint4 seed, uint64_t gid0, uint4 *blks, size_t n, uint32_t h, const uint32_t *te0, hipStream_t s) {
+    if (n == 0 || h == 0) return hipSuccess;
     const uint4 z = make_uint4(0, 0, 0, 0);
-    if (cot_classic() || h > 2) return launch_mitccrh_classic(seed, gid0, blks, n, h, te0, s);
-    if (h == 1) launch_cot_dual(k_cot_dual<0, 1>, n, s, seed, z, gid0, nullptr, nullptr, nullptr, blks, te0);
-    else launch_cot_dual(k_cot_dual<0, 2>, n, s, seed, z, gid0, nullptr, nullptr, nullptr, blks, te0);
+    if (cot_classic() || h > 2) {
+        launch_mitccrh_classic(seed, gid0, blks, n, h, te0, s);
+        return hipGetLastError();
+    }
+    if (h == 1) return launch_cot_dual(k_cot_dual<0, 1>, n, s, seed, z, gid0, nullptr, nullptr, nullptr, blks, te0);
+    return launch_cot_dual(k_cot_dual<0, 2>, n, s, seed, z, gid0, nullptr, nullptr, nullptr, blks, te0);
 }
 
-void launch_cot_send(uint4 seed, uint4 delta, const uint4 *data, const uint4 *wires, size_t n, uint4 *out,
-                     const uint32_t *te0, hipStream_t s) {
-    if (n == 0) return;
-    if (cot_classic()) return launch_cot_send_classic(seed, delta, data, wires, n, out, te0, s);
-    launch_cot_dual(k_cot_dual<1, 2>, n, s, seed, delta, 0, data, wires, nullptr, out, te0);
+hipError_t launch_cot_send(uint4 seed, uint4 delta, const uint4 *data, const uint4 *wires, size_t n, uint4 *out,
+                           const uint32_t *te0, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (cot_classic()) {
+        launch_cot_send_classic(seed, delta, data, wires, n, out, te0, s);
+        return hipGetLastError();
+    }
+    return launch_cot_dual(k_cot_dual<1, 2>, n, s, seed, delta, 0, data, wires, nullptr, out, te0);
 }
 
-void launch_cot_recv(uint4 seed, const uint8_t *flags, const uint4 *sent, uint4 *result, size_t n,
-                     const uint32_t *te0, hipStream_t s) {
-    if (n == 0) return;
-    if (cot_classic()) return launch_cot_recv_classic(seed, flags, sent, result, n, te0, s);
-    launch_cot_dual(k_cot_dual<2, 1>, n, s, seed, make_uint4(0, 0, 0, 0), 0, sent, nullptr, flags, result, te0);
+hipError_t launch_cot_recv(uint4 seed, const uint8_t *flags, const uint4 *sent, uint4 *result, size_t n,
+                           const uint32_t *te0, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (cot_classic()) {
+        launch_cot_recv_classic(seed, flags, sent, result, n, te0, s);
+        return hipGetLastError();
+    }
+    return launch_cot_dual(k_cot_dual<2, 1>, n, s, seed, make_uint4(0, 0, 0, 0), 0, sent, nullptr, flags, result, te0);
 }
 
 // ---- bit-COT helpers (gc_iknp_*_bits_dev) ------------------------------------------------------------------------

@@ -39,8 +39,9 @@ def base_setup(seed):
     return base, delta, k0
 
 
-# iknp_test.go:32-37 chunk-size cases + ragged / sub-byte / multi-chunk sizes
-SIZES = [0, 1, 2, 7, 8, 9, 129, 511, 512, 513, 700, 1024, 1025, 2049, 2560, 65536]
+# iknp_test.go:32-37 chunk-size cases + ragged / sub-byte / multi-chunk sizes; 128, 640, 896: a last chunk of 16, 16, 48
+# byte-rows, a multiple of 16 bytes short of a full one
+SIZES = [0, 1, 2, 7, 8, 9, 128, 129, 511, 512, 513, 640, 700, 896, 1024, 1025, 2049, 2560, 65536]
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -195,6 +196,37 @@ def test_iknp_device_resident_api_matches_host_api(ctx):
         assert d_lr.numpy().tobytes() == lr.tobytes()
         assert d_ls.numpy().tobytes() == ls.tobytes()
         assert rx_d.last_ms > 0 and tx_d.last_ms > 0
+    for o in (rx_h, tx_h, rx_d, tx_d):
+        o.close()
+
+
+def test_iknp_device_resident_u_of_a_short_call_needs_no_alignment(ctx):
+    """n = 128 is one chunk of 16 byte-rows: a multiple of 16 bytes short of a full chunk.  gc_iknp_receive_dev /
+    gc_iknp_send_dev move such a chunk byte by byte, so the u buffers may sit 4 bytes into their allocations (gcengine.h
+    asks no alignment of d_u_out / d_u_in); the labels and u are those of the host calls."""
+    n = 128
+    base, delta, k0 = base_setup("devmis")
+    rx_h, tx_h = engine.IKNPReceiver(ctx, base), engine.IKNPSender(ctx, delta, k0)
+    rx_d, tx_d = engine.IKNPReceiver(ctx, base), engine.IKNPSender(ctx, delta, k0)
+    b = np.frombuffer(drbg("devmisb", n), np.uint8) & 1
+    u, lr = rx_h.receive(b)
+    ls = tx_h.send(u, n)
+    assert len(u) == n // 8 * 128
+    packed = np.zeros(64, np.uint8)
+    packed[:n // 8] = np.packbits(b, bitorder="little")
+    d_c = ctx.to_device(packed)
+    d_ur, d_us = ctx.zeros(8192 + 16), ctx.zeros(8192 + 16)
+    d_lr, d_ls = ctx.zeros((n, 16)), ctx.zeros((n, 16))
+    rx_d.receive_dev(d_c, n, d_ur + 4, d_lr)
+    ctx.sync()
+    got_u = d_ur.numpy()
+    assert got_u[4:4 + len(u)].tobytes() == u
+    assert not got_u[:4].any() and not got_u[4 + len(u):].any()  # nothing written around it
+    d_us.upload(got_u[4:4 + len(u)], offset=4)
+    tx_d.send_dev(d_us + 4, n, d_ls)
+    ctx.sync()
+    assert d_lr.numpy().tobytes() == lr.tobytes()
+    assert d_ls.numpy().tobytes() == ls.tobytes()
     for o in (rx_h, tx_h, rx_d, tx_d):
         o.close()
 
