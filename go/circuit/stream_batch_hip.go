@@ -258,6 +258,51 @@ func NewStreamingBatchOut(s *StreamingBatch, windowBytes, nwindows int) (*Stream
 	return &StreamingBatchOut{h: h, sessions: s.sessions}, nil
 }
 
+// NewStreamingBatchOutSplit is NewStreamingBatchOut with the split rule: a step is cut over the windows, so every window but a
+// flushed one leaves exactly full and none grows.  A step larger than (nwindows-1) windows is refused.
+func NewStreamingBatchOutSplit(s *StreamingBatch, windowBytes, nwindows int) (*StreamingBatchOut, error) {
+	var st C.int
+	h := C.gc_stream_batch_out_create_split(s.h, C.size_t(windowBytes), C.uint32_t(nwindows), &st)
+	if h == nil {
+		return nil, statusError(st)
+	}
+	return &StreamingBatchOut{h: h, sessions: s.sessions}, nil
+}
+
+// SplitStats returns the steps that touched more than one window and the serialiser launches so far (zeros on a handle of
+// NewStreamingBatchOut).
+func (o *StreamingBatchOut) SplitStats() (splitSteps, segments uint64, err error) {
+	var a, b C.uint64_t
+	if st := C.gc_stream_batch_out_split_stats(o.h, &a, &b); st != C.GC_OK {
+		return 0, 0, statusError(st)
+	}
+	return uint64(a), uint64(b), nil
+}
+
+// SetFallback sends circuits loaded from now on that the key table alone keeps out of the keyed scope to the HBM-wire kernels.
+func (s *StreamingBatch) SetFallback(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if st := C.gc_stream_batch_set_fallback(s.h, v); st != C.GC_OK {
+		return statusError(st)
+	}
+	return nil
+}
+
+// SetFallback is (*StreamingBatch).SetFallback for the evaluator: EvalBlock, EvalBlockHost and the intake.
+func (e *StreamEvalBatch) SetFallback(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if st := C.gc_stream_eval_batch_set_fallback(e.h, v); st != C.GC_OK {
+		return statusError(st)
+	}
+	return nil
+}
+
 // Close waits for the copies in flight and frees the windows.
 func (o *StreamingBatchOut) Close() {
 	if o.h != nil {

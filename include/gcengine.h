@@ -661,6 +661,33 @@ int gc_stream_batch_out_next(gc_stream_batch_out *, const uint8_t **base, size_t
 int gc_stream_batch_out_release(gc_stream_batch_out *);
 int gc_stream_batch_out_stats(const gc_stream_batch_out *, uint64_t *sealed, uint64_t *bytes_per_session, uint64_t *grown, uint64_t *busy);
 
+/* The SPLIT form of the window handle (additive): a gc_stream_batch_out whose mode is fixed at creation and
+ * whose every other call is the one above.  It differs in what _garble does with a step of n bytes per session (prefix
+ * included): the bytes go behind what the filling window holds, at `off`, and on into the windows after it from their byte 0 —
+ * segments [0, min(n, cap - off)), then runs of cap bytes, then the rest, k = ceil((off + n) / cap) windows in all.  Every
+ * touched window that becomes exactly full is sealed (if off + n is a multiple of cap the last one too, and no empty window
+ * is touched); no window is sealed short but by _flush and none ever grows (`grown` stays 0), so the handle pins
+ * nwindows * sessions * cap bytes whatever the steps are and every handed-out window but a flushed one is exactly cap bytes
+ * long.  The keyed pass, the scatter into the store and the step's constants run once per step and the serialiser once per
+ * segment; a window's seal is queued right behind the launch of its segment, so window j leaves for the host while segment
+ * j + 1 is written.  For every session the windows in the order they are handed out are byte for byte `prefix | step` over
+ * the steps: what the unsplit handle delivers.
+ *   The step needs the filling window and the k - 1 windows behind it to be free; if they are not: GC_E_BUSY under the rule
+ * above (nothing has happened).  n > (nwindows - 1) * cap can never be guaranteed that room: GC_E_ARG with a gc_last_error()
+ * text that names both numbers, nothing has happened and the handle stays usable; any smaller step fits once enough windows
+ * are released (off < cap).  _create_split refuses what _create refuses.
+ *  _split_stats  steps that touched more than one window, serialiser launches (any pointer may be NULL); zeros on an unsplit
+ *                handle */
+gc_stream_batch_out *gc_stream_batch_out_create_split(gc_stream_batch *, size_t window_bytes, uint32_t nwindows, int *status);
+int gc_stream_batch_out_split_stats(const gc_stream_batch_out *, uint64_t *split_steps, uint64_t *segments);
+/* The fallback of the two handles: with on != 0, a step (a block) whose circuit is outside gc_batch_keyed_supported at this
+ * number of sessions for the ONE reason that its wires are in LDS and the tile's key table does not fit behind them is loaded
+ * with gc_batch_set_keyed_path(batch, 2) and runs on the keyed HBM-wire kernels — the same bytes and labels, cached and
+ * counted like any other step.  The setting holds for circuits loaded after the call; the default is 0: the refusal above.
+ * The evaluator's covers _circuit, _circuit_host and the intake. */
+int gc_stream_batch_set_fallback(gc_stream_batch *, int on);
+int gc_stream_eval_batch_set_fallback(gc_stream_eval_batch *, int on);
+
 /* gc_stream_eval_batch_circuit with the blocks in HOST memory: session s's block at blocks + s * stride, any stride >= len (the
  * layout of a garbler window: *base + offset of gc_stream_batch_out_next is a valid argument).  Session ref_session's bytes
  * are the reference block, parsed and refused exactly as there; the rest of the step is the same.  The blocks go into a ring

@@ -577,6 +577,8 @@ public:
               "gc_stream_batch_decode");
         return bits;
     }
+    // circuits loaded from now on that the key table alone keeps out of the keyed scope run on the HBM-wire kernels
+    void SetFallback(bool on) { check(gc_stream_batch_set_fallback(h_, on ? 1 : 0), "gc_stream_batch_set_fallback"); }
     gc_stream_batch *handle() const { return h_; }
     uint32_t sessions() const { return sessions_; }
 
@@ -589,10 +591,13 @@ private:
 // One thread may call Garble / Flush while one other calls Next / Release.
 class StreamingBatchOut {
 public:
-    StreamingBatchOut(StreamingBatch &sb, size_t window_bytes, uint32_t nwindows) {
+    // split: a step is cut over the windows (gc_stream_batch_out_create_split): every window but a flushed one leaves exactly
+    // full, none grows, and a step larger than nwindows - 1 windows is refused
+    StreamingBatchOut(StreamingBatch &sb, size_t window_bytes, uint32_t nwindows, bool split = false) {
         int st = GC_OK;
-        h_ = gc_stream_batch_out_create(sb.handle(), window_bytes, nwindows, &st);
-        if (!h_) check(st, "gc_stream_batch_out_create");
+        h_ = split ? gc_stream_batch_out_create_split(sb.handle(), window_bytes, nwindows, &st)
+                   : gc_stream_batch_out_create(sb.handle(), window_bytes, nwindows, &st);
+        if (!h_) check(st, split ? "gc_stream_batch_out_create_split" : "gc_stream_batch_out_create");
     }
     ~StreamingBatchOut() { gc_stream_batch_out_free(h_); }
     StreamingBatchOut(const StreamingBatchOut &) = delete;
@@ -626,6 +631,14 @@ public:
     Stats GetStats() const {
         Stats s;
         check(gc_stream_batch_out_stats(h_, &s.sealed, &s.bytes_per_session, &s.grown, &s.busy), "gc_stream_batch_out_stats");
+        return s;
+    }
+    struct SplitStats {
+        uint64_t split_steps = 0, segments = 0;  // steps that touched more than one window, serialiser launches
+    };
+    SplitStats GetSplitStats() const {
+        SplitStats s;
+        check(gc_stream_batch_out_split_stats(h_, &s.split_steps, &s.segments), "gc_stream_batch_out_split_stats");
         return s;
     }
 
@@ -669,6 +682,8 @@ public:
         return used;
     }
     void UploadsWait() { check(gc_stream_eval_batch_uploads_wait(h_), "gc_stream_eval_batch_uploads_wait"); }
+    // blocks whose circuit is loaded from now on and kept out of the keyed scope by the key table alone run on the HBM-wire kernels
+    void SetFallback(bool on) { check(gc_stream_eval_batch_set_fallback(h_, on ? 1 : 0), "gc_stream_eval_batch_set_fallback"); }
     // per session the structure bytes that differed in any EvalBlockHost since construction (waits)
     std::vector<uint32_t> Bad() {
         std::vector<uint32_t> bad(sessions_);

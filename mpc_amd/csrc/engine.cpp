@@ -1128,6 +1128,7 @@ int gc_batch_eval(gc_batch *ev, const uint8_t *key, size_t keylen, const gc_batc
 // (sized for AES-256, so that the answer does not depend on the key length) fits behind the wire slots; 2 = the level-walking
 // kernels with the wires in HBM, for a batch without a usable LDS plan (none, one that does not fit, one still pending) and
 // for any schedule-1 batch that gc_batch_set_keyed_path sent there; 0 = none, *why says what keeps the batch out.
+static const char kWhyKeyTable[] = "the tile's key table does not fit into LDS behind the wire slots (gc_batch_set_keyed_path)";
 static int keyed_path(const gc_batch *b, const char **why) {
     *why = nullptr;
     if (b->schedule != 1 || b->single_phase) {
@@ -1142,10 +1143,15 @@ static int keyed_path(const gc_batch *b, const char **why) {
     }
     const Plan &p = b->circ->plan.p;
     if (fused_flat_keyed_bytes(p.n_flat_slots, b->g.ti_log2, p.fl_unit_stride, 14) > kFlatLdsBytes) {
-        *why = "the tile's key table does not fit into LDS behind the wire slots (gc_batch_set_keyed_path)";
+        *why = kWhyKeyTable;
         return 0;
     }
     return 1;
+}
+
+extern "C++" bool gc::keyed_refused_for_key_table_only(const gc_batch *b) {
+    const char *why;
+    return b && keyed_path(b, &why) == 0 && why == kWhyKeyTable;
 }
 
 int gc_batch_keyed_path(const gc_batch *b) {

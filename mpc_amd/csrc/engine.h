@@ -66,6 +66,9 @@ namespace gc {
 hipError_t ctx_buf_get(gc_ctx *c, bool pinned, size_t need, void **p, size_t *cap);
 // back to the lists (nothing on the GPU may still use it); freed when the lists hold more than a few GiB
 void ctx_buf_put(gc_ctx *c, bool pinned, void *p, size_t cap);
+// gc_batch_keyed_path(b) is 0 and the one reason is that the tile's key table does not fit behind the wire slots: the batch that
+// gc_batch_set_keyed_path(b, 2) exists to serve (the fallback of the stream-batch handles asks this)
+bool keyed_refused_for_key_table_only(const ::gc_batch *b);
 }  // namespace gc
 // internal: notes a cooperative pass of this ctx that lost a workgroup (repeated on the device already) and switches the
 // cooperative passes off; GC_OK always

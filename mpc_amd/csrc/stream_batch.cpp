@@ -123,6 +123,7 @@ struct SbCore {
     size_t cache_bytes = 0;
     uint64_t tick = 0;
     uint64_t n_loads = 0, n_evictions = 0;  // misses that ended with an entry kept / entries the budget loop freed
+    bool fallback = false;  // gc_stream_*batch_set_fallback: a circuit kept out by the key table alone is loaded on path 2
     SbStage ring[kRing];
     uint32_t next = 0;
 
@@ -199,11 +200,15 @@ struct SbCore {
         e->circ = gc_circ_load(ctx, e->gates.data(), ngates, nwires, nin, nout, &st);
         if (!e->circ) return st;
         e->batch = gc_batch_create(e->circ, S, &st);
-        // (path 1 with the wires in LDS, path 2 with the wires in HBM; the handle does not force path 2 on a batch whose wires are
-        // in LDS and whose key table does not fit)
+        // (path 1 with the wires in LDS, path 2 with the wires in HBM; a batch whose wires are in LDS and whose key table does not
+        // fit is sent to path 2 when the handle's fallback is on — its arrays hold every wire slot whatever the kernel, so the
+        // movers around the pass read the slots they read on path 1 — and refused otherwise)
         if (e->batch && gc_batch_keyed_path(e->batch) == 0) {
-            st = refuse(what, "the step's circuit is outside gc_batch_keyed_supported at this number of sessions (its wires are in "
-                              "LDS and the tile's key table does not fit)");
+            if (fallback && gc::keyed_refused_for_key_table_only(e->batch))
+                st = gc_batch_set_keyed_path(e->batch, 2);
+            else
+                st = refuse(what, "the step's circuit is outside gc_batch_keyed_supported at this number of sessions (its wires are in "
+                                  "LDS and the tile's key table does not fit)");
         }
         if (!e->batch || st != GC_OK) {
             if (e->batch) gc_batch_free(e->batch);
@@ -412,11 +417,18 @@ bool rewrite_aliased(gc_stream_batch *s, const gc_gate **gates, uint32_t ngates,
 // where a step's bytes go once their number is known: the caller's place, or a window of a gc_stream_batch_out.  Called
 // when nothing can refuse the step any more and before anything of it is queued.
 using Placer = std::function<int(size_t nbytes, void **d_out, size_t *stride)>;
+// ... or the windows of a split handle: `plan` is called where a Placer is, and says in how many segments the bytes leave;
+// segment j is bytes [*b0, *b1) of the step, session s's at *d_out + s * *stride; `launched` runs right behind its launch
+struct SplitPlacer {
+    std::function<int(size_t nbytes, uint32_t *nseg)> plan;
+    std::function<void(uint32_t j, size_t *b0, size_t *b1, void **d_out, size_t *stride)> segment;
+    std::function<int(uint32_t j)> launched;
+};
 
 // prefix: bytes in front of every session's step (they join the skeleton: the same for all sessions)
 int garble_step(gc_stream_batch *s, const gc_gate *gates, uint32_t ngates, uint32_t nwires, const uint32_t *in, uint32_t nin,
                 const uint32_t *out, uint32_t nout, void *d_out, size_t stride, size_t *written, const uint8_t *prefix = nullptr,
-                size_t prefix_len = 0, const Placer *place = nullptr) {
+                size_t prefix_len = 0, const Placer *place = nullptr, const SplitPlacer *split = nullptr) {
     static const char *const what = "gc_stream_batch_garble";
     if (!s || !written || (ngates && !gates) || (nin && !in) || (nout && !out)) return GC_E_ARG;
     *written = 0;
@@ -442,7 +454,7 @@ int garble_step(gc_stream_batch *s, const gc_gate *gates, uint32_t ngates, uint3
     }
     *written = nbytes;
     if (nbytes >= 0x7fffffffu) return refuse(what, "a step of 2 GiB or more");
-    if (!place && (!d_out || stride % 4 != 0 || stride < nbytes))
+    if (!place && !split && (!d_out || stride % 4 != 0 || stride < nbytes))
         return refuse(what, "stride must be a multiple of 4 and >= the step's bytes");
     const gc_gate *run = gates;
     std::unordered_map<uint32_t, uint32_t> latest;
@@ -467,10 +479,10 @@ int garble_step(gc_stream_batch *s, const gc_gate *gates, uint32_t ngates, uint3
         auto it = latest.find(out[j]);
         if (it != latest.end()) s->out_marked[j] = it->second == nwires - nout + j ? out[j] : kNone;
     }
-    if (place) {
-        rc = (*place)(nbytes, &d_out, &stride);
-        if (rc != GC_OK) return rc;
-    }
+    uint32_t nseg = 0;
+    if (place) rc = (*place)(nbytes, &d_out, &stride);
+    if (split) rc = split->plan(nbytes, &nseg);
+    if (rc != GC_OK) return rc;
     StepBlob b;
     SbStage *st = nullptr;
     gcsb::StepDev dev{};
@@ -488,8 +500,19 @@ int garble_step(gc_stream_batch *s, const gc_gate *gates, uint32_t ngates, uint3
     if (e == hipSuccess && rc == GC_OK) {
         // 3. the output L0s into the store through out[]; 4. every session's bytes
         gcsb::launch_rows(bt->d_W, bt->g.lw, ent->circ->d_out_slots, s->d_store, s->store_layout(), d_outi, nout, s->S, q);
-        gcsb::launch_serialise(dev, bt->d_T, bt->g.lt, (uint8_t *)d_out, stride, s->S, q);
+        if (!split) gcsb::launch_serialise(dev, bt->d_T, bt->g.lt, (uint8_t *)d_out, stride, s->S, q);
         e = hipGetLastError();
+        // a split step: the pass, the scatter and the constants above ran once; one launch per window, its seal right behind it
+        for (uint32_t j = 0; j < nseg && e == hipSuccess && rc == GC_OK; j++) {
+            size_t b0 = 0, b1 = 0;
+            split->segment(j, &b0, &b1, &d_out, &stride);
+            if (nseg == 1)  // (not cut: the whole-step kernel, as on an unsplit handle)
+                gcsb::launch_serialise(dev, bt->d_T, bt->g.lt, (uint8_t *)d_out, stride, s->S, q);
+            else
+                gcsb::launch_serialise_range(dev, bt->d_T, bt->g.lt, (uint8_t *)d_out, stride, s->S, (uint32_t)b0, (uint32_t)b1, q);
+            e = hipGetLastError();
+            rc = split->launched(j);
+        }
     }
     const int rce = step_sent(*s, st);
     GC_HIP(e);
@@ -797,6 +820,8 @@ struct gc_stream_batch_out {
     std::vector<Win> win;
     hipStream_t copy = nullptr;
     bool whole_rows = false;  // copy [S][cap] in one piece instead of the used columns (GC_STREAM_BATCH_OUT_WHOLE_ROWS)
+    bool split = false;       // gc_stream_batch_out_create_split: a step is cut over the windows, none grows (fixed at creation)
+    uint64_t split_steps = 0, segments = 0;  // steps that touched more than one window / serialiser launches
 
     static void drop(Win &w) {
         if (w.dev) (void)hipFree(w.dev);
@@ -904,6 +929,65 @@ int decode_dev(gc_stream_batch *s, const uint32_t *ids, uint32_t n, const void *
     return ids_launched(*s, st);
 }
 
+// what a split handle answers to a step it cannot take now (busy: counted) or ever (too large: named); GC_OK: it fits
+int split_answer(gc_stream_batch_out *h, const gcsb::WindowRing::Split &p, size_t n) {
+    if (p.too_large) {
+        std::snprintf(gc::tls_error, sizeof gc::tls_error,
+                      "gc_stream_batch_out_garble: a step of %zu bytes per session can never be given room in %u windows of %zu bytes "
+                      "(at most %zu: one window less than the ring)",
+                      n, h->ring.count(), h->ring.cap[0], (size_t)(h->ring.count() - 1) * h->ring.cap[0]);
+        return GC_E_ARG;
+    }
+    if (p.is_busy) {
+        h->ring.note_busy();
+        return GC_E_BUSY;
+    }
+    return GC_OK;
+}
+
+// the split form of out_garble, under the handle's lock; size: the step's bytes if its shape is not refused, else 0
+int out_garble_split(gc_stream_batch_out *h, const uint8_t *prefix, size_t prefix_len, const gc_gate *gates, uint32_t ngates,
+                     uint32_t nwires, const uint32_t *in, uint32_t nin, const uint32_t *out, uint32_t nout, size_t *written, size_t size) {
+    gc_stream_batch *s = h->sb;
+    if (size) {
+        const int rc = split_answer(h, h->ring.plan_split(size), size);
+        if (rc != GC_OK) return rc;
+    }
+    GC_HIP(hipSetDevice(s->ctx->device));
+    gcsb::WindowRing::Split p;
+    size_t n = 0;
+    uint32_t sealed = 0;  // windows of the step whose seal has been queued
+    const size_t cap = h->ring.cap[0];
+    SplitPlacer sp;
+    sp.plan = [&](size_t nbytes, uint32_t *nseg) -> int {
+        const gcsb::WindowRing::Split q = h->ring.plan_split(nbytes);
+        const int rc = split_answer(h, q, nbytes);
+        if (rc != GC_OK) return rc;
+        h->ring.commit_split(q, nbytes);
+        h->segments += q.nwin, h->split_steps += q.nwin > 1;
+        p = q, n = nbytes, *nseg = q.nwin;
+        return GC_OK;
+    };
+    sp.segment = [&](uint32_t j, size_t *b0, size_t *b1, void **d_out, size_t *stride) {
+        *b0 = p.begin(j, n, cap), *b1 = p.begin(j + 1, n, cap);
+        *d_out = h->win[(p.win + j) % h->ring.count()].dev + (j ? 0 : p.at);
+        *stride = cap;
+    };
+    sp.launched = [&](uint32_t j) -> int {
+        if (j >= p.nsealed) return GC_OK;
+        sealed = j + 1;
+        return h->seal((p.win + j) % h->ring.count(), cap);
+    };
+    const int rc = garble_step(s, gates, ngates, nwires, in, nin, out, nout, nullptr, 0, written, prefix, prefix_len, nullptr, &sp);
+    // (the ring has the windows as sealed whatever became of the step's launches: their events must exist)
+    int rcs = GC_OK;
+    for (uint32_t j = sealed; j < p.nsealed; j++) {
+        const int r = h->seal((p.win + j) % h->ring.count(), cap);
+        if (rcs == GC_OK) rcs = r;
+    }
+    return rc != GC_OK ? rc : rcs;
+}
+
 int out_garble(gc_stream_batch_out *h, const uint8_t *prefix, size_t prefix_len, const gc_gate *gates, uint32_t ngates,
                uint32_t nwires, const uint32_t *in, uint32_t nin, const uint32_t *out, uint32_t nout, size_t *written) {
     if (!h || !written || prefix_len > 64 || (prefix_len && !prefix) || (ngates && !gates) || (nin && !in) || (nout && !out))
@@ -918,6 +1002,7 @@ int out_garble(gc_stream_batch_out *h, const uint8_t *prefix, size_t prefix_len,
     if (ngates && !s->ctx->capturing && !step_refused(gates, ngates, nwires, nin, nout, &shape))
         size = step_skeleton(gates, ngates, nwires, in, nin, out, nout, nullptr, nullptr) + prefix_len;
     std::lock_guard<std::mutex> lock(h->mu);
+    if (h->split) return out_garble_split(h, prefix, prefix_len, gates, ngates, nwires, in, nin, out, nout, written, size);
     if (size && h->ring.plan_step(size).is_busy) {
         h->ring.note_busy();
         return GC_E_BUSY;
@@ -1210,10 +1295,11 @@ int gc_stream_batch_decode(gc_stream_batch *s, const uint32_t *ids, uint32_t n, 
     return gc::on_exception();
 }
 
-gc_stream_batch_out *gc_stream_batch_out_create(gc_stream_batch *s, size_t window_bytes, uint32_t nwindows, int *status) try {
+static gc_stream_batch_out *out_create(gc_stream_batch *s, size_t window_bytes, uint32_t nwindows, bool split, int *status) try {
     int rc = GC_OK;
     std::unique_ptr<gc_stream_batch_out> h(new (std::nothrow) gc_stream_batch_out);
     if (!h) rc = GC_E_NOMEM;
+    if (h) h->split = split;
     if (rc == GC_OK && (!s || window_bytes == 0 || window_bytes > ((size_t)1 << 40) || nwindows > 4096)) rc = GC_E_ARG;
     if (rc == GC_OK && !h->ring.init(window_bytes, nwindows)) rc = GC_E_ARG;
     auto setup = [&]() -> int {
@@ -1238,6 +1324,36 @@ gc_stream_batch_out *gc_stream_batch_out_create(gc_stream_batch *s, size_t windo
     const int rc__ = gc::on_exception();
     if (status) *status = rc__;
     return nullptr;
+}
+
+gc_stream_batch_out *gc_stream_batch_out_create(gc_stream_batch *s, size_t window_bytes, uint32_t nwindows, int *status) {
+    return out_create(s, window_bytes, nwindows, false, status);
+}
+
+gc_stream_batch_out *gc_stream_batch_out_create_split(gc_stream_batch *s, size_t window_bytes, uint32_t nwindows, int *status) {
+    return out_create(s, window_bytes, nwindows, true, status);
+}
+
+int gc_stream_batch_out_split_stats(const gc_stream_batch_out *h, uint64_t *split_steps, uint64_t *segments) try {
+    if (!h) return GC_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (split_steps) *split_steps = h->split_steps;
+    if (segments) *segments = h->segments;
+    return GC_OK;
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_stream_batch_set_fallback(gc_stream_batch *s, int on) {
+    if (!s) return GC_E_ARG;
+    s->fallback = on != 0;
+    return GC_OK;
+}
+
+int gc_stream_eval_batch_set_fallback(gc_stream_eval_batch *e, int on) {
+    if (!e) return GC_E_ARG;
+    e->fallback = on != 0;
+    return GC_OK;
 }
 
 void gc_stream_batch_out_free(gc_stream_batch_out *h) { delete h; }

@@ -39,6 +39,10 @@ void launch_rows(const uint4 *src, const gc::Layout &sl, const uint32_t *srow, u
 // session s's step bytes at out + s * stride: the skeleton with row r = BE(D0) || BE(D1) of T[lt.at(r, s)]
 void launch_serialise(const StepDev &d, const uint4 *T, const gc::Layout &lt, uint8_t *out, size_t stride, uint32_t S,
                       hipStream_t s);
+// bytes [b0, b1) of the same, b1 <= d.nbytes: session s's byte b0 + i at out + s * stride + i (k_sb_serialise_range; any b0, any
+// alignment of out).  Writes b1 - b0 bytes per session and nothing else.
+void launch_serialise_range(const StepDev &d, const uint4 *T, const gc::Layout &lt, uint8_t *out, size_t stride, uint32_t S,
+                            uint32_t b0, uint32_t b1, hipStream_t s);
 // the inverse: rows of session s's block (in + s * stride) into T, and bad[s] += bytes outside the rows that differ from the
 // skeleton.  Reads bytes [0, nbytes) of every block and nothing else.
 void launch_ingest(const StepDev &d, uint4 *T, const gc::Layout &lt, const uint8_t *in, size_t stride, uint32_t S, uint32_t *bad,

@@ -73,6 +73,23 @@ __device__ __forceinline__ void piece_in(uint8_t *stage, const uint8_t *src, uin
 // room for the piece, its shift, and the 15 bytes by which a row that starts in the piece may reach beyond it
 constexpr uint32_t kStageBytes = kPieceBytes + 48;
 
+// session s's rows into the piece [lo, hi) at stage + sh, from row r0 on: every row that has a byte in the piece — a row across
+// a piece boundary is written by both pieces, each its own bytes
+__device__ __forceinline__ void piece_rows(uint8_t *stage, uint32_t sh, const StepDev &d, const uint4 *__restrict__ T, const Layout &lt,
+                                           uint32_t s, uint32_t r0, uint32_t lo, uint32_t hi) {
+    for (uint32_t r = r0 + threadIdx.x; r < d.nrows; r += kThreads) {
+        const uint32_t off = d.row_off[r];
+        if (off >= hi) break;
+        const uint4 v = label_be(T[lt.at(r, s)]);
+        const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (uint32_t k = 0; k < 16; k++) {
+            const uint32_t at = off + k;
+            if (at >= lo && at < hi) stage[sh + at - lo] = (uint8_t)(w4[k >> 2] >> (8 * (k & 3)));
+        }
+    }
+}
+
 __global__ __launch_bounds__(kThreads) void k_sb_serialise(StepDev d, const uint4 *__restrict__ T, Layout lt,
                                                            uint8_t *__restrict__ out, size_t stride) {
     __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
@@ -88,18 +105,54 @@ __global__ __launch_bounds__(kThreads) void k_sb_serialise(StepDev d, const uint
         q[0] = (uint8_t)w, q[1] = (uint8_t)(w >> 8), q[2] = (uint8_t)(w >> 16), q[3] = (uint8_t)(w >> 24);
     }
     __syncthreads();
-    // this session's rows: every row that has a byte in [lo, hi) — a row across a piece boundary is written by both pieces
-    for (uint32_t r = d.piece_row[p] + threadIdx.x; r < d.nrows; r += kThreads) {
-        const uint32_t off = d.row_off[r];
-        if (off >= hi) break;
-        const uint4 v = label_be(T[lt.at(r, s)]);
-        const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+    piece_rows(stage, sh, d, T, lt, s, d.piece_row[p], lo, hi);
+    __syncthreads();
+    piece_out(stage, dst, sh, nb);
+}
+
+// Bytes [b0, b1) of the step instead of all of them (a segment of a step that is split over windows: gc_stream_batch_out_create_split),
+// at out + s * stride + (byte - b0).  Piece p is [b0 + p * kPieceBytes, ...) of the step, so its first byte is at no particular
+// alignment in the skeleton (read as the aligned words around it) and its first row is not piece_row[]'s: it is found between
+// the table's entries for the two aligned pieces that the first byte lies between.
+__global__ __launch_bounds__(kThreads) void k_sb_serialise_range(StepDev d, const uint4 *__restrict__ T, Layout lt,
+                                                                 uint8_t *__restrict__ out, size_t stride, uint32_t b0, uint32_t b1) {
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
+    const uint32_t p = blockIdx.x, s = blockIdx.y;
+    const uint32_t lo = b0 + p * kPieceBytes, hi = min(lo + kPieceBytes, b1), nb = hi - lo;
+    uint8_t *dst = out + (size_t)s * stride + (lo - b0);
+    const uint32_t sh = (uint32_t)((uintptr_t)dst & 15u);
+    // the skeleton: the words [lo - a, ...) with the a bytes in front of the piece left out (behind it the stage has room, as above)
+    const uint32_t a = lo & 3u;
+    const uint32_t *sk = (const uint32_t *)(d.skel + (lo - a));
+    for (uint32_t k = threadIdx.x; 4 * k < nb + a; k += kThreads) {
+        const uint32_t w = sk[k];
+        uint8_t *q = stage + sh + 4 * k - a;
 #pragma unroll
-        for (uint32_t k = 0; k < 16; k++) {
-            const uint32_t at = off + k;
-            if (at >= lo && at < hi) stage[sh + at - lo] = (uint8_t)(w4[k >> 2] >> (8 * (k & 3)));
-        }
+        for (uint32_t j = 0; j < 4; j++)
+            if (4 * k + j >= a) q[j] = (uint8_t)(w >> (8 * j));
     }
+    // the first row that ends behind lo (row_off + 16 > lo; row_off ascends): rows [r0, r1) end in the aligned piece that holds lo,
+    // at most 256 of them (16 bytes each), so every lane looks at one and the barrier counts those that end at or before lo — a count per
+    // wave in the last 16 bytes of the stage, which a serialiser never fills (the piece ends at or before byte 15 + 4096 + 3)
+    static_assert(kThreads == 256 && kStageBytes >= 15 + kPieceBytes + 3 + 16 + 12, "four wave counts behind the piece");
+    uint32_t *cnt = (uint32_t *)(stage + kStageBytes - 16);
+    const uint32_t ap = lo / kPieceBytes;
+    uint32_t r0 = d.piece_row[ap], r1 = ap + 1 < d.npieces ? d.piece_row[ap + 1] : d.nrows;
+    if (r1 - r0 <= kThreads) {  // (uniform)
+        const uint32_t r = r0 + threadIdx.x;
+        const unsigned long long before = __ballot(r < r1 && d.row_off[r] + 16u <= lo);
+        if ((threadIdx.x & 63u) == 0) cnt[threadIdx.x >> 6] = (uint32_t)__popcll(before);
+        __syncthreads();
+        r0 += cnt[0] + cnt[1] + cnt[2] + cnt[3];
+    } else {  // (rows that overlap: no step_skeleton makes them; the same answer by bisection)
+        while (r0 < r1) {
+            const uint32_t mid = (r0 + r1) >> 1;
+            if (d.row_off[mid] + 16u > lo) r1 = mid;
+            else r0 = mid + 1;
+        }
+        __syncthreads();
+    }
+    piece_rows(stage, sh, d, T, lt, s, r0, lo, hi);
     __syncthreads();
     piece_out(stage, dst, sh, nb);
 }
@@ -317,6 +370,13 @@ void launch_rows(const uint4 *src, const Layout &sl, const uint32_t *srow, uint4
 void launch_serialise(const StepDev &d, const uint4 *T, const Layout &lt, uint8_t *out, size_t stride, uint32_t S, hipStream_t s) {
     if (d.npieces == 0 || S == 0) return;
     hipLaunchKernelGGL(k_sb_serialise, dim3(d.npieces, S), dim3(kThreads), 0, s, d, T, lt, out, stride);
+}
+
+void launch_serialise_range(const StepDev &d, const uint4 *T, const Layout &lt, uint8_t *out, size_t stride, uint32_t S, uint32_t b0,
+                            uint32_t b1, hipStream_t s) {
+    if (b0 >= b1 || b1 > d.nbytes || S == 0) return;
+    hipLaunchKernelGGL(k_sb_serialise_range, dim3((b1 - b0 + kPieceBytes - 1) / kPieceBytes, S), dim3(kThreads), 0, s, d, T, lt, out,
+                       stride, b0, b1);
 }
 
 void launch_ingest(const StepDev &d, uint4 *T, const Layout &lt, const uint8_t *in, size_t stride, uint32_t S, uint32_t *bad,

@@ -8,6 +8,8 @@
 //     [handed out ...][sealed ...][filling][free ...]
 // and three numbers describe it.  A step is planned first (plan_step changes nothing) and committed once the engine has
 // made what the plan asks for — a larger window — so that a failed allocation or a full ring leaves no trace.
+// A handle made by gc_stream_batch_out_create_split uses plan_split / commit_split instead of plan_step / commit (never both
+// on one ring): the same state, the same flush / next / release, and a step that is cut over the windows.
 #pragma once
 
 #include <cstddef>
@@ -82,6 +84,50 @@ struct WindowRing {
         bytes_per_session += n;
         if (p.seal_after) seal(p.win, off);
     }
+    // ---- the split rule (gc_stream_batch_out_create_split): a step goes behind what the filling window holds and
+    // on into the windows after it from their byte 0; no window is sealed short and none grows.  Every window has init's size.
+    struct Split {
+        bool is_busy = false;    // the filling window or one of the nwin - 1 behind it is sealed or handed out
+        bool too_large = false;  // n > (count - 1) * cap: no number of releases guarantees the room (off < cap)
+        uint32_t win = kNoWindow;  // the first window, written from offset `at`; window j of the step is (win + j) % count
+        size_t at = 0;
+        uint32_t nwin = 0;       // windows the step touches: ceil((at + n) / cap)
+        uint32_t nsealed = 0;    // the first nsealed of them become exactly full: nwin, or nwin - 1 when the last one does not
+        // segment j: bytes [begin(j), begin(j + 1)) of the step, written at offset (j ? 0 : at) of window j
+        size_t begin(uint32_t j, size_t n, size_t cap_) const { return j == 0 ? 0 : j >= nwin ? n : (size_t)j * cap_ - at; }
+    };
+
+    // what a step of n > 0 bytes per session does under the split rule; changes nothing
+    Split plan_split(size_t n) const {
+        Split p;
+        const size_t c = cap[0];
+        if (n > (size_t)(count() - 1) * c) {
+            p.too_large = true;
+            return p;
+        }
+        const uint32_t w = filling();
+        if (w == kNoWindow) {
+            p.is_busy = true;
+            return p;
+        }
+        const size_t end = off + n;
+        const uint32_t k = (uint32_t)((end + c - 1) / c);
+        if (n_out + n_sealed + k > count()) {
+            p.is_busy = true;
+            return p;
+        }
+        p.win = w, p.at = off, p.nwin = k;
+        p.nsealed = end % c == 0 ? k : k - 1;
+        return p;
+    }
+    // the plan has been carried out (every segment launched, the seals' events recorded by the caller)
+    void commit_split(const Split &p, size_t n) {
+        const size_t c = cap[0];
+        for (uint32_t j = 0; j < p.nsealed; j++) seal((p.win + j) % count(), c);
+        off = p.at + n - (size_t)p.nsealed * c;
+        bytes_per_session += n;
+    }
+
     // flush: the filling window if it holds any byte, else kNoWindow; *n = its bytes
     uint32_t plan_flush(size_t *n) const {
         const uint32_t w = filling();

@@ -150,6 +150,10 @@ def lib():
         "gc_stream_batch_out_next": (i32, [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
         "gc_stream_batch_out_release": (i32, [vp]),
         "gc_stream_batch_out_stats": (i32, [vp] + [C.POINTER(C.c_uint64)] * 4),
+        "gc_stream_batch_out_create_split": (vp, [vp, sz, u32, ip]),
+        "gc_stream_batch_out_split_stats": (i32, [vp] + [C.POINTER(C.c_uint64)] * 2),
+        "gc_stream_batch_set_fallback": (i32, [vp, i32]),
+        "gc_stream_eval_batch_set_fallback": (i32, [vp, i32]),
         "gc_stream_eval_batch_circuit_host": (i32, [vp, u32, u32, u32, vp, sz, sz, u32, C.POINTER(C.c_size_t)]),
         "gc_stream_eval_batch_uploads_wait": (i32, [vp]),
         "gc_stream_eval_batch_bad": (i32, [vp, vp]),
@@ -1148,9 +1152,14 @@ class StreamBatch:
         _check(lib().gc_stream_batch_decode(self.h, _p(i), len(i), _p(lab), _p(bits), _p(bad)), "gc_stream_batch_decode")
         return bits, bad
 
-    def out(self, window_bytes, nwindows):
-        """a StreamBatchOut of this handle: windows of stream bytes in pinned host memory; close it before this handle"""
-        return StreamBatchOut(self, window_bytes, nwindows)
+    def out(self, window_bytes, nwindows, split=False):
+        """a StreamBatchOut of this handle: windows of stream bytes in pinned host memory; close it before this handle.
+        split: a step is cut over the windows instead of sealing one short or growing it (gc_stream_batch_out_create_split)"""
+        return StreamBatchOut(self, window_bytes, nwindows, split)
+
+    def set_fallback(self, on=True):
+        """circuits loaded from now on whose key table alone keeps them out of the keyed scope run on the HBM-wire kernels"""
+        _check(lib().gc_stream_batch_set_fallback(self.h, 1 if on else 0), "gc_stream_batch_set_fallback")
 
     def cache_stats(self):
         """the circuit cache (gc_stream_batch_cache_stats): (entries, device bytes, loads, evictions)"""
@@ -1168,12 +1177,13 @@ class StreamBatchOut:
     """gc_stream_batch_out: the steps of a StreamBatch written into a ring of windows [S][cap] whose bytes arrive in pinned
     host memory while the next window fills.  One thread may garble / flush while one other takes windows and releases them."""
 
-    def __init__(self, sb, window_bytes, nwindows):
+    def __init__(self, sb, window_bytes, nwindows, split=False):
         self.sessions = sb.sessions
         st = C.c_int(0)
-        self.h = lib().gc_stream_batch_out_create(sb.h, window_bytes, nwindows, C.byref(st))
+        create = lib().gc_stream_batch_out_create_split if split else lib().gc_stream_batch_out_create
+        self.h = create(sb.h, window_bytes, nwindows, C.byref(st))
         if not self.h:
-            raise EngineError(st.value, "gc_stream_batch_out_create")
+            raise EngineError(st.value, "gc_stream_batch_out_create_split" if split else "gc_stream_batch_out_create")
 
     def garble(self, prefix, gates, nwires, in_, out_):
         """one step behind `prefix` (bytes, at most 64) for every session; returns the bytes written per session.  Raises
@@ -1215,6 +1225,12 @@ class StreamBatchOut:
         _check(lib().gc_stream_batch_out_stats(self.h, *[C.byref(x) for x in v]), "gc_stream_batch_out_stats")
         return tuple(int(x.value) for x in v)
 
+    def split_stats(self):
+        """(steps that touched more than one window, serialiser launches); zeros on an unsplit handle"""
+        v = [C.c_uint64(0) for _ in range(2)]
+        _check(lib().gc_stream_batch_out_split_stats(self.h, *[C.byref(x) for x in v]), "gc_stream_batch_out_split_stats")
+        return tuple(int(x.value) for x in v)
+
     def close(self):
         if self.h:
             lib().gc_stream_batch_out_free(self.h)
@@ -1235,6 +1251,11 @@ class StreamEvalBatch:
         """d_labels: device gc_label [S][len(ids)]; asynchronous"""
         i = np.ascontiguousarray(ids, dtype=np.uint32)
         _check(lib().gc_stream_eval_batch_set_wires(self.h, _p(i), len(i), _dp(d_labels)), "gc_stream_eval_batch_set_wires")
+
+    def set_fallback(self, on=True):
+        """blocks whose circuit is loaded from now on and kept out of the keyed scope by the key table alone run on the HBM-wire
+        kernels (circuit, circuit_host and the intake)"""
+        _check(lib().gc_stream_eval_batch_set_fallback(self.h, 1 if on else 0), "gc_stream_eval_batch_set_fallback")
 
     def get(self, w):
         """LABEL [S]: the active label of global wire w in every session (waits for the ctx stream)"""

@@ -33,6 +33,12 @@ session; four forms alternate after an untimed pass of each, a window is one who
 The criterion: all (c) windows below all (b) windows.  GC_STREAM_BATCH_OUT_WHOLE_ROWS=1 in the environment makes (c) copy whole
 windows in one piece instead of the used columns.
 
+--egress --split: today's window handle beside the split handle (gc_stream_batch_out_create_split), one JSON line
+per (S, --windows).  Windows of 1 MiB per session; the two handles alternate after an untimed pass of each with the consumer
+thread of (c); per form the time, the bytes the handle pins (the unsplit handle's windows grow to the step: its sizes are
+worked out from the rule of stream_batch_windows.h), `grown` and `sealed`.  With --program big130_16 every step exceeds the window.
+--split-once S runs three passes of each form and nothing else: the run a kernel trace is taken of.
+
 --intake: the evaluator driven from the garbler's windows, one JSON line per S.  The program is garbled ONCE
 through gc_stream_batch_out_* behind real OpCircuit headers, windows of 1 MiB per session, and every window is kept in pinned
 memory.  Two forms alternate after an untimed pass of each, which also checks that both leave the same store
@@ -312,6 +318,109 @@ def egress(ctx, prog, S, reps):
     return row
 
 
+class SplitEgress:
+    """today's window handle and the split handle on one Batch's garbler, each drained by a consumer thread that only releases"""
+
+    def __init__(self, ctx, prog, b, nwindows):
+        import threading
+        self.threading = threading
+        self.ctx, self.prog, self.b, self.S, self.cap, self.nwindows = ctx, prog, b, b.S, EGRESS_WINDOW, nwindows
+        if max(prog.sizes) + 20 > (nwindows - 1) * self.cap:
+            raise engine.EngineError(engine.GC_E_ARG, "a step of %d bytes needs more than %d windows" % (max(prog.sizes) + 20, nwindows))
+        self.out = {"windows": b.sb.out(self.cap, nwindows), "split": b.sb.out(self.cap, nwindows, split=True)}
+        self.prefix = np.arange(20, dtype=np.uint8)
+        self.n = C.c_size_t(0)
+
+    def unsplit_pinned_bytes(self):
+        """what the unsplit handle pins after a pass: an empty window grows to a step that exceeds it, to a multiple of 4 096"""
+        caps, w, off = [self.cap] * self.nwindows, 0, 0
+        for n in self.prog.sizes:
+            n += 20
+            if off and off + n > caps[w]:
+                w, off = (w + 1) % self.nwindows, 0
+            if off == 0 and n > caps[w]:
+                caps[w] = (n + 4095) & ~4095
+            off += n
+            if off == caps[w]:
+                w, off = (w + 1) % self.nwindows, 0
+        return self.S * sum(caps)
+
+    def run(self, form):
+        out = self.out[form]
+        L, pn, h = engine.lib(), C.byref(self.n), out.h
+        garble, pre = L.gc_stream_batch_out_garble, self.prefix.ctypes.data_as(C.c_void_p)
+        flushed = self.threading.Event()
+
+        def consumer():
+            while True:
+                last = flushed.is_set()
+                if out.next() is None:
+                    if last:
+                        return
+                    time.sleep(0.0001)
+                    continue
+                out.release()
+
+        t = self.threading.Thread(target=consumer)
+        t.start()
+        try:
+            for k, a in enumerate(self.prog.args.begin):
+                while True:
+                    rc = garble(h, pre, 20, *a, pn)
+                    if rc != engine.GC_E_BUSY:
+                        break
+                    time.sleep(0.00005)  # (no window is free: let the consumer run)
+                if rc:
+                    raise engine.EngineError(rc, "gc_stream_batch_out_garble(step %d, %s)" % (k, form))
+            out.flush()
+        finally:
+            flushed.set()
+            t.join()
+
+    def window(self, form):
+        self.ctx.sync()
+        t0 = time.perf_counter()
+        self.run(form)
+        self.ctx.sync()
+        return time.perf_counter() - t0
+
+    def close(self):
+        for o in self.out.values():
+            o.close()
+
+
+def egress_split(ctx, prog, S, reps, nwindows):
+    head = {"bench": "stream_batch_egress_split", "program": PROGRAM, "sessions": S, "window_bytes": EGRESS_WINDOW, "windows": nwindows}
+    b = Batch(ctx, prog, S, np.zeros(prog.bytes, np.uint8))  # (the evaluator is not run here)
+    try:
+        e = SplitEgress(ctx, prog, b, nwindows)
+    except engine.EngineError as err:
+        b.close()
+        return dict(head, skipped="windows not allocated: %s" % err)
+    forms = ("windows", "split")
+    for f in forms:
+        e.window(f)
+    first = {f: e.out[f].stats() for f in forms}
+    t = {f: [] for f in forms}
+    for _ in range(reps):
+        for f in forms:
+            t[f].append(e.window(f))
+    row = dict(head, key_bytes=32, steps=len(prog.steps), bytes_per_session=prog.bytes + 20 * len(prog.steps), reps=reps,
+               largest_step_bytes=max(prog.sizes) + 20)
+    for f in forms:
+        sealed, _, grown, busy = e.out[f].stats()
+        row[f] = {"seconds": statistics.median(t[f]), "seconds_all": t[f], "grown": grown,
+                  "sealed_per_pass": (sealed - first[f][0]) / reps, "busy_answers_per_pass": (busy - first[f][3]) / reps,
+                  "pinned_bytes_of_the_handle": e.unsplit_pinned_bytes() if f == "windows" else nwindows * S * e.cap}
+    steps, segments = e.out["split"].split_stats()
+    row["split"].update(split_steps_per_pass=steps / (reps + 1), segments_per_pass=segments / (reps + 1))
+    row["split_over_windows"] = row["split"]["seconds"] / row["windows"]["seconds"]
+    row["ranges_overlap"] = not (max(t["split"]) < min(t["windows"]) or max(t["windows"]) < min(t["split"]))
+    e.close()
+    b.close()
+    return row
+
+
 class Intake:
     """the garbler's windows of a Batch in pinned memory, and the two ways of an evaluator through them"""
 
@@ -485,6 +594,10 @@ def main():
     ap.add_argument("--out", default=None, help="also append the lines to this file")
     ap.add_argument("--egress", action="store_true", help="the garbler's bytes to host memory: device-only, synchronous download, "
                                                           "gc_stream_batch_out_* windows, the copy alone")
+    ap.add_argument("--split", action="store_true", help="with --egress: today's window handle beside the split handle")
+    ap.add_argument("--windows", type=int, nargs="*", default=[3, 4], help="with --egress --split: windows per handle")
+    ap.add_argument("--split-once", type=int, default=None, help="three passes through today's window handle, then three through "
+                                                                 "the split handle, at this many sessions (for a kernel trace)")
     ap.add_argument("--intake", action="store_true", help="the evaluator through the garbler's windows: one call per step beside "
                                                           "one gc_stream_eval_batch_in_feed per window")
     ap.add_argument("--intake-once", type=int, default=None, help="one intake pass at this many sessions (for a kernel trace)")
@@ -513,6 +626,17 @@ def main():
     elif a.intake:
         for S in a.sessions:
             emit(intake(ctx, prog, S, a.reps))
+    elif a.split_once:
+        b = Batch(ctx, prog, a.split_once, np.zeros(prog.bytes, np.uint8))
+        e = SplitEgress(ctx, prog, b, a.windows[0])
+        for f in ("windows", "split"):
+            print(f, [round(e.window(f), 4) for _ in range(3)], flush=True)
+        e.close()
+        b.close()
+    elif a.egress and a.split:
+        for S in a.sessions:
+            for nw in a.windows:
+                emit(egress_split(ctx, prog, S, a.reps, nw))
     elif a.egress:
         for S in a.sessions:
             emit(egress(ctx, prog, S, a.reps))
