@@ -256,6 +256,38 @@ func (p *BatchPipeline) SetKeysPath(path int) error {
 	return nil
 }
 
+// KeysHbmForm reports which form of the HBM-wire kernels the keyed calls run now (gc_batch_keyed_hbm_form): 0 when KeysPath is
+// not 2, 1 the plain form, 2 the split form, which gives the hashed and the free gates of a wide level to different waves.
+func (p *BatchPipeline) KeysHbmForm() int {
+	g, e := int(C.gc_batch_keyed_hbm_form(p.gb)), int(C.gc_batch_keyed_hbm_form(p.ev))
+	if g != e {
+		return 0
+	}
+	return g
+}
+
+// SetKeysHbmForm fixes the form for both batches: 0 the rule, 1 always plain, 2 always split.  The bytes do not change.
+func (p *BatchPipeline) SetKeysHbmForm(form int) error {
+	if st := C.gc_batch_set_keyed_hbm_form(p.gb, C.int(form)); st != C.GC_OK {
+		return statusError(st)
+	}
+	if st := C.gc_batch_set_keyed_hbm_form(p.ev, C.int(form)); st != C.GC_OK {
+		return statusError(st)
+	}
+	return nil
+}
+
+// DebugKeysHbmHashWaves fixes the hash waves of every split level (1 .. 15; 0 the rule), a developer aid for measurements.
+func (p *BatchPipeline) DebugKeysHbmHashWaves(garble, eval uint32) error {
+	if st := C.gc_batch_debug_keyed_hbm_hash_waves(p.gb, C.uint32_t(garble), C.uint32_t(eval)); st != C.GC_OK {
+		return statusError(st)
+	}
+	if st := C.gc_batch_debug_keyed_hbm_hash_waves(p.ev, C.uint32_t(garble), C.uint32_t(eval)); st != C.GC_OK {
+		return statusError(st)
+	}
+	return nil
+}
+
 func (p *BatchPipeline) uploadKeys(keys []byte, keylen int) error {
 	if keylen != 16 && keylen != 24 && keylen != 32 {
 		return aes.KeySizeError(keylen) // same error as Garble / Eval (garble.go:260, eval.go:20)

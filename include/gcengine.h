@@ -475,6 +475,20 @@ int gc_batch_keyed_path(const gc_batch *);
  * at the HBM-wire kernels' cost.  Other values, schedule 0 / 2: GC_E_ARG.  Graphs captured before stay valid for what
  * they captured. */
 int gc_batch_set_keyed_path(gc_batch *, int path);
+/* Path 2 has two forms with the same bytes, one launch each (gc_batch_last_launches 1), nothing reaching the host: the plain
+ * form walks a level in passes of the whole workgroup; the split form gives the hashed and the free gates of a level wider than
+ * 1 024 column lanes to different waves.  form 0 (default): the rule — the split form when the plan has such levels in that
+ * pass's lane count at the batch's tile width and they average three passes of 1 024 lanes or more (below that the split
+ * form measured no faster: DESIGN.md §15), the plain form otherwise.  1: always plain.  2: always split (a narrow circuit
+ * then runs the split kernels' single-pass branch throughout).  Other values: GC_E_ARG.  Holds for any path-2 pass of the
+ * batch, forced or natural.  Graphs captured before stay valid for what they captured. */
+int gc_batch_set_keyed_hbm_form(gc_batch *, int form);
+/* what the keyed calls would run now: 0 when gc_batch_keyed_path is not 2, else 1 (plain) or 2 (split); under the rule the
+ * answer is the garbler's (an evaluation splits only where its own, smaller lane count has a wide level) */
+int gc_batch_keyed_hbm_form(const gc_batch *);
+/* developer aid: hash waves of every split level of the garbler's / the evaluator's pass, 1 .. 15, still capped by the lanes
+ * the level has; 0 = the rule.  Values above 15: GC_E_ARG */
+int gc_batch_debug_keyed_hbm_hash_waves(gc_batch *, uint32_t garble_h, uint32_t eval_h);
 /* BitFromLabel (circuit/helpers.go:18-28) for every output wire: d_bits_out = u8 [batch][noutputs];
  * *d_mismatch (u32, device) counts labels that match neither L0 nor L1 */
 int gc_batch_decode(const gc_batch *garbler, const gc_batch *evaluator, void *d_bits_out, void *d_mismatch);

@@ -493,6 +493,10 @@ private:
 inline bool BatchKeysSupported(const gc_batch *b) { return gc_batch_keyed_supported(b) != 0; }
 inline int BatchKeysPath(const gc_batch *b) { return gc_batch_keyed_path(b); }
 inline void SetBatchKeysPath(gc_batch *b, int path) { check(gc_batch_set_keyed_path(b, path), "gc_batch_set_keyed_path"); }
+// BatchKeysHbmForm: gc_batch_keyed_hbm_form (0 not on path 2, 1 the plain form of the HBM-wire kernels, 2 the split form with
+// hash waves and free waves on wide levels); SetBatchKeysHbmForm: 0 the rule, 1 always plain, 2 always split
+inline int BatchKeysHbmForm(const gc_batch *b) { return gc_batch_keyed_hbm_form(b); }
+inline void SetBatchKeysHbmForm(gc_batch *b, int form) { check(gc_batch_set_keyed_hbm_form(b, form), "gc_batch_set_keyed_hbm_form"); }
 inline void GarbleBatchKeys(gc_batch *b, const void *d_keys, size_t keylen, const void *d_rnd) {
     if (keylen != 16 && keylen != 24 && keylen != 32) throw Error("crypto/aes: invalid key size " + std::to_string(keylen));
     check(gc_batch_garble_keyed(b, d_keys, keylen, d_rnd), "gc_batch_garble_keyed");

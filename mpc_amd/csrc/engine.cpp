@@ -1,6 +1,7 @@
 // engine.cpp — C ABI of libgcengine.so: contexts, circuits, batches, host-buffer entry points.
 // (HIP host code; kernels are in gc_kernels.hip / ot_kernels.hip.)
 #include "engine.h"
+#include "hbm_keyed_split.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1167,6 +1168,30 @@ int gc_batch_set_keyed_path(gc_batch *b, int path) {
     return GC_OK;
 }
 
+// Which form of the path-2 kernels a keyed pass of this batch runs: the split form (fused_hbm_keyed_split_kernels.hip) when the
+// plan's levels wider than one pass of the workgroup, in that role's lane count, hold three passes or more on average
+// (hks_plan_splits), the plain form otherwise, unless gc_batch_set_keyed_hbm_form fixed one.  The garbler's lane count of a
+// level is never below the evaluator's.
+static int keyed_hbm_form(const gc_batch *b, bool eval) {
+    const Plan &p = b->circ->plan.p;
+    return hks_form(b->keyed_hbm_form, hks_plan_splits(p.levels.data(), (uint32_t)p.levels.size(), b->g.ti_log2, eval));
+}
+
+int gc_batch_set_keyed_hbm_form(gc_batch *b, int form) {
+    if (!b || form < 0 || form > 2) return GC_E_ARG;
+    b->keyed_hbm_form = form;
+    return GC_OK;
+}
+
+int gc_batch_keyed_hbm_form(const gc_batch *b) { return gc_batch_keyed_path(b) == 2 ? keyed_hbm_form(b, false) : 0; }
+
+int gc_batch_debug_keyed_hbm_hash_waves(gc_batch *b, uint32_t garble_h, uint32_t eval_h) {
+    if (!b || garble_h >= kHksWaves || eval_h >= kHksWaves) return GC_E_ARG;
+    b->keyed_hbm_tune[0] = garble_h;
+    b->keyed_hbm_tune[1] = eval_h;
+    return GC_OK;
+}
+
 static int keyed_rounds(size_t keylen) { return keylen == 16 ? 10 : keylen == 24 ? 12 : keylen == 32 ? 14 : 0; }
 
 // d_keys u8 [batch][keylen] -> b->d_keyed_rk, on the ctx stream: part of the pass (and of a captured graph), so a replay
@@ -1195,7 +1220,11 @@ static int run_keyed(gc_batch *b, bool eval, const void *d_keys, size_t keylen, 
     if (path == 2 && !eval) launch_init_garble(rnd, p.info.ninputs, b->d_W, b->d_R, b->g, ctx->stream);
     return timed_pass(b, [&]() -> int {
         if (path == 2) {
-            GC_HIP(launch_fused_hbm_keyed(eval, fused_args(b, T, b->d_keyed_rk, rounds), b->d_keyed_rk, p.info.n_or != 0, b->g, ctx->stream));
+            const FusedArgs f = fused_args(b, T, b->d_keyed_rk, rounds);
+            if (keyed_hbm_form(b, eval) == 2)
+                GC_HIP(launch_fused_hbm_keyed_split(eval, f, b->d_keyed_rk, p.info.n_or != 0, b->g, b->keyed_hbm_tune[eval], ctx->stream));
+            else
+                GC_HIP(launch_fused_hbm_keyed(eval, f, b->d_keyed_rk, p.info.n_or != 0, b->g, ctx->stream));
             b->last_launches = 1;
             b->have_all_wires = true;
             return GC_OK;

@@ -140,6 +140,8 @@ struct gc_batch {
     bool single_phase = false;   // fused-LDS passes walk the XOR levels (fused_lds_kernels.hip) instead of the flat plan
     bool have_all_wires = false; // the global wire array holds every wire of the last pass
     int keyed_force = 0;         // gc_batch_set_keyed_path: 2 = the keyed calls take the HBM-wire kernels whatever the geometry
+    int keyed_hbm_form = 0;      // gc_batch_set_keyed_hbm_form: 0 = the rule (hbm_keyed_split.h), 1 = plain, 2 = split
+    uint32_t keyed_hbm_tune[2] = {0, 0};  // gc_batch_debug_keyed_hbm_hash_waves: garble, eval; 0 = the rule
     std::vector<gc_graph_entry> graphs;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;

@@ -186,6 +186,11 @@ hipError_t launch_fused_flat_keyed(bool eval, const FusedFlatArgs &a, const Batc
 size_t fused_hbm_keyed_bytes(uint32_t ti_log2, int rounds);
 hipError_t launch_fused_hbm_keyed(bool eval, const FusedArgs &a, const uint32_t *rk_per_instance, bool has_or, const BatchGeom &g,
                                   hipStream_t s);
+// The split form of the same pass (fused_hbm_keyed_split_kernels.hip): the same arguments, LDS image and bytes; levels wider than
+// one pass of the workgroup share its waves out between the hashed and the free gates (hbm_keyed_split.h).  tune: hash waves
+// of every split level, 1 .. 15, for measurements; 0 = the rule.
+hipError_t launch_fused_hbm_keyed_split(bool eval, const FusedArgs &a, const uint32_t *rk_per_instance, bool has_or,
+                                        const BatchGeom &g, uint32_t tune, hipStream_t s);
 
 // What one workgroup of the flattened kernels needs.  The batch launches pass ONE of these as the kernel argument (every
 // workgroup = one tile of the same circuit); the streaming engine's step groups pass an ARRAY in device memory, one

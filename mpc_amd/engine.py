@@ -185,6 +185,9 @@ def lib():
         "gc_batch_keyed_supported": (i32, [vp]),
         "gc_batch_keyed_path": (i32, [vp]),
         "gc_batch_set_keyed_path": (i32, [vp, i32]),
+        "gc_batch_set_keyed_hbm_form": (i32, [vp, i32]),
+        "gc_batch_keyed_hbm_form": (i32, [vp]),
+        "gc_batch_debug_keyed_hbm_hash_waves": (i32, [vp, u32, u32]),
         "gc_batch_debug_keyed_schedule": (i32, [vp, vp, sz, vp, vp]),
         "gc_batch_read_r": (i32, [vp, vp]),
         "gc_batch_read_slab": (i32, [vp, vp]),
@@ -787,6 +790,20 @@ class Batch:
     def set_keyed_path(self, path):
         """gc_batch_set_keyed_path: 2 sends the keyed calls to the HBM-wire kernels whatever the batch's geometry, 0 is the rule"""
         _check(lib().gc_batch_set_keyed_path(self.h, int(path)), "gc_batch_set_keyed_path")
+
+    @property
+    def keyed_hbm_form(self):
+        """which form of the HBM-wire kernels the keyed calls run on this batch now (gc_batch_keyed_hbm_form): 0 when keyed_path
+        is not 2, 1 the plain form, 2 the split form (hash waves and free waves on levels wider than 1 024 column lanes)"""
+        return int(lib().gc_batch_keyed_hbm_form(self.h))
+
+    def set_keyed_hbm_form(self, form):
+        """gc_batch_set_keyed_hbm_form: 0 the rule, 1 always the plain form, 2 always the split form"""
+        _check(lib().gc_batch_set_keyed_hbm_form(self.h, int(form)), "gc_batch_set_keyed_hbm_form")
+
+    def debug_keyed_hbm_hash_waves(self, garble_h, eval_h):
+        """gc_batch_debug_keyed_hbm_hash_waves: fix the hash waves of every split level (1 .. 15, 0 the rule), for measurements"""
+        _check(lib().gc_batch_debug_keyed_hbm_hash_waves(self.h, int(garble_h), int(eval_h)), "gc_batch_debug_keyed_hbm_hash_waves")
 
     def garble_keyed(self, d_keys, keylen, d_rnd):
         """gc_batch_garble_keyed: d_keys = device u8 [batch][keylen], one AES key per instance"""

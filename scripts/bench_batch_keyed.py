@@ -20,7 +20,11 @@ rounds is reported with every round beside it.
   (a) the synthetic levelised circuit of bench.py's `synthetic` row (131 072 gates, W = 1 024, f = 0.17) x 1 024, whose wires
       are in HBM: the one-key HBM-wire pass against keyed path 2;
   (b) aes_128 x 1 024: keyed path 1 (wires in LDS) against path 2 forced with gc_batch_set_keyed_path — what the fall-back
-      costs a batch that could run in LDS; the one-key pass beside them."""
+      costs a batch that could run in LDS; the one-key pass beside them.
+--form F (with --hbm): gc_batch_set_keyed_hbm_form on the path-2 batches, 0 the rule, 1 the plain form, 2 the split form (hash
+waves and free waves on wide levels); the line's `form` is what gc_batch_keyed_hbm_form then reports, `form_setting` is F.
+--hsweep (with --hbm): the synthetic row only, split form, the hash waves of every split level fixed at H = 4 .. 15 for both
+roles (gc_batch_debug_keyed_hbm_hash_waves), the plain form and the rule beside them: one text line per setting."""
 import argparse
 import json
 import os
@@ -139,7 +143,7 @@ def measure(ctx, c, batch, reps, seconds, sample):
     return row
 
 
-def measure_hbm(ctx, c, batch, reps, seconds, forced):
+def measure_hbm(ctx, c, batch, reps, seconds, forced, form=0):
     """forced = False: one key against keyed path 2 on a batch whose wires are in HBM; True: one key, keyed path 1 and keyed
     path 2 (a second pair of batches sent there) on a batch whose wires are in LDS"""
     rng = np.random.default_rng(7)
@@ -151,6 +155,9 @@ def measure_hbm(ctx, c, batch, reps, seconds, forced):
     keys = rng.integers(0, 256, (batch, 32), dtype=np.uint8)
     d_keys = ctx.to_device(keys)
     key = keys[0].tobytes()
+    if not forced:
+        for b in (gb, ev):
+            b.set_keyed_hbm_form(form)
     g1, e1 = graphs_of(ctx, gb, ev, d_bits, lambda: gb.garble(key, d_rnd), lambda: ev.eval(key, gb))
     gk, ek = graphs_of(ctx, gb, ev, d_bits, lambda: gb.garble_keyed(d_keys, 32, d_rnd), lambda: ev.eval_keyed(d_keys, 32, gb))
     passes = {"garble": g1.launch, "eval": e1.launch}
@@ -159,6 +166,7 @@ def measure_hbm(ctx, c, batch, reps, seconds, forced):
         gb2, ev2 = engine.Batch(dc, batch), engine.Batch(dc, batch)
         for b in (gb2, ev2):
             b.set_keyed_path(2)
+            b.set_keyed_hbm_form(form)
         g2, e2 = graphs_of(ctx, gb2, ev2, d_bits, lambda: gb2.garble_keyed(d_keys, 32, d_rnd), lambda: ev2.eval_keyed(d_keys, 32, gb2))
         passes.update({"path1_garble": gk.launch, "path1_eval": ek.launch, "path2_garble": g2.launch, "path2_eval": e2.launch})
         graphs += [g2, e2]
@@ -173,6 +181,7 @@ def measure_hbm(ctx, c, batch, reps, seconds, forced):
         "bench": "batch_keyed_hbm", "circuit": c.name, "batch": batch, "key_bytes": 32, "tile_instances": gb.tile_instances,
         "gates": int(dc.info.ngates), "and_gates": int(dc.info.n_and), "levels": int(dc.info.nlevels), "reps": reps,
         "window_s": seconds, "wires_in_lds_under_one_key": bool(forced),
+        "form": batches[-1].keyed_hbm_form, "form_setting": form,
         "one_key_garble_ms": med["garble"], "one_key_eval_ms": med["eval"],
         "path2_garble_ms": med["path2_garble"], "path2_eval_ms": med["path2_eval"],
         "path2_over": "keyed path 1" if forced else "the one-key HBM-wire pass",
@@ -191,13 +200,52 @@ def measure_hbm(ctx, c, batch, reps, seconds, forced):
     return row
 
 
+def main_hsweep(ctx, c, batch, reps, seconds, out):
+    """the synthetic row under the split form with H fixed for both roles, the plain form and the rule beside them"""
+    rng = np.random.default_rng(7)
+    dc = engine.DeviceCircuit(ctx, c)
+    gb, ev = engine.Batch(dc, batch), engine.Batch(dc, batch)
+    assert gb.keyed_path == ev.keyed_path == 2
+    d_rnd = ctx.random_u8((batch, c.num_inputs + 1, 16), 256, seed=1234)
+    d_bits = ctx.random_u8((batch, c.num_inputs), 2, seed=4321)
+    d_keys = ctx.to_device(rng.integers(0, 256, (batch, 32), dtype=np.uint8))
+    settings = [("plain", 1, 0)] + [("H=%d" % h, 2, h) for h in range(4, 16)] + [("rule", 0, 0), ("plain", 1, 0)]
+    head = "# %s x %d, tiles of %d, 32-byte keys; ms per pass, median of %d windows of %.2f s (all windows in brackets)" % (
+        c.name, batch, gb.tile_instances, reps, seconds)
+    lines = [head]
+    print(head, flush=True)
+    for name, form, h in settings:
+        for b in (gb, ev):
+            b.set_keyed_hbm_form(form)
+            b.debug_keyed_hbm_hash_waves(h, h)
+        gk, ek = graphs_of(ctx, gb, ev, d_bits, lambda: gb.garble_keyed(d_keys, 32, d_rnd), lambda: ev.eval_keyed(d_keys, 32, gb))
+        t = alternate(ctx, {"garble": gk.launch, "eval": ek.launch}, reps, seconds)
+        line = "%-6s form %d  garble %.3f ms %s  eval %.3f ms %s" % (
+            name, gb.keyed_hbm_form, statistics.median(t["garble"]), ["%.3f" % v for v in t["garble"]],
+            statistics.median(t["eval"]), ["%.3f" % v for v in t["eval"]])
+        print(line, flush=True)
+        lines.append(line)
+        gk.close()
+        ek.close()
+    if out:
+        with open(out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+    gb.close()
+    ev.close()
+    dc.close()
+
+
 def main_hbm(ctx, a):
-    syn = circuit.synthetic_levelised(128, 1024, 0.17, seed=101, ninputs=256)  # scripts/sweep_synthetic.py: the (1 024, 0.17) row
-    syn.name = "synthetic_w1024_f0.17"
+    w, frac = a.synthetic_width, a.synthetic_frac  # scripts/sweep_synthetic.py: the (1 024, 0.17) row by default
+    syn = circuit.synthetic_levelised(131072 // w, w, frac, seed=101, ninputs=256)
+    syn.name = "synthetic_w%d_f%g" % (w, frac)
+    if a.hsweep:
+        main_hsweep(ctx, syn, a.batch, a.reps, a.window, a.out)
+        return
     aes = parse_file(os.path.join(ROOT, "tests", "golden", "aes_128.gcf"))
     aes.name = "aes_128"
-    for c, forced in ((syn, False), (aes, True)):
-        line = json.dumps(measure_hbm(ctx, c, 1024, a.reps, a.window, forced))
+    for c, forced in ((syn, False), (aes, True))[: 2 if (w, frac, a.batch) == (1024, 0.17, 1024) else 1]:
+        line = json.dumps(measure_hbm(ctx, c, a.batch, a.reps, a.window, forced, a.form))
         print(line, flush=True)
         if a.out:
             with open(a.out, "a") as f:
@@ -207,6 +255,11 @@ def main_hbm(ctx, a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--hbm", action="store_true", help="the keyed HBM-wire kernels (path 2) instead: see the module docstring")
+    ap.add_argument("--form", type=int, default=0, choices=[0, 1, 2], help="with --hbm: the form of the path-2 kernels (0 the rule)")
+    ap.add_argument("--synthetic-width", type=int, default=1024, help="with --hbm: gates per level of the synthetic row (131 072 in all)")
+    ap.add_argument("--synthetic-frac", type=float, default=0.17, help="with --hbm: AND fraction of the synthetic row")
+    ap.add_argument("--batch", type=int, default=1024, help="with --hbm: instances (another shape than the default one drops the aes_128 row)")
+    ap.add_argument("--hsweep", action="store_true", help="with --hbm: the synthetic row with the hash waves fixed at 4 .. 15")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.2)
     ap.add_argument("--sample", type=int, default=64, help="one-instance batches the sequential row is timed on")
