@@ -1317,6 +1317,44 @@ int gc_sha2pc_evaluator_round4(gc_sha2pc_evaluator *, const gc_p256_point *A, co
                                const uint8_t *bits, const uint8_t *r3, uint8_t *digest_out, uint32_t *verdict,
                                size_t *bad_session);
 
+/* ------------------------------------------------------------------------------------------
+ * Device random streams: AES-CTR draws for S sessions per call (additive)
+ * Every call above takes its randomness as a device array.  A gc_rand handle writes such arrays from S seeds: stream s is
+ * what a Go host reads from cipher.StreamReader{S: cipher.NewCTR(aes.NewCipher(seed[s]), iv[s]), R: zeros}, the reader it
+ * would set as env.Config.Rand: block j of the stream is AES_seed[s](iv[s] + j), the sum taken on the 16-byte big-endian
+ * counter, carry through all 16 bytes, wrapping silently.  The engine invents no entropy: the seeds are the caller's, one
+ * per session, never reseeded; a handle serves at most 2^64 - 1 bytes per stream.
+ *   Create.  seeds [S][keylen] with keylen 16 / 24 / 32, ivs [S][16] or NULL for all-zero IVs (host arrays, or with _dev
+ *   device arrays read behind what is queued on the ctx stream).  Expands the S key schedules on the device into arrays the
+ *   handle owns; synchronous, not between gc_ctx_capture_begin and _end.  NULL and *status (which may be NULL): GC_E_KEYSIZE
+ *   for another keylen, GC_E_ARG for S = 0 or a NULL ctx or seeds, GC_E_NOMEM.  Free waits for the ctx stream first (free a
+ *   handle before its ctx); NULL is a no-op.
+ *   Position.  The handle holds ONE byte position for all S streams (as gc_iknp_multi: sessions advance in lock step).  A
+ *   draw of n bytes advances it by n, and successive draws continue the streams as successive Reads on the Go reader do,
+ *   whatever the block boundaries.  gc_rand_seek sets it, gc_rand_info reads it (any pointer may be NULL).
+ *   gc_rand_fill_dev: the next nbytes of stream s go to d_out + s * stride, stride >= nbytes; bytes of a slot behind nbytes
+ *   are not written.  One launch on the ctx stream; allocates nothing, waits for nothing.  Slots whose position-aligned
+ *   blocks fall on multiples of 16 bytes are written in 16-byte words, any other slot bytewise.  The garbler's order
+ *   (circuit/garbler.go:47-53, circuit/garble.go:253,272) is two draws on one handle: (32, d_keys, 32), then
+ *   (16 (1 + ninputs), d_rnd, 16 (1 + ninputs)): the d_keys and d_rnd of gc_batch_garble_keyed.
+ *   gc_rand_fill: the same into a host array (staged, synchronous).
+ *   gc_rand_gmw_shares_dev: tripleBatch's draw loop (gmw/triples.go:301-310): for each of `words` draws of 16 bytes,
+ *   a[s][i] = BE64(bytes 0..7), b[s][i] = BE64(bytes 8..15), native u64 [S][words] as gc_gmw_triples_local_dev and
+ *   gc_gmw_set_triples_dev take them; advances the position by 16 * words and needs a position that is a multiple of 16.
+ *   Errors.  nbytes = 0 and words = 0 return GC_OK and do nothing.  GC_E_ARG, the position unchanged: a NULL handle or
+ *   array, stride < nbytes, a position that is no multiple of 16 (shares), a position or size past uint64_t / size_t, any
+ *   draw between gc_ctx_capture_begin and _end (the position is a kernel argument; the rule of gc_iknp_multi_*).
+ *   Not offered: draws inside a captured graph, per-session positions, the rejection-sampled scalars of crand.Int. */
+typedef struct gc_rand gc_rand;
+gc_rand *gc_rand_create(gc_ctx *, const uint8_t *seeds, size_t keylen, const uint8_t *ivs, size_t S, int *status);
+gc_rand *gc_rand_create_dev(gc_ctx *, const void *d_seeds, size_t keylen, const void *d_ivs, size_t S, int *status);
+void gc_rand_free(gc_rand *); /* waits for the ctx stream; NULL is a no-op */
+int gc_rand_info(const gc_rand *, size_t *S, size_t *keylen, uint64_t *pos);
+int gc_rand_seek(gc_rand *, uint64_t pos); /* byte position of every stream */
+int gc_rand_fill_dev(gc_rand *, size_t nbytes, void *d_out, size_t stride);
+int gc_rand_fill(gc_rand *, size_t nbytes, uint8_t *out, size_t stride); /* host form, staged */
+int gc_rand_gmw_shares_dev(gc_rand *, size_t words, void *d_a, void *d_b);
+
 #ifdef __cplusplus
 }
 #endif

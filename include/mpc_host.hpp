@@ -13,6 +13,7 @@
 //   mpc::circuit::ParseBristol                circuit/parser.go:265-494
 //   mpc::circuit::Streaming                   circuit/stream_garble.go:41-192
 //   mpc::sha2pc::GarblerBatch / EvaluatorBatch sha2pc/garbler.go:37-136, evaluator.go:27-113 for S sessions per call
+//   mpc::rand::DeviceRand                     env.Config.Rand = cipher.StreamReader{cipher.NewCTR(...), zeros} for S sessions
 //
 // Go `error` returns become exceptions of type mpc::Error whose what() carries the reference's message.
 // Go io.Reader becomes mpc::Reader.  Everything compute-heavy goes through libgcengine.so; there is no
@@ -964,4 +965,61 @@ private:
 };
 
 }  // namespace sha2pc
+
+// The random streams of S sessions, expanded on the device (gcengine.h: gc_rand_*): stream s is what a Go host reads from
+// cipher.StreamReader{S: cipher.NewCTR(aes.NewCipher(seed[s]), iv[s]), R: zeros}, the reader it would set as env.Config.Rand.
+// One byte position for all streams; every draw is one launch on the ctx stream.
+namespace rand {
+
+class DeviceRand {
+public:
+    // seeds [S][keylen] (16 / 24 / 32), ivs [S][16] or nullptr for all-zero IVs
+    DeviceRand(Context &ctx, const uint8_t *seeds, size_t keylen, const uint8_t *ivs, size_t S) : S_(S) {
+        int st = GC_OK;
+        h_ = gc_rand_create(ctx.handle(), seeds, keylen, ivs, S, &st);
+        check(st, "gc_rand_create");
+    }
+    // device arrays, read behind what is queued on the ctx stream
+    static DeviceRand FromDevice(Context &ctx, const void *d_seeds, size_t keylen, const void *d_ivs, size_t S) {
+        int st = GC_OK;
+        gc_rand *h = gc_rand_create_dev(ctx.handle(), d_seeds, keylen, d_ivs, S, &st);
+        check(st, "gc_rand_create_dev");
+        return DeviceRand(h, S);
+    }
+    ~DeviceRand() { gc_rand_free(h_); }
+    DeviceRand(const DeviceRand &) = delete;
+    DeviceRand &operator=(const DeviceRand &) = delete;
+    DeviceRand(DeviceRand &&o) noexcept : h_(o.h_), S_(o.S_) { o.h_ = nullptr; }
+    gc_rand *handle() { return h_; }
+    size_t Sessions() const { return S_; }
+    uint64_t Pos() const {
+        uint64_t pos = 0;
+        check(gc_rand_info(h_, nullptr, nullptr, &pos), "gc_rand_info");
+        return pos;
+    }
+    void Seek(uint64_t pos) { check(gc_rand_seek(h_, pos), "gc_rand_seek"); }
+    // the next nbytes of stream s to d_out + s * stride
+    void Fill(size_t nbytes, void *d_out, size_t stride) { check(gc_rand_fill_dev(h_, nbytes, d_out, stride), "gc_rand_fill_dev"); }
+    // the same into host memory: [S][nbytes]
+    std::vector<uint8_t> FillHost(size_t nbytes) {
+        std::vector<uint8_t> out(S_ * nbytes);
+        check(gc_rand_fill(h_, nbytes, out.data(), nbytes), "gc_rand_fill");
+        return out;
+    }
+    // circuit.Garbler's order (circuit/garbler.go:47-53): the key, then R and the input labels: d_keys [S][32] and d_rnd
+    // [S][1 + ninputs][16] as circuit::GarbleBatchKeys takes them
+    void DrawGarbler(uint32_t ninputs, void *d_keys, void *d_rnd) {
+        Fill(32, d_keys, 32);
+        Fill(16 * (size_t)(1 + ninputs), d_rnd, 16 * (size_t)(1 + ninputs));
+    }
+    // tripleBatch's draws (gmw/triples.go:301-310): a, b u64 [S][words]
+    void GMWShares(size_t words, void *d_a, void *d_b) { check(gc_rand_gmw_shares_dev(h_, words, d_a, d_b), "gc_rand_gmw_shares_dev"); }
+
+private:
+    DeviceRand(gc_rand *h, size_t S) : h_(h), S_(S) {}
+    gc_rand *h_ = nullptr;
+    size_t S_ = 0;
+};
+
+}  // namespace rand
 }  // namespace mpc

@@ -13,6 +13,7 @@
 // LDS map: 64 KiB AES table | 256 B unused (the one-key kernels' column keys) | 2 x ustride stage | R[TI] | wires
 // [slot][TI] | keys [TI][NR + 1] uint4.
 #include "aes_device.h"
+#include "aes_schedule.h"
 #include "flat_lanes.h"
 
 namespace gc {
@@ -28,32 +29,12 @@ __global__ __launch_bounds__(kExpandThreads) void k_expand_keys(const uint8_t *_
                                                                 uint32_t *__restrict__ out) {
     constexpr int NK = NR - 6, NW = 4 * (NR + 1);
     __shared__ uint8_t sbox[256];
-    for (uint32_t i = threadIdx.x; i < 256; i += kExpandThreads) sbox[i] = (uint8_t)(g_te0[i] >> 8);
+    load_sbox(sbox, g_te0);
     __syncthreads();
     const uint32_t gi = blockIdx.x * kExpandThreads + threadIdx.x;
     if (gi >= batch) return;
-    auto subword = [&](uint32_t v) {
-        return ((uint32_t)sbox[v >> 24] << 24) | ((uint32_t)sbox[(v >> 16) & 0xff] << 16) |
-               ((uint32_t)sbox[(v >> 8) & 0xff] << 8) | (uint32_t)sbox[v & 0xff];
-    };
-    const uint8_t *key = keys + (size_t)gi * (4 * NK);
     uint32_t w[NW];
-#pragma unroll
-    for (int i = 0; i < NK; i++)
-        w[i] = ((uint32_t)key[4 * i] << 24) | ((uint32_t)key[4 * i + 1] << 16) | ((uint32_t)key[4 * i + 2] << 8) |
-               (uint32_t)key[4 * i + 3];
-    uint32_t rcon = 0x01u;
-#pragma unroll
-    for (int i = NK; i < NW; i++) {
-        uint32_t t = w[i - 1];
-        if (i % NK == 0) {
-            t = subword((t << 8) | (t >> 24)) ^ (rcon << 24);
-            rcon = ((rcon << 1) ^ ((rcon & 0x80u) ? 0x11bu : 0u)) & 0xffu;
-        } else if (NK > 6 && i % NK == 4) {
-            t = subword(t);
-        }
-        w[i] = w[i - NK] ^ t;
-    }
+    aes_key_schedule<NR>(keys + (size_t)gi * (4 * NK), sbox, w);
     uint32_t *o = out + (size_t)gi * NW;
 #pragma unroll
     for (int i = 0; i < NW; i++) o[i] = i >= 4 * NR ? w[i] ^ w[i - 4 * NR] : w[i];

@@ -423,6 +423,22 @@ void launch_vole_sender(const VoleMod &mod, const uint4 *labels, const uint4 *x,
                         uint4 *u_out, const uint32_t *te0, hipStream_t s);
 void launch_vole_receiver(const VoleMod &mod, const uint4 *u_msg, size_t m, uint4 *u_out, hipStream_t s);
 
+// ---- device random streams (rand_kernels.hip; the streams, their blocks and the units of work: rand_ctr.h) ----
+constexpr int kRandThreads = 1024;        // k_rand_fill: one lane = one AES-CTR block of a unit (a wave's run of 64 blocks)
+constexpr int kRandGrid = 256;            // ... at most this many workgroups, one per CU (unit += gridDim.x * 16 waves)
+constexpr int kRandExpandThreads = 256;   // k_rand_expand: one lane = one seed
+constexpr int kRandExpandGrid = 1024;     // ... at most this many workgroups (seed += gridDim.x * kRandExpandThreads)
+struct RandCtr;
+// seeds u8 [S][4 (rounds - 6)], ivs u8 [S][16] or null (all zero) -> rk [S][4 (rounds + 1)] plain round keys, iv [S]
+hipError_t launch_rand_expand(const uint8_t *d_seeds, int rounds, const uint8_t *d_ivs, size_t S, const uint32_t *te0,
+                              uint32_t *d_rk, RandCtr *d_iv, hipStream_t s);
+// bytes [pos, pos + n) of stream s to d_out + s * stride (n > 0, stride >= n; nothing behind n is written)
+hipError_t launch_rand_fill(int rounds, const uint32_t *d_rk, const RandCtr *d_iv, size_t S, uint64_t pos, uint64_t n,
+                            uint8_t *d_out, size_t stride, const uint32_t *te0, hipStream_t s);
+// draw i of `words` (16 bytes from pos, a multiple of 16): a[s][i] = BE64 of its first half, b[s][i] of its second
+hipError_t launch_rand_gmw_shares(int rounds, const uint32_t *d_rk, const RandCtr *d_iv, size_t S, uint64_t pos, uint64_t words,
+                                  uint64_t *d_a, uint64_t *d_b, const uint32_t *te0, hipStream_t s);
+
 // ---- Chou-Orlandi base OT kernels (co_kernels.hip) -------------------------------------------
 // The constants of one session, passed by value (uniform across the grid).  a: the sender's scalar mod N, non-zero, limbs
 // least significant first; ainv: AaInv = -(a * A); g, a: the generator and the sender's point A; points in Montgomery form.

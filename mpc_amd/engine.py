@@ -350,6 +350,14 @@ def lib():
         "gc_sha2pc_evaluator_round2": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_size_t)]),
         "gc_sha2pc_garbler_round3": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_size_t)]),
         "gc_sha2pc_evaluator_round4": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_size_t)]),
+        "gc_rand_create": (vp, [vp, vp, sz, vp, sz, ip]),
+        "gc_rand_create_dev": (vp, [vp, vp, sz, vp, sz, ip]),
+        "gc_rand_free": (None, [vp]),
+        "gc_rand_info": (i32, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+        "gc_rand_seek": (i32, [vp, C.c_uint64]),
+        "gc_rand_fill_dev": (i32, [vp, sz, vp, sz]),
+        "gc_rand_fill": (i32, [vp, sz, vp, sz]),
+        "gc_rand_gmw_shares_dev": (i32, [vp, sz, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -2566,3 +2574,87 @@ class Sha2pcEvaluator(_Sha2pc):
         v, bad = np.zeros(S, np.uint32), C.c_size_t(_NONE)
         rc = lib().gc_sha2pc_evaluator_round4(self.h, _p(A), _p(sid), _p(sc), _p(bits), _p(r3), _p(dg), _p(v), C.byref(bad))
         return self._host(rc, "gc_sha2pc_evaluator_round4", v, bad, dg)
+
+
+# ---- device random streams: AES-CTR draws for S sessions per call (gc_rand_*) ----
+
+
+def rand_kernel_shape():
+    """(grid cap, threads per workgroup, blocks per wave and unit) of the fill kernel, from the sources the library was built
+    from (csrc/kernels.h, rand_ctr.h): one sweep of the capped grid covers grid * threads blocks"""
+    import re
+    out = []
+    for name, header in (("kRandGrid", "kernels.h"), ("kRandThreads", "kernels.h"), ("kRandRun", "rand_ctr.h")):
+        with open(os.path.join(CSRC, header)) as f:
+            m = re.findall(r"^\s*constexpr\s+(?:int|unsigned|uint32_t|size_t)\s+%s\s*=\s*(\d+)\s*;" % name, f.read(), re.M)
+        if len(m) != 1:
+            raise EngineError(GC_E_ARG, "%s: %d definitions of %s" % (header, len(m), name))
+        out.append(int(m[0]))
+    return tuple(out)
+
+
+class RandStreams:
+    """gc_rand: S AES-CTR keystreams, stream s what Go reads from cipher.StreamReader{cipher.NewCTR(aes.NewCipher(seed[s]),
+    iv[s]), zeros}.  seeds: u8 [S, keylen] (host), ivs u8 [S, 16] or None (all zero); or device buffers of those with S and
+    keylen given.  One byte position for all streams; close the handle before its Context."""
+
+    def __init__(self, ctx, seeds, ivs=None, S=None, keylen=None):
+        st = C.c_int(0)
+        if S is None:
+            k = np.ascontiguousarray(seeds, dtype=np.uint8)
+            assert k.ndim == 2, "seeds: [S, keylen]"
+            S, keylen = k.shape
+            v = None if ivs is None else np.ascontiguousarray(ivs, dtype=np.uint8).reshape(S, 16)
+            h = lib().gc_rand_create(ctx.h, _p(k) if k.size else None, keylen, _p(v), S, C.byref(st))
+            what = "gc_rand_create"
+        else:
+            S, keylen = int(S), int(keylen)
+            h = lib().gc_rand_create_dev(ctx.h, _dp(seeds), keylen, None if ivs is None else _dp(ivs), S, C.byref(st))
+            what = "gc_rand_create_dev"
+        self.ctx, self.S, self.keylen, self.h = ctx, S, keylen, h  # gc_rand_free waits for this ctx's stream
+        if not self.h:
+            raise EngineError(st.value, what)
+
+    def info(self):
+        """gc_rand_info -> (S, keylen, pos)"""
+        S, k, pos = C.c_size_t(0), C.c_size_t(0), C.c_uint64(0)
+        _check(lib().gc_rand_info(self.h, C.byref(S), C.byref(k), C.byref(pos)), "gc_rand_info")
+        return S.value, k.value, pos.value
+
+    @property
+    def pos(self):
+        return self.info()[2]
+
+    def seek(self, pos):
+        _check(lib().gc_rand_seek(self.h, pos), "gc_rand_seek")
+
+    def fill(self, nbytes, d_out, stride=None):
+        """device pointer; asynchronous on the ctx stream, one kernel.  Stream s -> d_out + s * stride (default: nbytes)"""
+        _check(lib().gc_rand_fill_dev(self.h, nbytes, _dp(d_out), nbytes if stride is None else stride), "gc_rand_fill_dev")
+
+    def fill_host(self, nbytes, out=None, stride=None):
+        """gc_rand_fill -> u8 [S, stride]; with `out` given (u8 [S, stride]) only the first nbytes of every row are written"""
+        stride = nbytes if stride is None else stride
+        if out is None:
+            out = np.zeros((self.S, max(stride, 1)), np.uint8)[:, :stride]
+            out = np.ascontiguousarray(out)
+        assert out.dtype == np.uint8 and out.flags.c_contiguous and out.size >= self.S * stride
+        _check(lib().gc_rand_fill(self.h, nbytes, _p(out) if out.size else None, stride), "gc_rand_fill")
+        return out
+
+    def gmw_shares(self, words, d_a, d_b):
+        """tripleBatch's draws: u64 [S, words] each, a = BE64 of the first half of every 16-byte draw, b of the second"""
+        _check(lib().gc_rand_gmw_shares_dev(self.h, words, _dp(d_a), _dp(d_b)), "gc_rand_gmw_shares_dev")
+
+    def draw_garbler(self, ninputs, d_keys, d_rnd):
+        """circuit.Garbler's order (garbler.go:47-53): the 32-byte key, then R and the input labels: the d_keys [S, 32] and
+        d_rnd [S, 1 + ninputs, 16] of Batch.garble_keyed"""
+        self.fill(32, d_keys)
+        self.fill(16 * (1 + ninputs), d_rnd)
+
+    def close(self):
+        if self.h:
+            if self.ctx.h is None:  # the stream the free would wait for is gone with the ctx
+                raise EngineError(GC_E_ARG, "RandStreams.close: close the handle before its Context")
+            lib().gc_rand_free(self.h)
+            self.h = None
