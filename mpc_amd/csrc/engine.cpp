@@ -279,6 +279,7 @@ gc_ctx *gc_ctx_create(int device, int *status) try {
         c->device = device;
         hipError_t e = hipSetDevice(device);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+        c->pipe.work = c->stream;
         if (e == hipSuccess) e = hipMalloc((void **)&c->d_te0, 256 * sizeof(uint32_t));
         if (e == hipSuccess)
             e = hipMemcpy(c->d_te0, aes_tables().te0, 256 * sizeof(uint32_t), hipMemcpyHostToDevice);
@@ -311,12 +312,7 @@ void gc_ctx_destroy(gc_ctx *c) {
     if (c->d_co_g_tab) (void)hipFree(c->d_co_g_tab);
     if (c->d_coop) (void)hipFree(c->d_coop);
     if (c->h_coop_err) (void)hipHostFree(c->h_coop_err);
-    for (int b = 0; b < 2; b++) {
-        if (c->stage[b]) (void)hipFree(c->stage[b]);
-        if (c->ev_k[b]) (void)hipEventDestroy(c->ev_k[b]);
-        if (c->ev_c[b]) (void)hipEventDestroy(c->ev_c[b]);
-    }
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
+    c->pipe.release();
     gcs_fuse_cache_free(c);
     for (hipStream_t l : c->lanes) (void)hipStreamDestroy(l);
     for (hipStream_t l : c->lanes_aside) (void)hipStreamDestroy(l);
@@ -1298,81 +1294,22 @@ int gc_batch_read_r(gc_batch *b, gc_label *r_out) {
     return GC_OK;
 }
 
-// lazily: the copy stream, its events and two device staging buffers of at least `bytes` each
-static int ensure_pipeline(gc_ctx *ctx, size_t bytes) {
-    if (!ctx->copy_stream) GC_HIP(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    for (int b = 0; b < 2; b++) {
-        if (!ctx->ev_k[b]) GC_HIP(hipEventCreateWithFlags(&ctx->ev_k[b], hipEventDisableTiming));
-        if (!ctx->ev_c[b]) GC_HIP(hipEventCreateWithFlags(&ctx->ev_c[b], hipEventDisableTiming));
-    }
-    if (bytes > ctx->stage_cap) {
-        GC_HIP(hipStreamSynchronize(ctx->stream));
-        GC_HIP(hipStreamSynchronize(ctx->copy_stream));
-        for (int b = 0; b < 2; b++) {
-            if (ctx->stage[b]) (void)hipFree(ctx->stage[b]);
-            ctx->stage[b] = nullptr;
-        }
-        ctx->stage_cap = 0;
-        for (int b = 0; b < 2; b++) GC_HIP(hipMalloc(&ctx->stage[b], bytes));
-        ctx->stage_cap = bytes;
-    }
-    return GC_OK;
-}
+// the pipelined form of host_transfer.h pays from 1 MiB on, and needs the DMA engine to reach the caller's pages itself
+static bool pipelined(size_t bytes, const void *host) { return bytes >= ((size_t)1 << 20) && gc_host_is_pinned(host); }
 
-constexpr size_t kPipeChunkBytes = (size_t)32 << 20;  // per staging buffer: long enough for full PCIe rate, short
-                                                      // enough that the first chunk's transpose hides nothing big
-
-// device [row][instance] array -> PINNED host [instance][n]: transpose kernel of chunk k + 1 on the ctx stream while the
-// DMA of chunk k runs on the copy stream
-static int read_gather_pinned(gc_batch *b, const uint4 *src, const Layout &lay, const uint32_t *slots, uint32_t slot0,
-                              uint32_t n, int mode, void *host_out) {
-    gc_ctx *ctx = b->circ->ctx;
-    const size_t elems = (size_t)n * (mode ? 2 : 1), per_inst = elems * sizeof(uint4);
-    uint32_t chunk = (uint32_t)std::max<size_t>(32, std::min<size_t>(b->g.batch, kPipeChunkBytes / per_inst));
-    chunk = (chunk + 31u) & ~31u;
-    int rc = ensure_pipeline(ctx, (size_t)std::min<uint32_t>(chunk, (b->g.batch + 31u) & ~31u) * per_inst);
-    if (rc != GC_OK) return rc;
-    uint32_t k = 0;
-    for (uint32_t i0 = 0; i0 < b->g.batch; i0 += chunk, k++) {
-        const int sb = (int)(k & 1);
-        const uint32_t cnt = std::min(chunk, b->g.batch - i0);
-        if (k >= 2) GC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_c[sb], 0));  // the buffer's previous DMA is done
-        launch_gather(src, lay, i0, slots, slot0, n, b->d_R, mode, (uint4 *)ctx->stage[sb], elems, cnt, ctx->stream);
-        GC_HIP(hipGetLastError());
-        GC_HIP(hipEventRecord(ctx->ev_k[sb], ctx->stream));
-        GC_HIP(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_k[sb], 0));
-        GC_HIP(hipMemcpyAsync((uint8_t *)host_out + (size_t)i0 * per_inst, ctx->stage[sb], (size_t)cnt * per_inst,
-                              hipMemcpyDeviceToHost, ctx->copy_stream));
-        GC_HIP(hipEventRecord(ctx->ev_c[sb], ctx->copy_stream));
-    }
-    GC_HIP(hipStreamSynchronize(ctx->copy_stream));
-    return GC_OK;
-}
-
+// device [row][instance] array -> host [instance][n] (mode 1: [instance][n] wires {L0, L0 ^ R})
 static int read_gather(gc_batch *b, const uint4 *src, const Layout &lay, const uint32_t *slots, uint32_t slot0,
                        uint32_t n, int mode, void *host_out) {
     if (n == 0) return GC_OK;
     gc_ctx *ctx = b->circ->ctx;
     GC_HIP(hipSetDevice(ctx->device));
-    const size_t elems = (size_t)n * (mode ? 2 : 1);
-    if (elems * sizeof(uint4) * b->g.batch >= ((size_t)1 << 20) && gc_host_is_pinned(host_out))
-        return read_gather_pinned(b, src, lay, slots, slot0, n, mode, host_out);
-    // bounded staging in the ctx's persistent buffer (no hipMalloc / hipFree per call): at most 64 MiB per pass
-    const size_t per_inst = elems * sizeof(uint4);
-    uint32_t chunk = (uint32_t)std::max<size_t>(32, std::min<size_t>(b->g.batch, ((size_t)64 << 20) / per_inst));
-    chunk = (chunk + 31u) & ~31u;
-    int rcp = ensure_pipeline(ctx, (size_t)std::min<uint32_t>(chunk, (b->g.batch + 31u) & ~31u) * per_inst);
-    if (rcp != GC_OK) return rcp;
-    void *tmp = ctx->stage[0];
-    for (uint32_t i0 = 0; i0 < b->g.batch; i0 += chunk) {
-        const uint32_t cnt = std::min(chunk, b->g.batch - i0);
-        launch_gather(src, lay, i0, slots, slot0, n, b->d_R, mode, (uint4 *)tmp, elems, cnt, ctx->stream);
-        GC_HIP(hipGetLastError());
-        GC_HIP(hipMemcpyAsync((uint8_t *)host_out + (size_t)i0 * per_inst, tmp, (size_t)cnt * per_inst,
-                              hipMemcpyDeviceToHost, ctx->stream));
-        GC_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return GC_OK;
+    const size_t elems = (size_t)n * (mode ? 2 : 1), per_inst = elems * sizeof(uint4);
+    const bool pinned = pipelined(per_inst * b->g.batch, host_out);
+    return download(ctx->pipe, pinned, b->g.batch, per_inst, pinned ? kPipeChunkBytes : kPageableChunkBytes, host_out,
+                    [&](void *stage, uint32_t i0, uint32_t cnt) {
+                        launch_gather(src, lay, i0, slots, slot0, n, b->d_R, mode, (uint4 *)stage, elems, cnt, ctx->stream);
+                        return hipGetLastError();
+                    });
 }
 
 int gc_batch_read_slab(gc_batch *b, gc_label *slab_out) {
@@ -1403,66 +1340,19 @@ int gc_batch_read_outputs(gc_batch *b, gc_label *out) {
     return read_gather(b, b->d_W, b->g.lw, b->circ->d_out_slots, 0, b->circ->plan.p.info.noutputs, 0, out);
 }
 
-// PINNED host [instance][src_stride] -> device [row][instance]: DMA of chunk k + 1 on the copy stream while the
-// scatter kernel of chunk k runs on the ctx stream
-static int write_scatter_pinned(gc_batch *b, const void *host_src, size_t src_stride_elems, size_t col0, uint32_t n,
-                                const uint32_t *slots, uint32_t slot0, uint4 *dst, const Layout &lay) {
-    gc_ctx *ctx = b->circ->ctx;
-    const size_t per_inst = (size_t)n * sizeof(uint4);
-    uint32_t chunk = (uint32_t)std::max<size_t>(32, std::min<size_t>(b->g.batch, kPipeChunkBytes / per_inst));
-    chunk = (chunk + 31u) & ~31u;
-    int rc = ensure_pipeline(ctx, (size_t)std::min<uint32_t>(chunk, (b->g.batch + 31u) & ~31u) * per_inst);
-    if (rc != GC_OK) return rc;
-    // what is already queued on the ctx stream may still read the staging buffers (an earlier pipelined call)
-    GC_HIP(hipEventRecord(ctx->ev_k[0], ctx->stream));
-    GC_HIP(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_k[0], 0));
-    uint32_t k = 0;
-    for (uint32_t i0 = 0; i0 < b->g.batch; i0 += chunk, k++) {
-        const int sb = (int)(k & 1);
-        const uint32_t cnt = std::min(chunk, b->g.batch - i0);
-        const uint8_t *src = (const uint8_t *)host_src + ((size_t)i0 * src_stride_elems + col0) * sizeof(uint4);
-        if (k >= 2) GC_HIP(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_k[sb], 0));  // its previous scatter is done
-        if (src_stride_elems == n)
-            GC_HIP(hipMemcpyAsync(ctx->stage[sb], src, (size_t)cnt * per_inst, hipMemcpyHostToDevice, ctx->copy_stream));
-        else
-            GC_HIP(hipMemcpy2DAsync(ctx->stage[sb], per_inst, src, src_stride_elems * sizeof(uint4), per_inst, cnt,
-                                    hipMemcpyHostToDevice, ctx->copy_stream));
-        GC_HIP(hipEventRecord(ctx->ev_c[sb], ctx->copy_stream));
-        GC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_c[sb], 0));
-        launch_scatter((const uint4 *)ctx->stage[sb], n, n, slots, slot0, dst, lay, i0, cnt, ctx->stream);
-        GC_HIP(hipGetLastError());
-        GC_HIP(hipEventRecord(ctx->ev_k[sb], ctx->stream));
-    }
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    return GC_OK;
-}
-
+// host [instance][src_stride_elems], labels [col0, col0 + n) of every instance -> device [row][instance]
 static int write_scatter(gc_batch *b, const void *host_src, size_t src_stride_elems, size_t col0, uint32_t n,
                          const uint32_t *slots, uint32_t slot0, uint4 *dst, const Layout &lay) {
     if (n == 0) return GC_OK;
     gc_ctx *ctx = b->circ->ctx;
     GC_HIP(hipSetDevice(ctx->device));
     const size_t per_inst = (size_t)n * sizeof(uint4);
-    if (per_inst * b->g.batch >= ((size_t)1 << 20) && gc_host_is_pinned(host_src))
-        return write_scatter_pinned(b, host_src, src_stride_elems, col0, n, slots, slot0, dst, lay);
-    uint32_t chunk = (uint32_t)std::max<size_t>(32, std::min<size_t>(b->g.batch, ((size_t)64 << 20) / per_inst));
-    chunk = (chunk + 31u) & ~31u;
-    int rcp = ensure_pipeline(ctx, (size_t)std::min<uint32_t>(chunk, (b->g.batch + 31u) & ~31u) * per_inst);
-    if (rcp != GC_OK) return rcp;
-    void *tmp = ctx->stage[0];
-    for (uint32_t i0 = 0; i0 < b->g.batch; i0 += chunk) {
-        const uint32_t cnt = std::min(chunk, b->g.batch - i0);
-        const uint8_t *src = (const uint8_t *)host_src + ((size_t)i0 * src_stride_elems + col0) * sizeof(uint4);
-        if (src_stride_elems == n)
-            GC_HIP(hipMemcpyAsync(tmp, src, (size_t)cnt * per_inst, hipMemcpyHostToDevice, ctx->stream));
-        else
-            GC_HIP(hipMemcpy2DAsync(tmp, per_inst, src, src_stride_elems * sizeof(uint4), per_inst, cnt,
-                                    hipMemcpyHostToDevice, ctx->stream));
-        launch_scatter((const uint4 *)tmp, n, n, slots, slot0, dst, lay, i0, cnt, ctx->stream);
-        GC_HIP(hipGetLastError());
-        GC_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return GC_OK;
+    const bool pinned = pipelined(per_inst * b->g.batch, host_src);
+    return upload(ctx->pipe, pinned, b->g.batch, per_inst, pinned ? kPipeChunkBytes : kPageableChunkBytes,
+                  (const uint4 *)host_src + col0, src_stride_elems * sizeof(uint4), [&](const void *stage, uint32_t i0, uint32_t cnt) {
+                      launch_scatter((const uint4 *)stage, n, n, slots, slot0, dst, lay, i0, cnt, ctx->stream);
+                      return hipGetLastError();
+                  });
 }
 
 int gc_batch_write_slab(gc_batch *b, const gc_label *slab) {
@@ -1659,6 +1549,73 @@ static void pool_put(gc_circ *c, gc_batch *b) {
     gc_batch_free(b);
 }
 
+// One host-buffer call on a pooled batch of the circuit: begin() takes the batch (or is handed one), locks the ctx — one HIP
+// stream per ctx: the host-buffer calls that share it are serialised — and sets the device; layout() goes before anything is
+// written into the batch's arrays.  A call that succeeded says so with done(), or keep() where the caller gets the batch.  On
+// every other way out the streams of the ctx are waited for before the batch goes back to the pool, where the next call may
+// take it at once.
+struct PooledPass {
+    gc_circ *const c;
+    gc_ctx *const ctx;
+    gc_batch *b = nullptr;
+    std::unique_lock<std::mutex> lk;
+    bool ok = false;
+    explicit PooledPass(gc_circ *circ) : c(circ), ctx(circ->ctx) {}
+    PooledPass(const PooledPass &) = delete;
+    PooledPass &operator=(const PooledPass &) = delete;
+    int begin(uint32_t batch, gc_batch *have = nullptr) {
+        int rc = GC_OK;
+        b = have ? have : pool_get(c, batch, &rc);
+        if (!b) return rc;
+        lk = std::unique_lock<std::mutex>(ctx->mu);
+        GC_HIP(hipSetDevice(ctx->device));
+        return GC_OK;
+    }
+    // a pooled batch keeps the geometry of its last use: keeping every wire runs the level-walking kernel, whose tile may be
+    // smaller than the flattened kernels' (relayout re-sizes the arrays if it is)
+    int layout(bool store_all) {
+        b->store_all = store_all;
+        return relayout(b);
+    }
+    int done() {
+        ok = true;
+        return GC_OK;
+    }
+    int keep(gc_batch **bout) {
+        *bout = b;
+        b = nullptr;
+        return GC_OK;
+    }
+    ~PooledPass() {
+        if (!b) return;
+        if (!ok) {
+            (void)hipStreamSynchronize(ctx->stream);
+            if (ctx->pipe.copy) (void)hipStreamSynchronize(ctx->pipe.copy);
+        }
+        pool_put(c, b);
+    }
+};
+
+// Wires[0:ninputs] then Wires[nwires-noutputs:] of every instance -> io_out: both ranges gathered on the device into one dense
+// [batch][ninputs + noutputs] wire array (two launches, column offset) and one copy to the caller, behind which the call waits
+static int read_io_wires(gc_batch *b, gc_wire *io_out) {
+    gc_circ *c = b->circ;
+    gc_ctx *ctx = c->ctx;
+    const gc_plan_info &info = c->plan.p.info;
+    const uint32_t nio = info.ninputs + info.noutputs;
+    const size_t bytes = (size_t)b->g.batch * nio * sizeof(gc_wire);
+    int rc = ctx->pipe.ensure(std::max(bytes, (size_t)1 << 20));
+    if (rc != GC_OK) return rc;
+    uint4 *st = (uint4 *)ctx->pipe.stage[0];
+    // a wire = 2 labels: row stride 2 * nio elements, the output range starts 2 * ninputs elements in
+    launch_gather(b->d_W, b->g.lw, 0, nullptr, 0, info.ninputs, b->d_R, 1, st, 2 * (size_t)nio, b->g.batch, ctx->stream);
+    launch_gather(b->d_W, b->g.lw, 0, c->d_out_slots, 0, info.noutputs, b->d_R, 1, st + 2 * (size_t)info.ninputs, 2 * (size_t)nio,
+                  b->g.batch, ctx->stream);
+    GC_HIP(hipGetLastError());
+    GC_HIP(hipMemcpyAsync(io_out, st, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return GC_OK;
+}
+
 int gc_garble(gc_circ *c, const uint8_t *key, size_t keylen, const uint8_t *rnd, size_t rndlen, uint32_t batch,
               gc_label *r_out, gc_wire *wires_out, gc_wire *io_out, gc_label *slab_out) try {
     if (!c || !rnd || batch == 0) return GC_E_ARG;
@@ -1670,66 +1627,27 @@ int gc_garble(gc_circ *c, const uint8_t *key, size_t keylen, const uint8_t *rnd,
     if (!key || !aes_expand_key(key, keylen, &k)) return GC_E_KEYSIZE;
     const size_t stride = 16 * ((size_t)p.info.ninputs + 1);
     if (rndlen < stride * batch) return GC_E_RAND;
-    int rc = GC_OK;
     Trace tr("gc_garble");
-    gc_batch *b = pool_get(c, batch, &rc);
-    if (!b) return rc;
-    gc_ctx *ctx = c->ctx;
-    // one HIP stream per ctx: serialise host-buffer calls that share the ctx
-    std::lock_guard<std::mutex> lk(ctx->mu);
+    PooledPass pass(c);
+    int rc = pass.begin(batch);
+    if (rc != GC_OK) return rc;
+    gc_batch *b = pass.b;
     tr.lap("pool + lock");
-    do {
-        DevBuf d_rnd;
-        hipError_t e = hipSetDevice(ctx->device);
-        if (e == hipSuccess) e = d_rnd.alloc(stride * batch);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_rnd.p, rnd, stride * batch, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) {
-            set_error("gc_garble", e);
-            rc = e == hipErrorOutOfMemory ? GC_E_NOMEM : GC_E_HIP;
-            break;
-        }
-        // a pooled batch keeps the geometry of its last use: keeping every wire runs the level-walking kernel, whose
-        // tile may be smaller than the flattened kernels' (relayout re-sizes the arrays if it is)
-        b->store_all = wires_out != nullptr;
-        if ((rc = relayout(b)) != GC_OK) break;
-        tr.lap("rnd h2d + layout");
-        rc = gc_batch_garble(b, key, keylen, d_rnd.p);
-        if (rc != GC_OK) break;
-        if (r_out && (rc = gc_batch_read_r(b, r_out)) != GC_OK) break;
-        tr.lap("garble + R");
-        if (slab_out && (rc = gc_batch_read_slab(b, slab_out)) != GC_OK) break;
-        tr.lap("slab d2h");
-        if (wires_out && (rc = gc_batch_read_wires(b, wires_out)) != GC_OK) break;
-        if (io_out) {
-            // Wires[0:ninputs] then Wires[nwires-noutputs:]: both ranges gathered on the device into one dense
-            // [batch][ninputs + noutputs] wire array (two launches, column offset), one copy to the caller
-            const uint32_t nio = p.info.ninputs + p.info.noutputs;
-            const size_t bytes = (size_t)batch * nio * sizeof(gc_wire);
-            if ((rc = ensure_pipeline(ctx, std::max(bytes, (size_t)1 << 20))) != GC_OK) break;
-            uint4 *st = (uint4 *)ctx->stage[0];
-            // a wire = 2 labels: row stride 2 * nio elements, the output range starts 2 * ninputs elements in
-            launch_gather(b->d_W, b->g.lw, 0, nullptr, 0, p.info.ninputs, b->d_R, 1, st, 2 * (size_t)nio, batch, ctx->stream);
-            launch_gather(b->d_W, b->g.lw, 0, c->d_out_slots, 0, p.info.noutputs, b->d_R, 1, st + 2 * (size_t)p.info.ninputs,
-                          2 * (size_t)nio, batch, ctx->stream);
-            hipError_t eg = hipGetLastError();
-            if (eg == hipSuccess) eg = hipMemcpyAsync(io_out, st, bytes, hipMemcpyDeviceToHost, ctx->stream);
-            if (eg == hipSuccess) eg = hipStreamSynchronize(ctx->stream);
-            if (eg != hipSuccess) {
-                set_error("gc_garble (io wires)", eg);
-                rc = GC_E_HIP;
-                break;
-            }
-        }
-        tr.lap("wires / io d2h");
-        hipError_t es = hipStreamSynchronize(ctx->stream);
-        if (es != hipSuccess) {
-            set_error("gc_garble", es);
-            rc = GC_E_HIP;
-        }
-    } while (0);
-    tr.lap("sync + frees");
-    pool_put(c, b);
-    return rc;
+    Staged d_rnd[] = {{rnd, nullptr, stride * batch}};
+    if ((rc = stage_in(d_rnd, 1, pass.ctx->stream)) != GC_OK) return rc;
+    if ((rc = pass.layout(wires_out != nullptr)) != GC_OK) return rc;
+    tr.lap("rnd h2d + layout");
+    if ((rc = gc_batch_garble(b, key, keylen, d_rnd[0].d.p)) != GC_OK) return rc;
+    if (r_out && (rc = gc_batch_read_r(b, r_out)) != GC_OK) return rc;
+    tr.lap("garble + R");
+    if (slab_out && (rc = gc_batch_read_slab(b, slab_out)) != GC_OK) return rc;
+    tr.lap("slab d2h");
+    if (wires_out && (rc = gc_batch_read_wires(b, wires_out)) != GC_OK) return rc;
+    if (io_out && (rc = read_io_wires(b, io_out)) != GC_OK) return rc;
+    tr.lap("wires / io d2h");
+    if ((rc = stage_out(d_rnd, 1, pass.ctx->stream)) != GC_OK) return rc;  // (nothing to copy back: the wait of the call)
+    tr.lap("sync");
+    return pass.done();
 } catch (...) {
     return gc::on_exception();
 }
@@ -1744,33 +1662,18 @@ int gc_garble_labels_keep(gc_circ *c, const uint8_t *key, size_t keylen, const g
     *bout = nullptr;
     const Plan &p = c->plan.p;
     if (p.info.ninputs && !inputs) return GC_E_ARG;
-    int rc = GC_OK;
-    gc_batch *b = pool_get(c, 1, &rc);
-    if (!b) return rc;
-    gc_ctx *ctx = c->ctx;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    do {
-        hipError_t e = hipSetDevice(ctx->device);
-        b->store_all = false;
-        if (e == hipSuccess && (rc = relayout(b)) != GC_OK) break;  // before anything is written into the arrays
-        if (e == hipSuccess) e = upload_r(b, r);
-        if (e != hipSuccess) {
-            set_error("gc_garble_labels", e);
-            rc = GC_E_HIP;
-            break;
-        }
-        if (p.info.ninputs) rc = write_scatter(b, inputs, p.info.ninputs, 0, p.info.ninputs, nullptr, 0, b->d_W, b->g.lw);
-        if (rc != GC_OK) break;
-        if ((rc = set_key(b, key, keylen)) != GC_OK) break;
-        if ((rc = run_levels(b, pass_path(b, false), false, b->d_T)) != GC_OK) break;
-        if (out_l0 && (rc = gc_batch_read_outputs(b, out_l0)) != GC_OK) break;
-    } while (0);
-    if (rc != GC_OK) {
-        pool_put(c, b);
+    PooledPass pass(c);
+    int rc = pass.begin(1);
+    if (rc != GC_OK) return rc;
+    gc_batch *b = pass.b;
+    if ((rc = pass.layout(false)) != GC_OK) return rc;
+    GC_HIP(upload_r(b, r));
+    if (p.info.ninputs && (rc = write_scatter(b, inputs, p.info.ninputs, 0, p.info.ninputs, nullptr, 0, b->d_W, b->g.lw)) != GC_OK)
         return rc;
-    }
-    *bout = b;
-    return GC_OK;
+    if ((rc = set_key(b, key, keylen)) != GC_OK) return rc;
+    if ((rc = run_levels(b, pass_path(b, false), false, b->d_T)) != GC_OK) return rc;
+    if (out_l0 && (rc = gc_batch_read_outputs(b, out_l0)) != GC_OK) return rc;
+    return pass.keep(bout);
 }
 
 bool gc_circ_flat_poll(gc_circ *c, bool start) {
@@ -1833,65 +1736,43 @@ int gc_pass_dev(gc_circ *c, bool eval, const uint8_t *key, size_t keylen, const 
         if (b) pool_put(c, b);
         return GC_E_ROWS;
     }
-    int rc = GC_OK;
-    if (!b) b = pool_get(c, 1, &rc);
-    if (!b) return rc;
+    PooledPass pass(c);
+    int rc = pass.begin(1, b);
+    if (rc != GC_OK) return rc;
+    b = pass.b;
     gc_ctx *ctx = c->ctx;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    do {
-        hipError_t e = hipSetDevice(ctx->device);
-        b->store_all = false;
-        if ((rc = gc_ctx_coop_check(ctx)) != GC_OK) break;
-        if (e == hipSuccess && (rc = relayout(b)) != GC_OK) break;
-        if (e == hipSuccess && !eval) e = upload_r(b, r);
-        // one instance: a tile of one, the table array is the dense slab [row] and wire slot w is element w
-        if (e == hipSuccess && eval && slab_rows && slab_host)
-            e = hipMemcpyAsync(b->d_T, slab_host, slab_rows * sizeof(gc_label), hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) {
-            set_error("gc_pass_dev", e);
-            rc = GC_E_HIP;
-            break;
-        }
-        // a cooperative pass exchanges the labels with the store itself (a kernel before and one behind it were 10 us
-        // plus their gaps of a 230 us step)
-        // (the caller has put the same pointers into *d_xchg, in device memory, with its other uploads)
-        // (the path is decided once: the exchange here and the kernel in run_levels cannot disagree)
-        const Path path = pass_path(b, eval);
-        const bool in_pass = d_xchg && path == Path::WideCoop;
-        if (!in_pass) launch_store_gather(b->d_W, (const uint4 *)d_store, d_in_idx, p.info.ninputs, ctx->stream);
-        if ((rc = set_key(b, key, keylen)) != GC_OK) break;
-        b->xchg = in_pass ? d_xchg : nullptr;
-        rc = run_levels(b, path, eval, b->d_T);
-        b->xchg = nullptr;
-        if (rc != GC_OK) break;
-        if (!in_pass)
-            launch_store_scatter((uint4 *)const_cast<void *>(d_store), b->d_W, c->d_out_slots, d_out_idx, p.info.noutputs, ctx->stream);
-        e = hipGetLastError();
-        if (e != hipSuccess) {
-            set_error("gc_pass_dev", e);
-            rc = GC_E_HIP;
-        }
-    } while (0);
-    if (rc != GC_OK) {
-        pool_put(c, b);
-        return rc;
-    }
-    *bout = b;
-    return GC_OK;
+    if ((rc = gc_ctx_coop_check(ctx)) != GC_OK) return rc;
+    if ((rc = pass.layout(false)) != GC_OK) return rc;
+    if (!eval) GC_HIP(upload_r(b, r));
+    // one instance: a tile of one, the table array is the dense slab [row] and wire slot w is element w
+    if (eval && slab_rows && slab_host)
+        GC_HIP(hipMemcpyAsync(b->d_T, slab_host, slab_rows * sizeof(gc_label), hipMemcpyHostToDevice, ctx->stream));
+    // a cooperative pass exchanges the labels with the store itself (a kernel before and one behind it were 10 us
+    // plus their gaps of a 230 us step)
+    // (the caller has put the same pointers into *d_xchg, in device memory, with its other uploads)
+    // (the path is decided once: the exchange here and the kernel in run_levels cannot disagree)
+    const Path path = pass_path(b, eval);
+    const bool in_pass = d_xchg && path == Path::WideCoop;
+    if (!in_pass) launch_store_gather(b->d_W, (const uint4 *)d_store, d_in_idx, p.info.ninputs, ctx->stream);
+    if ((rc = set_key(b, key, keylen)) != GC_OK) return rc;
+    b->xchg = in_pass ? d_xchg : nullptr;
+    rc = run_levels(b, path, eval, b->d_T);
+    b->xchg = nullptr;
+    if (rc != GC_OK) return rc;
+    if (!in_pass)
+        launch_store_scatter((uint4 *)const_cast<void *>(d_store), b->d_W, c->d_out_slots, d_out_idx, p.info.noutputs, ctx->stream);
+    GC_HIP(hipGetLastError());
+    return pass.keep(bout);
 }
 
 int gc_pass_batch(gc_circ *c, gc_batch **bout) {
     if (!c || !bout) return GC_E_ARG;
-    int rc = GC_OK;
-    *bout = pool_get(c, 1, &rc);
-    if (!*bout) return rc;
-    std::lock_guard<std::mutex> lk(c->ctx->mu);
-    if (hipSetDevice(c->ctx->device) != hipSuccess || (rc = relayout(*bout)) != GC_OK) {
-        pool_put(c, *bout);
-        *bout = nullptr;
-        return rc != GC_OK ? rc : GC_E_HIP;
-    }
-    return GC_OK;
+    *bout = nullptr;
+    PooledPass pass(c);
+    int rc = pass.begin(1);
+    if (rc != GC_OK) return rc;
+    if ((rc = relayout(pass.b)) != GC_OK) return rc;  // (as its last pass left it: gc_pass_dev decides what the next one keeps)
+    return pass.keep(bout);
 }
 
 extern "C" {
@@ -1901,12 +1782,10 @@ int gc_garble_labels(gc_circ *c, const uint8_t *key, size_t keylen, const gc_lab
     gc_batch *b = nullptr;
     int rc = gc_garble_labels_keep(c, key, keylen, r, inputs, out_l0, &b);
     if (rc != GC_OK) return rc;
-    if (slab_out) {
-        std::lock_guard<std::mutex> lk(c->ctx->mu);
-        rc = gc_batch_read_slab(b, slab_out);
-    }
-    pool_put(c, b);
-    return rc;
+    PooledPass pass(c);
+    if ((rc = pass.begin(1, b)) != GC_OK) return rc;
+    if (slab_out && (rc = gc_batch_read_slab(b, slab_out)) != GC_OK) return rc;
+    return pass.done();
 } catch (...) {
     return gc::on_exception();
 }
@@ -1918,36 +1797,26 @@ int gc_eval(gc_circ *c, const uint8_t *key, size_t keylen, uint32_t batch, gc_la
     AesKey k;
     if (!key || !aes_expand_key(key, keylen, &k)) return GC_E_KEYSIZE;
     if (slab_rows_given != p.info.slab_rows || (!slab && p.info.slab_rows)) return GC_E_ROWS;
-    int rc = GC_OK;
     Trace tr("gc_eval");
-    gc_batch *b = pool_get(c, batch, &rc);
-    if (!b) return rc;
-    gc_ctx *ctx = c->ctx;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    do {
-        b->store_all = wires_inout != nullptr;
-        if ((rc = relayout(b)) != GC_OK) break;  // before the tables and labels go into the arrays
-        if (p.info.slab_rows && (rc = gc_batch_write_slab(b, slab)) != GC_OK) break;
-        tr.lap("slab h2d");
-        if (wires_inout)
-            rc = write_scatter(b, wires_inout, p.info.nwires, 0, p.info.ninputs, nullptr, 0, b->d_W, b->g.lw);
-        else
-            rc = write_scatter(b, inputs, p.info.ninputs, 0, p.info.ninputs, nullptr, 0, b->d_W, b->g.lw);
-        if (rc != GC_OK) break;
-        tr.lap("inputs h2d");
-        rc = gc_batch_eval(b, key, keylen, b);
-        if (rc != GC_OK) break;
-        if (wires_inout && (rc = gc_batch_read_labels(b, wires_inout)) != GC_OK) break;
-        if (out_labels && (rc = gc_batch_read_outputs(b, out_labels)) != GC_OK) break;
-        hipError_t es = hipStreamSynchronize(ctx->stream);
-        tr.lap("eval + outputs");
-        if (es != hipSuccess) {
-            set_error("gc_eval", es);
-            rc = GC_E_HIP;
-        }
-    } while (0);
-    pool_put(c, b);
-    return rc;
+    PooledPass pass(c);
+    int rc = pass.begin(batch);
+    if (rc != GC_OK) return rc;
+    gc_batch *b = pass.b;
+    if ((rc = pass.layout(wires_inout != nullptr)) != GC_OK) return rc;  // before the tables and labels go into the arrays
+    if (p.info.slab_rows && (rc = gc_batch_write_slab(b, slab)) != GC_OK) return rc;
+    tr.lap("slab h2d");
+    if (wires_inout)
+        rc = write_scatter(b, wires_inout, p.info.nwires, 0, p.info.ninputs, nullptr, 0, b->d_W, b->g.lw);
+    else
+        rc = write_scatter(b, inputs, p.info.ninputs, 0, p.info.ninputs, nullptr, 0, b->d_W, b->g.lw);
+    if (rc != GC_OK) return rc;
+    tr.lap("inputs h2d");
+    if ((rc = gc_batch_eval(b, key, keylen, b)) != GC_OK) return rc;
+    if (wires_inout && (rc = gc_batch_read_labels(b, wires_inout)) != GC_OK) return rc;
+    if (out_labels && (rc = gc_batch_read_outputs(b, out_labels)) != GC_OK) return rc;
+    GC_HIP(hipStreamSynchronize(pass.ctx->stream));
+    tr.lap("eval + outputs");
+    return pass.done();
 } catch (...) {
     return gc::on_exception();
 }
@@ -1970,57 +1839,23 @@ int gc_garble_wire(gc_circ *c, const uint8_t *key, size_t keylen, const uint8_t 
     if (!key || !aes_expand_key(key, keylen, &k)) return GC_E_KEYSIZE;
     const size_t rstride = 16 * ((size_t)p.info.ninputs + 1);
     if (rndlen < rstride * batch) return GC_E_RAND;
-    int rc = GC_OK;
-    gc_batch *b = pool_get(c, batch, &rc);
-    if (!b) return rc;
-    gc_ctx *ctx = c->ctx;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    do {
-        DevBuf d_rnd, d_wire;
-        hipError_t e = hipSetDevice(ctx->device);
-        if (e == hipSuccess) e = d_rnd.alloc(rstride * batch);
-        if (e == hipSuccess) e = d_wire.alloc(stride * batch);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_rnd.p, rnd, rstride * batch, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) {
-            set_error("gc_garble_wire", e);
-            rc = e == hipErrorOutOfMemory ? GC_E_NOMEM : GC_E_HIP;
-            break;
-        }
-        b->store_all = false;
-        if ((rc = relayout(b)) != GC_OK) break;
-        if ((rc = gc_batch_garble(b, key, keylen, d_rnd.p)) != GC_OK) break;
-        if ((rc = gc_batch_egress_tables(b, d_wire.p, stride)) != GC_OK) break;
-        e = hipMemcpyAsync(wire_out, d_wire.p, stride * batch, hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) {
-            set_error("gc_garble_wire", e);
-            rc = GC_E_HIP;
-            break;
-        }
-        if (r_out && (rc = gc_batch_read_r(b, r_out)) != GC_OK) break;
-        if (io_out) {
-            const uint32_t nio = p.info.ninputs + p.info.noutputs;
-            const size_t bytes = (size_t)batch * nio * sizeof(gc_wire);
-            if ((rc = ensure_pipeline(ctx, std::max(bytes, (size_t)1 << 20))) != GC_OK) break;
-            uint4 *st = (uint4 *)ctx->stage[0];
-            launch_gather(b->d_W, b->g.lw, 0, nullptr, 0, p.info.ninputs, b->d_R, 1, st, 2 * (size_t)nio, batch, ctx->stream);
-            launch_gather(b->d_W, b->g.lw, 0, c->d_out_slots, 0, p.info.noutputs, b->d_R, 1, st + 2 * (size_t)p.info.ninputs,
-                          2 * (size_t)nio, batch, ctx->stream);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(io_out, st, bytes, hipMemcpyDeviceToHost, ctx->stream);
-            if (e != hipSuccess) {
-                set_error("gc_garble_wire (io wires)", e);
-                rc = GC_E_HIP;
-                break;
-            }
-        }
-        e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            set_error("gc_garble_wire", e);
-            rc = GC_E_HIP;
-        }
-    } while (0);
-    pool_put(c, b);
-    return rc;
+    PooledPass pass(c);
+    int rc = pass.begin(batch);
+    if (rc != GC_OK) return rc;
+    gc_batch *b = pass.b;
+    gc_ctx *ctx = pass.ctx;
+    // (the serialised tables go out where the serialiser has run, ahead of R and the io wires, not with stage_out's copies)
+    Staged io[] = {{rnd, nullptr, rstride * batch}, {nullptr, nullptr, 0, stride * batch}};
+    const Staged &d_rnd = io[0], &d_wire = io[1];
+    if ((rc = stage_in(io, 2, ctx->stream)) != GC_OK) return rc;
+    if ((rc = pass.layout(false)) != GC_OK) return rc;
+    if ((rc = gc_batch_garble(b, key, keylen, d_rnd.d.p)) != GC_OK) return rc;
+    if ((rc = gc_batch_egress_tables(b, d_wire.d.p, stride)) != GC_OK) return rc;
+    GC_HIP(hipMemcpyAsync(wire_out, d_wire.d.p, stride * batch, hipMemcpyDeviceToHost, ctx->stream));
+    if (r_out && (rc = gc_batch_read_r(b, r_out)) != GC_OK) return rc;
+    if (io_out && (rc = read_io_wires(b, io_out)) != GC_OK) return rc;
+    if ((rc = stage_out(io, 2, ctx->stream)) != GC_OK) return rc;  // (the wait of the call)
+    return pass.done();
 } catch (...) {
     return gc::on_exception();
 }
@@ -2032,48 +1867,27 @@ int gc_eval_wire(gc_circ *c, const uint8_t *key, size_t keylen, uint32_t batch, 
     if (stride < gc_tables_wire_bytes(c) || (stride & 3)) return GC_E_ARG;
     AesKey k;
     if (!key || !aes_expand_key(key, keylen, &k)) return GC_E_KEYSIZE;
-    int rc = GC_OK;
-    gc_batch *b = pool_get(c, batch, &rc);
-    if (!b) return rc;
-    gc_ctx *ctx = c->ctx;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    do {
-        DevBuf d_wire, d_bad;
-        hipError_t e = hipSetDevice(ctx->device);
-        if (e == hipSuccess) e = d_wire.alloc(stride * batch);
-        if (e == hipSuccess) e = d_bad.alloc(sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemsetAsync(d_bad.p, 0, sizeof(uint32_t), ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_wire.p, wire_in, stride * batch, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) {
-            set_error("gc_eval_wire", e);
-            rc = e == hipErrorOutOfMemory ? GC_E_NOMEM : GC_E_HIP;
-            break;
-        }
-        b->store_all = false;
-        if ((rc = relayout(b)) != GC_OK) break;
-        if ((rc = gc_batch_ingest_tables(b, d_wire.p, stride, d_bad.p)) != GC_OK) break;
-        e = hipMemcpyAsync(bad, d_bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            set_error("gc_eval_wire", e);
-            rc = GC_E_HIP;
-            break;
-        }
-        if (*bad) {  // "wrong number of gates" (evaluator.go:44-47) / a row count Eval would reject (eval.go:54-56,86-89)
-            rc = GC_E_ROWS;
-            break;
-        }
-        if ((rc = write_scatter(b, inputs, p.info.ninputs, 0, p.info.ninputs, nullptr, 0, b->d_W, b->g.lw)) != GC_OK) break;
-        if ((rc = gc_batch_eval(b, key, keylen, b)) != GC_OK) break;
-        if (out_labels && (rc = gc_batch_read_outputs(b, out_labels)) != GC_OK) break;
-        e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            set_error("gc_eval_wire", e);
-            rc = GC_E_HIP;
-        }
-    } while (0);
-    pool_put(c, b);
-    return rc;
+    PooledPass pass(c);
+    int rc = pass.begin(batch);
+    if (rc != GC_OK) return rc;
+    gc_batch *b = pass.b;
+    gc_ctx *ctx = pass.ctx;
+    Staged io[] = {{wire_in, nullptr, stride * batch}, {nullptr, nullptr, 0, sizeof(uint32_t)}};
+    const Staged &d_wire = io[0], &d_bad = io[1];
+    if ((rc = stage_in(io, 2, ctx->stream)) != GC_OK) return rc;
+    GC_HIP(hipMemsetAsync(d_bad.d.p, 0, sizeof(uint32_t), ctx->stream));
+    if ((rc = pass.layout(false)) != GC_OK) return rc;
+    if ((rc = gc_batch_ingest_tables(b, d_wire.d.p, stride, d_bad.d.p)) != GC_OK) return rc;
+    // the verdict of the ingest decides whether the pass runs at all: a copy and a wait of its own
+    GC_HIP(hipMemcpyAsync(bad, d_bad.d.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));
+    // "wrong number of gates" (evaluator.go:44-47) / a row count Eval would reject (eval.go:54-56,86-89)
+    if (*bad) return GC_E_ROWS;
+    if ((rc = write_scatter(b, inputs, p.info.ninputs, 0, p.info.ninputs, nullptr, 0, b->d_W, b->g.lw)) != GC_OK) return rc;
+    if ((rc = gc_batch_eval(b, key, keylen, b)) != GC_OK) return rc;
+    if (out_labels && (rc = gc_batch_read_outputs(b, out_labels)) != GC_OK) return rc;
+    if ((rc = stage_out(io, 2, ctx->stream)) != GC_OK) return rc;  // (the wait of the call)
+    return pass.done();
 } catch (...) {
     return gc::on_exception();
 }

@@ -12,6 +12,7 @@
 #include "../../include/gcengine.h"
 #include "aes_host.h"
 #include "host_staging.h"  // DevBuf, GC_HIP, gc::set_error; Staged, stage_in / stage_out
+#include "host_transfer.h"  // TransferPipe, chunk_rule, download / upload
 #include "kernels.h"
 #include "plan.h"
 
@@ -26,13 +27,10 @@ struct gc_ctx {
     gc::CoTabEntry *d_co_g_tab = nullptr;  // the generator's window table (co_table.h), uploaded by the first gc_co_base_create
     std::mutex mu;              // serialises host-buffer calls sharing this ctx's stream
     bool capturing = false;     // between gc_ctx_capture_begin / _end: launches are recorded, not run
-    // host-buffer calls on PINNED caller memory (gc_host_alloc / gc_host_register): the DMA runs on its own stream,
-    // chunk k in flight while the transpose kernel of chunk k + 1 fills the other staging buffer (lazily created)
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_k[2] = {nullptr, nullptr};  // kernel on stage[b] done
-    hipEvent_t ev_c[2] = {nullptr, nullptr};  // copy from / to stage[b] done
-    void *stage[2] = {nullptr, nullptr};
-    size_t stage_cap = 0;
+    // host-buffer calls move their arrays in chunks through this (host_transfer.h; its work stream is `stream`): staging buffers
+    // that the transpose kernels fill or empty and, for PINNED caller memory (gc_host_alloc / gc_host_register), a stream of its
+    // own for the DMA, chunk k in flight while the kernel of chunk k + 1 works on the other buffer.  Created at first use.
+    gc::TransferPipe pipe;
     // ONE instance of a wide circuit as one cooperative launch (fused_kernels.hip: k_garble_coop): barrier state in device
     // memory, the verdict of the self-test (0 not run, 1 passed, -1 off), and a pinned word a pass raises when a workgroup
     // gives up at a barrier (checked when the next pass is enqueued and by gc_ctx_sync)

@@ -128,3 +128,59 @@ def test_host_wire_calls_match_oracle(aes_circ):
         assert e.value.code == engine.GC_E_ROWS
         dc.close()
     ctx.close()
+
+
+def test_good_calls_after_refused_calls_on_one_handle(add64_circ):
+    """one DeviceCircuit at batch 3, so that every call gets the same pooled batch: after each refused call — gc_eval_wire with
+    the gate count of the last instance flipped (GC_E_ROWS, the one refusal that arrives with work already queued), gc_eval a row
+    short (GC_E_ROWS), gc_garble with a 15-byte key (GC_E_KEYSIZE) and with a short random stream (GC_E_RAND) — the next good
+    gc_garble / gc_eval / gc_garble_wire / gc_eval_wire give the oracle's bytes"""
+    c, batch, key = add64_circ, 3, bytes(range(32))
+    nin, nout = c.num_inputs, c.num_outputs
+    ctx = engine.Context(0)
+    dc = engine.DeviceCircuit(ctx, c)
+    srnd = 16 * (nin + 1)
+    rnd = drbg("refused", srnd * batch)
+    refs = [oracle.garble(c.Gates, c.NumWires, nin, key, rnd[i * srnd:(i + 1) * srnd]) for i in range(batch)]
+    bits = (np.frombuffer(drbg("refused/bits", batch * nin), np.uint8) & 1).reshape(batch, -1).astype(bool)
+    inputs = np.stack([np.where(bits[i], refs[i]["wires"]["l1"][:nin], refs[i]["wires"]["l0"][:nin]) for i in range(batch)])
+    slab = np.stack([r["slab"] for r in refs])
+    want_wire = [oracle.tables_serialize(c.Gates, r["slab"]) for r in refs]
+    want_out = []
+    for i in range(batch):
+        w = np.zeros(c.NumWires, engine.LABEL)
+        w[:nin] = inputs[i]
+        oracle.eval_(c.Gates, c.NumWires, key, w, refs[i]["slab"])
+        want_out.append(w[c.NumWires - nout:])
+    nbytes = dc.tables_wire_bytes
+
+    def good_calls():
+        g = dc.garble(key, rnd, batch=batch)
+        gw = dc.garble_wire(key, rnd, batch=batch)
+        out = dc.eval(key, slab, inputs=inputs, batch=batch)
+        out_w = dc.eval_wire(key, gw["wire"], inputs, batch=batch)
+        for i in range(batch):
+            assert g["R"][i] == refs[i]["R"] and gw["R"][i] == refs[i]["R"]
+            assert (g["slab"][i] == refs[i]["slab"]).all()
+            assert gw["wire"][i, :nbytes].tobytes() == want_wire[i]
+            for io in (g["io"], gw["io"]):
+                assert (io[i][:nin] == refs[i]["wires"][:nin]).all() and (io[i][nin:] == refs[i]["wires"][c.NumWires - nout:]).all()
+            assert (out[i] == want_out[i]).all() and (out_w[i] == want_out[i]).all()
+        return gw["wire"]
+
+    wire = good_calls()
+    flipped = wire.copy()
+    flipped[batch - 1, 3] ^= 1
+    refused = [
+        (engine.GC_E_ROWS, lambda: dc.eval_wire(key, flipped, inputs, batch=batch)),
+        (engine.GC_E_ROWS, lambda: dc.eval(key, np.ascontiguousarray(slab[:, :-1]), inputs=inputs, batch=batch)),
+        (engine.GC_E_KEYSIZE, lambda: dc.garble(bytes(15), rnd, batch=batch)),
+        (engine.GC_E_RAND, lambda: dc.garble(key, rnd[:-1], batch=batch)),
+    ]
+    for code, call in refused:
+        with pytest.raises(engine.EngineError) as e:
+            call()
+        assert e.value.code == code
+        good_calls()
+    dc.close()
+    ctx.close()
