@@ -871,8 +871,7 @@ static int set_key(gc_batch *b, const uint8_t *key, size_t keylen) {
     return GC_OK;
 }
 
-// enqueue the level launches of one garble (eval == false) or eval pass; the first launch error (a geometry the launcher
-// refused, or what hipGetLastError() reports after the last launch)
+// enqueue the level launches of one garble (eval == false) or eval pass; the first launch error
 static hipError_t enqueue_levels(gc_batch *b, bool eval, const uint4 *T, hipStream_t s) {
     const Plan &p = b->circ->plan.p;
     LevelArgs a{};
@@ -887,10 +886,10 @@ static hipError_t enqueue_levels(gc_batch *b, bool eval, const uint4 *T, hipStre
         a.count = st.count;
         a.nonfree = st.nonfree;
         a.out_slot0 = p.info.ninputs + st.first;
-        const hipError_t e = eval ? launch_eval_level(a, b->g, s) : launch_garble_level(a, b->g, s);
+        const hipError_t e = launch_level(eval, a, b->g, s);
         if (e != hipSuccess) return e;
     }
-    return hipGetLastError();
+    return hipSuccess;
 }
 
 // the kernel arguments of the level-walking passes with the wires in HBM / of the flattened passes: rk = the round keys of
@@ -1031,9 +1030,7 @@ static int run_levels(gc_batch *b, Path path, bool eval, const uint4 *T, const u
     }
     case Path::FusedHbm: {
         const FusedArgs a = fused_args(b, T, b->d_rk, b->rounds);
-        if (eval) launch_eval_fused(a, b->g, s);
-        else launch_garble_fused(a, b->g, s);
-        GC_HIP(hipGetLastError());
+        GC_HIP(launch_fused(eval, a, b->g, s));
         b->last_launches = a.nsteps ? 1 : 0;
         return GC_OK;
     }
@@ -1042,8 +1039,7 @@ static int run_levels(gc_batch *b, Path path, bool eval, const uint4 *T, const u
         // a workgroup that gives up raises the pinned word *h_coop_err itself (no copy per pass); it stays up until
         // gc_ctx_coop_check (gc_ctx_sync, gc_pass_dev, the streaming calls that hand results out) notes it (with its stand-by
         // workgroup: a pass that loses a workgroup is done again inside the same launch)
-        launch_coop(eval, a, ctx->d_coop, b->xchg, ctx->coop_launched, s);
-        GC_HIP(hipGetLastError());
+        GC_HIP(launch_coop(eval, a, ctx->d_coop, b->xchg, ctx->coop_launched, s));
         if (a.nsteps) ctx->coop_launched++;  // (a launch that really went out) = the device's count of passes once this one has run
         b->last_launches = 1;
         return GC_OK;
@@ -1051,10 +1047,7 @@ static int run_levels(gc_batch *b, Path path, bool eval, const uint4 *T, const u
     case Path::WideLevels: {
         const FusedArgs a = fused_args(b, T, b->d_rk, b->rounds);
         b->last_launches = a.nsteps;
-        auto levels = [&] {
-            launch_levels1(eval, a, p.levels.data(), s);
-            return hipGetLastError();
-        };
+        auto levels = [&] { return launch_levels1(eval, a, p.levels.data(), s); };
         if (b->use_graph && !ctx->capturing && live_contexts() <= 1) return launch_graphed(b, eval, T, kGraphWide, levels);
         GC_HIP(levels());
         return GC_OK;

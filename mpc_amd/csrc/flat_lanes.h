@@ -1,6 +1,7 @@
 // flat_lanes.h — lane-level pieces of the flattened fused kernels that fused_flat_kernels.hip (one key per batch, round
 // keys in SGPRs) and fused_flat_keyed_kernels.hip (one key per instance, round keys in LDS) share: DPP and LDS label
-// helpers, the unit header, the hash-lane map and the XOR part.  Device code only; every function is inlined.
+// helpers, the unit header, the hash-lane map and the XOR part, every device function inlined; and the host's fill of their
+// kernel argument.
 #pragma once
 
 #include "aes_device.h"
@@ -72,6 +73,33 @@ __device__ __forceinline__ uint4 lxor3(uint4 a, uint4 b, uint4 c) {
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 using FlArgs = FlatJob;  // kernels.h
+
+// host: the kernel argument of a batch launch, every workgroup one tile of the same circuit
+inline FlArgs flat_job(bool eval, const FusedFlatArgs &f, const BatchGeom &g) {
+    FlArgs a{};
+    a.prog = (const uint4 *)f.prog;
+    a.units = f.units;
+    a.hgslot = f.hgslot;
+    a.ogslot = f.ogslot;
+    a.in_lds = f.in_lds;
+    a.nunits = f.nunits;
+    a.ninputs = f.ninputs;
+    a.ti_log2 = g.ti_log2;
+    a.zslot = f.nls - 1;
+    a.ustride = f.ustride;
+    a.w_tile = g.lw.tile_stride;
+    a.t_tile = g.lt.tile_stride;
+    a.W = f.W;
+    a.R = f.R;
+    a.T = f.T;
+    a.rk = f.rk;
+    a.te0 = f.te0;
+    a.prof = f.prof;
+    a.rnd = eval ? nullptr : f.rnd;
+    a.Rout = const_cast<uint4 *>(f.R);
+    a.batch = g.batch;
+    return a;
+}
 
 // Unit header i.  Loaded with VECTOR loads on purpose (vz is a zero the compiler cannot see through): scalar loads
 // share the lgkm counter with LDS and return out of order, so with a header in flight the first LDS read of the

@@ -740,71 +740,29 @@ size_t fused_flat_bytes(uint32_t nls, uint32_t ti_log2, uint32_t ustride) {
     return (size_t)(kStageOff + 2 * ustride) * sizeof(uint4) + ((size_t)(nls + 1) << ti_log2) * sizeof(uint4);
 }
 
-template <typename K>
-static hipError_t launch_fl(K kern, const FlArgs &a, uint32_t ntiles, size_t lds, hipStream_t s) {
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(TF), lds, s, a);
-    return hipGetLastError();
-}
-
 hipError_t launch_fused_flat(bool eval, const FusedFlatArgs &f, const BatchGeom &g, hipStream_t s) {
-    FlArgs a{};
-    a.prog = (const uint4 *)f.prog;
-    a.units = f.units;
-    a.hgslot = f.hgslot;
-    a.ogslot = f.ogslot;
-    a.in_lds = f.in_lds;
-    a.nunits = f.nunits;
-    a.ninputs = f.ninputs;
-    a.ti_log2 = g.ti_log2;
-    a.zslot = f.nls - 1;
-    a.ustride = f.ustride;
-    a.w_tile = g.lw.tile_stride;
-    a.t_tile = g.lt.tile_stride;
-    a.W = f.W;
-    a.R = f.R;
-    a.T = f.T;
-    a.rk = f.rk;
-    a.te0 = f.te0;
-    a.prof = f.prof;
-    a.rnd = eval ? nullptr : f.rnd;
-    a.Rout = const_cast<uint4 *>(f.R);
-    a.batch = g.batch;
+    const FlArgs a = flat_job(eval, f, g);
     if (a.nunits == 0) return hipSuccess;
     const size_t lds = fused_flat_bytes(f.nls, g.ti_log2, f.ustride);
-#define GC_M3(KERN, NR)                                                                      \
-    (f.prof ? (f.has_or ? launch_fl(KERN<NR, true, true>, a, g.ntiles, lds, s)               \
-                        : launch_fl(KERN<NR, true, false>, a, g.ntiles, lds, s))             \
-            : f.has_or ? launch_fl(KERN<NR, false, true>, a, g.ntiles, lds, s)              \
-                       : launch_fl(KERN<NR, false, false>, a, g.ntiles, lds, s))
-#define GC_M2(KERN) (f.rounds == 10 ? GC_M3(KERN, 10) : f.rounds == 12 ? GC_M3(KERN, 12) : GC_M3(KERN, 14))
-    return eval ? GC_M2(k_eval_flat) : GC_M2(k_garble_flat);
-#undef GC_M2
-#undef GC_M3
+    const dim3 grid(g.ntiles), block(TF);
+    return with_rounds(f.rounds, [&](auto nr) {
+        return with_flag(f.prof != nullptr, [&](auto prof) {
+            return with_flag(f.has_or, [&](auto has_or) {
+                constexpr int NR = decltype(nr)::value;
+                constexpr bool PROF = decltype(prof)::value, OR = decltype(has_or)::value;
+                if (eval) return launch_with_lds(k_eval_flat<NR, PROF, OR>, grid, block, lds, s, a);
+                return launch_with_lds(k_garble_flat<NR, PROF, OR>, grid, block, lds, s, a);
+            });
+        });
+    });
 }
 
-template <typename K>
-static hipError_t launch_jobs(K kern, const FlatJob *jobs, const uint32_t *first, uint32_t *sync, uint32_t nunits, size_t lds,
-                              hipStream_t s) {
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(nunits), dim3(TF), lds, s, jobs, first, sync);
-    return hipGetLastError();
-}
-
-template <typename K>
-static hipError_t launch_pool(K kern, PoolCtl *ctl, uint32_t nworkers, size_t lds, hipStream_t s) {
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(nworkers), dim3(TF), lds, s, ctl);
-    return hipGetLastError();
-}
+// (k_garble_flat_pool has one build per key length: no HAS_OR)
 hipError_t launch_fused_flat_pool(int rounds, PoolCtl *ctl, uint32_t nworkers, size_t lds_bytes, hipStream_t s) {
     if (nworkers == 0) return hipSuccess;
-    return rounds == 10 ? launch_pool(k_garble_flat_pool<10>, ctl, nworkers, lds_bytes, s)
-           : rounds == 12 ? launch_pool(k_garble_flat_pool<12>, ctl, nworkers, lds_bytes, s)
-                          : launch_pool(k_garble_flat_pool<14>, ctl, nworkers, lds_bytes, s);
+    return with_rounds(rounds, [&](auto nr) {
+        return launch_with_lds(k_garble_flat_pool<decltype(nr)::value>, dim3(nworkers), dim3(TF), lds_bytes, s, ctl);
+    });
 }
 void launch_pool_publish(PoolCtl *ctl, const PoolEntry *d_entries, uint32_t first_ticket, uint32_t n, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_pool_publish, dim3(1), dim3(256), 0, s, ctl, d_entries, first_ticket, n);
@@ -818,14 +776,18 @@ hipError_t launch_fused_flat_jobs(bool eval, int rounds, bool has_or, const Flat
                                   size_t lds_bytes, hipStream_t s, uint32_t *d_sync) {
     if (nunits == 0) return hipSuccess;
     if (d_sync && !d_first) return hipErrorInvalidValue;
-    const bool chain = d_first != nullptr;  // (nullptr: unit u is record u)
-#define GC_J4(KERN, NR, OR) (chain ? launch_jobs(KERN<NR, OR, true>, d_jobs, d_first, d_sync, nunits, lds_bytes, s) : launch_jobs(KERN<NR, OR, false>, d_jobs, d_first, nullptr, nunits, lds_bytes, s))
-#define GC_J3(KERN, NR) (has_or ? GC_J4(KERN, NR, true) : GC_J4(KERN, NR, false))
-#define GC_J2(KERN) (rounds == 10 ? GC_J3(KERN, 10) : rounds == 12 ? GC_J3(KERN, 12) : GC_J3(KERN, 14))
-    return eval ? GC_J2(k_eval_flat_jobs) : GC_J2(k_garble_flat_jobs);
-#undef GC_J2
-#undef GC_J3
-#undef GC_J4
+    const dim3 grid(nunits), block(TF);
+    return with_rounds(rounds, [&](auto nr) {
+        return with_flag(has_or, [&](auto has_or_t) {
+            return with_flag(d_first != nullptr, [&](auto chain) {  // (nullptr: unit u is record u, and nothing to wait for)
+                constexpr int NR = decltype(nr)::value;
+                constexpr bool OR = decltype(has_or_t)::value, CHAIN = decltype(chain)::value;
+                uint32_t *sync = CHAIN ? d_sync : nullptr;
+                if (eval) return launch_with_lds(k_eval_flat_jobs<NR, OR, CHAIN>, grid, block, lds_bytes, s, d_jobs, d_first, sync);
+                return launch_with_lds(k_garble_flat_jobs<NR, OR, CHAIN>, grid, block, lds_bytes, s, d_jobs, d_first, sync);
+            });
+        });
+    });
 }
 
 }  // namespace gc

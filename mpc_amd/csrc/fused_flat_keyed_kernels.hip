@@ -279,51 +279,27 @@ size_t fused_flat_keyed_bytes(uint32_t nls, uint32_t ti_log2, uint32_t ustride, 
 hipError_t launch_expand_keys(const uint8_t *d_keys, int rounds, uint32_t batch, const uint32_t *te0, uint32_t *d_out,
                               hipStream_t s) {
     const dim3 grid((batch + kExpandThreads - 1) / kExpandThreads), block(kExpandThreads);
-    if (rounds == 10) hipLaunchKernelGGL(k_expand_keys<10>, grid, block, 0, s, d_keys, batch, te0, d_out);
-    else if (rounds == 12) hipLaunchKernelGGL(k_expand_keys<12>, grid, block, 0, s, d_keys, batch, te0, d_out);
-    else hipLaunchKernelGGL(k_expand_keys<14>, grid, block, 0, s, d_keys, batch, te0, d_out);
-    return hipGetLastError();
+    return with_rounds(rounds, [&](auto nr) {
+        return launch_kernel(k_expand_keys<decltype(nr)::value>, grid, block, s, d_keys, batch, te0, d_out);
+    });
 }
 
-template <typename K>
-static hipError_t launch_keyed(K kern, const FlArgs &a, uint32_t ntiles, size_t lds, hipStream_t s) {
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(TF), lds, s, a);
-    return hipGetLastError();
-}
-
+// (a.prof is carried along and ignored)
 hipError_t launch_fused_flat_keyed(bool eval, const FusedFlatArgs &f, const BatchGeom &g, hipStream_t s) {
-    FlArgs a{};
-    a.prog = (const uint4 *)f.prog;
-    a.units = f.units;
-    a.hgslot = f.hgslot;
-    a.ogslot = f.ogslot;
-    a.in_lds = f.in_lds;
-    a.nunits = f.nunits;
-    a.ninputs = f.ninputs;
-    a.ti_log2 = g.ti_log2;
-    a.zslot = f.nls - 1;
-    a.ustride = f.ustride;
-    a.w_tile = g.lw.tile_stride;
-    a.t_tile = g.lt.tile_stride;
-    a.W = f.W;
-    a.R = f.R;
-    a.T = f.T;
-    a.rk = f.rk;
-    a.te0 = f.te0;
-    a.rnd = eval ? nullptr : f.rnd;
-    a.Rout = const_cast<uint4 *>(f.R);
-    a.batch = g.batch;
+    const FlArgs a = flat_job(eval, f, g);
     if (a.nunits == 0) return hipSuccess;
     if (!eval && !f.rnd) return hipErrorInvalidValue;
     const size_t lds = fused_flat_keyed_bytes(f.nls, g.ti_log2, f.ustride, f.rounds);
     if (lds > kFlatLdsBytes) return hipErrorInvalidConfiguration;
-#define GC_K3(KERN, NR) (f.has_or ? launch_keyed(KERN<NR, true>, a, g.ntiles, lds, s) : launch_keyed(KERN<NR, false>, a, g.ntiles, lds, s))
-#define GC_K2(KERN) (f.rounds == 10 ? GC_K3(KERN, 10) : f.rounds == 12 ? GC_K3(KERN, 12) : GC_K3(KERN, 14))
-    return eval ? GC_K2(k_eval_flat_keyed) : GC_K2(k_garble_flat_keyed);
-#undef GC_K2
-#undef GC_K3
+    const dim3 grid(g.ntiles), block(TF);
+    return with_rounds(f.rounds, [&](auto nr) {
+        return with_flag(f.has_or, [&](auto has_or) {
+            constexpr int NR = decltype(nr)::value;
+            constexpr bool OR = decltype(has_or)::value;
+            if (eval) return launch_with_lds(k_eval_flat_keyed<NR, OR>, grid, block, lds, s, a);
+            return launch_with_lds(k_garble_flat_keyed<NR, OR>, grid, block, lds, s, a);
+        });
+    });
 }
 
 }  // namespace gc

@@ -247,35 +247,26 @@ __global__ __launch_bounds__(kHbmKeyedThreads) void k_eval_hbm_keyed_split(const
     }
 }
 
-template <typename K, typename... A>
-static hipError_t launch_hbm_keyed_split(K kern, uint32_t ntiles, size_t lds, hipStream_t s, A... args) {
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(kHbmKeyedThreads), lds, s, args...);
-    return hipGetLastError();
-}
-
 hipError_t launch_fused_hbm_keyed_split(bool eval, const FusedArgs &a, const uint32_t *rk_per_instance, bool has_or,
                                         const BatchGeom &g, uint32_t tune, hipStream_t s) {
     if (a.nsteps == 0) return hipSuccess;
-    if (g.ti_log2 > 6 || !rk_per_instance || tune >= kHksWaves || (a.rounds != 10 && a.rounds != 12 && a.rounds != 14))
-        return hipErrorInvalidValue;
+    if (g.ti_log2 > 6 || !rk_per_instance || tune >= kHksWaves) return hipErrorInvalidValue;
     const size_t lds = fused_hbm_keyed_bytes(g.ti_log2, a.rounds);
     if (lds > kFlatLdsBytes) return hipErrorInvalidConfiguration;  // (the LDS of a CU: never with TI <= 64)
+    const dim3 grid(g.ntiles), block(kHbmKeyedThreads);
     const size_t wt = g.lw.tile_stride, tt = g.lt.tile_stride;
-#define GC_HG(NR, OR)                                                                                                         \
-    launch_hbm_keyed_split(k_garble_hbm_keyed_split<NR, OR>, g.ntiles, lds, s, a.descs, a.steps, a.nsteps, a.ninputs, g.ti_log2, \
-                           g.batch, wt, tt, a.W, a.R, a.T, rk_per_instance, a.te0, tune)
-#define GC_HE(NR, OR)                                                                                                       \
-    launch_hbm_keyed_split(k_eval_hbm_keyed_split<NR, OR>, g.ntiles, lds, s, a.descs, a.steps, a.nsteps, a.ninputs, g.ti_log2, \
-                           g.batch, wt, tt, a.W, (const uint4 *)a.T, rk_per_instance, a.te0, tune)
-#define GC_H3(M, NR) (has_or ? M(NR, true) : M(NR, false))
-#define GC_H2(M) (a.rounds == 10 ? GC_H3(M, 10) : a.rounds == 12 ? GC_H3(M, 12) : GC_H3(M, 14))
-    return eval ? GC_H2(GC_HE) : GC_H2(GC_HG);
-#undef GC_H2
-#undef GC_H3
-#undef GC_HE
-#undef GC_HG
+    const uint4 *Tc = a.T;
+    return with_rounds(a.rounds, [&](auto nr) {
+        return with_flag(has_or, [&](auto has_or_t) {
+            constexpr int NR = decltype(nr)::value;
+            constexpr bool OR = decltype(has_or_t)::value;
+            if (eval)
+                return launch_with_lds(k_eval_hbm_keyed_split<NR, OR>, grid, block, lds, s, a.descs, a.steps, a.nsteps, a.ninputs,
+                                       g.ti_log2, g.batch, wt, tt, a.W, Tc, rk_per_instance, a.te0, tune);
+            return launch_with_lds(k_garble_hbm_keyed_split<NR, OR>, grid, block, lds, s, a.descs, a.steps, a.nsteps, a.ninputs,
+                                   g.ti_log2, g.batch, wt, tt, a.W, a.R, a.T, rk_per_instance, a.te0, tune);
+        });
+    });
 }
 
 }  // namespace gc

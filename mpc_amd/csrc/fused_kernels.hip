@@ -1296,58 +1296,46 @@ void launch_coop_selftest(CoopCtl *ctl, hipStream_t s) {
     hipLaunchKernelGGL(k_coop_selftest, dim3(8 * kCoopGroups), dim3(kCoopThreads), 0, s, ctl);
 }
 
-void launch_coop(bool eval, const FusedArgs &a, CoopCtl *ctl, const StoreXchg *x, uint32_t seq, hipStream_t s) {
-    if (a.nsteps == 0) return;
+hipError_t launch_coop(bool eval, const FusedArgs &a, CoopCtl *ctl, const StoreXchg *x, uint32_t seq, hipStream_t s) {
+    if (a.nsteps == 0) return hipSuccess;
     // ctl->count is zero here: the self-test's host code and every pass leave it so (coop_leave)
     const dim3 grid(8 * (kCoopGroups + 1)), block(kCoopThreads);  // + the stand-by, on the same XCD
-#define GC_CO(NR)                                                                                                          \
-    if (eval)                                                                                                              \
-        hipLaunchKernelGGL((k_eval_coop<NR>), grid, block, 0, s, a.descs, a.steps, a.nsteps, a.ninputs, a.W,               \
-                           (const uint4 *)a.T, a.rk, a.te0, ctl, x, seq);                                                 \
-    else                                                                                                                   \
-        hipLaunchKernelGGL((k_garble_coop<NR>), grid, block, 0, s, a.descs, a.steps, a.nsteps, a.ninputs, a.W, a.R, a.T,   \
-                           a.rk, a.te0, ctl, x, seq)
-    switch (a.rounds) {
-    case 10: GC_CO(10); break;
-    case 12: GC_CO(12); break;
-    default: GC_CO(14); break;
-    }
-#undef GC_CO
+    const uint4 *Tc = a.T;
+    return with_rounds(a.rounds, [&](auto nr) {
+        constexpr int NR = decltype(nr)::value;
+        if (eval)
+            return launch_kernel(k_eval_coop<NR>, grid, block, s, a.descs, a.steps, a.nsteps, a.ninputs, a.W, Tc, a.rk, a.te0, ctl,
+                                 x, seq);
+        return launch_kernel(k_garble_coop<NR>, grid, block, s, a.descs, a.steps, a.nsteps, a.ninputs, a.W, a.R, a.T, a.rk, a.te0,
+                             ctl, x, seq);
+    });
 }
 
+// lanes of a level for one instance: a hash per lane, a free gate per lane
+static uint32_t level1_lanes(const Step &st, bool eval) {
+    return eval ? (st.n_and << 1) + st.n_or + st.n_inv + (st.count - st.nonfree)
+                : ((st.n_and + st.n_or) << 2) + (st.n_inv << 1) + (st.count - st.nonfree);
+}
 // passes (1024-lane workgroups) of a level for one instance: the measure of "wide" (plan.h: wide_for_one_instance)
-uint32_t level1_passes(const Step &st, bool eval) {
-    const uint32_t lanes = eval ? (st.n_and << 1) + st.n_or + st.n_inv + (st.count - st.nonfree)
-                                : ((st.n_and + st.n_or) << 2) + (st.n_inv << 1) + (st.count - st.nonfree);
-    return (lanes + kFusedThreads - 1) / kFusedThreads;
-}
-// workgroups of a level launch (kLevelLanes lanes each)
-static uint32_t level1_groups(const Step &st, bool eval) {
-    const uint32_t lanes = eval ? (st.n_and << 1) + st.n_or + st.n_inv + (st.count - st.nonfree)
-                                : ((st.n_and + st.n_or) << 2) + (st.n_inv << 1) + (st.count - st.nonfree);
-    return (lanes + kLevelLanes - 1) / kLevelLanes;
-}
+uint32_t level1_passes(const Step &st, bool eval) { return (level1_lanes(st, eval) + kFusedThreads - 1) / kFusedThreads; }
 
-// one launch per level of `levels` (host copy of the device step array a.steps)
-void launch_levels1(bool eval, const FusedArgs &a, const Step *levels, hipStream_t s) {
-    for (uint32_t lv = 0; lv < a.nsteps; lv++) {
-        const Step &st = levels[lv];
-        const uint32_t grid = level1_groups(st, eval);
-        if (grid == 0) continue;
-#define GC_L1(NR)                                                                                                      \
-    if (eval)                                                                                                          \
-        hipLaunchKernelGGL((k_eval_level1<NR>), dim3(grid), dim3(kFusedThreads), 0, s, a.descs, st, a.ninputs, a.W,    \
-                           (const uint4 *)a.T, a.rk, a.te0);                                                           \
-    else                                                                                                               \
-        hipLaunchKernelGGL((k_garble_level1<NR>), dim3(grid), dim3(kFusedThreads), 0, s, a.descs, st, a.ninputs, a.W,  \
-                           a.R, a.T, a.rk, a.te0)
-        switch (a.rounds) {
-        case 10: GC_L1(10); break;
-        case 12: GC_L1(12); break;
-        default: GC_L1(14); break;
+// one launch per level of `levels` (host copy of the device step array a.steps), of workgroups of kLevelLanes lanes
+hipError_t launch_levels1(bool eval, const FusedArgs &a, const Step *levels, hipStream_t s) {
+    const dim3 block(kFusedThreads);
+    const uint4 *Tc = a.T;
+    return with_rounds(a.rounds, [&](auto nr) {
+        constexpr int NR = decltype(nr)::value;
+        for (uint32_t lv = 0; lv < a.nsteps; lv++) {
+            const Step &st = levels[lv];
+            const dim3 grid((level1_lanes(st, eval) + kLevelLanes - 1) / kLevelLanes);
+            if (grid.x == 0) continue;
+            const hipError_t e = eval ? launch_kernel(k_eval_level1<NR>, grid, block, s, a.descs, st, a.ninputs, a.W, Tc, a.rk, a.te0)
+                                      : launch_kernel(k_garble_level1<NR>, grid, block, s, a.descs, st, a.ninputs, a.W, a.R, a.T,
+                                                      a.rk, a.te0);
+            if (e != hipSuccess) return e;
         }
-#undef GC_L1
-    }
+        return hipSuccess;
+    });
 }
 
 static uint32_t tune_env() {
@@ -1368,66 +1356,29 @@ bool fused_col_form_fits(const Step *levels, uint32_t nsteps, uint32_t ti_log2) 
     return hashed != 0;  // (a circuit without hashed gates gains nothing from the form)
 }
 
-void launch_garble_fused(const FusedArgs &a, const BatchGeom &g, hipStream_t s) {
-    if (a.nsteps == 0) return;
-    dim3 grid(g.ntiles), block(kFusedThreads);
-    if (a.narrow_col && !a.prof) {
-#define GC_GN(NR)                                                                                                          \
-    hipLaunchKernelGGL((k_garble_col<NR>), grid, block, 0, s, a.descs, a.steps, a.nsteps, a.ninputs, g.ti_log2,            \
-                       g.lw.tile_stride, g.lt.tile_stride, a.W, a.R, a.T, a.rk, a.te0)
-        switch (a.rounds) {
-        case 10: GC_GN(10); break;
-        case 12: GC_GN(12); break;
-        default: GC_GN(14); break;
+// k_*_col where every level is narrow (never built with the profile), k_*_fused otherwise
+hipError_t launch_fused(bool eval, const FusedArgs &a, const BatchGeom &g, hipStream_t s) {
+    if (a.nsteps == 0) return hipSuccess;
+    const dim3 grid(g.ntiles), block(kFusedThreads);
+    const uint4 *Tc = a.T;
+    return with_rounds(a.rounds, [&](auto nr) {
+        constexpr int NR = decltype(nr)::value;
+        if (a.narrow_col && !a.prof) {
+            if (eval)
+                return launch_kernel(k_eval_col<NR>, grid, block, s, a.descs, a.steps, a.nsteps, a.ninputs, g.ti_log2,
+                                     g.lw.tile_stride, g.lt.tile_stride, a.W, Tc, a.rk, a.te0);
+            return launch_kernel(k_garble_col<NR>, grid, block, s, a.descs, a.steps, a.nsteps, a.ninputs, g.ti_log2,
+                                 g.lw.tile_stride, g.lt.tile_stride, a.W, a.R, a.T, a.rk, a.te0);
         }
-#undef GC_GN
-        return;
-    }
-#define GC_GF(NR)                                                                                               \
-    if (a.prof)                                                                                                 \
-        hipLaunchKernelGGL((k_garble_fused<NR, true>), grid, block, 0, s, a.descs, a.steps, a.nsteps, a.ninputs,    \
-                           g.ti_log2, g.lw.tile_stride, g.lt.tile_stride, a.W, a.R, a.T, a.rk, a.te0, a.prof, tune_env());  \
-    else                                                                                                        \
-        hipLaunchKernelGGL((k_garble_fused<NR, false>), grid, block, 0, s, a.descs, a.steps, a.nsteps, a.ninputs,   \
-                           g.ti_log2, g.lw.tile_stride, g.lt.tile_stride, a.W, a.R, a.T, a.rk, a.te0, a.prof, tune_env())
-    switch (a.rounds) {
-    case 10: GC_GF(10); break;
-    case 12: GC_GF(12); break;
-    default: GC_GF(14); break;
-    }
-#undef GC_GF
-}
-
-void launch_eval_fused(const FusedArgs &a, const BatchGeom &g, hipStream_t s) {
-    if (a.nsteps == 0) return;
-    dim3 grid(g.ntiles), block(kFusedThreads);
-    if (a.narrow_col && !a.prof) {
-#define GC_EN(NR)                                                                                                          \
-    hipLaunchKernelGGL((k_eval_col<NR>), grid, block, 0, s, a.descs, a.steps, a.nsteps, a.ninputs, g.ti_log2,              \
-                       g.lw.tile_stride, g.lt.tile_stride, a.W, (const uint4 *)a.T, a.rk, a.te0)
-        switch (a.rounds) {
-        case 10: GC_EN(10); break;
-        case 12: GC_EN(12); break;
-        default: GC_EN(14); break;
-        }
-#undef GC_EN
-        return;
-    }
-#define GC_EF(NR)                                                                                               \
-    if (a.prof)                                                                                                 \
-        hipLaunchKernelGGL((k_eval_fused<NR, true>), grid, block, 0, s, a.descs, a.steps, a.nsteps, a.ninputs,      \
-                           g.ti_log2, g.lw.tile_stride, g.lt.tile_stride, a.W, (const uint4 *)a.T, a.rk, a.te0, \
-                           a.prof, tune_env());                                                                             \
-    else                                                                                                        \
-        hipLaunchKernelGGL((k_eval_fused<NR, false>), grid, block, 0, s, a.descs, a.steps, a.nsteps, a.ninputs,     \
-                           g.ti_log2, g.lw.tile_stride, g.lt.tile_stride, a.W, (const uint4 *)a.T, a.rk, a.te0, \
-                           a.prof, tune_env())
-    switch (a.rounds) {
-    case 10: GC_EF(10); break;
-    case 12: GC_EF(12); break;
-    default: GC_EF(14); break;
-    }
-#undef GC_EF
+        return with_flag(a.prof != nullptr, [&](auto prof) {
+            constexpr bool PROF = decltype(prof)::value;
+            if (eval)
+                return launch_kernel(k_eval_fused<NR, PROF>, grid, block, s, a.descs, a.steps, a.nsteps, a.ninputs, g.ti_log2,
+                                     g.lw.tile_stride, g.lt.tile_stride, a.W, Tc, a.rk, a.te0, a.prof, tune_env());
+            return launch_kernel(k_garble_fused<NR, PROF>, grid, block, s, a.descs, a.steps, a.nsteps, a.ninputs, g.ti_log2,
+                                 g.lw.tile_stride, g.lt.tile_stride, a.W, a.R, a.T, a.rk, a.te0, a.prof, tune_env());
+        });
+    });
 }
 
 }  // namespace gc

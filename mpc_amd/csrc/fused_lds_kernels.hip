@@ -549,14 +549,6 @@ size_t fused_lds_bytes(uint32_t nls, uint32_t ti_log2) {
     return (size_t)kStageEnd * sizeof(uint4) + ((size_t)(nls + 1) << ti_log2) * sizeof(uint4);
 }
 
-template <typename K>
-static hipError_t launch_lds(K kern, int threads, const LdsArgs &a, uint32_t ntiles, size_t lds, hipStream_t s) {
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(threads), lds, s, a);
-    return hipGetLastError();
-}
-
 // Workgroup shape: 1024 threads, ONE AES chain per hash lane.  Measured alternatives on MI355X (aes_128 x
 // 1024, AES-256 key, garble pass): 1024 x ILP1 1.12 ms | 512 x ILP2 1.49 ms | 256 x ILP4 2.35 ms | 1024 x ILP2
 // with per-wave narrowing 1.26 ms | two 1024-thread workgroups per CU on a 32 KiB table 1.45 ms.  A CDNA4
@@ -584,14 +576,18 @@ hipError_t launch_fused_lds(bool eval, const FusedLdsArgs &f, const BatchGeom &g
     a.prof = f.prof;
     if (a.nsteps == 0) return hipSuccess;
     const size_t lds = fused_lds_bytes(f.nls, g.ti_log2);
-#define GC_L3(KERN, NR)                                                                      \
-    (f.prof ? launch_lds(KERN<NR, 1024, 1, false, true>, 1024, a, g.ntiles, lds, s)              \
-            : f.store_all ? launch_lds(KERN<NR, 1024, 1, true, false>, 1024, a, g.ntiles, lds, s) \
-                          : launch_lds(KERN<NR, 1024, 1, false, false>, 1024, a, g.ntiles, lds, s))
-#define GC_L2(KERN) (f.rounds == 10 ? GC_L3(KERN, 10) : f.rounds == 12 ? GC_L3(KERN, 12) : GC_L3(KERN, 14))
-    return eval ? GC_L2(k_eval_lds) : GC_L2(k_garble_lds);
-#undef GC_L2
-#undef GC_L3
+    const dim3 grid(g.ntiles), block(1024);
+    return with_rounds(f.rounds, [&](auto nr) {
+        constexpr int NR = decltype(nr)::value;
+        auto launch = [&](auto store_all, auto prof) {
+            constexpr bool ALL = decltype(store_all)::value, PROF = decltype(prof)::value;
+            if (eval) return launch_with_lds(k_eval_lds<NR, 1024, 1, ALL, PROF>, grid, block, lds, s, a);
+            return launch_with_lds(k_garble_lds<NR, 1024, 1, ALL, PROF>, grid, block, lds, s, a);
+        };
+        // three builds, not four: the profiled one never stores every wire
+        if (f.prof) return launch(std::false_type{}, std::true_type{});
+        return with_flag(f.store_all, [&](auto store_all) { return launch(store_all, std::false_type{}); });
+    });
 }
 
 }  // namespace gc

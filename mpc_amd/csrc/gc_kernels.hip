@@ -277,61 +277,37 @@ static bool level_whole_gates() {
     return v;
 }
 
-#define GC_DISPATCH_LEVEL(KERNEL, ...)                                                                     \
-    do {                                                                                                   \
-        dim3 grid((a.count + (256u >> g.lg) - 1) / (256u >> g.lg), g.yblocks), block(256);                 \
-        const bool uni = g.lg >= 6;                                                                        \
-        switch (a.rounds) {                                                                                \
-        case 10:                                                                                           \
-            if (uni) hipLaunchKernelGGL((KERNEL<10, true>), grid, block, 0, s, __VA_ARGS__);               \
-            else hipLaunchKernelGGL((KERNEL<10, false>), grid, block, 0, s, __VA_ARGS__);                  \
-            break;                                                                                         \
-        case 12:                                                                                           \
-            if (uni) hipLaunchKernelGGL((KERNEL<12, true>), grid, block, 0, s, __VA_ARGS__);               \
-            else hipLaunchKernelGGL((KERNEL<12, false>), grid, block, 0, s, __VA_ARGS__);                  \
-            break;                                                                                         \
-        default:                                                                                           \
-            if (uni) hipLaunchKernelGGL((KERNEL<14, true>), grid, block, 0, s, __VA_ARGS__);               \
-            else hipLaunchKernelGGL((KERNEL<14, false>), grid, block, 0, s, __VA_ARGS__);                  \
-            break;                                                                                         \
-        }                                                                                                  \
-    } while (0)
-
-// the list of workgroups and its grid come from split_grid (split_grid.h): 64-bit block count, spread over grid.y past 2^24 - 1
-#define GC_DISPATCH_SPLIT(KERNEL, PER, ...)                                                                \
-    do {                                                                                                   \
-        const SplitGrid sg = split_grid(a.count, a.nonfree, g.batch, g.lg, (PER));                         \
-        if (!sg.ok) return hipErrorInvalidConfiguration;                                                   \
-        const dim3 grid(sg.gx, sg.gy), block(256);                                                         \
-        switch (a.rounds) {                                                                                \
-        case 10: hipLaunchKernelGGL((KERNEL<10>), grid, block, 0, s, __VA_ARGS__, sg.chunks, sg.nb_hash, sg.gx_free, sg.nblocks); break; \
-        case 12: hipLaunchKernelGGL((KERNEL<12>), grid, block, 0, s, __VA_ARGS__, sg.chunks, sg.nb_hash, sg.gx_free, sg.nblocks); break; \
-        default: hipLaunchKernelGGL((KERNEL<14>), grid, block, 0, s, __VA_ARGS__, sg.chunks, sg.nb_hash, sg.gx_free, sg.nblocks); break; \
-        }                                                                                                  \
-    } while (0)
-
-hipError_t launch_garble_level(const LevelArgs &a, const BatchGeom &g, hipStream_t s) {
+// a level's launch: split (a hash per wave; the list of workgroups and its grid come from split_grid.h: 64-bit block count,
+// spread over grid.y past 2^24 - 1) when it has hashed gates, a gate per thread otherwise
+hipError_t launch_level(bool eval, const LevelArgs &a, const BatchGeom &g, hipStream_t s) {
     if (a.count == 0) return hipSuccess;
+    const dim3 block(256);
+    const uint4 *Tc = a.T;
     if (a.nonfree && !level_whole_gates()) {
-        GC_DISPATCH_SPLIT(k_garble_level_split, 64u, a.descs, a.count, a.nonfree, a.out_slot0, g.batch, g.bstride, g.lg, a.W, a.R,
-                          a.T, a.rk, a.te0);
-        return hipSuccess;
+        const SplitGrid sg = split_grid(a.count, a.nonfree, g.batch, g.lg, eval ? 128u : 64u);
+        if (!sg.ok) return hipErrorInvalidConfiguration;
+        const dim3 grid(sg.gx, sg.gy);
+        return with_rounds(a.rounds, [&](auto nr) {
+            constexpr int NR = decltype(nr)::value;
+            if (eval)
+                return launch_kernel(k_eval_level_split<NR>, grid, block, s, a.descs, a.count, a.nonfree, a.out_slot0, g.batch,
+                                     g.bstride, g.lg, a.W, Tc, a.rk, a.te0, sg.chunks, sg.nb_hash, sg.gx_free, sg.nblocks);
+            return launch_kernel(k_garble_level_split<NR>, grid, block, s, a.descs, a.count, a.nonfree, a.out_slot0, g.batch,
+                                 g.bstride, g.lg, a.W, a.R, a.T, a.rk, a.te0, sg.chunks, sg.nb_hash, sg.gx_free, sg.nblocks);
+        });
     }
-    GC_DISPATCH_LEVEL(k_garble_level, a.descs, a.count, a.nonfree, a.out_slot0, g.batch, g.bstride, g.lg, a.W, a.R,
-                      a.T, a.rk, a.te0);
-    return hipSuccess;
-}
-
-hipError_t launch_eval_level(const LevelArgs &a, const BatchGeom &g, hipStream_t s) {
-    if (a.count == 0) return hipSuccess;
-    if (a.nonfree && !level_whole_gates()) {
-        GC_DISPATCH_SPLIT(k_eval_level_split, 128u, a.descs, a.count, a.nonfree, a.out_slot0, g.batch, g.bstride, g.lg, a.W,
-                          (const uint4 *)a.T, a.rk, a.te0);
-        return hipSuccess;
-    }
-    GC_DISPATCH_LEVEL(k_eval_level, a.descs, a.count, a.nonfree, a.out_slot0, g.batch, g.bstride, g.lg, a.W,
-                      (const uint4 *)a.T, a.rk, a.te0);
-    return hipSuccess;
+    const dim3 grid((a.count + (256u >> g.lg) - 1) / (256u >> g.lg), g.yblocks);
+    return with_rounds(a.rounds, [&](auto nr) {
+        return with_flag(g.lg >= 6, [&](auto uni) {
+            constexpr int NR = decltype(nr)::value;
+            constexpr bool UNI = decltype(uni)::value;
+            if (eval)
+                return launch_kernel(k_eval_level<NR, UNI>, grid, block, s, a.descs, a.count, a.nonfree, a.out_slot0, g.batch,
+                                     g.bstride, g.lg, a.W, Tc, a.rk, a.te0);
+            return launch_kernel(k_garble_level<NR, UNI>, grid, block, s, a.descs, a.count, a.nonfree, a.out_slot0, g.batch,
+                                 g.bstride, g.lg, a.W, a.R, a.T, a.rk, a.te0);
+        });
+    });
 }
 
 // ------------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@
 
 #include "co_multi_table.h"
 #include "co_table.h"
+#include "launch_dispatch.h"
 #include "p256.h"
 #include "plan.h"
 #include "vole_mod.h"
@@ -63,8 +64,7 @@ struct LevelArgs {
 };
 
 // hipErrorInvalidConfiguration (nothing launched) when a split level's workgroups fit no legal grid (split_grid.h)
-hipError_t launch_garble_level(const LevelArgs &a, const BatchGeom &g, hipStream_t s);
-hipError_t launch_eval_level(const LevelArgs &a, const BatchGeom &g, hipStream_t s);
+hipError_t launch_level(bool eval, const LevelArgs &a, const BatchGeom &g, hipStream_t s);
 
 // Fused schedule: ONE launch walks all levels; a workgroup owns a tile of instances and
 // synchronises its own waves between levels (no inter-workgroup dependency at all).
@@ -82,12 +82,12 @@ struct FusedArgs {
     bool narrow_col; // every level fits one column-sliced pass (fused_col_form_fits): k_garble_col / k_eval_col
 };
 bool fused_col_form_fits(const Step *levels, uint32_t nsteps, uint32_t ti_log2);
-void launch_garble_fused(const FusedArgs &a, const BatchGeom &g, hipStream_t s);
-void launch_eval_fused(const FusedArgs &a, const BatchGeom &g, hipStream_t s);
+hipError_t launch_fused(bool eval, const FusedArgs &a, const BatchGeom &g, hipStream_t s);
 // ONE instance with wires in HBM: one launch per level, pass k of the level = workgroup k (lanes along the gates);
 // levels = host copy of the step array
 uint32_t level1_passes(const Step &st, bool eval);
-void launch_levels1(bool eval, const FusedArgs &a, const Step *levels, hipStream_t s);
+// (stops at the first level whose launch fails)
+hipError_t launch_levels1(bool eval, const FusedArgs &a, const Step *levels, hipStream_t s);
 // the same walk as ONE launch: kCoopGroups workgroups of one XCD (one L2) walk the levels together, a counter in that L2
 // is the barrier between levels (fused_kernels.hip: k_garble_coop).  ctl lives in device memory; a pass leaves the counters
 // at zero for the next one (no memset between passes: a fill kernel plus its gaps was 10 us of a 250 us step).
@@ -124,7 +124,7 @@ struct StoreXchg {
 // barrier of its own (slow, correct: the per-gate code of the level launches, level_gate.h), including the exchange with the
 // wire store that the failed pass skipped, and clears the flag.  The kernel ends when the stand-by does, so a lost workgroup
 // costs time, never a result: what follows on the stream sees the labels and table rows of a good pass.
-void launch_coop(bool eval, const FusedArgs &a, CoopCtl *ctl, const StoreXchg *x, uint32_t seq, hipStream_t s);
+hipError_t launch_coop(bool eval, const FusedArgs &a, CoopCtl *ctl, const StoreXchg *x, uint32_t seq, hipStream_t s);
 void launch_coop_selftest(CoopCtl *ctl, hipStream_t s);
 
 // Fused schedule with LDS-resident wires (fused_lds_kernels.hip)
@@ -332,16 +332,6 @@ inline bool iknp_counters_fit_32(uint64_t pos0, uint64_t chunks) {
     const char *gen = std::getenv("GC_IKNP_GENERIC");
     return ((pos0 >> 4) + 4 * chunks + 8) < (1ull << 32) && !(gen && gen[0] == '1');
 }
-#if defined(__HIPCC__)
-// a kernel with `lds` bytes of dynamic LDS: set the size, launch, return the first error
-template <typename K, typename... A>
-hipError_t launch_with_lds(K kern, unsigned grid, unsigned threads, size_t lds, hipStream_t s, A... args) {
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, args...);
-    return hipGetLastError();
-}
-#endif
 // IKNP OT extension, fused (iknp_fused_kernels.hip): column AES-128-CTR PRG + u-matrix / delta fold + createLabels.
 // rk0/rk1: [128][44] expanded column keys (big-endian words); pos0: bytes every column stream has already
 // produced; n OTs in chunks of 512.
@@ -356,8 +346,8 @@ void launch_pack_bits(const uint8_t *b, size_t n, uint8_t *out, hipStream_t s);
 void launch_fold_choice_words(const uint64_t *choices, size_t n, uint64_t *bbuf, hipStream_t s);
 void launch_pack_label_bit0(const uint4 *labels, size_t n, uint64_t *result, hipStream_t s);
 // KOS check accumulators: acc[0..3] ^= XOR chi_i * v_i (256 bit), acc[4..5] ^= XOR_{bits_i} chi_i
-void launch_kos_accumulate(const uint32_t *rk, uint64_t idx0, const uint4 *v, const uint8_t *bits, size_t n,
-                           unsigned long long *acc, const uint32_t *te0, hipStream_t s);
+hipError_t launch_kos_accumulate(const uint32_t *rk, uint64_t idx0, const uint4 *v, const uint8_t *bits, size_t n,
+                                 unsigned long long *acc, const uint32_t *te0, hipStream_t s);
 // blk[j*h + t] ^= AES_{key(gid0+j)}(blk[j*h+t])
 hipError_t launch_mitccrh(uint4 seed, uint64_t gid0, uint4 *blks, size_t n, uint32_t h, const uint32_t *te0,
                           hipStream_t s);
@@ -419,9 +409,9 @@ hipError_t launch_kos_multi_check(const uint4 *seed2, const uint4 *result, const
 // ---- VOLE kernels (vole_kernels.hip) ---------------------------------------------------------
 // every value 32 bytes big-endian (2 uint4 per element); labels: gc_label [m].  sender: r = BE256(AES-CTR_label(0^32))
 // mod p, u = (r + x * y) mod p; receiver: u_out = u_msg mod p (u_out may be u_msg)
-void launch_vole_sender(const VoleMod &mod, const uint4 *labels, const uint4 *x, const uint4 *y_msg, size_t m, uint4 *r_out,
-                        uint4 *u_out, const uint32_t *te0, hipStream_t s);
-void launch_vole_receiver(const VoleMod &mod, const uint4 *u_msg, size_t m, uint4 *u_out, hipStream_t s);
+hipError_t launch_vole_sender(const VoleMod &mod, const uint4 *labels, const uint4 *x, const uint4 *y_msg, size_t m, uint4 *r_out,
+                              uint4 *u_out, const uint32_t *te0, hipStream_t s);
+hipError_t launch_vole_receiver(const VoleMod &mod, const uint4 *u_msg, size_t m, uint4 *u_out, hipStream_t s);
 
 // ---- device random streams (rand_kernels.hip; the streams, their blocks and the units of work: rand_ctr.h) ----
 constexpr int kRandThreads = 1024;        // k_rand_fill: one lane = one AES-CTR block of a unit (a wave's run of 64 blocks)

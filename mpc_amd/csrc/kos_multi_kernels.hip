@@ -160,12 +160,8 @@ hipError_t launch(K kern, bool wg, const uint4 *seed2, const uint4 *result, cons
                   const uint8_t *bcv, const uint4 *delta, const uint4 *tags_in, size_t S, size_t per, uint4 *tags_out,
                   uint8_t *ok, unsigned long long *status, const uint32_t *te0, hipStream_t s) {
     const size_t lds = kTeDualBytes + (wg ? kFoldBytes : 0);
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    const unsigned grid = kos_multi_grid(S, kKosMultiGrid);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(KT), lds, s, seed2, result, choice, cv, bcv, delta, tags_in, (uint64_t)S,
-                       (uint64_t)per, tags_out, ok, status, te0);
-    return hipGetLastError();
+    return launch_with_lds(kern, kos_multi_grid(S, kKosMultiGrid), KT, lds, s, seed2, result, choice, cv, bcv, delta, tags_in,
+                           (uint64_t)S, (uint64_t)per, tags_out, ok, status, te0);
 }
 
 }  // namespace

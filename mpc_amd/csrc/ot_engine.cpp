@@ -363,9 +363,8 @@ static int kos_sums(gc_ctx *ctx, const gc_label *seed2, const gc_label *result, 
         size_t n;
     } parts[2] = {{0, d_res, d_bits, n}, {n, io[1].d.p, io[2].d.p, 256}};
     for (const auto &part : parts)
-        launch_kos_accumulate((const uint32_t *)io[0].d.p, part.idx0, (const uint4 *)part.v, (const uint8_t *)part.bits, part.n,
-                              (unsigned long long *)io[3].d.p, ctx->d_te0, s);
-    GC_HIP(hipGetLastError());
+        GC_HIP(launch_kos_accumulate((const uint32_t *)io[0].d.p, part.idx0, (const uint4 *)part.v, (const uint8_t *)part.bits,
+                                     part.n, (unsigned long long *)io[3].d.p, ctx->d_te0, s));
     return stage_out(io, k, s);
 }
 

@@ -314,12 +314,11 @@ __global__ __launch_bounds__(kCotThreads) void k_kos_accumulate(const uint32_t *
     }
 }
 
-void launch_kos_accumulate(const uint32_t *rk, uint64_t idx0, const uint4 *v, const uint8_t *bits, size_t n,
-                           unsigned long long *acc, const uint32_t *te0, hipStream_t s) {
-    if (n == 0) return;
-    (void)hipFuncSetAttribute((const void *)k_kos_accumulate, hipFuncAttributeMaxDynamicSharedMemorySize, kTeDualBytes);
+hipError_t launch_kos_accumulate(const uint32_t *rk, uint64_t idx0, const uint4 *v, const uint8_t *bits, size_t n,
+                                 unsigned long long *acc, const uint32_t *te0, hipStream_t s) {
+    if (n == 0) return hipSuccess;
     const unsigned grid = (unsigned)std::min<size_t>(kCotGrid, (n + kCotThreads - 1) / kCotThreads);
-    hipLaunchKernelGGL(k_kos_accumulate, dim3(grid), dim3(kCotThreads), kTeDualBytes, s, rk, idx0, v, bits, n, acc, te0);
+    return launch_with_lds(k_kos_accumulate, grid, kCotThreads, kTeDualBytes, s, rk, idx0, v, bits, n, acc, te0);
 }
 
 hipError_t launch_mitccrh(uint4 seed, uint64_t gid0, uint4 *blks, size_t n, uint32_t h, const uint32_t *te0, hipStream_t s) {

@@ -129,19 +129,10 @@ hipError_t launch_fill(int rounds, const uint32_t *rk, const RandCtr *ivs, size_
                        size_t stride, uint64_t *out_b, const uint32_t *te0, hipStream_t s) {
     const uint64_t units = (uint64_t)S * rand_units(rand_cover(pos, n).nblocks);
     const unsigned grid = (unsigned)std::min<uint64_t>(kRandGrid, (units + kRandWaves - 1) / kRandWaves);
-    const dim3 g(grid), b(kRandThreads);
-#define GC_RAND_LAUNCH(NR)                                                                                             \
-    do {                                                                                                               \
-        (void)hipFuncSetAttribute((const void *)k_rand_fill<NR, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                                  kTeDualBytes);                                                                       \
-        hipLaunchKernelGGL((k_rand_fill<NR, MODE>), g, b, kTeDualBytes, s, rk, ivs, (uint64_t)S, pos, n, (uint8_t *)out, \
-                           (uint64_t)stride, out_b, te0);                                                              \
-    } while (0)
-    if (rounds == 10) GC_RAND_LAUNCH(10);
-    else if (rounds == 12) GC_RAND_LAUNCH(12);
-    else GC_RAND_LAUNCH(14);
-#undef GC_RAND_LAUNCH
-    return hipGetLastError();
+    return with_rounds(rounds, [&](auto nr) {
+        return launch_with_lds(k_rand_fill<decltype(nr)::value, MODE>, grid, kRandThreads, kTeDualBytes, s, rk, ivs, (uint64_t)S, pos,
+                               n, (uint8_t *)out, (uint64_t)stride, out_b, te0);
+    });
 }
 
 }  // namespace
@@ -149,11 +140,10 @@ hipError_t launch_fill(int rounds, const uint32_t *rk, const RandCtr *ivs, size_
 hipError_t launch_rand_expand(const uint8_t *d_seeds, int rounds, const uint8_t *d_ivs, size_t S, const uint32_t *te0,
                               uint32_t *d_rk, RandCtr *d_iv, hipStream_t s) {
     const unsigned grid = (unsigned)std::min<uint64_t>(kRandExpandGrid, ((uint64_t)S + kRandExpandThreads - 1) / kRandExpandThreads);
-    const dim3 g(grid), b(kRandExpandThreads);
-    if (rounds == 10) hipLaunchKernelGGL(k_rand_expand<10>, g, b, 0, s, d_seeds, d_ivs, (uint64_t)S, te0, d_rk, d_iv);
-    else if (rounds == 12) hipLaunchKernelGGL(k_rand_expand<12>, g, b, 0, s, d_seeds, d_ivs, (uint64_t)S, te0, d_rk, d_iv);
-    else hipLaunchKernelGGL(k_rand_expand<14>, g, b, 0, s, d_seeds, d_ivs, (uint64_t)S, te0, d_rk, d_iv);
-    return hipGetLastError();
+    return with_rounds(rounds, [&](auto nr) {
+        return launch_kernel(k_rand_expand<decltype(nr)::value>, grid, kRandExpandThreads, s, d_seeds, d_ivs, (uint64_t)S, te0, d_rk,
+                             d_iv);
+    });
 }
 
 hipError_t launch_rand_fill(int rounds, const uint32_t *d_rk, const RandCtr *d_iv, size_t S, uint64_t pos, uint64_t n,

@@ -17,14 +17,12 @@ bool bytes_fit(size_t m) { return m <= SIZE_MAX / 32; }
 // The operations on device pointers, the device set: what a _dev form does behind its argument checks
 int sender_run(gc_ctx *ctx, const VoleMod &mod, const void *d_labels, const void *d_x, const void *d_y_msg, size_t m,
                void *d_r_out, void *d_u_msg_out) {
-    launch_vole_sender(mod, (const uint4 *)d_labels, (const uint4 *)d_x, (const uint4 *)d_y_msg, m, (uint4 *)d_r_out,
-                       (uint4 *)d_u_msg_out, ctx->d_te0, ctx->stream);
-    GC_HIP(hipGetLastError());
+    GC_HIP(launch_vole_sender(mod, (const uint4 *)d_labels, (const uint4 *)d_x, (const uint4 *)d_y_msg, m, (uint4 *)d_r_out,
+                              (uint4 *)d_u_msg_out, ctx->d_te0, ctx->stream));
     return GC_OK;
 }
 int receiver_run(gc_ctx *ctx, const VoleMod &mod, const void *d_u_msg, size_t m, void *d_u_out) {
-    launch_vole_receiver(mod, (const uint4 *)d_u_msg, m, (uint4 *)d_u_out, ctx->stream);
-    GC_HIP(hipGetLastError());
+    GC_HIP(launch_vole_receiver(mod, (const uint4 *)d_u_msg, m, (uint4 *)d_u_out, ctx->stream));
     return GC_OK;
 }
 

@@ -83,19 +83,17 @@ __global__ __launch_bounds__(kVoleRecvThreads) void k_vole_receiver(VoleMod mod,
 }  // namespace
 
 // grids are computed in 64 bits and capped; the kernels' grid-stride loops cover any m
-void launch_vole_sender(const VoleMod &mod, const uint4 *labels, const uint4 *x, const uint4 *y_msg, size_t m, uint4 *r_out,
-                        uint4 *u_out, const uint32_t *te0, hipStream_t s) {
-    if (m == 0) return;
-    (void)hipFuncSetAttribute((const void *)k_vole_sender, hipFuncAttributeMaxDynamicSharedMemorySize, kTeDualBytes);
+hipError_t launch_vole_sender(const VoleMod &mod, const uint4 *labels, const uint4 *x, const uint4 *y_msg, size_t m, uint4 *r_out,
+                              uint4 *u_out, const uint32_t *te0, hipStream_t s) {
+    if (m == 0) return hipSuccess;
     const unsigned grid = (unsigned)std::min<size_t>(kVoleGrid, (m + kVoleThreads - 1) / kVoleThreads);
-    hipLaunchKernelGGL(k_vole_sender, dim3(grid), dim3(kVoleThreads), kTeDualBytes, s, mod, labels, x, y_msg, m, r_out, u_out,
-                       te0);
+    return launch_with_lds(k_vole_sender, grid, kVoleThreads, kTeDualBytes, s, mod, labels, x, y_msg, m, r_out, u_out, te0);
 }
 
-void launch_vole_receiver(const VoleMod &mod, const uint4 *u_msg, size_t m, uint4 *u_out, hipStream_t s) {
-    if (m == 0) return;
+hipError_t launch_vole_receiver(const VoleMod &mod, const uint4 *u_msg, size_t m, uint4 *u_out, hipStream_t s) {
+    if (m == 0) return hipSuccess;
     const unsigned grid = (unsigned)std::min<size_t>(kVoleRecvGrid, (m + kVoleRecvThreads - 1) / kVoleRecvThreads);
-    hipLaunchKernelGGL(k_vole_receiver, dim3(grid), dim3(kVoleRecvThreads), 0, s, mod, u_msg, m, u_out);
+    return launch_kernel(k_vole_receiver, grid, kVoleRecvThreads, s, mod, u_msg, m, u_out);
 }
 
 }  // namespace gc

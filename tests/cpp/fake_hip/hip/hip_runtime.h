@@ -10,7 +10,7 @@
 #include <cstring>
 #include <vector>
 
-enum hipError_t { hipSuccess = 0, hipErrorOutOfMemory = 2, hipErrorUnknown = 999 };
+enum hipError_t { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorOutOfMemory = 2, hipErrorUnknown = 999 };
 enum hipMemcpyKind { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2 };
 typedef struct fake_hip_stream *hipStream_t;
 typedef struct fake_hip_event *hipEvent_t;
