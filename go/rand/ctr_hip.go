@@ -22,10 +22,12 @@ import (
 	"crypto/cipher"
 	"fmt"
 	"io"
+	"math/big"
 	"unsafe"
 )
 
-// DeviceRand holds the expanded seeds of S sessions and the one byte position their streams share.
+// DeviceRand holds the expanded seeds of S sessions and the one byte position their streams share; the cursor calls
+// (SetCursors, FillAt, Ints) keep one position per session in an array of the caller's instead.
 type DeviceRand struct {
 	h      *C.gc_rand
 	seeds  [][]byte
@@ -153,6 +155,93 @@ func (d *DeviceRand) GMWShares(words int, dA, dB unsafe.Pointer) error {
 	return nil
 }
 
+// Per-session cursors: dCur is uint64 [S] in device memory (8-byte aligned), dCur[s] the byte position of stream s; dStatus
+// is uint64 [2] = {bad sessions, lowest bad session}.  The calls below read the positions from dCur and advance it on the
+// device, leave Pos alone and may be recorded between gc_ctx_capture_begin and _end: a replayed graph continues every
+// stream where the array stands.  A bad session (its range would pass 2^64-1, or Ints would need more than 4*count+256
+// candidates) keeps its outputs and its cursor untouched and is counted in dStatus.
+
+// SetCursors sets dCur[s] = pos for every session.
+func (d *DeviceRand) SetCursors(dCur unsafe.Pointer, pos uint64) error {
+	if st := C.gc_rand_cur_set_dev(d.h, dCur, C.uint64_t(pos)); st != C.GC_OK {
+		return randErr(st)
+	}
+	return nil
+}
+
+// FillAt writes bytes [cur[s], cur[s]+nbytes) of stream s to dOut + s*stride and advances cur[s] by nbytes.
+func (d *DeviceRand) FillAt(dCur unsafe.Pointer, nbytes int, dOut unsafe.Pointer, stride int, dStatus unsafe.Pointer) error {
+	if st := C.gc_rand_fill_cur_dev(d.h, dCur, C.size_t(nbytes), dOut, C.size_t(stride), dStatus); st != C.GC_OK {
+		return randErr(st)
+	}
+	return nil
+}
+
+func maxBytes(max *big.Int) ([]byte, error) {
+	if max.Sign() <= 0 || max.BitLen() > 256 {
+		return nil, fmt.Errorf("invalid modulus: %v bits", max.BitLen())
+	}
+	return max.FillBytes(make([]byte, 32)), nil
+}
+
+// Ints is count successive crand.Int(reader_s, max) draws for every session, exactly as crypto/rand makes them on
+// HostReader(s) positioned at cur[s]: dOut [S][count][32] big-endian, zero-padded on the left (the d_a of
+// gc_co_multi_sender_setup_dev with count = 1, the d_scalars of gc_co_multi_receiver_choices_dev).  cur[s] advances by
+// the bytes the draws consumed, rejected candidates included.  2 <= max < 2^256.
+func (d *DeviceRand) Ints(dCur unsafe.Pointer, max *big.Int, count int, dOut, dStatus unsafe.Pointer) error {
+	m, err := maxBytes(max)
+	if err != nil {
+		return err
+	}
+	if st := C.gc_rand_scalars_cur_dev(d.h, dCur, (*C.uint8_t)(unsafe.Pointer(&m[0])), C.size_t(count), dOut, dStatus); st != C.GC_OK {
+		return randErr(st)
+	}
+	return nil
+}
+
+// FillAtHost is FillAt on host memory: cur [S] is read and written back, out holds S*stride bytes.  With a bad session it
+// returns an error that names the lowest one; every good session is written and advanced all the same.
+func (d *DeviceRand) FillAtHost(cur []uint64, nbytes int, out []byte, stride int) error {
+	if len(cur) != len(d.seeds) || stride < nbytes || len(out) < len(d.seeds)*stride {
+		return fmt.Errorf("invalid sizes: %v cursors, %v bytes for %v sessions of %v", len(cur), len(out), len(d.seeds), stride)
+	}
+	if nbytes == 0 {
+		return nil
+	}
+	bad := ^C.size_t(0)
+	st := C.gc_rand_fill_cur(d.h, (*C.uint64_t)(unsafe.Pointer(&cur[0])), C.size_t(nbytes), (*C.uint8_t)(unsafe.Pointer(&out[0])),
+		C.size_t(stride), &bad)
+	return cursorErr(st, bad)
+}
+
+// IntsHost is Ints on host memory: out holds S*count*32 bytes.
+func (d *DeviceRand) IntsHost(cur []uint64, max *big.Int, count int, out []byte) error {
+	m, err := maxBytes(max)
+	if err != nil {
+		return err
+	}
+	if len(cur) != len(d.seeds) || len(out) < len(d.seeds)*count*32 {
+		return fmt.Errorf("invalid sizes: %v cursors, %v bytes for %v sessions of %v scalars", len(cur), len(out), len(d.seeds), count)
+	}
+	if count == 0 {
+		return nil
+	}
+	bad := ^C.size_t(0)
+	st := C.gc_rand_scalars_cur(d.h, (*C.uint64_t)(unsafe.Pointer(&cur[0])), (*C.uint8_t)(unsafe.Pointer(&m[0])), C.size_t(count),
+		(*C.uint8_t)(unsafe.Pointer(&out[0])), &bad)
+	return cursorErr(st, bad)
+}
+
+func cursorErr(st C.int, bad C.size_t) error {
+	if st == C.GC_E_ARG && bad != ^C.size_t(0) {
+		return fmt.Errorf("session %v: the stream ends before the draw does", uint64(bad))
+	}
+	if st != C.GC_OK {
+		return randErr(st)
+	}
+	return nil
+}
+
 // HostReader builds the stream of session s from its start with crypto/cipher: what code that stays in Go sets as
 // env.Config.Rand to read the bytes the device draws.
 func (d *DeviceRand) HostReader(s int) (io.Reader, error) {
@@ -165,4 +254,17 @@ func (d *DeviceRand) HostReader(s int) (io.Reader, error) {
 		copy(iv, d.ivs[s])
 	}
 	return cipher.StreamReader{S: cipher.NewCTR(block, iv), R: zeros{}}, nil
+}
+
+// HostReaderAt is HostReader(s) with the first pos bytes read and dropped: the reader whose crand.Int draws Ints makes
+// for a session whose cursor stands at pos, and whose Reads FillAt makes.
+func (d *DeviceRand) HostReaderAt(s int, pos uint64) (io.Reader, error) {
+	r, err := d.HostReader(s)
+	if err != nil {
+		return nil, err
+	}
+	if _, err := io.CopyN(io.Discard, r, int64(pos)); err != nil {
+		return nil, err
+	}
+	return r, nil
 }

@@ -1343,8 +1343,38 @@ int gc_sha2pc_evaluator_round4(gc_sha2pc_evaluator *, const gc_p256_point *A, co
  *   gc_gmw_set_triples_dev take them; advances the position by 16 * words and needs a position that is a multiple of 16.
  *   Errors.  nbytes = 0 and words = 0 return GC_OK and do nothing.  GC_E_ARG, the position unchanged: a NULL handle or
  *   array, stride < nbytes, a position that is no multiple of 16 (shares), a position or size past uint64_t / size_t, any
- *   draw between gc_ctx_capture_begin and _end (the position is a kernel argument; the rule of gc_iknp_multi_*).
- *   Not offered: draws inside a captured graph, per-session positions, the rejection-sampled scalars of crand.Int. */
+ *   draw on the handle's position between gc_ctx_capture_begin and _end (that position is a kernel argument; the rule of
+ *   gc_iknp_multi_*).
+ *   Cursors.  The calls with _cur in their name take the positions from the caller instead: d_cur is uint64_t [S] in device
+ *   memory, 8-byte aligned and the caller's, d_cur[s] the byte position of stream s.  They read it and advance it on the
+ *   device, so sessions may consume different amounts; they allocate nothing, wait for nothing, leave the handle's own
+ *   position alone and are legal between gc_ctx_capture_begin and _end: a replayed graph continues every stream where the
+ *   array stands.  d_status is uint64_t [2] = {bad sessions, lowest bad session}, 8-byte aligned; the call resets it on the
+ *   stream to {0, ~0} and its kernels fill it.  A BAD session's outputs are left untouched, never zeroed, and its cursor
+ *   unchanged; the other sessions are served.
+ *   gc_rand_cur_set_dev: d_cur[s] = pos for every s.
+ *   gc_rand_fill_cur_dev: bytes [cur[s], cur[s] + nbytes) of stream s go to d_out + s * stride, then cur[s] += nbytes; the
+ *   slot rules are gc_rand_fill_dev's, decided per slot.  Bad: cur[s] > 2^64 - 1 - nbytes.  Two launches: the fill, then the
+ *   advance of the cursors (several workgroups serve one stream and all of them read its cursor).
+ *   gc_rand_scalars_cur_dev: for every session `count` successive crand.Int(reader_s, max) draws as Go's crypto/rand makes
+ *   them (GenerateCOSenderSetup ot/co_helpers.go:83: one per session; BuildCOChoices ot/co_helpers.go:150-151: per OT).  max is 32 bytes big-endian on the host, 2 <= max < 2^256.  With bitlen = BitLen(max - 1), k = ceil(bitlen / 8) and
+ *   b = bitlen % 8 (8 for 0) a candidate is the next k bytes of the stream, the first byte cut to its low b bits, read
+ *   big-endian, and is accepted if < max; a rejected candidate consumes k bytes like an accepted one.  d_out [S][count][32]
+ *   takes the first `count` accepted candidates of each session, big-endian, zero-padded on the left: the d_a of
+ *   gc_co_multi_sender_setup_dev (count = 1), the d_scalars of gc_co_multi_receiver_choices_dev and of the sha2pc rounds.
+ *   cur[s] advances by k * (candidates consumed).  A session looks at no more than cap = 4 * count + 256 candidates: that
+ *   bound is part of the contract (a candidate is accepted with probability above 1/2; needing more has probability below
+ *   2^-90 for every count).  Bad: a session that would need more, and one with cur[s] > 2^64 - 1 - k * cap.  The second test
+ *   is conservative: it asks for room for every candidate the session MAY look at, about twice what it will.
+ *   gc_rand_fill_cur, gc_rand_scalars_cur: the same on host arrays (staged, synchronous, not inside a capture); cur is read
+ *   and written back.  With a bad session they return GC_E_ARG and *bad_session = the lowest one (bad_session may be NULL);
+ *   every good session is written and advanced all the same.
+ *   Errors of the _cur calls, checked before anything is launched, nothing changed: GC_E_ARG for a NULL handle, array or
+ *   d_status, stride < nbytes, a last slot that ends past size_t, S * count * 32 past size_t, a d_cur or d_status that is
+ *   not 8-byte aligned, max of 0 (Go panics) or 1 (Go reads nothing).  nbytes = 0 or count = 0: GC_OK, nothing done, the
+ *   status included.
+ *   Not offered: gc_rand_gmw_shares_dev on cursors, a draw of one very long session by more than one wave, moduli past
+ *   256 bits. */
 typedef struct gc_rand gc_rand;
 gc_rand *gc_rand_create(gc_ctx *, const uint8_t *seeds, size_t keylen, const uint8_t *ivs, size_t S, int *status);
 gc_rand *gc_rand_create_dev(gc_ctx *, const void *d_seeds, size_t keylen, const void *d_ivs, size_t S, int *status);
@@ -1354,6 +1384,14 @@ int gc_rand_seek(gc_rand *, uint64_t pos); /* byte position of every stream */
 int gc_rand_fill_dev(gc_rand *, size_t nbytes, void *d_out, size_t stride);
 int gc_rand_fill(gc_rand *, size_t nbytes, uint8_t *out, size_t stride); /* host form, staged */
 int gc_rand_gmw_shares_dev(gc_rand *, size_t words, void *d_a, void *d_b);
+/* d_status: uint64_t[2] = {bad sessions, lowest bad session}; the call resets it on the stream to {0, ~0} and the kernels
+ * fill it */
+int gc_rand_cur_set_dev(gc_rand *, void *d_cur, uint64_t pos); /* d_cur[s] = pos for every s */
+int gc_rand_fill_cur_dev(gc_rand *, void *d_cur, size_t nbytes, void *d_out, size_t stride, void *d_status);
+int gc_rand_scalars_cur_dev(gc_rand *, void *d_cur, const uint8_t max[32], size_t count, void *d_out, void *d_status);
+/* host forms: staged and synchronous like gc_rand_fill; cur is in/out */
+int gc_rand_fill_cur(gc_rand *, uint64_t *cur, size_t nbytes, uint8_t *out, size_t stride, size_t *bad_session);
+int gc_rand_scalars_cur(gc_rand *, uint64_t *cur, const uint8_t max[32], size_t count, uint8_t *out, size_t *bad_session);
 
 #ifdef __cplusplus
 }

@@ -968,7 +968,8 @@ private:
 
 // The random streams of S sessions, expanded on the device (gcengine.h: gc_rand_*): stream s is what a Go host reads from
 // cipher.StreamReader{S: cipher.NewCTR(aes.NewCipher(seed[s]), iv[s]), R: zeros}, the reader it would set as env.Config.Rand.
-// One byte position for all streams; every draw is one launch on the ctx stream.
+// One byte position for all streams; every draw is one launch on the ctx stream.  The cursor calls (SetCursors, FillAt, Ints)
+// keep one position per session in a device array of the caller's, advance it on the device and may be captured.
 namespace rand {
 
 class DeviceRand {
@@ -1015,7 +1016,38 @@ public:
     // tripleBatch's draws (gmw/triples.go:301-310): a, b u64 [S][words]
     void GMWShares(size_t words, void *d_a, void *d_b) { check(gc_rand_gmw_shares_dev(h_, words, d_a, d_b), "gc_rand_gmw_shares_dev"); }
 
+    // Per-session cursors: d_cur u64 [S] (8-byte aligned), d_status u64 [2] = {bad sessions, lowest bad session}.  A bad
+    // session keeps its outputs and its cursor untouched.
+    void SetCursors(void *d_cur, uint64_t pos) { check(gc_rand_cur_set_dev(h_, d_cur, pos), "gc_rand_cur_set_dev"); }
+    // bytes [cur[s], cur[s] + nbytes) of stream s to d_out + s * stride; cur[s] += nbytes
+    void FillAt(void *d_cur, size_t nbytes, void *d_out, size_t stride, void *d_status) {
+        check(gc_rand_fill_cur_dev(h_, d_cur, nbytes, d_out, stride, d_status), "gc_rand_fill_cur_dev");
+    }
+    // `count` crand.Int(reader_s, max) draws per session, max 32 bytes big-endian: d_out [S][count][32] as
+    // gc_co_multi_sender_setup_dev (count = 1) and gc_co_multi_receiver_choices_dev take their scalars
+    void Ints(void *d_cur, const uint8_t max[32], size_t count, void *d_out, void *d_status) {
+        check(gc_rand_scalars_cur_dev(h_, d_cur, max, count, d_out, d_status), "gc_rand_scalars_cur_dev");
+    }
+    // the host forms: cur [S] is read and written back; false and *bad_session = the lowest bad session when one is bad
+    // (the good ones are written and advanced all the same)
+    bool FillAtHost(uint64_t *cur, size_t nbytes, uint8_t *out, size_t stride, size_t *bad_session = nullptr) {
+        size_t bad = (size_t)-1;
+        return host_form(gc_rand_fill_cur(h_, cur, nbytes, out, stride, &bad), bad, bad_session, "gc_rand_fill_cur");
+    }
+    bool IntsHost(uint64_t *cur, const uint8_t max[32], size_t count, uint8_t *out, size_t *bad_session = nullptr) {
+        size_t bad = (size_t)-1;
+        return host_form(gc_rand_scalars_cur(h_, cur, max, count, out, &bad), bad, bad_session, "gc_rand_scalars_cur");
+    }
+
 private:
+    static bool host_form(int st, size_t bad, size_t *bad_session, const char *what) {
+        if (st == GC_E_ARG && bad != (size_t)-1) {
+            if (bad_session) *bad_session = bad;
+            return false;
+        }
+        check(st, what);
+        return true;
+    }
     DeviceRand(gc_rand *h, size_t S) : h_(h), S_(S) {}
     gc_rand *h_ = nullptr;
     size_t S_ = 0;

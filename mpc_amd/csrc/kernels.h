@@ -428,6 +428,18 @@ hipError_t launch_rand_fill(int rounds, const uint32_t *d_rk, const RandCtr *d_i
 // draw i of `words` (16 bytes from pos, a multiple of 16): a[s][i] = BE64 of its first half, b[s][i] of its second
 hipError_t launch_rand_gmw_shares(int rounds, const uint32_t *d_rk, const RandCtr *d_iv, size_t S, uint64_t pos, uint64_t words,
                                   uint64_t *d_a, uint64_t *d_b, const uint32_t *te0, hipStream_t s);
+// Per-session cursors (rand_cursor_kernels.hip): d_cur u64 [S] holds the byte position of every stream and the kernels advance
+// it; d_status u64 [2] = {bad sessions, lowest bad session}, reset on the stream by every launch_ below but _set.
+struct RandIntShape;
+hipError_t launch_rand_cur_set(uint64_t *d_cur, size_t S, uint64_t pos, hipStream_t s);
+// bytes [cur[s], cur[s] + n) of stream s to d_out + s * stride, cur[s] += n; a session whose range would pass 2^64 - 1 is bad:
+// slot and cursor untouched.  Two launches: the fill, then the advance.
+hipError_t launch_rand_cur_fill(int rounds, const uint32_t *d_rk, const RandCtr *d_iv, size_t S, uint64_t *d_cur, uint64_t n,
+                                uint8_t *d_out, size_t stride, uint64_t *d_status, const uint32_t *te0, hipStream_t s);
+// `count` > 0 draws of crand.Int per session (rand_int.h) to d_out [S][count][32], big-endian
+hipError_t launch_rand_cur_scalars(int rounds, const uint32_t *d_rk, const RandCtr *d_iv, size_t S, uint64_t *d_cur,
+                                   const RandIntShape &shape, uint64_t count, uint8_t *d_out, uint64_t *d_status,
+                                   const uint32_t *te0, hipStream_t s);
 
 // ---- Chou-Orlandi base OT kernels (co_kernels.hip) -------------------------------------------
 // The constants of one session, passed by value (uniform across the grid).  a: the sender's scalar mod N, non-zero, limbs

@@ -3,10 +3,13 @@
 // rand_kernels.hip is the device side.  The handle holds the expanded seeds and one byte position for all S streams; a call
 // is one launch on the ctx stream with the position as a kernel argument.  The host form is staging (host_staging.h) around
 // the operation of the _dev form.
+// The _cur calls take the positions from a caller-owned device array instead, one per session, which the kernels of
+// rand_cursor_kernels.hip read and advance: they leave h->pos alone and, with nothing of the call in a kernel argument that a
+// replay would have to change, are legal inside a capture.  crand.Int's arithmetic is rand_int.h's.
 #include <new>
 
 #include "engine.h"
-#include "rand_ctr.h"
+#include "rand_int.h"
 
 using namespace gc;
 
@@ -92,6 +95,61 @@ int fill_run(gc_rand *h, size_t nbytes, void *d_out, size_t stride) {
     return GC_OK;
 }
 
+// ---- per-session cursors ----
+
+struct CurStatus {
+    uint64_t bad, lowest;  // what d_status holds
+};
+
+bool misaligned8(const void *p) { return ((uintptr_t)p & 7u) != 0; }
+
+// the checks of a cursor fill of n > 0 bytes; nothing is launched or changed where they fail
+int fill_cur_args(const gc_rand *h, const void *cur, uint64_t n, const void *out, size_t stride, const void *status, bool dev) {
+    if (!cur || !out || (dev && !status) || stride < n) return GC_E_ARG;
+    if (dev && (misaligned8(cur) || misaligned8(status))) return GC_E_ARG;
+    if (h->S - 1 > (SIZE_MAX - (size_t)n) / stride) return GC_E_ARG;  // the last slot ends past size_t
+    return GC_OK;
+}
+
+// ... of `count` > 0 scalars below max; the shape of max on the way
+int scalars_cur_args(const gc_rand *h, const void *cur, const uint8_t *max, size_t count, const void *out, const void *status,
+                     bool dev, RandIntShape &shape) {
+    if (!cur || !max || !out || (dev && !status)) return GC_E_ARG;
+    if (dev && (misaligned8(cur) || misaligned8(status))) return GC_E_ARG;
+    if (count > SIZE_MAX / 32 / h->S) return GC_E_ARG;  // S * count * 32 past size_t
+    return rand_int_shape(max, shape) ? GC_OK : GC_E_ARG;  // max of 0 or 1
+}
+
+int fill_cur_run(gc_rand *h, void *d_cur, size_t nbytes, void *d_out, size_t stride, void *d_status) {
+    GC_HIP(launch_rand_cur_fill(h->rounds, h->d_rk, h->d_iv, h->S, (uint64_t *)d_cur, nbytes, (uint8_t *)d_out, stride,
+                                (uint64_t *)d_status, h->ctx->d_te0, h->ctx->stream));
+    return GC_OK;
+}
+
+int scalars_cur_run(gc_rand *h, void *d_cur, const RandIntShape &shape, size_t count, void *d_out, void *d_status) {
+    GC_HIP(launch_rand_cur_scalars(h->rounds, h->d_rk, h->d_iv, h->S, (uint64_t *)d_cur, shape, count, (uint8_t *)d_out,
+                                   (uint64_t *)d_status, h->ctx->d_te0, h->ctx->stream));
+    return GC_OK;
+}
+
+// A host form: the cursors go in and come back, the output array goes in and comes back whole (a bad session's part and the
+// gaps between slots return as they came), the status block comes back.  `run` is the _dev operation on the device copies.
+template <typename Run>
+int cur_host_form(gc_rand *h, uint64_t *cur, uint8_t *out, size_t out_bytes, size_t *bad_session, Run run) {
+    gc_ctx *ctx = h->ctx;
+    if (ctx->capturing) return GC_E_ARG;  // allocates and waits
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GC_HIP(hipSetDevice(ctx->device));
+    CurStatus st{0, 0};
+    Staged io[] = {{cur, cur, h->S * sizeof(uint64_t)}, {out, out, out_bytes}, {nullptr, &st, sizeof st}};
+    int rc = stage_in(io, 3, ctx->stream);
+    if (rc == GC_OK) rc = run(io[0].d.p, io[1].d.p, io[2].d.p);
+    if (rc == GC_OK) rc = stage_out(io, 3, ctx->stream);
+    if (rc != GC_OK || st.bad == 0) return rc;
+    if (bad_session) *bad_session = (size_t)st.lowest;
+    return GC_E_ARG;
+}
+
 }  // namespace
 
 extern "C" {
@@ -173,6 +231,57 @@ int gc_rand_gmw_shares_dev(gc_rand *h, size_t words, void *d_a, void *d_b) {
                                   h->ctx->d_te0, h->ctx->stream));
     h->pos += 16 * (uint64_t)words;
     return GC_OK;
+}
+
+int gc_rand_cur_set_dev(gc_rand *h, void *d_cur, uint64_t pos) {
+    if (!h || !d_cur || misaligned8(d_cur)) return GC_E_ARG;
+    GC_HIP(hipSetDevice(h->ctx->device));
+    GC_HIP(launch_rand_cur_set((uint64_t *)d_cur, h->S, pos, h->ctx->stream));
+    return GC_OK;
+}
+
+int gc_rand_fill_cur_dev(gc_rand *h, void *d_cur, size_t nbytes, void *d_out, size_t stride, void *d_status) {
+    if (!h) return GC_E_ARG;
+    if (nbytes == 0) return GC_OK;
+    int rc = fill_cur_args(h, d_cur, nbytes, d_out, stride, d_status, true);
+    if (rc != GC_OK) return rc;
+    GC_HIP(hipSetDevice(h->ctx->device));
+    return fill_cur_run(h, d_cur, nbytes, d_out, stride, d_status);
+}
+
+int gc_rand_scalars_cur_dev(gc_rand *h, void *d_cur, const uint8_t max[32], size_t count, void *d_out, void *d_status) {
+    if (!h) return GC_E_ARG;
+    if (count == 0) return GC_OK;
+    RandIntShape shape;
+    int rc = scalars_cur_args(h, d_cur, max, count, d_out, d_status, true, shape);
+    if (rc != GC_OK) return rc;
+    GC_HIP(hipSetDevice(h->ctx->device));
+    return scalars_cur_run(h, d_cur, shape, count, d_out, d_status);
+}
+
+int gc_rand_fill_cur(gc_rand *h, uint64_t *cur, size_t nbytes, uint8_t *out, size_t stride, size_t *bad_session) try {
+    if (!h) return GC_E_ARG;
+    if (nbytes == 0) return GC_OK;
+    int rc = fill_cur_args(h, cur, nbytes, out, stride, nullptr, false);
+    if (rc != GC_OK) return rc;
+    return cur_host_form(h, cur, out, (h->S - 1) * stride + nbytes, bad_session, [&](void *d_cur, void *d_out, void *d_status) {
+        return fill_cur_run(h, d_cur, nbytes, d_out, stride, d_status);
+    });
+} catch (...) {
+    return gc::on_exception();
+}
+
+int gc_rand_scalars_cur(gc_rand *h, uint64_t *cur, const uint8_t max[32], size_t count, uint8_t *out, size_t *bad_session) try {
+    if (!h) return GC_E_ARG;
+    if (count == 0) return GC_OK;
+    RandIntShape shape;
+    int rc = scalars_cur_args(h, cur, max, count, out, nullptr, false, shape);
+    if (rc != GC_OK) return rc;
+    return cur_host_form(h, cur, out, h->S * count * 32, bad_session, [&](void *d_cur, void *d_out, void *d_status) {
+        return scalars_cur_run(h, d_cur, shape, count, d_out, d_status);
+    });
+} catch (...) {
+    return gc::on_exception();
 }
 
 }  // extern "C"

@@ -358,6 +358,11 @@ def lib():
         "gc_rand_fill_dev": (i32, [vp, sz, vp, sz]),
         "gc_rand_fill": (i32, [vp, sz, vp, sz]),
         "gc_rand_gmw_shares_dev": (i32, [vp, sz, vp, vp]),
+        "gc_rand_cur_set_dev": (i32, [vp, vp, C.c_uint64]),
+        "gc_rand_fill_cur_dev": (i32, [vp, vp, sz, vp, sz, vp]),
+        "gc_rand_scalars_cur_dev": (i32, [vp, vp, vp, sz, vp, vp]),
+        "gc_rand_fill_cur": (i32, [vp, vp, sz, vp, sz, C.POINTER(C.c_size_t)]),
+        "gc_rand_scalars_cur": (i32, [vp, vp, vp, sz, vp, C.POINTER(C.c_size_t)]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -2593,10 +2598,31 @@ def rand_kernel_shape():
     return tuple(out)
 
 
+class RandSessionError(EngineError):
+    """a bad session of a host-form cursor draw (GC_E_ARG): .bad_session = the lowest one, .out = the outputs all the same
+    (a bad session's part as it came), .cur = the cursors (a bad session's unchanged)"""
+
+    def __init__(self, what, bad_session, out, cur):
+        super().__init__(GC_E_ARG, what)
+        self.bad_session, self.out, self.cur = bad_session, out, cur
+
+
+P256_N = 0xffffffff00000000ffffffffffffffffbce6faada7179e84f3b9cac2fc632551  # Chou-Orlandi draws its scalars below it
+
+
+def _max32(mx):
+    """the modulus of a scalar draw as gc_rand_scalars_cur* take it: 32 bytes big-endian"""
+    mx = int(mx)
+    if not 0 <= mx < 1 << 256:
+        raise EngineError(GC_E_ARG, "RandStreams: max must lie below 2^256")
+    return np.frombuffer(mx.to_bytes(32, "big"), np.uint8)
+
+
 class RandStreams:
     """gc_rand: S AES-CTR keystreams, stream s what Go reads from cipher.StreamReader{cipher.NewCTR(aes.NewCipher(seed[s]),
     iv[s]), zeros}.  seeds: u8 [S, keylen] (host), ivs u8 [S, 16] or None (all zero); or device buffers of those with S and
-    keylen given.  One byte position for all streams; close the handle before its Context."""
+    keylen given.  One byte position for all streams, or with the *_cur methods one per session in an array of the caller's
+    (u64 [S]: device for the device forms, numpy for the _host forms); close the handle before its Context."""
 
     def __init__(self, ctx, seeds, ivs=None, S=None, keylen=None):
         st = C.c_int(0)
@@ -2651,6 +2677,62 @@ class RandStreams:
         d_rnd [S, 1 + ninputs, 16] of Batch.garble_keyed"""
         self.fill(32, d_keys)
         self.fill(16 * (1 + ninputs), d_rnd)
+
+    # ---- per-session cursors: d_cur u64 [S] and d_status u64 [2] = {bad sessions, lowest bad session} on the device; every
+    # call is asynchronous on the ctx stream, leaves .pos alone and may be captured ----
+
+    def cur_set(self, d_cur, pos=0):
+        """d_cur[s] = pos for every s"""
+        _check(lib().gc_rand_cur_set_dev(self.h, _dp(d_cur), pos), "gc_rand_cur_set_dev")
+
+    def fill_cur(self, d_cur, nbytes, d_out, d_status, stride=None):
+        """bytes [cur[s], cur[s] + nbytes) of stream s -> d_out + s * stride (default: nbytes); cur[s] += nbytes"""
+        _check(lib().gc_rand_fill_cur_dev(self.h, _dp(d_cur), nbytes, _dp(d_out), nbytes if stride is None else stride,
+                                          _dp(d_status)), "gc_rand_fill_cur_dev")
+
+    def scalars_cur(self, d_cur, mx, count, d_out, d_status):
+        """`count` crand.Int(reader_s, mx) draws per session -> d_out u8 [S, count, 32] big-endian; mx a Python int"""
+        _check(lib().gc_rand_scalars_cur_dev(self.h, _dp(d_cur), _p(_max32(mx)), count, _dp(d_out), _dp(d_status)),
+               "gc_rand_scalars_cur_dev")
+
+    def _cur_host(self, cur):
+        cur = np.ascontiguousarray(cur, dtype=np.uint64).reshape(self.S).copy()
+        return cur, C.c_size_t(_NONE)
+
+    def fill_cur_host(self, cur, nbytes, out=None, stride=None):
+        """gc_rand_fill_cur: cur u64 [S] -> (out u8 [S, stride], the new cursors); raises RandSessionError"""
+        stride = nbytes if stride is None else stride
+        if out is None:
+            out = np.zeros((self.S, stride), np.uint8)
+        assert out.dtype == np.uint8 and out.flags.c_contiguous and out.size >= self.S * stride
+        cur, bad = self._cur_host(cur)
+        rc = lib().gc_rand_fill_cur(self.h, _p(cur), nbytes, _p(out) if out.size else None, stride, C.byref(bad))
+        if rc == GC_E_ARG and _bad(bad) is not None:
+            raise RandSessionError("gc_rand_fill_cur", bad.value, out, cur)
+        _check(rc, "gc_rand_fill_cur")
+        return out, cur
+
+    def scalars_cur_host(self, cur, mx, count, out=None):
+        """gc_rand_scalars_cur: cur u64 [S] -> (out u8 [S, count, 32], the new cursors); raises RandSessionError"""
+        if out is None:
+            out = np.zeros((self.S, count, 32), np.uint8)
+        assert out.dtype == np.uint8 and out.flags.c_contiguous and out.size >= self.S * count * 32
+        cur, bad = self._cur_host(cur)
+        rc = lib().gc_rand_scalars_cur(self.h, _p(cur), _p(_max32(mx)), count, _p(out) if out.size else None, C.byref(bad))
+        if rc == GC_E_ARG and _bad(bad) is not None:
+            raise RandSessionError("gc_rand_scalars_cur", bad.value, out, cur)
+        _check(rc, "gc_rand_scalars_cur")
+        return out, cur
+
+    def draw_co_sender(self, d_cur, d_a, d_status):
+        """GenerateCOSenderSetup's draw (ot/co_helpers.go:83): one crand.Int(rand, N) per session: the d_a [S, 32] of
+        gc_co_multi_sender_setup_dev"""
+        self.scalars_cur(d_cur, P256_N, 1, d_a, d_status)
+
+    def draw_co_receiver(self, per, d_cur, d_scalars, d_status):
+        """BuildCOChoices' draws (ot/co_helpers.go:150-151): `per` crand.Int(rand, N) one after the other per session: the
+        d_scalars [S, per, 32] of gc_co_multi_receiver_choices_dev"""
+        self.scalars_cur(d_cur, P256_N, per, d_scalars, d_status)
 
     def close(self):
         if self.h:
