@@ -1393,6 +1393,95 @@ int gc_rand_scalars_cur_dev(gc_rand *, void *d_cur, const uint8_t max[32], size_
 int gc_rand_fill_cur(gc_rand *, uint64_t *cur, size_t nbytes, uint8_t *out, size_t stride, size_t *bad_session);
 int gc_rand_scalars_cur(gc_rand *, uint64_t *cur, const uint8_t max[32], size_t count, uint8_t *out, size_t *bad_session);
 
+/* ------------------------------------------------------------------------------------------
+ * circuit.Garbler / circuit.Evaluator for S sessions per call: the messages built and read on the device (additive;
+ * DESIGN.md §23; circuit/garbler.go:38-180, circuit/evaluator.go:20-157, framing p2p/protocol.go:216-261)
+ * Session s of a call is byte for byte what the two drivers write through p2p.Conn for that session alone.  The OT stays
+ * the caller's: the handles hand over and take the arrays of gc_co_multi_* / gc_iknp_multi_* / gc_cot_multi_*.  The 8-byte
+ * offset / count exchange (garbler.go:119-131, evaluator.go:92-97) and CO's point framing stay in the Go shim.
+ *   Geometry.  A handle serves one 2-party circuit and ONE key length: ng garbler inputs (wires 0 .. ng), ne evaluator
+ *   inputs (the next ne), nout outputs (the last nout wires), keylen 16, 24 or 32.  Messages per session (gc_yao_layout;
+ *   index 0 .. 2 = M1 .. M3):
+ *     M1  garbler -> evaluator   BE32(keylen) key | BE32(ngates) | per gate BE32(rows) rows x 16 | ng x 16
+ *                                                                       4 + keylen + gc_tables_wire_bytes() + 16 ng
+ *     M2  evaluator -> garbler   nout x 16                              16 nout
+ *     M3  garbler -> evaluator   BE32(n) | n bytes of result.Bytes()    a slot of 4 + ceil(nout / 8); 4 + n in len3[s]
+ *   A label is BE(D0) || BE(D1) (SendLabel).  result.Bytes() is big-endian and minimal, n = 0 for a zero result; output i is
+ *   bit i of the integer.  A DEVICE array of messages is [S][stride] bytes, 16-byte aligned, stride a multiple of 16 and >=
+ *   the message's length (M3: its slot); a slot's padding is never written.  The HOST forms take and give packed arrays
+ *   [S][len]; M3 is packed at slot size with zeros behind a message, and len3 [S] comes with it.
+ *   d_keys u8 [S][keylen] (16-byte aligned); d_rnd that of gc_batch_garble_keyed, circuit.Garbler's read order after the
+ *   key; d_bits u8 [S][ng], non-zero: 1 (may be NULL when ng = 0); d_wires_out gc_wire [S][ne] and d_labels gc_label [S][ne],
+ *   session-major as gc_co_multi_* / gc_cot_multi_* take and give them; d_bits_out u8 [S][ceil(nout / 8)], output i in bit
+ *   i % 8 of byte i / 8 (the sha2pc digest layout); d_len3_out u32 [S].
+ *   Create.  The handle owns one keyed gc_batch of S instances (schedule 1; gc_yao_*_batch hands it out for
+ *   gc_batch_set_keyed_path / _keyed_hbm_form / gc_batch_last_ms, the handle keeps owning it) and every scratch array;
+ *   synchronous, not between gc_ctx_capture_begin and _end.  NULL and *status (which may be NULL): GC_E_KEYSIZE for another
+ *   keylen; GC_E_ARG with a gc_last_error() text when gc_batch_keyed_supported is 0 for that batch, when ng + ne is not the
+ *   circuit's input count, when ne or nout is 0, when M1 does not fit 32 bits or a size does not fit size_t (S must fit
+ *   uint32_t).  ng = 0 is allowed: M1 then carries no labels.  One call at a time per handle; free waits for the ctx stream
+ *   first (free a handle before its circuit and its ctx); NULL is a no-op.
+ *   _dev calls allocate nothing and wait for nothing: a fixed sequence of launches on the ctx stream, legal between
+ *   gc_ctx_capture_begin and _end; a replayed send garbles with whatever d_keys, d_rnd and d_bits hold then.
+ *     garbler    send       gc_batch_garble_keyed, then M1
+ *                ot_wires   the gc_wire of the evaluator's inputs (oti.Send's argument, garbler.go:132)
+ *                result     M2 -> BitFromLabel against the handle's output wires -> bits, M3, len3
+ *     evaluator  accept     M1 -> the handle's keys, tables and the garbler's labels
+ *                eval       the OT's labels, gc_batch_eval_keyed, then M2
+ *                result     M3 -> bits
+ *   d_verdict: u32 [S] in device memory, written by every call that takes one for every session.  0: good.  Otherwise
+ *   code | index << 8 (the index's low 24 bits), the first check that fails:
+ *     GC_YAO_KEY     M1's first word is not keylen: a handle serves one key length (the reference takes any aes.NewCipher does)
+ *     GC_YAO_GATES   the gate count is not the circuit's (evaluator.go:45-48)
+ *     GC_YAO_ROWS    gate `index` is the lowest whose row word is not its op's row count (gc_batch_ingest_tables' rule)
+ *     GC_YAO_LABEL   output `index` is the lowest whose label is neither L0 nor L1 (BitFromLabel, helpers.go:18-27)
+ *     GC_YAO_LENGTH  M3's n with 4 + n > stride3; any other n is read as a big-endian integer and the bits at index nout
+ *                    and above are dropped, as IO.Split does (ioarg.go:51-65)
+ *   A bad session gets zero bytes in every output of that call (M3 over its slot bytes, its bits, its len3) and changes
+ *   nothing in any other session.  A session that accept found bad stays bad in the handle until the next accept: eval
+ *   writes a zero M2 for it and repeats the verdict.
+ *   Host forms: host pointers, packed messages, synchronous, staged, not inside a capture.  Every good session is written;
+ *   with a bad session the call returns GC_E_ROWS (GATES, ROWS) or GC_E_ARG (every other code) for the LOWEST bad session
+ *   and *bad_session = its number (verdict [S] and bad_session may be NULL).
+ *   gc_yao_kernel_shape: sessions per workgroup and bytes per piece of the M1 kernels as create would choose them now
+ *   (developer aid; either pointer may be NULL).
+ *   Not offered: sessions on different circuits or key lengths in one handle, the OT's own messages, Timing. */
+typedef struct gc_yao_garbler gc_yao_garbler;
+typedef struct gc_yao_evaluator gc_yao_evaluator;
+enum {
+    GC_YAO_KEY = 1,
+    GC_YAO_GATES = 2,
+    GC_YAO_ROWS = 3,
+    GC_YAO_LABEL = 4,
+    GC_YAO_LENGTH = 5
+};
+gc_yao_garbler *gc_yao_garbler_create(gc_ctx *, gc_circ *, uint32_t ng, uint32_t ne, size_t keylen, size_t S, int *status);
+gc_yao_evaluator *gc_yao_evaluator_create(gc_ctx *, gc_circ *, uint32_t ng, uint32_t ne, size_t keylen, size_t S, int *status);
+void gc_yao_garbler_free(gc_yao_garbler *);
+void gc_yao_evaluator_free(gc_yao_evaluator *);
+/* len[3] of M1, M2 and M3's slot; GC_E_KEYSIZE / GC_E_ARG as create.  The _plan form needs no device. */
+int gc_yao_layout(const gc_circ *, uint32_t ng, uint32_t ne, size_t keylen, size_t len[3]);
+int gc_yao_layout_plan(const gc_plan *, uint32_t ng, uint32_t ne, size_t keylen, size_t len[3]);
+int gc_yao_kernel_shape(uint32_t *session_tile, uint32_t *piece_bytes);
+gc_batch *gc_yao_garbler_batch(gc_yao_garbler *);
+gc_batch *gc_yao_evaluator_batch(gc_yao_evaluator *);
+
+int gc_yao_garbler_send_dev(gc_yao_garbler *, const void *d_keys, const void *d_rnd, const void *d_bits, void *d_m1_out,
+                            size_t stride1);
+int gc_yao_garbler_ot_wires_dev(gc_yao_garbler *, void *d_wires_out);
+int gc_yao_garbler_result_dev(gc_yao_garbler *, const void *d_m2, size_t stride2, void *d_m3_out, size_t stride3,
+                              void *d_len3_out, void *d_bits_out, void *d_verdict);
+int gc_yao_evaluator_accept_dev(gc_yao_evaluator *, const void *d_m1, size_t stride1, void *d_verdict);
+int gc_yao_evaluator_eval_dev(gc_yao_evaluator *, const void *d_labels, void *d_m2_out, size_t stride2, void *d_verdict);
+int gc_yao_evaluator_result_dev(gc_yao_evaluator *, const void *d_m3, size_t stride3, void *d_bits_out, void *d_verdict);
+int gc_yao_garbler_send(gc_yao_garbler *, const uint8_t *keys, const uint8_t *rnd, const uint8_t *bits, uint8_t *m1_out);
+int gc_yao_garbler_ot_wires(gc_yao_garbler *, gc_wire *wires_out);
+int gc_yao_garbler_result(gc_yao_garbler *, const uint8_t *m2, uint8_t *m3_out, uint32_t *len3_out, uint8_t *bits_out,
+                          uint32_t *verdict, size_t *bad_session);
+int gc_yao_evaluator_accept(gc_yao_evaluator *, const uint8_t *m1, uint32_t *verdict, size_t *bad_session);
+int gc_yao_evaluator_eval(gc_yao_evaluator *, const gc_label *labels, uint8_t *m2_out, uint32_t *verdict, size_t *bad_session);
+int gc_yao_evaluator_result(gc_yao_evaluator *, const uint8_t *m3, uint8_t *bits_out, uint32_t *verdict, size_t *bad_session);
+
 #ifdef __cplusplus
 }
 #endif

@@ -966,6 +966,107 @@ private:
 
 }  // namespace sha2pc
 
+// circuit.Garbler / circuit.Evaluator for S sessions of one circuit per call (circuit/garbler.go:38-180, evaluator.go:20-157;
+// gcengine.h: gc_yao_*), on packed messages [S][len].  The OT between Send and Result is the caller's (mpc::ot, on the wires
+// of OtWires).  A check that a session fails is reported in verdict[s] (GC_YAO_* | index << 8) with zero bytes for that
+// session's outputs; the calls throw only for their own failures.
+namespace yao {
+
+struct Layout {
+    size_t len[3];  // M1, M2, M3's slot
+    size_t bits_bytes() const { return len[2] - 4; }
+};
+
+inline Layout MessageLayout(const gc_circ *circ, uint32_t ng, uint32_t ne, size_t keylen) {
+    Layout l{};
+    check(gc_yao_layout(circ, ng, ne, keylen, l.len), "gc_yao_layout");
+    return l;
+}
+
+// a bad session is the verdicts' to report
+inline void check_call(int st, size_t bad, const char *what) {
+    if ((st == GC_E_ARG || st == GC_E_ROWS) && bad != (size_t)-1) return;
+    check(st, what);
+}
+
+class GarblerBatch {
+public:
+    GarblerBatch(Context &ctx, gc_circ *circ, uint32_t ng, uint32_t ne, size_t keylen, size_t S)
+        : S_(S), ne_(ne), l_(MessageLayout(circ, ng, ne, keylen)) {
+        int st = GC_OK;
+        h_ = gc_yao_garbler_create(ctx.handle(), circ, ng, ne, keylen, S, &st);
+        check(st, "gc_yao_garbler_create");
+    }
+    ~GarblerBatch() { gc_yao_garbler_free(h_); }
+    GarblerBatch(const GarblerBatch &) = delete;
+    GarblerBatch &operator=(const GarblerBatch &) = delete;
+    const Layout &layout() const { return l_; }
+    gc_yao_garbler *handle() { return h_; }
+    // Garble and the messages before the OT: keys [S][keylen], rnd [S][16 (1 + ng + ne)], bits [S][ng] -> m1 [S][len1]
+    void Send(const uint8_t *keys, const uint8_t *rnd, const uint8_t *bits, std::vector<uint8_t> &m1) {
+        m1.resize(S_ * l_.len[0]);
+        check(gc_yao_garbler_send(h_, keys, rnd, bits, m1.data()), "gc_yao_garbler_send");
+    }
+    // garbled.Wires[offset : offset + count] of every session, session-major
+    void OtWires(std::vector<gc_wire> &wires) {
+        wires.resize(S_ * ne_);
+        check(gc_yao_garbler_ot_wires(h_, wires.data()), "gc_yao_garbler_ot_wires");
+    }
+    // m2 [S][16 nout] -> m3 [S][4 + bits_bytes] (4 + n bytes used: len3 [S]), bits [S][bits_bytes]
+    void Result(const uint8_t *m2, std::vector<uint8_t> &m3, std::vector<uint32_t> &len3, std::vector<uint8_t> &bits,
+                std::vector<uint32_t> &verdict) {
+        m3.resize(S_ * l_.len[2]), len3.resize(S_), bits.resize(S_ * l_.bits_bytes()), verdict.resize(S_);
+        size_t bad = (size_t)-1;
+        check_call(gc_yao_garbler_result(h_, m2, m3.data(), len3.data(), bits.data(), verdict.data(), &bad), bad,
+                   "gc_yao_garbler_result");
+    }
+
+private:
+    gc_yao_garbler *h_ = nullptr;
+    size_t S_, ne_;
+    Layout l_;
+};
+
+class EvaluatorBatch {
+public:
+    EvaluatorBatch(Context &ctx, gc_circ *circ, uint32_t ng, uint32_t ne, size_t keylen, size_t S)
+        : S_(S), l_(MessageLayout(circ, ng, ne, keylen)) {
+        int st = GC_OK;
+        h_ = gc_yao_evaluator_create(ctx.handle(), circ, ng, ne, keylen, S, &st);
+        check(st, "gc_yao_evaluator_create");
+    }
+    ~EvaluatorBatch() { gc_yao_evaluator_free(h_); }
+    EvaluatorBatch(const EvaluatorBatch &) = delete;
+    EvaluatorBatch &operator=(const EvaluatorBatch &) = delete;
+    const Layout &layout() const { return l_; }
+    gc_yao_evaluator *handle() { return h_; }
+    // m1 [S][len1]: key, tables and the garbler's labels into the handle
+    void Accept(const uint8_t *m1, std::vector<uint32_t> &verdict) {
+        verdict.resize(S_);
+        size_t bad = (size_t)-1;
+        check_call(gc_yao_evaluator_accept(h_, m1, verdict.data(), &bad), bad, "gc_yao_evaluator_accept");
+    }
+    // labels [S][ne] from the OT -> m2 [S][16 nout]
+    void Eval(const gc_label *labels, std::vector<uint8_t> &m2, std::vector<uint32_t> &verdict) {
+        m2.resize(S_ * l_.len[1]), verdict.resize(S_);
+        size_t bad = (size_t)-1;
+        check_call(gc_yao_evaluator_eval(h_, labels, m2.data(), verdict.data(), &bad), bad, "gc_yao_evaluator_eval");
+    }
+    // m3 [S][4 + bits_bytes] -> bits [S][bits_bytes]
+    void Result(const uint8_t *m3, std::vector<uint8_t> &bits, std::vector<uint32_t> &verdict) {
+        bits.resize(S_ * l_.bits_bytes()), verdict.resize(S_);
+        size_t bad = (size_t)-1;
+        check_call(gc_yao_evaluator_result(h_, m3, bits.data(), verdict.data(), &bad), bad, "gc_yao_evaluator_result");
+    }
+
+private:
+    gc_yao_evaluator *h_ = nullptr;
+    size_t S_;
+    Layout l_;
+};
+
+}  // namespace yao
+
 // The random streams of S sessions, expanded on the device (gcengine.h: gc_rand_*): stream s is what a Go host reads from
 // cipher.StreamReader{S: cipher.NewCTR(aes.NewCipher(seed[s]), iv[s]), R: zeros}, the reader it would set as env.Config.Rand.
 // One byte position for all streams; every draw is one launch on the ctx stream.  The cursor calls (SetCursors, FillAt, Ints)

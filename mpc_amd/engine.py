@@ -363,6 +363,27 @@ def lib():
         "gc_rand_scalars_cur_dev": (i32, [vp, vp, vp, sz, vp, vp]),
         "gc_rand_fill_cur": (i32, [vp, vp, sz, vp, sz, C.POINTER(C.c_size_t)]),
         "gc_rand_scalars_cur": (i32, [vp, vp, vp, sz, vp, C.POINTER(C.c_size_t)]),
+        "gc_yao_garbler_create": (vp, [vp, vp, C.c_uint32, C.c_uint32, sz, sz, ip]),
+        "gc_yao_evaluator_create": (vp, [vp, vp, C.c_uint32, C.c_uint32, sz, sz, ip]),
+        "gc_yao_garbler_free": (None, [vp]),
+        "gc_yao_evaluator_free": (None, [vp]),
+        "gc_yao_layout": (i32, [vp, C.c_uint32, C.c_uint32, sz, C.POINTER(C.c_size_t)]),
+        "gc_yao_layout_plan": (i32, [vp, C.c_uint32, C.c_uint32, sz, C.POINTER(C.c_size_t)]),
+        "gc_yao_kernel_shape": (i32, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "gc_yao_garbler_batch": (vp, [vp]),
+        "gc_yao_evaluator_batch": (vp, [vp]),
+        "gc_yao_garbler_send_dev": (i32, [vp, vp, vp, vp, vp, sz]),
+        "gc_yao_garbler_ot_wires_dev": (i32, [vp, vp]),
+        "gc_yao_garbler_result_dev": (i32, [vp, vp, sz, vp, sz, vp, vp, vp]),
+        "gc_yao_evaluator_accept_dev": (i32, [vp, vp, sz, vp]),
+        "gc_yao_evaluator_eval_dev": (i32, [vp, vp, vp, sz, vp]),
+        "gc_yao_evaluator_result_dev": (i32, [vp, vp, sz, vp, vp]),
+        "gc_yao_garbler_send": (i32, [vp, vp, vp, vp, vp]),
+        "gc_yao_garbler_ot_wires": (i32, [vp, vp]),
+        "gc_yao_garbler_result": (i32, [vp, vp, vp, vp, vp, vp, C.POINTER(C.c_size_t)]),
+        "gc_yao_evaluator_accept": (i32, [vp, vp, vp, C.POINTER(C.c_size_t)]),
+        "gc_yao_evaluator_eval": (i32, [vp, vp, vp, vp, C.POINTER(C.c_size_t)]),
+        "gc_yao_evaluator_result": (i32, [vp, vp, vp, vp, C.POINTER(C.c_size_t)]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -2579,6 +2600,169 @@ class Sha2pcEvaluator(_Sha2pc):
         v, bad = np.zeros(S, np.uint32), C.c_size_t(_NONE)
         rc = lib().gc_sha2pc_evaluator_round4(self.h, _p(A), _p(sid), _p(sc), _p(bits), _p(r3), _p(dg), _p(v), C.byref(bad))
         return self._host(rc, "gc_sha2pc_evaluator_round4", v, bad, dg)
+
+
+# ---- circuit.Garbler / circuit.Evaluator for S sessions per call (gc_yao_*) ---------------------------------------------------
+
+YAO_KEY, YAO_GATES, YAO_ROWS, YAO_LABEL, YAO_LENGTH = 1, 2, 3, 4, 5
+
+
+class YaoSessionError(EngineError):
+    """a bad session of a gc_yao_* host call: .bad_session = the lowest one, .verdict = u32 [S] (code | index << 8),
+    .out = the outputs all the same (zeros in the bad sessions)"""
+
+    def __init__(self, code, what, bad_session, verdict, out):
+        super().__init__(code, what)
+        self.bad_session, self.verdict, self.out = bad_session, verdict, out
+
+
+def yao_layout(plan_or_circ, ng, ne, keylen):
+    """gc_yao_layout / _layout_plan -> [len of M1, len of M2, slot bytes of M3]; a Plan needs no device"""
+    ln = (C.c_size_t * 3)()
+    if isinstance(plan_or_circ, DeviceCircuit):
+        rc = lib().gc_yao_layout(plan_or_circ.h, ng, ne, keylen, ln)
+    else:
+        rc = lib().gc_yao_layout_plan(plan_or_circ.h if plan_or_circ is not None else None, ng, ne, keylen, ln)
+    _check(rc, "gc_yao_layout")
+    return list(ln)
+
+
+def yao_kernel_shape():
+    """gc_yao_kernel_shape -> (sessions per workgroup, bytes per piece) of the M1 kernels as create would choose them now"""
+    tile, piece = C.c_uint32(0), C.c_uint32(0)
+    _check(lib().gc_yao_kernel_shape(C.byref(tile), C.byref(piece)), "gc_yao_kernel_shape")
+    return tile.value, piece.value
+
+
+class _HandleBatch(Batch):
+    """the gc_batch a gc_yao_* handle owns (path, form, last_ms): closing it leaves the batch to its handle"""
+
+    def __init__(self, dcirc, batch, h):
+        self.dc, self.batch, self.h = dcirc, batch, h
+
+    def close(self):
+        self.h = None
+
+
+class _Yao:
+    """what the two handles share: geometry, the strides of device message arrays, the verdict of a host call"""
+
+    def __init__(self, dcirc, ng, ne, keylen, S, create, free, batch_of, what):
+        self.ctx, self.dc, self.ng, self.ne, self.keylen, self.S = dcirc.ctx, dcirc, int(ng), int(ne), int(keylen), int(S)
+        self._free, self.h = free, None
+        st = C.c_int(0)
+        self.h = create(self.ctx.h, dcirc.h, ng, ne, keylen, S, C.byref(st))
+        if not self.h:
+            raise EngineError(st.value, what)
+        self.len = yao_layout(dcirc, ng, ne, keylen)
+        self.stride = [(ln + 15) // 16 * 16 for ln in self.len]
+        self.bits_bytes = self.len[2] - 4
+        self.batch = _HandleBatch(dcirc, self.S, batch_of(self.h))
+
+    def _host(self, rc, what, verdict, bad, out):
+        if rc in (GC_E_ARG, GC_E_ROWS) and _bad(bad) is not None:
+            raise YaoSessionError(rc, what, bad.value, verdict, out)
+        _check(rc, what)
+        return out
+
+    def close(self):
+        """free the handle BEFORE its circuit and its ctx; behind either the handle is dropped unfreed (its free would wait
+        for a stream that is gone)"""
+        if self.h and self.dc.h and self.ctx.h:
+            self._free(self.h)
+        self.h = None
+        self.batch.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class YaoGarbler(_Yao):
+    """gc_yao_garbler: circuit.Garbler's messages (circuit/garbler.go:38-180) for S sessions per call"""
+
+    def __init__(self, dcirc, ng, ne, keylen, S):
+        super().__init__(dcirc, ng, ne, keylen, S, lib().gc_yao_garbler_create, lib().gc_yao_garbler_free,
+                         lib().gc_yao_garbler_batch, "gc_yao_garbler_create")
+
+    def send_dev(self, d_keys, d_rnd, d_bits, d_m1_out, stride1):
+        _check(lib().gc_yao_garbler_send_dev(self.h, _dp(d_keys), _dp(d_rnd), _dp(d_bits), _dp(d_m1_out), stride1),
+               "gc_yao_garbler_send_dev")
+
+    def ot_wires_dev(self, d_wires_out):
+        _check(lib().gc_yao_garbler_ot_wires_dev(self.h, _dp(d_wires_out)), "gc_yao_garbler_ot_wires_dev")
+
+    def result_dev(self, d_m2, stride2, d_m3_out, stride3, d_len3_out, d_bits_out, d_verdict):
+        _check(lib().gc_yao_garbler_result_dev(self.h, _dp(d_m2), stride2, _dp(d_m3_out), stride3, _dp(d_len3_out),
+                                               _dp(d_bits_out), _dp(d_verdict)), "gc_yao_garbler_result_dev")
+
+    def send(self, keys, rnd, bits):
+        """keys u8 [S, keylen], rnd u8 [S, 16 * (1 + ng + ne)], bits u8 [S, ng] -> packed M1 u8 [S, len1]"""
+        S = self.S
+        keys, rnd = _bytes2(keys, S, self.keylen), _bytes2(rnd, S, 16 * (1 + self.ng + self.ne))
+        bits = np.ascontiguousarray(bits, dtype=np.uint8).reshape(S, self.ng)
+        m1 = np.zeros((S, self.len[0]), np.uint8)
+        _check(lib().gc_yao_garbler_send(self.h, _p(keys), _p(rnd), _p(bits) if self.ng else None, _p(m1)), "gc_yao_garbler_send")
+        return m1
+
+    def ot_wires(self):
+        """-> WIRE [S, ne]: oti.Send's argument of every session"""
+        w = np.zeros((self.S, self.ne), WIRE)
+        _check(lib().gc_yao_garbler_ot_wires(self.h, _p(w)), "gc_yao_garbler_ot_wires")
+        return w
+
+    def result(self, m2):
+        """packed M2 u8 [S, 16 nout] -> (M3 u8 [S, 4 + bits_bytes], len3 u32 [S], bits u8 [S, bits_bytes]); raises YaoSessionError"""
+        S = self.S
+        m2 = _bytes2(m2, S, self.len[1])
+        m3, len3, bits = np.zeros((S, self.len[2]), np.uint8), np.zeros(S, np.uint32), np.zeros((S, self.bits_bytes), np.uint8)
+        v, bad = np.zeros(S, np.uint32), C.c_size_t(_NONE)
+        rc = lib().gc_yao_garbler_result(self.h, _p(m2), _p(m3), _p(len3), _p(bits), _p(v), C.byref(bad))
+        return self._host(rc, "gc_yao_garbler_result", v, bad, (m3, len3, bits))
+
+
+class YaoEvaluator(_Yao):
+    """gc_yao_evaluator: circuit.Evaluator's messages (circuit/evaluator.go:20-157) for S sessions per call"""
+
+    def __init__(self, dcirc, ng, ne, keylen, S):
+        super().__init__(dcirc, ng, ne, keylen, S, lib().gc_yao_evaluator_create, lib().gc_yao_evaluator_free,
+                         lib().gc_yao_evaluator_batch, "gc_yao_evaluator_create")
+
+    def accept_dev(self, d_m1, stride1, d_verdict):
+        _check(lib().gc_yao_evaluator_accept_dev(self.h, _dp(d_m1), stride1, _dp(d_verdict)), "gc_yao_evaluator_accept_dev")
+
+    def eval_dev(self, d_labels, d_m2_out, stride2, d_verdict):
+        _check(lib().gc_yao_evaluator_eval_dev(self.h, _dp(d_labels), _dp(d_m2_out), stride2, _dp(d_verdict)),
+               "gc_yao_evaluator_eval_dev")
+
+    def result_dev(self, d_m3, stride3, d_bits_out, d_verdict):
+        _check(lib().gc_yao_evaluator_result_dev(self.h, _dp(d_m3), stride3, _dp(d_bits_out), _dp(d_verdict)),
+               "gc_yao_evaluator_result_dev")
+
+    def accept(self, m1):
+        """packed M1 u8 [S, len1] -> verdicts u32 [S] (all zero); raises YaoSessionError"""
+        m1 = _bytes2(m1, self.S, self.len[0])
+        v, bad = np.zeros(self.S, np.uint32), C.c_size_t(_NONE)
+        rc = lib().gc_yao_evaluator_accept(self.h, _p(m1), _p(v), C.byref(bad))
+        return self._host(rc, "gc_yao_evaluator_accept", v, bad, v)
+
+    def eval(self, labels):
+        """labels LABEL [S, ne] from the OT -> packed M2 u8 [S, 16 nout]; raises YaoSessionError for a session accept found bad"""
+        lab = np.ascontiguousarray(labels, dtype=LABEL).reshape(self.S, self.ne)
+        m2 = np.zeros((self.S, self.len[1]), np.uint8)
+        v, bad = np.zeros(self.S, np.uint32), C.c_size_t(_NONE)
+        rc = lib().gc_yao_evaluator_eval(self.h, _p(lab), _p(m2), _p(v), C.byref(bad))
+        return self._host(rc, "gc_yao_evaluator_eval", v, bad, m2)
+
+    def result(self, m3):
+        """packed M3 u8 [S, 4 + bits_bytes] -> bits u8 [S, bits_bytes]; raises YaoSessionError"""
+        m3 = _bytes2(m3, self.S, self.len[2])
+        bits = np.zeros((self.S, self.bits_bytes), np.uint8)
+        v, bad = np.zeros(self.S, np.uint32), C.c_size_t(_NONE)
+        rc = lib().gc_yao_evaluator_result(self.h, _p(m3), _p(bits), _p(v), C.byref(bad))
+        return self._host(rc, "gc_yao_evaluator_result", v, bad, bits)
 
 
 # ---- device random streams: AES-CTR draws for S sessions per call (gc_rand_*) ----
