@@ -4,7 +4,7 @@
 // big-endian and minimal, n = ceil(bitlen / 8), n = 0 for a zero result.  circuit/evaluator.go:144-148 reads any n with
 // SetBytes, and IO.Split (ioarg.go:51-65) keeps the low nout bits.  The engine's bits array is the sha2pc digest layout:
 // output i in bit i % 8 of byte i / 8, nb8 = ceil(nout / 8) bytes, so payload byte k of n is bits byte n - 1 - k.
-// The kernels (one lane per byte), the CPU test (tests/cpp/yao_m3_check.cpp) and nothing else restate this.  Plain C++.
+// The kernels (one lane per byte), the CPU test (tests/cpp/yao_host_check.cpp) and nothing else restate this.  Plain C++.
 #pragma once
 
 #include <cstdint>

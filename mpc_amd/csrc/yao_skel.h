@@ -1,5 +1,5 @@
 // yao_skel.h — the skeleton and the piece table of circuit.Garbler's first message (gc_yao_*), built once per
-// handle on the host.  No HIP here: yao_engine.cpp uploads the arrays, and tests/cpp/yao_piece_walk.cpp walks them.
+// handle on the host.  No HIP here: yao_engine.cpp uploads the arrays, and tests/cpp/yao_host_check.cpp walks them.
 //
 // M1 of one session (circuit/garbler.go:64-102, p2p/protocol.go:216-261), offsets in bytes from the slot:
 //   0            BE32(keylen)                     SendData(key)
